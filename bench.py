@@ -33,6 +33,12 @@ Kernel time: HIP events on the launch stream around the timed region, divided by
 `roofline.traffic` comes from rocprofv3 PMC passes, which cannot run inside this process: it is read from
 profiles/traffic.json and reported ONLY if that file was captured with the very sources the loaded library was built from
 (`source_digest`) on the same workload size; otherwise it is null and `traffic_source` says why. Capture: tools/final_profile.sh.
+
+--dump-outputs DIR: right after the timed region (before the eager-rho steps) the state the last timed step produced - its output
+populations and velocity and the density, as download() returns them (reference layout [8,8,8,block,K], float32) - is written as
+DIR/f.npy, DIR/vel.npy, DIR/rho.npy for a fixed, seeded sample of DUMP_BLOCKS whole blocks (every block when the box has no more),
+with the sampled block indices in DIR/block.npy (float64). N > 1: every rank writes its share of the sample from its owned blocks,
+names suffixed _rank<r>. The inputs depend on the arguments only, so two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -47,6 +53,8 @@ sys.path.insert(0, ROOT)
 
 ALGO_BYTES_PER_LUP = 216.0        # 27 x 4 B read + 27 x 4 B write
 HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BLOCKS = 512                 # --dump-outputs: blocks sampled over all ranks; 512 x 31 fields x 2 KiB = 32.5 MB
+DUMP_SEED = 20260101
 
 
 def parse():
@@ -73,7 +81,11 @@ def parse():
     ap.add_argument("--preheat-ms", type=float, default=60.0,
                     help="keep the device busy with plain memory copies (no stepping) for this long right before the warm-up steps, so that "
                          "the W + K steps run at settled clocks (0 = off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region write the state its last step produced (f, vel, rho of a seeded block sample) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.size is None:
         a.size = 512 if a.scaling == "strong" else 256
     return a
@@ -186,6 +198,32 @@ def kernel_label(info) -> str:
     general = "true" if info.n_general_blocks > 0 and info.n_fast_blocks == 0 else "false"
     wide = "true" if (info.n_blocks * 27 * 2048 >= 2 ** 32 or os.environ.get("LUDWIG_WIDE_ADDR")) else "false"
     return f"void lw::k_stream_collide_xrun<4, {general}, false, false, false, {wide}>(lw::SCParams)"
+
+
+def dump_sample(n_owned: int, rank: int, world: int):
+    """--dump-outputs: the owned blocks (reference order) whose state is written - all of them when they fit the rank's share of
+    DUMP_BLOCKS, else a seeded draw, sorted; the same for every run with the same arguments"""
+    import numpy as np
+    n = min(n_owned, max(1, DUMP_BLOCKS // world))
+    if n == n_owned:
+        return np.arange(n_owned, dtype=np.int64)
+    return np.sort(np.random.default_rng([DUMP_SEED, rank]).choice(n_owned, size=n, replace=False))
+
+
+def dump_outputs(level, t_last: int, rank: int, world: int, out_dir: str) -> None:
+    """write the state step t_last produced: its output buffers (f_temp / vel_temp after an even sub-step, f / vel after an odd one:
+    the A/B roles of src/solver_control.jl:35-41) and rho, one field downloaded at a time so only the sample is kept"""
+    import numpy as np
+    n_owned = level.n_owned if 0 < level.n_owned <= level.n_blocks else level.n_blocks
+    blocks = dump_sample(n_owned, rank, world)
+    f_name, vel_name = ("f_temp", "vel_temp") if t_last % 2 == 0 else ("f", "vel")
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, field in (("f", f_name), ("vel", vel_name), ("rho", "rho")):
+        a = level.download(field)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a[:, :, :, blocks], dtype=np.float32))
+        del a
+    np.save(os.path.join(out_dir, f"block{suffix}.npy"), blocks.astype(np.float64))
 
 
 def main():
@@ -324,6 +362,9 @@ def main():
         w = torch.tensor([wall, kern_ms], dtype=torch.float64, device=red_dev)
         dist.all_reduce(w, op=dist.ReduceOp.MAX)      # slowest rank defines the step time
         wall, kern_ms = float(w[0].item()), float(w[1].item())
+
+    if args.dump_outputs:
+        dump_outputs(level, t - 1, rank, world, args.dump_outputs)
 
     # N = 1, after the timed region: the same kernel with rho stored by every step, as the reference's kernel does
     # (src/physics_kernels.jl:243-246) - the driver-observed price of the elided store

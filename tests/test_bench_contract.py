@@ -41,6 +41,59 @@ def test_bench_prints_exactly_one_json_line_with_the_contract_keys(gpu):
     assert abs(d["value"] - 64 ** 3 * 4 / (d["ms_per_step"] * 4 * 1e-3) / 1e6) / d["value"] < 1e-2
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: the sampled blocks depend on the arguments only, stay inside the owned blocks, and the files fit in 64 MB"""
+    import numpy as np
+    bench = _bench_module()
+    a, b = bench.dump_sample(32 ** 3, 0, 1), bench.dump_sample(32 ** 3, 0, 1)
+    assert np.array_equal(a, b) and a.size == bench.DUMP_BLOCKS and np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 32 ** 3
+    assert np.array_equal(bench.dump_sample(100, 0, 1), np.arange(100))
+    per_rank = [bench.dump_sample(64 ** 3, r, 8) for r in range(8)]
+    assert sum(s.size for s in per_rank) <= bench.DUMP_BLOCKS and not np.array_equal(per_rank[0], per_rank[1])
+    assert bench.DUMP_BLOCKS * (8 ** 3 * (27 + 3 + 1) * 4 + 8) <= 64e6
+
+
+def test_bench_rejects_zero_steps():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert res.returncode != 0 and res.stdout.strip() == "" and "--steps" in res.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("steps", [3, 4])
+def test_bench_dumps_the_state_of_its_last_timed_step(gpu, tmp_path, steps):
+    """--dump-outputs after --warmup 2 --steps K: the sampled blocks' f, vel, rho are those of the CPU oracle after exactly 2 + K steps
+    of the same box, bit for bit (odd and even K: both output buffers). 72^3 = 729 blocks, more than DUMP_BLOCKS: the sample is drawn."""
+    import numpy as np
+    from open_ludwig_amd import cases
+    from oracle import oracle
+    out = tmp_path / "dump"
+    res = _run_bench("--size", "72", "--steps", str(steps), "--warmup", "2", "--cpu-seconds", "0", "--eager-rho-steps", "0",
+                     "--preheat-ms", "5", "--dump-outputs", str(out))
+    assert res.returncode == 0, res.stderr[-2000:]
+    assert json.loads(res.stdout.strip())["steps"] == steps
+    files = sorted(os.listdir(out))
+    assert files == ["block.npy", "f.npy", "rho.npy", "vel.npy"]
+    assert sum(os.path.getsize(out / f) for f in files) <= 64e6
+    d = {f[:-4]: np.load(out / f) for f in files}
+    assert d["block"].dtype == np.float64 and all(d[k].dtype == np.float32 for k in ("f", "vel", "rho"))
+    blocks = d["block"].astype(np.int64)
+    assert blocks.size == 512 and np.all(np.diff(blocks) > 0) and blocks[-1] < 9 ** 3
+    grids, params = cases.periodic_box((9, 9, 9))
+    oracle.execute_timestep_batch(grids, 1, 2 + steps, np.float32(0.0), params)
+    fn, vn = oracle.newest_buffers(0, 2 + steps)
+    for name, field in (("f", fn), ("vel", vn), ("rho", "rho")):
+        want = getattr(grids[0], field)[:, :, :, blocks]
+        assert d[name].shape == want.shape and np.array_equal(d[name], want), f"{name}: bench dump != oracle after {2 + steps} steps"
+
+
 def _run_bench(*argv, env=None, timeout=600):
     return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=timeout, cwd=ROOT,
                           env=dict(os.environ, **(env or {})))
