@@ -255,6 +255,22 @@ int  ludwig_level_rho_min(const LudwigLevel *level, float *rho_min);
  * (LUDWIG_EAGER_RHO=1 in the environment does it for every level), 0 lets the library elide again. Results never depend on it. */
 int  ludwig_level_set_rho_store(LudwigLevel *level, int every_step);
 
+/* ---- time-averaged statistics (no reference counterpart) ----
+ * Per cell of the blocks this device owns, in double precision: S_rho += rho, S_u[i] += u_i, S_uu[m] += u_i u_j (m = xx, yy, zz, xy,
+ * yz, xz: VTK's symmetric-tensor order). Each sum is a plain sequential addition in sample order, so a float64 replay on the host
+ * reproduces it bit for bit. The accumulators (80 B per cell) are allocated by the first reset; a level that never resets allocates
+ * and launches nothing. A level created with n_owned < 0 accepts every call and does nothing. */
+enum LudwigStat { LUDWIG_STAT_RHO = 0, LUDWIG_STAT_VEL = 1, LUDWIG_STAT_VEL2 = 2 };   /* K = 1, 3, 6 components */
+/* allocate on the first call, zero the sums, n = 0 (queued on the level's stream) */
+int  ludwig_level_stats_reset(LudwigLevel *level);
+/* add one sample: rho as ludwig_level_download(LUDWIG_RHO) would return it now (an elided store is replayed first) and the velocity
+ * buffer sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd). Queued on the level's stream, no host synchronisation.
+ * LUDWIG_ERR_STATE before the first reset. */
+int  ludwig_level_stats_accumulate(LudwigLevel *level, int64_t t_sub);
+/* the sums of one statistic in the reference layout [8,8,8,n_blocks,K] Float64, reference block order, ghost blocks zero; bytes =
+ * 4096 n_blocks K; *n_samples (may be NULL) = samples since the last reset. Synchronizes the stream. LUDWIG_ERR_STATE before the first reset. */
+int  ludwig_level_stats_download(const LudwigLevel *level, int stat, double *host, size_t bytes, int64_t *n_samples);
+
 /* ---- halo exchange helpers (no reference counterpart: the reference is single-device) ---- */
 /* dst[i] = field[index[i]] / field[index[i]] = src[i]; index, dst, src are DEVICE pointers, index holds element
  * offsets into the field in the reference layout. hip_stream: the stream to queue on (hipStream_t), NULL = the

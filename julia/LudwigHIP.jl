@@ -104,6 +104,21 @@ function rho_min(d::DeviceLevel)
     return v[]
 end
 
+# time-averaged statistics (no reference counterpart): double-precision sums of rho, u_i and u_i u_j over the owned cells
+const STAT_RHO, STAT_VEL, STAT_VEL2 = Int32(0), Int32(1), Int32(2)      # K = 1, 3, 6 (xx, yy, zz, xy, yz, xz)
+"""zero the sums (allocates them on the first call)"""
+stats_reset!(d::DeviceLevel) = check(ccall((:ludwig_level_stats_reset, LIB), Cint, (Ptr{Cvoid},), d.handle))
+"""add the newest state of the level after sub-step `timestep` (vel_temp if even, vel if odd; rho as stored)"""
+stats_accumulate!(d::DeviceLevel, timestep::Integer) =
+    check(ccall((:ludwig_level_stats_accumulate, LIB), Cint, (Ptr{Cvoid}, Int64), d.handle, Int64(timestep)))
+"""the sums of one statistic into a preallocated Array{Float64}(8,8,8,n_blocks,K); returns the number of samples"""
+function stats_download!(a::Array{Float64}, d::DeviceLevel, stat::Int32)
+    n = Ref{Int64}(0)
+    GC.@preserve a check(ccall((:ludwig_level_stats_download, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Csize_t, Ref{Int64}),
+                               d.handle, stat, pointer(a), sizeof(a), n))
+    return n[]
+end
+
 """
 Multi-GPU hosts only: a HIP stream for the stepping kernels that leaves `reserved_cus` compute units to the halo exchange
 (`ludwig_stream_create`, include/ludwig_hip.h); hand it to `ludwig_level_set_stream`. No counterpart in the reference.

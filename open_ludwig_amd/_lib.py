@@ -18,6 +18,9 @@ FIELD_NAMES = {
     "vel": VEL, "vel_temp": VEL_TEMP, "vel_old": VEL_OLD, "obstacle": OBSTACLE, "sponge": SPONGE,
     "wall_dist": WALL_DIST,
 }
+# enum LudwigStat: accumulated statistic -> (id, components)
+STAT_RHO, STAT_VEL, STAT_VEL2 = range(3)
+STAT_NAMES = {"rho": (STAT_RHO, 1), "vel": (STAT_VEL, 3), "vel2": (STAT_VEL2, 6)}
 # enum LudwigPart
 PART_ALL, PART_BOUNDARY, PART_INTERIOR = 0, 1, 2
 
@@ -34,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_halo_plan_create", "ludwig_halo_plan_destroy", "ludwig_halo_exchange", "ludwig_halo_wait",
     "ludwig_halo_plan_pack", "ludwig_halo_plan_unpack", "ludwig_halo_plan_buffers", "ludwig_halo_plan_timing", "ludwig_halo_plan_in_stream",
     "ludwig_halo_plan_exchange_ms", "ludwig_step_distributed",
+    "ludwig_level_stats_reset", "ludwig_level_stats_accumulate", "ludwig_level_stats_download",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -150,6 +154,9 @@ def load() -> C.CDLL:
         "ludwig_halo_plan_in_stream": (C.c_int, [vp, i32]),
         "ludwig_halo_plan_exchange_ms": (C.c_int, [vp, vp, i32, C.POINTER(C.c_int32)]),
         "ludwig_step_distributed": (C.c_int, [vp, vp, vp, i64, f32, f32, f32, C.POINTER(StepFlags)]),
+        "ludwig_level_stats_reset": (C.c_int, [vp]),
+        "ludwig_level_stats_accumulate": (C.c_int, [vp, i64]),
+        "ludwig_level_stats_download": (C.c_int, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

@@ -338,6 +338,25 @@ class DeviceLevel:
         _lib.check(self._lib.ludwig_level_rho_min(self.handle, C.byref(v)))
         return float(v.value)
 
+    # -- time-averaged statistics (no reference counterpart) --
+    def stats_reset(self) -> None:
+        """zero the device sums of rho, u_i, u_i u_j (allocated by the first call) and the sample count"""
+        _lib.check(self._lib.ludwig_level_stats_reset(self.handle))
+
+    def stats_accumulate(self, t_sub: int) -> None:
+        """add the newest state after sub-step t_sub (vel_temp if t_sub is even, vel if odd; rho as download('rho') gives it),
+        queued on the level's stream"""
+        _lib.check(self._lib.ludwig_level_stats_accumulate(self.handle, int(t_sub)))
+
+    def stats_download(self, stat: str) -> Tuple[np.ndarray, int]:
+        """('rho' | 'vel' | 'vel2') -> (Float64 sums [8,8,8,n_blocks(,K)] in the reference layout, samples); ghost blocks are 0"""
+        sid, k = _lib.STAT_NAMES[stat]
+        B = BLOCK_SIZE
+        a = np.empty((B, B, B, self.n_blocks) + ((k,) if k > 1 else ()), dtype=np.float64, order="F")
+        n = C.c_int64(0)
+        _lib.check(self._lib.ludwig_level_stats_download(self.handle, sid, a.ctypes.data if a.size else None, a.nbytes, C.byref(n)))
+        return a, int(n.value)
+
     def init_equilibrium(self) -> None:
         """init_eq! (src/main.jl:109-134)"""
         _lib.check(self._lib.ludwig_init_equilibrium(self.handle))

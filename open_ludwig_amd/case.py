@@ -17,6 +17,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from . import forces as forces_mod
+from . import statistics as stats_mod
 from .blocks import adapt
 from .preprocess import CaseConfig, DomainParameters, setup_multilevel_domain, solver_params
 from .solver_control import execute_timestep_batch, ramp_velocity
@@ -56,6 +57,26 @@ class HipStepper:
     def rho_min(self, level: int) -> float:
         """compute_flow_stats (src/diagnostics.jl:56-94), reduced on the device"""
         return self.dev[level].rho_min()
+
+    # -- time-averaged statistics (no reference counterpart) --
+    def stats_reset(self) -> None:
+        for d in self.dev:
+            d.stats_reset()
+
+    def stats_sample(self, t_coarse: int) -> None:
+        """add every level's newest state after coarse step t_coarse to its device sums (queued, no synchronisation)"""
+        for lvl, d in enumerate(self.dev):
+            d.stats_accumulate(stats_mod.t_sub_after(lvl, t_coarse))
+
+    def stats_sums(self, level: int):
+        """(S_rho, S_u, S_uu, n) of a level, Float64 in the reference layout"""
+        d = self.dev[level]
+        (r, n), (u, _), (uu, _) = (d.stats_download(k) for k in ("rho", "vel", "vel2"))
+        return r, u, uu, n
+
+    def statistics(self, level: int):
+        """finalised statistics of a level (statistics.finalize)"""
+        return stats_mod.finalize(*self.stats_sums(level))
 
     def close(self):
         for d in self.dev:
@@ -198,6 +219,45 @@ class DistributedStepper:
                 out[:, :, :, l2g] = a
         return out
 
+    # -- time-averaged statistics: every rank accumulates its owned blocks; results gathered like field() --
+    def _held(self):
+        return [(lvl, lv) for lvl, lv in enumerate(self.runner.levels) if lv is not None and self.runner.views[lvl].n_owned > 0]
+
+    def stats_reset(self) -> None:
+        for _, lv in self._held():
+            lv.stats_reset()
+
+    def stats_sample(self, t_coarse: int) -> None:
+        for lvl, lv in self._held():
+            lv.stats_accumulate(stats_mod.t_sub_after(lvl, t_coarse))
+
+    def stats_sums(self, level: int):
+        """(S_rho, S_u, S_uu, n) of the GLOBAL level, assembled on rank 0 (None elsewhere); collective"""
+        lv, view = self.runner.levels[level], self.runner.views[level]
+        mine = None
+        if lv is not None and view.n_owned > 0:
+            sums = [lv.stats_download(k) for k in ("rho", "vel", "vel2")]
+            mine = (view.local_to_global[: view.n_owned], [a[:, :, :, : view.n_owned] for a, _ in sums], sums[0][1])
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        if self.rank != 0:
+            return None
+        nb = self.host[level].n_blocks
+        out = [np.zeros((8, 8, 8, nb) + ((k,) if k > 1 else ()), dtype=np.float64, order="F") for k in (1, 3, 6)]
+        n = 0
+        for part in parts:
+            if part is None:
+                continue
+            l2g, arrs, n = part
+            for o, a in zip(out, arrs):
+                o[:, :, :, l2g] = a
+        return out[0], out[1], out[2], n
+
+    def statistics(self, level: int):
+        """finalised statistics of a level on rank 0 (None elsewhere); collective"""
+        sums = self.stats_sums(level)
+        return None if sums is None else stats_mod.finalize(*sums)
+
     def close(self):
         if self.runner is not None:
             self.runner.close()          # plans, communicator, levels; the views and plans stay readable (statistics)
@@ -229,7 +289,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     """solve_main (src/main.jl:54-249). Returns (rows, setup_report, params).
 
     out_dir: when given, the reference's result files are written there (row N4): convergence.csv and forces.csv at every
-    diagnostics step, flow_%06d.vtu (+ surface_%06d.vtu) every `output_freq` steps. Unlike the reference (main.jl:79) an
+    diagnostics step, flow_%06d.vtu (+ surface_%06d.vtu) every `output_freq` steps, and with cfg.statistics_enabled
+    flow_mean_%06d.vtu (the average over the samples so far, statistics.py) on those steps once a sample exists. Unlike the reference (main.jl:79) an
     existing directory is NOT emptied first. write_files=False on all ranks but one of a distributed run."""
     import time as _time
     from . import output as out_mod
@@ -250,12 +311,29 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     t0 = last_diag = _time.time()
     total_cells = sum(g.n_blocks * 512 for g in grids)
     fr = None
+    stats_on = bool(cfg.statistics_enabled)
+    stats_window = [0, 0, 0]             # samples, first and last sampled step
     try:
         while t <= total_steps:
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            st.batch(t, actual, u_curr, sp)
+            if stats_on:
+                # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
+                seg = t
+                for s_step in stats_mod.sample_steps(t, batch_end, cfg.statistics_start_step, cfg.statistics_interval):
+                    st.batch(seg, s_step - seg + 1, u_curr, sp)
+                    if s_step == cfg.statistics_start_step:
+                        st.stats_reset()
+                        stats_window = [0, s_step, s_step]
+                    st.stats_sample(s_step)
+                    stats_window[0] += 1
+                    stats_window[2] = s_step
+                    seg = s_step + 1
+                if seg <= batch_end:
+                    st.batch(seg, batch_end - seg + 1, u_curr, sp)
+            else:
+                st.batch(t, actual, u_curr, sp)
             if batch_end % cfg.diag_freq < actual or batch_end == total_steps:
                 diag_step = (batch_end // cfg.diag_freq) * cfg.diag_freq
                 if t <= diag_step <= batch_end:
@@ -304,6 +382,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         out_mod.export_merged_mesh(out_step, grids, fields, out_dir, cfg.output_fields)
                         if cfg.forces_enabled:
                             out_mod.save_surface_vtk(os.path.join(out_dir, "surface_%06d" % out_step), mesh, *fr.maps)
+                    if stats_on and stats_window[0] > 0:
+                        finals = {lvl: st.statistics(lvl) for lvl in sorted({l for l, _ in mesh_arrays_needed})}   # collective
+                        if writing:
+                            out_mod.export_mean_mesh(out_step, grids, finals.__getitem__, tuple(stats_window), out_dir)
             t = batch_end + 1
     finally:
         if hasattr(st, "close"):

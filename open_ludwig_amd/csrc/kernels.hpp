@@ -1062,6 +1062,34 @@ __global__ __launch_bounds__(256) void k_rho_min(const float *__restrict__ rho, 
     }
 }
 
+// ---- time-averaged statistics (ludwig_level_stats_*; no reference counterpart) ----
+// stats: [internal block][STAT_COMPONENTS][512] doubles - S_rho, S_u (x, y, z), S_uu (xx, yy, zz, xy, yz, xz: VTK's symmetric-tensor
+// order); rho: [block][512], vel: [block][3][512] floats (block-major). One workgroup per owned block, two x-consecutive cells per
+// lane: a wave covers two 8x8 planes of a component, 512 B of floats in and 1 KiB of doubles in and out, contiguous. Every sum is a
+// plain sequential addition per cell in sample order; a product of two floats is exact in double, so contraction cannot change a bit.
+constexpr int STAT_COMPONENTS = 10;
+__global__ __launch_bounds__(256) void k_accumulate_stats(double *__restrict__ stats, const float *__restrict__ rho,
+                                                          const float *__restrict__ vel)
+{
+    const int64_t b = blockIdx.x;
+    const int c = 2 * (int)threadIdx.x;
+    const float2 r = *(const float2 *)(rho + b * CELLS + c);
+    const float *v = vel + b * 3 * CELLS + c;
+    const float2 vx = *(const float2 *)v, vy = *(const float2 *)(v + CELLS), vz = *(const float2 *)(v + 2 * CELLS);
+    const double x0 = vx.x, x1 = vx.y, y0 = vy.x, y1 = vy.y, z0 = vz.x, z1 = vz.y;
+    const double add[STAT_COMPONENTS][2] = {{r.x, r.y}, {x0, x1}, {y0, y1}, {z0, z1}, {x0 * x0, x1 * x1}, {y0 * y0, y1 * y1},
+                                            {z0 * z0, z1 * z1}, {x0 * y0, x1 * y1}, {y0 * z0, y1 * z1}, {x0 * z0, x1 * z1}};
+    double *s = stats + b * STAT_COMPONENTS * CELLS + c;
+#pragma unroll
+    for (int m = 0; m < STAT_COMPONENTS; ++m) {
+        double2 *p = (double2 *)(s + m * CELLS);
+        double2 a = *p;
+        a.x += add[m][0];
+        a.y += add[m][1];
+        *p = a;
+    }
+}
+
 // ---- internal storage (ludwig_hip.hip "block order", "block-major"): the caller's arrays keep the reference's layout,
 // [8,8,8,n_blocks,K] with the reference's block order; the device arrays hold the blocks in the library's own order, block-major.
 // ref2int[b_reference] = b_internal (nullptr = same order) ----

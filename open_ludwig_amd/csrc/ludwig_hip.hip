@@ -180,6 +180,11 @@ struct LudwigLevel {
     int n_links[N_PARTS] = {};
     int n_sources[N_PARTS] = {};
     int iface_dims[3] = {-1, -1, -1};
+    // time-averaged statistics (ludwig_level_stats_*): [n_blocks][STAT_COMPONENTS][512] doubles in the internal block order, allocated
+    // by the first reset; only the owned blocks are ever accumulated, the ghost blocks stay zero
+    double *stats = nullptr;
+    bool stats_ready = false;           // reset has been called
+    int64_t stats_n = 0;                // samples accumulated since
 };
 
 namespace {
@@ -1046,6 +1051,7 @@ void ludwig_level_destroy(LudwigLevel *L)
         if (L->source_mac2[a]) (void)hipFree(L->source_mac2[a]);
     }
     if (L->f_iface) (void)hipFree(L->f_iface);
+    if (L->stats) (void)hipFree(L->stats);
     if (L->d_ref2int) (void)hipFree(L->d_ref2int);
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->own_stream) (void)hipStreamDestroy(L->own_stream);
@@ -1871,6 +1877,71 @@ int ludwig_level_rho_min(const LudwigLevel *L, float *rho_min)
     if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "rho_min: %s", hipGetErrorString(e));
     memcpy(rho_min, &res[0], sizeof(float));
     if (res[1]) *rho_min = __builtin_nanf("");            // minimum() of the reference propagates NaN (src/diagnostics.jl:71)
+    return LUDWIG_OK;
+}
+
+int ludwig_level_stats_reset(LudwigLevel *L)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    L->stats_ready = true;
+    L->stats_n = 0;
+    if (L->n_owned == 0) return LUDWIG_OK;           // no owned blocks: nothing to accumulate, nothing allocated
+    LW_HIP(hipSetDevice(L->device));
+    const size_t n = (size_t)L->n_blocks * STAT_COMPONENTS * CELLS;
+    if (!L->stats) {
+        const int r = dev_alloc(L, &L->stats, n);
+        if (r) { L->stats_ready = false; return r; }
+    }
+    LW_HIP(hipMemsetAsync(L->stats, 0, n * sizeof(double), L->stream));
+    return LUDWIG_OK;
+}
+
+int ludwig_level_stats_accumulate(LudwigLevel *L, int64_t t_sub)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    if (!L->stats_ready) return fail(LUDWIG_ERR_STATE, "statistics: accumulate before ludwig_level_stats_reset");
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "statistics: t_sub %lld < 0", (long long)t_sub);
+    if (L->n_owned == 0) return LUDWIG_OK;
+    LW_HIP(hipSetDevice(L->device));
+    {   // rho as ludwig_level_download(LUDWIG_RHO) would return it now: an elided store is replayed first, on the level's stream
+        const int r = ensure_rho(L);
+        if (r) return r;
+    }
+    const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];    // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+    hipLaunchKernelGGL(k_accumulate_stats, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->stats, L->rho, vel);
+    LW_HIP(hipGetLastError());
+    ++L->stats_n;
+    return LUDWIG_OK;
+}
+
+int ludwig_level_stats_download(const LudwigLevel *L, int stat, double *host, size_t bytes, int64_t *n_samples)
+{
+    if (!L || (!host && bytes > 0)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (stat < LUDWIG_STAT_RHO || stat > LUDWIG_STAT_VEL2) return fail(LUDWIG_ERR_INVALID, "bad statistic %d", stat);
+    if (!L->stats_ready) return fail(LUDWIG_ERR_STATE, "statistics: download before ludwig_level_stats_reset");
+    const int K = stat == LUDWIG_STAT_RHO ? 1 : stat == LUDWIG_STAT_VEL ? 3 : 6, first = stat == LUDWIG_STAT_RHO ? 0 : stat == LUDWIG_STAT_VEL ? 1 : 4;
+    const size_t plane = (size_t)L->sk * sizeof(double);
+    if (bytes != plane * K) return fail(LUDWIG_ERR_INVALID, "statistic %d: got %zu bytes, expected %zu", stat, bytes, plane * K);
+    if (n_samples) *n_samples = L->stats_n;
+    if (plane == 0) return LUDWIG_OK;
+    if (!L->stats) {                                  // no owned blocks: every block is a ghost
+        memset(host, 0, bytes);
+        return LUDWIG_OK;
+    }
+    LW_HIP(hipSetDevice(L->device));
+    double *tmp = nullptr;                            // one component in the reference order; a result-file call, allocated per call
+    LW_HIP(hipMalloc((void **)&tmp, plane));
+    hipError_t e = hipSuccess;
+    const int64_t n = L->sk;
+    for (int k = 0; k < K && e == hipSuccess; ++k) {
+        hipLaunchKernelGGL(k_component_to_reference<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L->stream, tmp,
+                           (const double *)L->stats, L->d_ref2int, n, STAT_COMPONENTS, first + k);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync((char *)host + (size_t)k * plane, tmp, plane, hipMemcpyDeviceToHost, L->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
+    }
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "statistics download: %s", hipGetErrorString(e));
     return LUDWIG_OK;
 }
 

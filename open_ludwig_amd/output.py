@@ -63,14 +63,22 @@ def _data_array(name: str, a: np.ndarray, compress: bool, ncomp: int = 1) -> str
 
 
 def write_vtu(filename: str, points: np.ndarray, connectivity: np.ndarray, offsets: np.ndarray, types: np.ndarray,
-              cell_data: Sequence[Tuple[str, np.ndarray]], compress: bool = True) -> str:
-    """points [n,3]; connectivity 0-based; cell_data: (name, [ncells] or [ncells, ncomp]). Returns the path written."""
+              cell_data: Sequence[Tuple[str, np.ndarray]], compress: bool = True,
+              field_data: Optional[Sequence[Tuple[str, np.ndarray]]] = None) -> str:
+    """points [n,3]; connectivity 0-based; cell_data: (name, [ncells] or [ncells, ncomp]). field_data: (name, 1-D array) of the
+    whole dataset (VTK FieldData, e.g. an averaging window); None writes no FieldData element. Returns the path written."""
     path = filename if filename.endswith(".vtu") else filename + ".vtu"
     comp_attr = ' compressor="vtkZLibDataCompressor"' if compress else ""
     with open(path, "w") as io:
         io.write('<?xml version="1.0" encoding="utf-8"?>\n')
         io.write(f'<VTKFile type="UnstructuredGrid" version="1.0" byte_order="LittleEndian" header_type="UInt64"{comp_attr}>\n')
         io.write("<UnstructuredGrid>\n")
+        if field_data is not None:
+            io.write("<FieldData>\n")
+            for name, v in field_data:
+                v = np.atleast_1d(v)
+                io.write(f'<DataArray type="{_VTK_TYPE[v.dtype]}" Name="{name}" NumberOfTuples="{v.size}" format="binary">{_encode(v, compress)}</DataArray>\n')
+            io.write("</FieldData>\n")
         io.write(f'<Piece NumberOfPoints="{points.shape[0]}" NumberOfCells="{types.shape[0]}">\n')
         io.write("<Points>\n" + _data_array("Points", points, compress, 3) + "</Points>\n")
         io.write("<Cells>\n")
@@ -110,49 +118,37 @@ def _scrub(a: np.ndarray) -> np.ndarray:
     return a
 
 
-def build_flow_mesh(t_step: int, grids, fields) -> Dict[str, np.ndarray]:
-    """The arrays of export_merged_mesh_sync before they hit the file. `grids`: host levels (active_block_coords, dx);
-    `fields(level_index, name)` returns the named array of that level ('rho', 'vel', 'vel_temp', 'obstacle')."""
+def _cells_of(a: np.ndarray, blocks: np.ndarray) -> np.ndarray:
+    """[8,8,8,nb(,K)] -> [len(blocks), 512(, K)] with the cell index x fastest; whole 512-cell chunks when the array is Fortran-ordered"""
+    n_cells = BLOCK_SIZE ** 3
+    if a.flags.f_contiguous:
+        nb = a.shape[3]
+        if a.ndim == 4:
+            return np.take(a.T.reshape(nb, n_cells), blocks, axis=0)
+        return np.take(a.T.reshape(a.shape[4], nb, n_cells), blocks, axis=1).transpose(1, 2, 0)
+    sub = a[:, :, :, blocks]
+    if a.ndim == 4:
+        return sub.reshape(n_cells, len(blocks), order="F").T
+    return sub.reshape(n_cells, len(blocks), a.shape[4], order="F").transpose(1, 0, 2)
+
+
+def _flow_geometry(grids, valid: List[Tuple[int, int]]) -> Dict[str, np.ndarray]:
+    """points, voxel connectivity, offsets, types and Level of the exported blocks `valid` (select_export_blocks), plus the
+    per-block level / block index arrays (lv_of, blk_of) the cell arrays are gathered by"""
     B = BLOCK_SIZE
-    valid = select_export_blocks([g.active_block_coords for g in grids])
     n_total = len(valid)
     n_pts, n_cells = (B + 1) ** 3, B ** 3
-    vel_name = "vel_temp" if t_step % 2 == 0 else "vel"
-    data = {}
-    for lvl in sorted({l for l, _ in valid}):
-        data[lvl] = (fields(lvl, "rho"), fields(lvl, vel_name), np.asarray(fields(lvl, "obstacle")).astype(bool), np.float32(grids[lvl].dx))
     points = np.empty((n_total, n_pts, 3), dtype=np.float32)
-    rho = np.empty((n_total, n_cells), dtype=np.float32)
-    vel = np.empty((n_total, n_cells, 3), dtype=np.float32)
-    obst = np.empty((n_total, n_cells), dtype=np.uint8)
     level = np.empty((n_total, n_cells), dtype=np.int32)
     pz, py, px = np.meshgrid(np.arange(B + 1), np.arange(B + 1), np.arange(B + 1), indexing="ij")      # px fastest
     pxyz = np.stack([px.reshape(-1), py.reshape(-1), pz.reshape(-1)], axis=1).astype(np.float32)
     lv_of = np.array([l for l, _ in valid], dtype=np.int64)
     blk_of = np.array([b for _, b in valid], dtype=np.int64)
-
-    def cells_of(a, blocks):
-        """[8,8,8,nb(,K)] -> [len(blocks), 512(, K)] with the cell index x fastest; whole 512-cell chunks when the array is Fortran-ordered"""
-        if a.flags.f_contiguous:
-            nb = a.shape[3]
-            if a.ndim == 4:
-                return np.take(a.T.reshape(nb, n_cells), blocks, axis=0)
-            return np.take(a.T.reshape(a.shape[4], nb, n_cells), blocks, axis=1).transpose(1, 2, 0)
-        sub = a[:, :, :, blocks]
-        if a.ndim == 4:
-            return sub.reshape(n_cells, len(blocks), order="F").T
-        return sub.reshape(n_cells, len(blocks), a.shape[4], order="F").transpose(1, 0, 2)
-
-    for lvl in sorted(data):                                         # a level at a time (the valid list is level-major, blocks ascending)
-        r, v, o, dx = data[lvl]
+    for lvl in sorted({l for l, _ in valid}):                        # a level at a time (the valid list is level-major, blocks ascending)
         rows = np.flatnonzero(lv_of == lvl)
-        blocks = blk_of[rows]
-        bc = np.asarray(grids[lvl].active_block_coords, dtype=np.int64)[blocks]
+        bc = np.asarray(grids[lvl].active_block_coords, dtype=np.int64)[blk_of[rows]]
         off = ((bc - 1) * B).astype(np.float32)
-        points[rows] = (off[:, None, :] + pxyz[None, :, :]) * dx      # (off + p) * dx in Float32, as the reference
-        rho[rows] = cells_of(r, blocks)                               # cell order x fastest
-        vel[rows] = cells_of(v, blocks)
-        obst[rows] = cells_of(o, blocks)
+        points[rows] = (off[:, None, :] + pxyz[None, :, :]) * np.float32(grids[lvl].dx)      # (off + p) * dx in Float32, as the reference
         level[rows] = lvl + 1
     z, y, x = np.meshgrid(np.arange(B), np.arange(B), np.arange(B), indexing="ij")
     sy, sz = B + 1, (B + 1) ** 2
@@ -160,14 +156,40 @@ def build_flow_mesh(t_step: int, grids, fields) -> Dict[str, np.ndarray]:
     corner = np.array([0, 1, sy, sy + 1, sz, sz + 1, sz + sy, sz + sy + 1])
     conn_block = base[:, None] + corner[None, :]                      # 0-based within the block's points
     conn = (conn_block[None, :, :] + (np.arange(n_total) * n_pts)[:, None, None]).reshape(-1)
-    vel = _scrub(vel.reshape(-1, 3))
     return {
         "points": points.reshape(-1, 3), "connectivity": np.asarray(conn, dtype=np.int64),
         "offsets": np.arange(8, 8 * (n_total * n_cells + 1), 8, dtype=np.int64),
         "types": np.full(n_total * n_cells, VTK_VOXEL, dtype=np.uint8),
-        "Density": _scrub(rho.reshape(-1)), "Velocity": vel,
+        "Level": level.reshape(-1), "lv_of": lv_of, "blk_of": blk_of,
+    }
+
+
+def _gather_cells(geo: Dict[str, np.ndarray], arrays_of_level, dtypes: Sequence, ncomps: Sequence[int]) -> List[np.ndarray]:
+    """cell arrays of the exported blocks: arrays_of_level(lvl) -> one [8,8,8,nb(,K)] array per output; [n_exported_cells(, K)] each"""
+    n_total, n_cells = geo["lv_of"].size, BLOCK_SIZE ** 3
+    outs = [np.empty((n_total, n_cells) + ((k,) if k > 1 else ()), dtype=dt) for dt, k in zip(dtypes, ncomps)]
+    for lvl in sorted(set(geo["lv_of"].tolist())):
+        rows = np.flatnonzero(geo["lv_of"] == lvl)
+        blocks = geo["blk_of"][rows]
+        for o, a in zip(outs, arrays_of_level(lvl)):
+            o[rows] = _cells_of(a, blocks)                            # cell order x fastest
+    return [o.reshape((n_total * n_cells,) + o.shape[2:]) for o in outs]
+
+
+def build_flow_mesh(t_step: int, grids, fields) -> Dict[str, np.ndarray]:
+    """The arrays of export_merged_mesh_sync before they hit the file. `grids`: host levels (active_block_coords, dx);
+    `fields(level_index, name)` returns the named array of that level ('rho', 'vel', 'vel_temp', 'obstacle')."""
+    valid = select_export_blocks([g.active_block_coords for g in grids])
+    vel_name = "vel_temp" if t_step % 2 == 0 else "vel"
+    geo = _flow_geometry(grids, valid)
+    rho, vel, obst = _gather_cells(geo, lambda lvl: (fields(lvl, "rho"), fields(lvl, vel_name), np.asarray(fields(lvl, "obstacle")).astype(bool)),
+                                   (np.float32, np.float32, np.uint8), (1, 3, 1))
+    vel = _scrub(vel)
+    return {
+        "points": geo["points"], "connectivity": geo["connectivity"], "offsets": geo["offsets"], "types": geo["types"],
+        "Density": _scrub(rho), "Velocity": vel,
         "VelocityMagnitude": np.sqrt(vel[:, 0] ** 2 + vel[:, 1] ** 2 + vel[:, 2] ** 2),
-        "Obstacle": obst.reshape(-1), "Level": level.reshape(-1),
+        "Obstacle": obst, "Level": geo["Level"],
     }
 
 
@@ -182,6 +204,28 @@ def export_merged_mesh(t_step: int, grids, fields, out_dir: str, output_fields: 
         return None
     cd = [(n, m[n]) for n in DEFAULT_FLOW_FIELDS if n in output_fields]
     return write_vtu(os.path.join(out_dir, "flow_%06d" % t_step), m["points"], m["connectivity"], m["offsets"], m["types"], cd, compress)
+
+
+def export_mean_mesh(t_step: int, grids, stats_of_level, window: Tuple[int, int, int], out_dir: str, compress: bool = True) -> Optional[str]:
+    """<out_dir>/flow_mean_%06d.vtu: the time-averaged flow (no reference counterpart) on the mesh of flow_%06d.vtu - same blocks
+    (select_export_blocks), points and cell order. stats_of_level(lvl) -> the finalised statistics of that level
+    (statistics.finalize: mean_rho, mean_u, reynolds_stress, tke; Float64 in the reference layout); window = (samples, first
+    step, last step), written as Int64 FieldData. Cell arrays Float32 except Obstacle (UInt8) and Level (Int32)."""
+    valid = select_export_blocks([g.active_block_coords for g in grids])
+    if not valid:
+        return None
+    geo = _flow_geometry(grids, valid)
+
+    def arrays(lvl):
+        st = stats_of_level(lvl)
+        return (st["mean_rho"].astype(np.float32), st["mean_u"].astype(np.float32), st["reynolds_stress"].astype(np.float32),
+                st["tke"].astype(np.float32), np.asarray(grids[lvl].obstacle).astype(bool))
+    rho, u, rs, k, obst = _gather_cells(geo, arrays, (np.float32,) * 4 + (np.uint8,), (1, 3, 6, 1, 1))
+    cd = [("MeanDensity", rho), ("MeanVelocity", u), ("ReynoldsStress", rs), ("TurbulentKineticEnergy", k),
+          ("Obstacle", obst), ("Level", geo["Level"])]
+    fd = [(name, np.array([v], dtype=np.int64)) for name, v in zip(("StatisticsSamples", "StatisticsFirstStep", "StatisticsLastStep"), window)]
+    return write_vtu(os.path.join(out_dir, "flow_mean_%06d" % t_step), geo["points"], geo["connectivity"], geo["offsets"], geo["types"],
+                     cd, compress, field_data=fd)
 
 
 # ----------------------------------------------------------------------------------------------------------------

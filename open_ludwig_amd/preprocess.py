@@ -94,6 +94,10 @@ class CaseConfig:
     async_depth: int = 8
     case_dir: str = ""
     output_fields: Tuple[str, ...] = ("Density", "Velocity", "VelocityMagnitude", "Obstacle", "Level")   # io_vtk.jl:116-120
+    # time-averaged statistics, advanced.statistics (no reference counterpart; its loader ignores the keys): flow_mean_%06d.vtu
+    statistics_enabled: bool = False
+    statistics_start_step: int = 1      # first sampled coarse step (the sums are reset there); YAML default: ramp_steps
+    statistics_interval: int = 10       # coarse steps between samples
 
     @property
     def reference_area_config(self) -> float:
@@ -116,6 +120,12 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         merge(cfg, overrides)
     f32 = np.float32
     g = lambda *k, **kw: _get(cfg, *k, **kw)
+    ramp_steps = int(g("basic", "simulation", "ramp_steps", required=True))
+    # averaging the ramp means nothing: sampling starts at ramp_steps unless told otherwise (at step 1 at the earliest)
+    stats_start = int(g("advanced", "statistics", "start_step", default=ramp_steps))
+    stats_interval = int(g("advanced", "statistics", "interval", default=10))
+    if stats_interval < 1:
+        raise ValueError(f"advanced.statistics.interval must be >= 1, got {stats_interval}")
     return CaseConfig(
         stl_file=g("basic", "stl_file", required=True), stl_scale=float(g("basic", "stl_scale", required=True)),
         surface_resolution=int(g("basic", "surface_resolution", required=True)), num_levels=int(g("basic", "num_levels", required=True)),
@@ -156,6 +166,8 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         output_fields=tuple(name for key, name in (("density", "Density"), ("velocity", "Velocity"), ("velocity_magnitude", "VelocityMagnitude"),
                                                    ("obstacle", "Obstacle"), ("level", "Level"))
                             if bool(g("basic", "simulation", "output_fields", key, default=True))),
+        statistics_enabled=bool(g("advanced", "statistics", "enabled", default=False)),
+        statistics_start_step=max(stats_start, 1), statistics_interval=stats_interval,
     )
 
 
