@@ -271,6 +271,21 @@ int  ludwig_level_stats_accumulate(LudwigLevel *level, int64_t t_sub);
  * 4096 n_blocks K; *n_samples (may be NULL) = samples since the last reset. Synchronizes the stream. LUDWIG_ERR_STATE before the first reset. */
 int  ludwig_level_stats_download(const LudwigLevel *level, int stat, double *host, size_t bytes, int64_t *n_samples);
 
+/* ---- velocity-gradient fields (no reference counterpart for the output; the gradient is compute_velocity_gradients,
+ * src/physics_utils.jl:44-82, the one WALE uses) ----
+ * Per cell of the blocks this device owns, from one velocity buffer u: g_ij = (0.5f (u_i(+e_j) - u_i(-e_j))) * scale with the
+ * neighbour value of get_velocity_neighbor (across a block face through the neighbour table; no block there: the cell's own
+ * value), vorticity = (g32 - g23, g13 - g31, g21 - g12) and Q = -0.5f (((g11 g11 + g22 g22) + g33 g33) + 2 ((g12 g21 + g13 g31)
+ * + g23 g32)), float32 in this order; obstacle cells 0. The output buffer (16 B per cell) is allocated by the first compute; a
+ * level that never computes allocates and launches nothing. A level created with n_owned < 0 accepts every call and does nothing. */
+enum LudwigGradField { LUDWIG_GRAD_VORTICITY = 0 /* K = 3 */, LUDWIG_GRAD_Q = 1 /* K = 1 */ };
+/* vel_field: LUDWIG_VEL or LUDWIG_VEL_TEMP; scale: finite, non-zero (1/dx for derivatives per unit length). Reads vel, obstacle and
+ * the neighbour table only; queued on the level's stream, no host synchronisation. */
+int  ludwig_level_gradient_fields_compute(LudwigLevel *level, int vel_field, float scale);
+/* the last computed field in the reference layout [8,8,8,n_blocks,K] Float32, reference block order, ghost blocks zero; bytes =
+ * 2048 n_blocks K. Synchronizes the stream. LUDWIG_ERR_STATE before the first compute. */
+int  ludwig_level_gradient_fields_download(const LudwigLevel *level, int which, float *host, size_t bytes);
+
 /* ---- halo exchange helpers (no reference counterpart: the reference is single-device) ---- */
 /* dst[i] = field[index[i]] / field[index[i]] = src[i]; index, dst, src are DEVICE pointers, index holds element
  * offsets into the field in the reference layout. hip_stream: the stream to queue on (hipStream_t), NULL = the

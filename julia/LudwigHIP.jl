@@ -119,6 +119,16 @@ function stats_download!(a::Array{Float64}, d::DeviceLevel, stat::Int32)
     return n[]
 end
 
+# velocity-gradient fields (no reference counterpart for the output; the gradient is compute_velocity_gradients, the one WALE uses)
+const GRAD_VORTICITY, GRAD_Q = Int32(0), Int32(1)                       # K = 3, 1
+"""vorticity and Q-criterion of the owned cells from `vel_field` (VEL or VEL_TEMP), derivatives times `scale` (1/dx)"""
+gradient_fields_compute!(d::DeviceLevel, vel_field::Integer, scale::Real) =
+    check(ccall((:ludwig_level_gradient_fields_compute, LIB), Cint, (Ptr{Cvoid}, Cint, Cfloat), d.handle, Cint(vel_field), Float32(scale)))
+"""the last computed field into a preallocated Array{Float32}(8,8,8,n_blocks,K) (K = 3 for GRAD_VORTICITY, 1 for GRAD_Q)"""
+gradient_fields_download!(a::Array{Float32}, d::DeviceLevel, which::Int32) =
+    GC.@preserve a check(ccall((:ludwig_level_gradient_fields_download, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Csize_t),
+                               d.handle, which, pointer(a), sizeof(a)))
+
 """
 Multi-GPU hosts only: a HIP stream for the stepping kernels that leaves `reserved_cus` compute units to the halo exchange
 (`ludwig_stream_create`, include/ludwig_hip.h); hand it to `ludwig_level_set_stream`. No counterpart in the reference.

@@ -21,6 +21,9 @@ FIELD_NAMES = {
 # enum LudwigStat: accumulated statistic -> (id, components)
 STAT_RHO, STAT_VEL, STAT_VEL2 = range(3)
 STAT_NAMES = {"rho": (STAT_RHO, 1), "vel": (STAT_VEL, 3), "vel2": (STAT_VEL2, 6)}
+# enum LudwigGradField: velocity-gradient field -> (id, components)
+GRAD_VORTICITY, GRAD_Q = range(2)
+GRAD_NAMES = {"vorticity": (GRAD_VORTICITY, 3), "q": (GRAD_Q, 1)}
 # enum LudwigPart
 PART_ALL, PART_BOUNDARY, PART_INTERIOR = 0, 1, 2
 
@@ -38,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_halo_plan_pack", "ludwig_halo_plan_unpack", "ludwig_halo_plan_buffers", "ludwig_halo_plan_timing", "ludwig_halo_plan_in_stream",
     "ludwig_halo_plan_exchange_ms", "ludwig_step_distributed",
     "ludwig_level_stats_reset", "ludwig_level_stats_accumulate", "ludwig_level_stats_download",
+    "ludwig_level_gradient_fields_compute", "ludwig_level_gradient_fields_download",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -157,6 +161,8 @@ def load() -> C.CDLL:
         "ludwig_level_stats_reset": (C.c_int, [vp]),
         "ludwig_level_stats_accumulate": (C.c_int, [vp, i64]),
         "ludwig_level_stats_download": (C.c_int, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int64)]),
+        "ludwig_level_gradient_fields_compute": (C.c_int, [vp, i32, f32]),
+        "ludwig_level_gradient_fields_download": (C.c_int, [vp, i32, vp, C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

@@ -357,6 +357,22 @@ class DeviceLevel:
         _lib.check(self._lib.ludwig_level_stats_download(self.handle, sid, a.ctypes.data if a.size else None, a.nbytes, C.byref(n)))
         return a, int(n.value)
 
+    # -- velocity-gradient fields (no reference counterpart for the output; the gradient is the WALE one) --
+    def gradient_fields(self, vel_name: str, scale) -> Tuple[np.ndarray, np.ndarray]:
+        """vorticity [8,8,8,n_blocks,3] and Q-criterion [8,8,8,n_blocks] (Float32, reference layout, ghost blocks 0) of the owned
+        cells, from the velocity buffer `vel_name` ('vel' | 'vel_temp') with derivatives times `scale` (float32, e.g. 1/dx)"""
+        if vel_name not in ("vel", "vel_temp"):
+            raise ValueError(f"gradient fields: vel_name must be 'vel' or 'vel_temp', got {vel_name!r}")
+        _lib.check(self._lib.ludwig_level_gradient_fields_compute(self.handle, _lib.FIELD_NAMES[vel_name], float(np.float32(scale))))
+        B = BLOCK_SIZE
+        out = []
+        for name in ("vorticity", "q"):
+            gid, k = _lib.GRAD_NAMES[name]
+            a = np.empty((B, B, B, self.n_blocks) + ((k,) if k > 1 else ()), dtype=np.float32, order="F")
+            _lib.check(self._lib.ludwig_level_gradient_fields_download(self.handle, gid, a.ctypes.data if a.size else None, a.nbytes))
+            out.append(a)
+        return out[0], out[1]
+
     def init_equilibrium(self) -> None:
         """init_eq! (src/main.jl:109-134)"""
         _lib.check(self._lib.ludwig_init_equilibrium(self.handle))

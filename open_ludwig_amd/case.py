@@ -78,6 +78,11 @@ class HipStepper:
         """finalised statistics of a level (statistics.finalize)"""
         return stats_mod.finalize(*self.stats_sums(level))
 
+    # -- velocity-gradient fields (no reference counterpart for the output) --
+    def gradient_fields(self, level: int, vel_name: str, scale):
+        """(vorticity [8,8,8,nb,3], Q [8,8,8,nb]) of a level from its `vel_name` buffer, derivatives times `scale` (Float32)"""
+        return self.dev[level].gradient_fields(vel_name, scale)
+
     def close(self):
         for d in self.dev:
             d.close()
@@ -258,6 +263,29 @@ class DistributedStepper:
         sums = self.stats_sums(level)
         return None if sums is None else stats_mod.finalize(*sums)
 
+    # -- velocity-gradient fields: every rank computes on its owned blocks after batch() (its 'vel' halo ghosts are current for
+    # both buffers: each level step exchanges the buffer it wrote, and nothing writes that buffer again before the next such step) --
+    def gradient_fields(self, level: int, vel_name: str, scale):
+        """(vorticity, Q) of the GLOBAL level, assembled on rank 0 (None elsewhere); collective"""
+        lv, view = self.runner.levels[level], self.runner.views[level]
+        mine = None
+        if lv is not None and view.n_owned > 0:
+            w, q = lv.gradient_fields(vel_name, scale)
+            mine = (view.local_to_global[: view.n_owned], w[:, :, :, : view.n_owned], q[:, :, :, : view.n_owned])
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        if self.rank != 0:
+            return None
+        nb = self.host[level].n_blocks
+        w_all = np.zeros((8, 8, 8, nb, 3), dtype=np.float32, order="F")
+        q_all = np.zeros((8, 8, 8, nb), dtype=np.float32, order="F")
+        for part in parts:
+            if part is not None:
+                l2g, w, q = part
+                w_all[:, :, :, l2g] = w
+                q_all[:, :, :, l2g] = q
+        return w_all, q_all
+
     def close(self):
         if self.runner is not None:
             self.runner.close()          # plans, communicator, levels; the views and plans stay readable (statistics)
@@ -290,7 +318,9 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
 
     out_dir: when given, the reference's result files are written there (row N4): convergence.csv and forces.csv at every
     diagnostics step, flow_%06d.vtu (+ surface_%06d.vtu) every `output_freq` steps, and with cfg.statistics_enabled
-    flow_mean_%06d.vtu (the average over the samples so far, statistics.py) on those steps once a sample exists. Unlike the reference (main.jl:79) an
+    flow_mean_%06d.vtu (the average over the samples so far, statistics.py) on those steps once a sample exists; "Vorticity" /
+    "QCriterion" in cfg.output_fields add those arrays to the flow file, computed on the device from the file's velocity buffer with
+    derivatives per unit length of the file's coordinates (scale 1/dx). Unlike the reference (main.jl:79) an
     existing directory is NOT emptied first. write_files=False on all ranks but one of a distributed run."""
     import time as _time
     from . import output as out_mod
@@ -313,6 +343,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     fr = None
     stats_on = bool(cfg.statistics_enabled)
     stats_window = [0, 0, 0]             # samples, first and last sampled step
+    # derived flow arrays on output steps: (VTU name, index into gradient_fields' result, components)
+    grad_names = [g for g in (("Vorticity", 0, 3), ("QCriterion", 1, 1)) if g[0] in cfg.output_fields]
     try:
         while t <= total_steps:
             batch_end = min(t + batch - 1, total_steps)
@@ -376,10 +408,16 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     vel_name = "vel_temp" if out_step % 2 == 0 else "vel"
                     for lvl in sorted({l for l, _ in mesh_arrays_needed}):
                         fields(lvl, "rho"); fields(lvl, vel_name)
+                    derived = None
+                    if grad_names:
+                        # the buffer the file's Velocity comes from, derivatives per unit length of the file's coordinates
+                        grad = {lvl: st.gradient_fields(lvl, vel_name, np.float32(1.0 / grids[lvl].dx))      # collective
+                                for lvl in sorted({l for l, _ in mesh_arrays_needed})}
+                        derived = [(name, (lambda lvl, k=k: grad[lvl][k]), ncomp) for name, k, ncomp in grad_names]
                     if cfg.forces_enabled and (fr is None or fr.maps is None or out_step != (out_step // cfg.diag_freq) * cfg.diag_freq):
                         fr = _aerodynamics(st, grids, mesh, params, cfg.symmetric_analysis, want_maps=True)
                     if writing:
-                        out_mod.export_merged_mesh(out_step, grids, fields, out_dir, cfg.output_fields)
+                        out_mod.export_merged_mesh(out_step, grids, fields, out_dir, cfg.output_fields, derived=derived)
                         if cfg.forces_enabled:
                             out_mod.save_surface_vtk(os.path.join(out_dir, "surface_%06d" % out_step), mesh, *fr.maps)
                     if stats_on and stats_window[0] > 0:

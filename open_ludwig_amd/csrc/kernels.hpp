@@ -1090,6 +1090,90 @@ __global__ __launch_bounds__(256) void k_accumulate_stats(double *__restrict__ s
     }
 }
 
+// ---- velocity-gradient fields (ludwig_level_gradient_fields_*; the gradient is compute_velocity_gradients, reference
+// src/physics_utils.jl:44-82, the one the WALE model uses) ----
+// out: [internal block][GRAD_COMPONENTS][512] floats - vorticity x, y, z and Q; vel: [block][3][512]; obstacle: [block][512].
+// One workgroup per owned block. The block and a one-cell face halo of every component are staged in LDS, [3][10][10][10] floats
+// (12 KB): a face neighbour block that exists gives its adjacent layer, a missing one (meta entry -1: domain edge, level boundary)
+// the block's own edge layer, which is get_velocity_neighbor's own-value rule. Then two x-consecutive cells per lane, float2 stores.
+// g_ij = du_i/dx_j = (0.5 (u_i(+e_j) - u_i(-e_j))) scale, the WALE expression times one multiply; vorticity = (g32 - g23,
+// g13 - g31, g21 - g12), Q = -0.5 (((g11^2 + g22^2) + g33^2) + 2 ((g12 g21 + g13 g31) + g23 g32)) = (|Omega|^2 - |S|^2) / 2,
+// in exactly this order (-ffp-contract=off: a float32 restatement reproduces every bit). Obstacle cells get 0.
+constexpr int GRAD_COMPONENTS = 4;
+constexpr int GRAD_TILE = 10;                                   // 8 cells + one halo layer on each side
+constexpr int GRAD_HALO = 6 * 3 * 64;                           // faces x components x cells of a face layer
+__global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restrict__ out, const float *__restrict__ vel,
+                                                                  const uint8_t *__restrict__ obstacle,
+                                                                  const int32_t *__restrict__ meta, float scale)
+{
+    constexpr int T = GRAD_TILE, T2 = GRAD_TILE * GRAD_TILE, T3 = T2 * GRAD_TILE;
+    __shared__ float u[3 * T3];
+    const int64_t b = blockIdx.x;
+    const int t = (int)threadIdx.x;
+    const int c = 2 * t, x = c & 7, y = (c >> 3) & 7, z = c >> 6;
+    const int at = (x + 1) + T * (y + 1) + T2 * (z + 1);
+    const float *vb = vel + b * 3 * CELLS;
+    float2 own[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) own[k] = *(const float2 *)(vb + k * CELLS + c);
+    // face layers: element i = (face * 3 + component) * 64 + cell of the face; 64 consecutive i are one wave, so face and component
+    // are wave-uniform and the neighbour id is a scalar load. Faces: -x, +x, -y, +y, -z, +z.
+    float h[5];
+    int hat[5];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        const int i = t + 256 * r;
+        hat[r] = -1;
+        h[r] = 0.0f;
+        if (i < GRAD_HALO) {
+            const int g = __builtin_amdgcn_readfirstlane(i >> 6);
+            const int face = g / 3, k = g - 3 * face, axis = face >> 1, up = face & 1;
+            const int p = i & 7, q = (i >> 3) & 7;
+            const int step = axis == 0 ? 1 : (axis == 1 ? 3 : 9);
+            const int nb = meta[b * NBR_STRIDE + 13 + (up ? step : -step)];
+            const int src = nb >= 0 ? (up ? 0 : 7) : (up ? 7 : 0);   // the neighbour's adjacent layer, or the block's own edge layer
+            const int dst = up ? T - 1 : 0;
+            int sx, sy, sz, lx, ly, lz;
+            if (axis == 0) { sx = src; sy = p; sz = q; lx = dst; ly = p + 1; lz = q + 1; }
+            else if (axis == 1) { sx = p; sy = src; sz = q; lx = p + 1; ly = dst; lz = q + 1; }
+            else { sx = p; sy = q; sz = src; lx = p + 1; ly = q + 1; lz = dst; }
+            const int64_t sb = nb >= 0 ? (int64_t)nb : b;
+            h[r] = vel[(sb * 3 + k) * CELLS + sx + 8 * sy + 64 * sz];
+            hat[r] = k * T3 + lx + T * ly + T2 * lz;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        u[k * T3 + at] = own[k].x;
+        u[k * T3 + at + 1] = own[k].y;
+    }
+#pragma unroll
+    for (int r = 0; r < 5; ++r)
+        if (hat[r] >= 0) u[hat[r]] = h[r];
+    const uint8_t ob0 = obstacle[b * CELLS + c], ob1 = obstacle[b * CELLS + c + 1];
+    __syncthreads();
+    float res[GRAD_COMPONENTS][2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int a = at + s;
+        const float *ux = u, *uy = u + T3, *uz = u + 2 * T3;
+        const float g11 = (0.5f * (ux[a + 1] - ux[a - 1])) * scale, g12 = (0.5f * (ux[a + T] - ux[a - T])) * scale;
+        const float g13 = (0.5f * (ux[a + T2] - ux[a - T2])) * scale;
+        const float g21 = (0.5f * (uy[a + 1] - uy[a - 1])) * scale, g22 = (0.5f * (uy[a + T] - uy[a - T])) * scale;
+        const float g23 = (0.5f * (uy[a + T2] - uy[a - T2])) * scale;
+        const float g31 = (0.5f * (uz[a + 1] - uz[a - 1])) * scale, g32 = (0.5f * (uz[a + T] - uz[a - T])) * scale;
+        const float g33 = (0.5f * (uz[a + T2] - uz[a - T2])) * scale;
+        const bool solid = (s == 0 ? ob0 : ob1) != 0;
+        res[0][s] = solid ? 0.0f : g32 - g23;
+        res[1][s] = solid ? 0.0f : g13 - g31;
+        res[2][s] = solid ? 0.0f : g21 - g12;
+        res[3][s] = solid ? 0.0f : -0.5f * (((g11 * g11 + g22 * g22) + g33 * g33) + 2.0f * ((g12 * g21 + g13 * g31) + g23 * g32));
+    }
+    float *o = out + b * GRAD_COMPONENTS * CELLS + c;
+#pragma unroll
+    for (int m = 0; m < GRAD_COMPONENTS; ++m) *(float2 *)(o + m * CELLS) = make_float2(res[m][0], res[m][1]);
+}
+
 // ---- internal storage (ludwig_hip.hip "block order", "block-major"): the caller's arrays keep the reference's layout,
 // [8,8,8,n_blocks,K] with the reference's block order; the device arrays hold the blocks in the library's own order, block-major.
 // ref2int[b_reference] = b_internal (nullptr = same order) ----

@@ -185,6 +185,10 @@ struct LudwigLevel {
     double *stats = nullptr;
     bool stats_ready = false;           // reset has been called
     int64_t stats_n = 0;                // samples accumulated since
+    // velocity-gradient fields (ludwig_level_gradient_fields_*): [n_blocks][GRAD_COMPONENTS][512] floats in the internal block order,
+    // allocated (and zeroed) by the first compute; only the owned blocks are ever written, the ghost blocks stay zero
+    float *grad = nullptr;
+    bool grad_ready = false;            // compute has been called
 };
 
 namespace {
@@ -1052,6 +1056,7 @@ void ludwig_level_destroy(LudwigLevel *L)
     }
     if (L->f_iface) (void)hipFree(L->f_iface);
     if (L->stats) (void)hipFree(L->stats);
+    if (L->grad) (void)hipFree(L->grad);
     if (L->d_ref2int) (void)hipFree(L->d_ref2int);
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->own_stream) (void)hipStreamDestroy(L->own_stream);
@@ -1942,6 +1947,59 @@ int ludwig_level_stats_download(const LudwigLevel *L, int stat, double *host, si
     }
     (void)hipFree(tmp);
     if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "statistics download: %s", hipGetErrorString(e));
+    return LUDWIG_OK;
+}
+
+int ludwig_level_gradient_fields_compute(LudwigLevel *L, int vel_field, float scale)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    if (vel_field != LUDWIG_VEL && vel_field != LUDWIG_VEL_TEMP) return fail(LUDWIG_ERR_INVALID, "vel_field must be LUDWIG_VEL or LUDWIG_VEL_TEMP");
+    if (!std::isfinite(scale) || scale == 0.0f) return fail(LUDWIG_ERR_INVALID, "gradient fields: scale %g must be finite and non-zero", (double)scale);
+    if (L->n_owned == 0) {                            // no owned blocks: nothing to compute, nothing allocated
+        L->grad_ready = true;
+        return LUDWIG_OK;
+    }
+    LW_HIP(hipSetDevice(L->device));
+    if (!L->grad) {
+        const size_t n = (size_t)L->n_blocks * GRAD_COMPONENTS * CELLS;
+        const int r = dev_alloc(L, &L->grad, n);
+        if (r) return r;
+        LW_HIP(hipMemsetAsync(L->grad, 0, n * sizeof(float), L->stream));   // the ghost blocks are never written
+    }
+    hipLaunchKernelGGL(k_velocity_gradient_fields, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->grad,
+                       (const float *)L->vel[vel_field == LUDWIG_VEL ? 0 : 1], (const uint8_t *)L->obstacle, (const int32_t *)L->meta, scale);
+    LW_HIP(hipGetLastError());
+    L->grad_ready = true;
+    return LUDWIG_OK;
+}
+
+int ludwig_level_gradient_fields_download(const LudwigLevel *L, int which, float *host, size_t bytes)
+{
+    if (!L || (!host && bytes > 0)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (which != LUDWIG_GRAD_VORTICITY && which != LUDWIG_GRAD_Q) return fail(LUDWIG_ERR_INVALID, "bad gradient field %d", which);
+    if (!L->grad_ready) return fail(LUDWIG_ERR_STATE, "gradient fields: download before ludwig_level_gradient_fields_compute");
+    const int K = which == LUDWIG_GRAD_VORTICITY ? 3 : 1, first = which == LUDWIG_GRAD_VORTICITY ? 0 : 3;
+    const size_t plane = (size_t)L->sk * sizeof(float);
+    if (bytes != plane * K) return fail(LUDWIG_ERR_INVALID, "gradient field %d: got %zu bytes, expected %zu", which, bytes, plane * K);
+    if (plane == 0) return LUDWIG_OK;
+    if (!L->grad) {                                   // no owned blocks: every block is a ghost
+        memset(host, 0, bytes);
+        return LUDWIG_OK;
+    }
+    LW_HIP(hipSetDevice(L->device));
+    float *tmp = nullptr;                             // one component in the reference order; a result-file call, allocated per call
+    LW_HIP(hipMalloc((void **)&tmp, plane));
+    hipError_t e = hipSuccess;
+    const int64_t n = L->sk;
+    for (int k = 0; k < K && e == hipSuccess; ++k) {
+        hipLaunchKernelGGL(k_component_to_reference<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L->stream, tmp,
+                           (const float *)L->grad, L->d_ref2int, n, GRAD_COMPONENTS, first + k);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync((char *)host + (size_t)k * plane, tmp, plane, hipMemcpyDeviceToHost, L->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
+    }
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "gradient fields download: %s", hipGetErrorString(e));
     return LUDWIG_OK;
 }
 

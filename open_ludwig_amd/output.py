@@ -13,7 +13,7 @@ from __future__ import annotations
 import base64
 import os
 import zlib
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -176,33 +176,40 @@ def _gather_cells(geo: Dict[str, np.ndarray], arrays_of_level, dtypes: Sequence,
     return [o.reshape((n_total * n_cells,) + o.shape[2:]) for o in outs]
 
 
-def build_flow_mesh(t_step: int, grids, fields) -> Dict[str, np.ndarray]:
+def build_flow_mesh(t_step: int, grids, fields, derived: Optional[Sequence[Tuple[str, Callable, int]]] = None) -> Dict[str, np.ndarray]:
     """The arrays of export_merged_mesh_sync before they hit the file. `grids`: host levels (active_block_coords, dx);
-    `fields(level_index, name)` returns the named array of that level ('rho', 'vel', 'vel_temp', 'obstacle')."""
+    `fields(level_index, name)` returns the named array of that level ('rho', 'vel', 'vel_temp', 'obstacle').
+    derived: optional extra cell arrays (no reference counterpart), (name, array_of_level, components) with array_of_level(lvl) ->
+    Float32 [8,8,8,nb(,K)]; gathered on the same blocks and cell order, NaN / Inf scrubbed, returned under `name`."""
     valid = select_export_blocks([g.active_block_coords for g in grids])
     vel_name = "vel_temp" if t_step % 2 == 0 else "vel"
     geo = _flow_geometry(grids, valid)
     rho, vel, obst = _gather_cells(geo, lambda lvl: (fields(lvl, "rho"), fields(lvl, vel_name), np.asarray(fields(lvl, "obstacle")).astype(bool)),
                                    (np.float32, np.float32, np.uint8), (1, 3, 1))
     vel = _scrub(vel)
-    return {
+    m = {
         "points": geo["points"], "connectivity": geo["connectivity"], "offsets": geo["offsets"], "types": geo["types"],
         "Density": _scrub(rho), "Velocity": vel,
         "VelocityMagnitude": np.sqrt(vel[:, 0] ** 2 + vel[:, 1] ** 2 + vel[:, 2] ** 2),
         "Obstacle": obst, "Level": geo["Level"],
     }
+    for name, array_of_level, k in derived or ():
+        m[name] = _scrub(_gather_cells(geo, lambda lvl: (array_of_level(lvl),), (np.float32,), (k,))[0])
+    return m
 
 
 DEFAULT_FLOW_FIELDS = ("Density", "Velocity", "VelocityMagnitude", "Obstacle", "Level")
 
 
 def export_merged_mesh(t_step: int, grids, fields, out_dir: str, output_fields: Sequence[str] = DEFAULT_FLOW_FIELDS,
-                       compress: bool = True) -> Optional[str]:
-    """export_merged_mesh_sync (src/io_vtk.jl:13-129): writes <out_dir>/flow_%06d.vtu; None when nothing to export."""
-    m = build_flow_mesh(t_step, grids, fields)
+                       compress: bool = True, derived: Optional[Sequence[Tuple[str, Callable, int]]] = None) -> Optional[str]:
+    """export_merged_mesh_sync (src/io_vtk.jl:13-129): writes <out_dir>/flow_%06d.vtu; None when nothing to export.
+    derived (build_flow_mesh; e.g. Vorticity, QCriterion): written after the reference's arrays, in the order given. Without it the
+    file is the reference's arrays alone."""
+    m = build_flow_mesh(t_step, grids, fields, derived)
     if m["types"].size == 0:
         return None
-    cd = [(n, m[n]) for n in DEFAULT_FLOW_FIELDS if n in output_fields]
+    cd = [(n, m[n]) for n in DEFAULT_FLOW_FIELDS if n in output_fields] + [(n, m[n]) for n, _, _ in derived or ()]
     return write_vtu(os.path.join(out_dir, "flow_%06d" % t_step), m["points"], m["connectivity"], m["offsets"], m["types"], cd, compress)
 
 

@@ -162,10 +162,14 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         moment_center=tuple(float(v) for v in g("advanced", "forces", "moment_center", default=[0.25, 0.0, 0.0])),
         diag_freq=int(g("advanced", "diagnostics", "freq", default=500)), async_depth=int(g("advanced", "gpu", "async_depth", default=8)),
         case_dir=os.path.dirname(os.path.abspath(config_path)),
-        # vorticity / bouzidi are read by the reference's loader (config_loader.jl:145,148) but never written by io_vtk.jl
+        # bouzidi is read by the reference's loader (config_loader.jl:148) but never written by io_vtk.jl. vorticity (the reference's
+        # loader defaults it to true, config_loader.jl:145, and never writes it) and q_criterion (not a reference key) add device-computed
+        # arrays to the flow file; both default to FALSE here, because the reference writes neither and every shipped config says false.
         output_fields=tuple(name for key, name in (("density", "Density"), ("velocity", "Velocity"), ("velocity_magnitude", "VelocityMagnitude"),
                                                    ("obstacle", "Obstacle"), ("level", "Level"))
-                            if bool(g("basic", "simulation", "output_fields", key, default=True))),
+                            if bool(g("basic", "simulation", "output_fields", key, default=True)))
+                      + tuple(name for key, name in (("vorticity", "Vorticity"), ("q_criterion", "QCriterion"))
+                              if bool(g("basic", "simulation", "output_fields", key, default=False))),
         statistics_enabled=bool(g("advanced", "statistics", "enabled", default=False)),
         statistics_start_step=max(stats_start, 1), statistics_interval=stats_interval,
     )
