@@ -286,6 +286,37 @@ int  ludwig_level_gradient_fields_compute(LudwigLevel *level, int vel_field, flo
  * 2048 n_blocks K. Synchronizes the stream. LUDWIG_ERR_STATE before the first compute. */
 int  ludwig_level_gradient_fields_download(const LudwigLevel *level, int which, float *host, size_t bytes);
 
+/* ---- probes: time series of rho and u at points (no reference counterpart) ----
+ * A probe set is made over a level array (the batch's). Probe p lives on level level_index[p] (0-based) and has 8 stencil corners
+ * c = dx + 2 dy + 4 dz: (reference block index blocks[8p + c], cell cells[8p + c] = x + 8 y + 64 z) - the caller has replaced every
+ * corner that is no fluid cell of the level by the base cell - and the weights weights[3p + 0..2] along x, y, z in [0, 1]. A sample
+ * of a probe is rho, ux, uy, uz of the level's newest state, trilinear in float32 in one fixed order: x first (corners 0-1, 2-3,
+ * 4-5, 6-7), then y, then z, each lerp (1 - w) a + w b. Samples go to a device ring [capacity][n_probes][4] float32, one slot per
+ * sampled coarse step. Creating the set makes every probed level store rho after every step (+4 of 216 B per cell where a level
+ * elided that store); destroying the set leaves that setting as it is (ludwig_level_set_rho_store(level, 0) undoes it). Entries of
+ * `levels` no probe refers to may be null. A probed level may hold at most 2^31 / 512 blocks (32-bit cell indices). */
+typedef struct LudwigProbes LudwigProbes;   /* opaque */
+int  ludwig_probes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_probes, const int32_t *level_index,
+                          const int32_t *blocks, const int32_t *cells, const float *weights, int32_t capacity, LudwigProbes **out);
+/* frees the set, not the levels; it does not touch them, so it may come before or after their destruction */
+void ludwig_probes_destroy(LudwigProbes *probes);
+/* sample the probes of level level_index after its sub-step t_sub (vel_temp if t_sub is even, vel if odd; rho as a download would
+ * return it: an elided store is replayed first), queued on the level's stream. The slot is that of coarse step t_sub >> level_index:
+ * the newest slot if it is for that step and this level has not written it, else a new one (its other probes NaN until written).
+ * All probed levels must be on one stream here (the NaN fill and the writes of every level are ordered by it): LUDWIG_ERR_STATE
+ * otherwise, and when the ring is full. */
+int  ludwig_probes_sample(LudwigProbes *probes, int32_t level_index, int64_t t_sub);
+/* the samples taken since the last download, oldest first: values [n][n_probes][4], steps [n] (coarse steps); *n_samples = n.
+ * Synchronizes the streams of the probed levels, then empties the ring. LUDWIG_ERR_INVALID when n > max_samples. */
+int  ludwig_probes_download(LudwigProbes *probes, float *values, int64_t *steps, int32_t max_samples, int32_t *n_samples);
+/* ludwig_execute_timestep_batch with the probes sampled inside the batch: at coarse steps start_step + k interval (k >= 0), one
+ * launch per probed level on that level's own stream, right after its last sub-step of the coarse step. probes = NULL is
+ * ludwig_execute_timestep_batch itself. Fails before stepping anything with LUDWIG_ERR_STATE if the batch's samples would overflow
+ * the free ring, with LUDWIG_ERR_INVALID if the set was made over other levels or interval < 1. */
+int  ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
+                                          float u_curr, const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step,
+                                          int32_t interval);
+
 /* ---- halo exchange helpers (no reference counterpart: the reference is single-device) ---- */
 /* dst[i] = field[index[i]] / field[index[i]] = src[i]; index, dst, src are DEVICE pointers, index holds element
  * offsets into the field in the reference layout. hip_stream: the stream to queue on (hipStream_t), NULL = the

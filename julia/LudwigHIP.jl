@@ -129,6 +129,31 @@ gradient_fields_download!(a::Array{Float32}, d::DeviceLevel, which::Int32) =
     GC.@preserve a check(ccall((:ludwig_level_gradient_fields_download, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Csize_t),
                                d.handle, which, pointer(a), sizeof(a)))
 
+# probes (no reference counterpart): rho, u at points, trilinear in float32 (x, then y, then z), sampled into a device ring
+"""a probe set over `grids`: per probe its 0-based level, 8 stencil corners (reference block index, cell x + 8y + 64z; corners that
+are no fluid cell of that level already replaced by the base cell) as 8 x n Int32 matrices, weights 3 x n Float32, ring capacity in
+samples. Free it with `probes_destroy`."""
+function probes_create(grids::Vector{DeviceLevel}, level::Vector{Int32}, blocks::Matrix{Int32}, cells::Matrix{Int32},
+                       weights::Matrix{Float32}, capacity::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles level blocks cells weights check(ccall((:ludwig_probes_create, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Int32, Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int32(length(level)), level, blocks, cells, weights, Int32(capacity), out))
+    return out[]
+end
+probes_destroy(p::Ptr{Cvoid}) = ccall((:ludwig_probes_destroy, LIB), Cvoid, (Ptr{Cvoid},), p)
+"""sample the probes of 0-based level `level` after its sub-step `timestep` (queued on the level's stream)"""
+probes_sample!(p::Ptr{Cvoid}, level::Integer, timestep::Integer) =
+    check(ccall((:ludwig_probes_sample, LIB), Cint, (Ptr{Cvoid}, Int32, Int64), p, Int32(level), Int64(timestep)))
+"""the samples since the last download into values (4 x n_probes x max) and steps (max); returns how many, oldest first"""
+function probes_download!(values::Array{Float32,3}, steps::Vector{Int64}, p::Ptr{Cvoid})
+    n = Ref{Int32}(0)
+    GC.@preserve values steps check(ccall((:ludwig_probes_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int64}, Int32, Ref{Int32}),
+                                          p, values, steps, Int32(length(steps)), n))
+    return Int(n[])
+end
+
 """
 Multi-GPU hosts only: a HIP stream for the stepping kernels that leaves `reserved_cus` compute units to the halo exchange
 (`ludwig_stream_create`, include/ludwig_hip.h); hand it to `ludwig_level_set_stream`. No counterpart in the reference.
@@ -237,6 +262,16 @@ function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch
     GC.@preserve handles check(ccall((:ludwig_execute_timestep_batch, LIB), Cint,
                                      (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}),
                                      handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags))
+end
+
+"""execute_timestep_batch! with the probes of `probes` sampled inside the batch at coarse steps start_step + k interval"""
+function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                                 probes::Ptr{Cvoid}, start_step::Integer, interval::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    GC.@preserve handles check(ccall((:ludwig_execute_timestep_batch_probes, LIB), Cint,
+                                     (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{Cvoid}, Int64, Int32),
+                                     handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, probes,
+                                     Int64(start_step), Int32(interval)))
 end
 
 end # module

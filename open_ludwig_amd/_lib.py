@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "ludwig_halo_plan_exchange_ms", "ludwig_step_distributed",
     "ludwig_level_stats_reset", "ludwig_level_stats_accumulate", "ludwig_level_stats_download",
     "ludwig_level_gradient_fields_compute", "ludwig_level_gradient_fields_download",
+    "ludwig_probes_create", "ludwig_probes_destroy", "ludwig_probes_sample", "ludwig_probes_download",
+    "ludwig_execute_timestep_batch_probes",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -163,6 +165,11 @@ def load() -> C.CDLL:
         "ludwig_level_stats_download": (C.c_int, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int64)]),
         "ludwig_level_gradient_fields_compute": (C.c_int, [vp, i32, f32]),
         "ludwig_level_gradient_fields_download": (C.c_int, [vp, i32, vp, C.c_size_t]),
+        "ludwig_probes_create": (C.c_int, [C.POINTER(vp), i32, i32, vp, vp, vp, vp, i32, C.POINTER(vp)]),
+        "ludwig_probes_destroy": (None, [vp]),
+        "ludwig_probes_sample": (C.c_int, [vp, i32, i64]),
+        "ludwig_probes_download": (C.c_int, [vp, vp, vp, i32, C.POINTER(C.c_int32)]),
+        "ludwig_execute_timestep_batch_probes": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), vp, i64, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

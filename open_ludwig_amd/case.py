@@ -17,6 +17,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from . import forces as forces_mod
+from . import probes as probes_mod
 from . import statistics as stats_mod
 from .blocks import adapt
 from .preprocess import CaseConfig, DomainParameters, setup_multilevel_domain, solver_params
@@ -42,9 +43,36 @@ class HipStepper:
         self.dev = [adapt(g, device, upload_state=False) for g in host_grids]
         for d in self.dev:
             d.init_equilibrium()               # src/main.jl:126-135 (every state array: nothing of the host's to upload first)
+        self.probes = None                     # probes_setup
+        self._series = None
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
-        execute_timestep_batch(self.dev, t_start, n, u_curr, params)
+        if self.probes is None:
+            execute_timestep_batch(self.dev, t_start, n, u_curr, params)
+            return
+        # sampled inside the C batch, the ring drained after it; a batch with more samples than the ring holds is cut where it fills
+        # (the same inlet speed: the same steps, the same bits)
+        P, t, end = self.probes, t_start, t_start + n - 1
+        while t <= end:
+            seg_end = end
+            if probes_mod.samples_in(t, end, P.start_step, P.interval) > P.capacity:
+                first = P.start_step + max(0, -(-(t - P.start_step) // P.interval)) * P.interval
+                seg_end = first + (P.capacity - 1) * P.interval
+            execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P)
+            self._series.append(*P.download())
+            t = seg_end + 1
+
+    # -- probes (no reference counterpart) --
+    def probes_setup(self, plan, start_step: int = 1, interval: int = 1, capacity: int = 64) -> None:
+        """sample the probes of `plan` (probes.plan_probes over this stepper's grids) at coarse steps start_step + k interval"""
+        if self.probes is not None:
+            self.probes.close()
+        self.probes = probes_mod.DeviceProbes(plan, self.dev, capacity, start_step, interval)
+        self._series = probes_mod.Series(plan.n)
+
+    def probes_series(self):
+        """(coarse steps [n] int64, values [n, n_probes, 4] float32: rho, ux, uy, uz) of every sample so far"""
+        return self._series.arrays()
 
     def field(self, level: int, name: str) -> np.ndarray:
         return self.dev[level].download(name)
@@ -84,6 +112,9 @@ class HipStepper:
         return self.dev[level].gradient_fields(vel_name, scale)
 
     def close(self):
+        if self.probes is not None:
+            self.probes.close()
+            self.probes = None
         for d in self.dev:
             d.close()
 
@@ -123,21 +154,90 @@ class DistributedStepper:
         self.transport = transport
         self.runner = None
         self._tri = {}                         # level -> static triangle map (see surface_forces)
+        self._probe_cfg = None                 # probes_setup: (plan, start_step, interval, capacity)
+        self.probes = None                     # this rank's probe set (None: it owns no probe)
+
+    def _level_owner(self, level: int) -> np.ndarray:
+        g = self.host[level]
+        return np.asarray(self.owners[level] if not isinstance(self.owners, np.ndarray) else
+                          self.partition.ancestor_owner(g.level_id, g.active_block_coords, self.host[0].active_block_coords, self.owners))
 
     def _start(self, params) -> None:
+        probe_cells, mine = None, None
+        if self._probe_cfg is not None:
+            # a probe belongs to the rank that owns its base cell's block; its corners in a peer's block are read from the ghost copy,
+            # so they join the level's 'rho' and 'vel' halo
+            plan = self._probe_cfg[0]
+            base_owner = np.array([self._level_owner(int(l))[b] for l, b in zip(plan.level, plan.blocks[:, 0])], dtype=np.int64)
+            mine = np.flatnonzero(base_owner == self.rank)
+            probe_cells = [np.zeros(0, np.int64) for _ in self.host]
+            for p in mine:
+                li = int(plan.level[p])
+                probe_cells[li] = np.concatenate([probe_cells[li], plan.blocks[p].astype(np.int64) * 512 + plan.cells[p]])
         self.runner = self.partition.MultiLevelRunner(self.host, self.owners, params, self.rank, self.world, self.device, self.stage,
-                                                      overlap=self.overlap, transport=self.transport, upload_state=False)
+                                                      overlap=self.overlap, transport=self.transport, upload_state=False,
+                                                      probe_cells=probe_cells)
         for lv in self.runner.levels:
             if lv is not None:
                 lv.init_equilibrium()          # src/main.jl:126-135 (ghost blocks included: same rest state everywhere)
+        if mine is not None and mine.size:
+            plan, start, interval, capacity = self._probe_cfg
+            local = plan.subset(mine)
+            for p in range(local.n):
+                g2l = self.runner.views[int(local.level[p])].global_to_local
+                local.blocks[p] = [g2l[int(b)] for b in local.blocks[p]]
+            self.probes = probes_mod.DeviceProbes(local, self.runner.levels, capacity, start, interval)
+            self._probe_cols = mine
+            self._probe_pending = 0
+            self._series = probes_mod.Series(local.n)          # this rank's probes, in the order of _probe_cols
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.runner is None:
             self._start(params)
         self.runner.params = params
+        P = self.probes
         for t in range(t_start, t_start + n):
             self.runner.step(t, u_curr)
+            if P is not None and probes_mod.is_sample_step(t, P.start_step, P.interval):
+                if self._probe_pending == P.capacity:
+                    self._series.append(*P.download())
+                    self._probe_pending = 0
+                for lvl in P.levels_with_probes:
+                    self.runner._join(lvl)     # the level's ghosts (peer corners) are in place
+                    P.sample(lvl, stats_mod.t_sub_after(lvl, t))
+                self._probe_pending += 1
         self.runner.synchronize()
+        if P is not None:
+            self._series.append(*P.download())
+            self._probe_pending = 0
+
+    # -- probes: each rank samples the probes whose base cell it owns; the series is gathered to rank 0 in probe order --
+    def probes_setup(self, plan, start_step: int = 1, interval: int = 1, capacity: int = 64) -> None:
+        """before the first batch: the probe corners change the halo plans, which the first batch builds"""
+        if self.runner is not None:
+            raise RuntimeError("DistributedStepper.probes_setup must come before the first batch")
+        self._probe_cfg = (plan, int(start_step), int(interval), int(capacity))
+
+    def probes_series(self):
+        """(coarse steps [n] int64, values [n, n_probes, 4] float32) on rank 0 (None elsewhere); collective. Valid at any time after
+        probes_setup, also before the first batch or the first sampled step (then n = 0)."""
+        mine = None
+        if self.probes is not None:
+            steps, vals = self._series.arrays()
+            mine = (self._probe_cols, steps, vals)
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        if self.rank != 0:
+            return None
+        n_total = self._probe_cfg[0].n
+        got = [p for p in parts if p is not None]
+        steps = got[0][1] if got else np.zeros(0, np.int64)
+        out = np.full((steps.size, n_total, 4), np.nan, dtype=np.float32)
+        for cols, st, vals in got:
+            assert np.array_equal(st, steps), "ranks sampled different steps"
+            assert vals.shape == (steps.size, len(cols), 4)
+            out[:, cols] = vals
+        return steps, out
 
     # -- collectives of a few scalars --
     def _comm_device(self):
@@ -287,6 +387,9 @@ class DistributedStepper:
         return w_all, q_all
 
     def close(self):
+        if self.probes is not None:
+            self.probes.close()
+            self.probes = None
         if self.runner is not None:
             self.runner.close()          # plans, communicator, levels; the views and plans stay readable (statistics)
 
@@ -321,23 +424,45 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     flow_mean_%06d.vtu (the average over the samples so far, statistics.py) on those steps once a sample exists; "Vorticity" /
     "QCriterion" in cfg.output_fields add those arrays to the flow file, computed on the device from the file's velocity buffer with
     derivatives per unit length of the file's coordinates (scale 1/dx). Unlike the reference (main.jl:79) an
-    existing directory is NOT emptied first. write_files=False on all ranks but one of a distributed run."""
+    existing directory is NOT emptied first. write_files=False on all ranks but one of a distributed run.
+    With cfg.probes_enabled, probes_points.csv is written once and probes.csv gains the new samples at every diagnostics step and at
+    the end of the run (probes.py); batches are not cut for probes."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
     sp = solver_params(cfg, params)
+    probes_on = bool(cfg.probes_enabled)
+    # points are refused (outside the domain, inside the body) before anything is allocated on a device
+    pplan = probes_mod.plan_probes(cfg.probes_points, grids, params.mesh_offset, cfg.probes_names) if probes_on else None
     st = stepper_factory(grids)
     total_steps = steps if steps is not None else cfg.steps
     rows: List[DiagRow] = []
     batch = cfg.async_depth
     t = 1
     writing = out_dir is not None and write_files
+    if probes_on:
+        st.probes_setup(pplan, cfg.probes_start_step, cfg.probes_interval, max(batch, 1))
     if writing:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "convergence.csv"), "w") as io:
             io.write(out_mod.CONVERGENCE_CSV_HEADER + "\n")
         if cfg.forces_enabled:
             out_mod.write_force_csv_header(os.path.join(out_dir, "forces.csv"))
+        if probes_on:
+            probes_mod.write_points_csv(os.path.join(out_dir, "probes_points.csv"), pplan, grids)
+            with open(os.path.join(out_dir, "probes.csv"), "w") as io:
+                io.write(probes_mod.series_csv_header(pplan.names) + "\n")
+    probes_written = [0]
+
+    def flush_probes():
+        """append the samples not yet in probes.csv (collective in a distributed run)"""
+        series = st.probes_series()
+        if writing and series is not None:
+            p_steps, p_vals = series
+            new_rows = probes_mod.series_csv_rows(p_steps[probes_written[0]:], p_vals[probes_written[0]:], params.time_scale)
+            with open(os.path.join(out_dir, "probes.csv"), "a") as io:
+                io.writelines(r + "\n" for r in new_rows)
+            probes_written[0] = p_steps.size
     t0 = last_diag = _time.time()
     total_cells = sum(g.n_blocks * 512 for g in grids)
     fr = None
@@ -392,6 +517,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                                                                  cd if cfg.forces_enabled else None, cl if cfg.forces_enabled else None) + "\n")
                     if log:
                         log(f"{diag_step:8d} | {float(u_curr):.4f} | {rho_min:.4f} | {cd:8.4f} | {cl:8.4f}")
+                    if probes_on:
+                        flush_probes()
             if out_dir is not None and batch_end % cfg.output_freq < actual:                      # src/main.jl:213-231
                 out_step = (batch_end // cfg.output_freq) * cfg.output_freq
                 if t <= out_step <= batch_end:
@@ -425,6 +552,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         if writing:
                             out_mod.export_mean_mesh(out_step, grids, finals.__getitem__, tuple(stats_window), out_dir)
             t = batch_end + 1
+        if probes_on:
+            flush_probes()
     finally:
         if hasattr(st, "close"):
             st.close()

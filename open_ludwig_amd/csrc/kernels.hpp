@@ -1174,6 +1174,41 @@ __global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restr
     for (int m = 0; m < GRAD_COMPONENTS; ++m) *(float2 *)(o + m * CELLS) = make_float2(res[m][0], res[m][1]);
 }
 
+// ---- probes (ludwig_probes_*; no reference counterpart) ----
+// One lane per probe of one level. cell[8 p + c] = internal block * 512 + (x + 8 y + 64 z) of stencil corner c = dx + 2 dy + 4 dz;
+// w[3 p + a] = the weights along x, y, z; col[p] = the probe's place in the set. rho: [block][512], vel: [block][3][512] floats
+// (block-major). Trilinear in float32 in ONE fixed order - x first (corners 0-1, 2-3, 4-5, 6-7), then y, then z, every lerp
+// (1 - w) a + w b - with -ffp-contract=off, so open_ludwig_amd/probes.py (trilinear) restates it bit for bit. out = the slot,
+// [n_set][4]: rho, ux, uy, uz. Bounded by a launch latency, not by bandwidth: 128 B gathered per probe.
+__device__ __forceinline__ float probe_lerp(float a, float b, float w) { return (1.0f - w) * a + w * b; }
+
+__global__ __launch_bounds__(64) void k_probe_sample(float *__restrict__ out, const int32_t *__restrict__ cell, const float *__restrict__ w,
+                                                     const int32_t *__restrict__ col, int n, const float *__restrict__ rho,
+                                                     const float *__restrict__ vel)
+{
+    const int p = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (p >= n) return;
+    int64_t e[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) e[c] = cell[8 * p + c];
+    const float wx = w[3 * p], wy = w[3 * p + 1], wz = w[3 * p + 2];
+    float res[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float v[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const int64_t b = e[c] >> 9, cc = e[c] & 511;
+            v[c] = k == 0 ? rho[e[c]] : vel[(b * 3 + (k - 1)) * CELLS + cc];
+        }
+        const float x00 = probe_lerp(v[0], v[1], wx), x10 = probe_lerp(v[2], v[3], wx);
+        const float x01 = probe_lerp(v[4], v[5], wx), x11 = probe_lerp(v[6], v[7], wx);
+        const float y0 = probe_lerp(x00, x10, wy), y1 = probe_lerp(x01, x11, wy);
+        res[k] = probe_lerp(y0, y1, wz);
+    }
+    *(float4 *)(out + 4 * (int64_t)col[p]) = make_float4(res[0], res[1], res[2], res[3]);
+}
+
 // ---- internal storage (ludwig_hip.hip "block order", "block-major"): the caller's arrays keep the reference's layout,
 // [8,8,8,n_blocks,K] with the reference's block order; the device arrays hold the blocks in the library's own order, block-major.
 // ref2int[b_reference] = b_internal (nullptr = same order) ----

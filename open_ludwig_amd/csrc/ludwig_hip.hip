@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1659,8 +1660,85 @@ static int save_old_impl(LudwigLevel *L, int64_t t_sub, bool defer_rho)
 // LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
 static bool level_streams() { static const bool v = getenv("LUDWIG_BATCH_SERIAL") == nullptr; return v; }
 
+// ---- probes (ludwig_probes_*; no reference counterpart) ----
+// A probe set over a level array: per level the probes it holds (stencil cells in the internal block order, weights, place in the set)
+// and one device ring [capacity][n_probes][4] of samples. The host keeps the coarse step of every used slot; _download empties it.
+struct LudwigProbes {
+    int device = 0;
+    int n_levels = 0, n_probes = 0, capacity = 0;
+    std::vector<LudwigLevel *> levels;          // as given; an entry without probes may be null (a rank that holds no copy of it)
+    struct PerLevel {
+        int n = 0;
+        int32_t *cell = nullptr;                // [n][8] internal block * 512 + cell
+        float *w = nullptr;                     // [n][3]
+        int32_t *col = nullptr;                 // [n] place in the set
+    };
+    std::vector<PerLevel> per;
+    float *ring = nullptr;
+    std::vector<int64_t> slot_step;             // coarse step of each used slot, oldest first
+    std::vector<uint64_t> slot_levels;          // bit li: level li has written its probes into the slot
+};
+
+namespace {
+
+bool probe_step_sampled(int64_t t, int64_t start_step, int32_t interval)
+{
+    return t >= start_step && (t - start_step) % interval == 0;
+}
+
+int64_t probe_samples_in(int64_t first, int64_t last, int64_t start_step, int32_t interval)
+{
+    const int64_t lo = std::max(first, start_step);
+    if (last < lo) return 0;
+    const int64_t k0 = (lo - start_step + interval - 1) / interval, s0 = start_step + k0 * interval;
+    return s0 > last ? 0 : (last - s0) / interval + 1;
+}
+
+uint64_t probed_levels_mask(const LudwigProbes *P)
+{
+    uint64_t m = 0;
+    for (int li = 0; li < P->n_levels; ++li)
+        if (P->per[li].n > 0) m |= (uint64_t)1 << li;
+    return m;
+}
+
+// a new slot for coarse step t, every probed level writing it (the batch; the caller has checked the free capacity)
+int probes_open_slot(LudwigProbes *P, int64_t t)
+{
+    P->slot_step.push_back(t);
+    P->slot_levels.push_back(probed_levels_mask(P));
+    return (int)P->slot_step.size() - 1;
+}
+
+}  // namespace
+
+static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub)
+{
+    const LudwigProbes::PerLevel &q = P->per[li];
+    if (q.n == 0) return LUDWIG_OK;                       // a level without probes launches nothing
+    LudwigLevel *L = P->levels[li];
+    {   // rho as a download would return it now; a no-op on the probed levels, which store it every step
+        const int r = ensure_rho(L);
+        if (r) return r;
+    }
+    const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];  // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+    float *out = P->ring + (size_t)slot * P->n_probes * 4;
+    hipLaunchKernelGGL(k_probe_sample, dim3((unsigned)((q.n + 63) / 64)), dim3(64), 0, L->stream, out, q.cell, q.w, q.col, q.n, L->rho, vel);
+    LW_HIP(hipGetLastError());
+    return LUDWIG_OK;
+}
+
+// Probe sampling inside a batch (ludwig_execute_timestep_batch_probes): the coarse step being run and its ring slot, -1 = not sampled.
+struct ProbeHook {
+    LudwigProbes *P = nullptr;
+    int64_t t = 0;
+    int slot = -1;
+};
+static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub);
+
 static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-based*/, int64_t t_sub, const LudwigLevel *parent,
-                          float parent_tau, float temporal_weight, float u_vel, const LudwigStepFlags *fl, bool concurrent)
+                          float parent_tau, float temporal_weight, float u_vel, const LudwigStepFlags *fl, bool concurrent,
+                          const ProbeHook *ph = nullptr)
 {
     // recursive_step! / recursive_step_temporal!, reference src/solver_control.jl:21-143
     if (lvl > n_levels) return LUDWIG_OK;
@@ -1712,15 +1790,20 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         LW_HIP(hipEventRecord(L->ev_stepped, L->stream));
         ++L->stepped_gen;
     }
+    if (ph && ph->slot >= 0) {
+        // the level's last sub-step of a sampled coarse step: the probes of this level read its newest rho / vel on its own stream,
+        // behind the step (and behind the event its children wait for) and ahead of the next write to either
+        const int64_t m = (int64_t)1 << (lvl - 1);
+        if (t_sub == m * ph->t + m - 1 && (rc = probes_launch(ph->P, lvl - 1, ph->slot, t_sub))) return rc;
+    }
     if (has_children) {
-        if ((rc = recursive_step(levels, n_levels, lvl + 1, 2 * t_sub, L, L->tau, 0.0f, u_vel, fl, concurrent))) return rc;
-        if ((rc = recursive_step(levels, n_levels, lvl + 1, 2 * t_sub + 1, L, L->tau, 0.5f, u_vel, fl, concurrent))) return rc;
+        if ((rc = recursive_step(levels, n_levels, lvl + 1, 2 * t_sub, L, L->tau, 0.0f, u_vel, fl, concurrent, ph))) return rc;
+        if ((rc = recursive_step(levels, n_levels, lvl + 1, 2 * t_sub + 1, L, L->tau, 0.5f, u_vel, fl, concurrent, ph))) return rc;
     }
     return LUDWIG_OK;
 }
 
-int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                                  const LudwigStepFlags *flags)
+static int check_batch_levels(LudwigLevel *const *levels, int32_t n_levels, int32_t batch_size, const LudwigStepFlags *flags)
 {
     if (!levels || !flags || n_levels < 1 || batch_size < 0) return fail(LUDWIG_ERR_INVALID, "bad argument");
     for (int i = 0; i < n_levels; ++i) {
@@ -1728,6 +1811,23 @@ int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, 
         if (levels[i]->device != levels[0]->device || levels[i]->stream != levels[0]->stream)
             return fail(LUDWIG_ERR_INVALID, "all levels must share one device and one stream");
     }
+    return LUDWIG_OK;
+}
+
+static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                      const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval);
+
+int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                  const LudwigStepFlags *flags)
+{
+    const int r = check_batch_levels(levels, n_levels, batch_size, flags);
+    if (r) return r;
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr, 0, 1);
+}
+
+static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                      const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval)
+{
     const bool concurrent = n_levels > 1 && level_streams();
     hipStream_t user_stream = levels[0]->stream;
     if (concurrent) {
@@ -1786,8 +1886,18 @@ int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, 
     }
     for (int i = 0; i < n_levels; ++i) levels[i]->rho_old_pending = false;      // (only an aborted batch could have left one)
     int rc = LUDWIG_OK;
-    for (int32_t o = 0; o < batch_size && rc == LUDWIG_OK; ++o)
-        rc = recursive_step(levels, n_levels, 1, t_start + o, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent);
+    for (int32_t o = 0; o < batch_size && rc == LUDWIG_OK; ++o) {
+        const int64_t t = t_start + o;
+        if (!probes) {
+            rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent);
+            continue;
+        }
+        ProbeHook ph;
+        ph.P = probes;
+        ph.t = t;
+        if (probe_step_sampled(t, start_step, interval)) ph.slot = probes_open_slot(probes, t);
+        rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
+    }
     if (concurrent) {
         hipError_t e = hipSuccess;
         for (int i = 0; i < n_levels; ++i) {
@@ -2001,6 +2111,168 @@ int ludwig_level_gradient_fields_download(const LudwigLevel *L, int which, float
     (void)hipFree(tmp);
     if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "gradient fields download: %s", hipGetErrorString(e));
     return LUDWIG_OK;
+}
+
+void ludwig_probes_destroy(LudwigProbes *P)
+{
+    if (!P) return;
+    (void)hipSetDevice(P->device);
+    for (LudwigProbes::PerLevel &q : P->per) {
+        if (q.cell) (void)hipFree(q.cell);
+        if (q.w) (void)hipFree(q.w);
+        if (q.col) (void)hipFree(q.col);
+    }
+    if (P->ring) (void)hipFree(P->ring);
+    delete P;
+}
+
+int ludwig_probes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_probes, const int32_t *level_index,
+                         const int32_t *blocks, const int32_t *cells, const float *weights, int32_t capacity, LudwigProbes **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels || !level_index || !blocks || !cells || !weights) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > 64) return fail(LUDWIG_ERR_INVALID, "probes: n_levels %d not in 1..64", n_levels);
+    if (n_probes < 1) return fail(LUDWIG_ERR_INVALID, "probes: n_probes %d < 1", n_probes);
+    if (capacity < 1) return fail(LUDWIG_ERR_INVALID, "probes: capacity %d < 1", capacity);
+    if ((int64_t)capacity * n_probes * 16 > ((int64_t)1 << 34)) return fail(LUDWIG_ERR_INVALID, "probes: ring of %d x %d samples too large", capacity, n_probes);
+    // everything is checked before anything is allocated
+    const LudwigLevel *first = nullptr;
+    for (int32_t p = 0; p < n_probes; ++p) {
+        const int li = level_index[p];
+        if (li < 0 || li >= n_levels) return fail(LUDWIG_ERR_INVALID, "probe %d: level index %d not in 0..%d", p, li, n_levels - 1);
+        const LudwigLevel *L = levels[li];
+        if (!L) return fail(LUDWIG_ERR_INVALID, "probe %d: level %d is null", p, li);
+        if (first && L->device != first->device) return fail(LUDWIG_ERR_INVALID, "probes: levels on different devices");
+        if (!first) first = L;
+        // the kernel indexes cells as internal block * 512 + cell in 32 bits
+        if ((int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+            return fail(LUDWIG_ERR_INVALID, "probe %d: level %d has %d blocks, more than 32-bit cell indices reach", p, li, L->n_blocks);
+        for (int c = 0; c < 8; ++c) {
+            const int32_t b = blocks[8 * p + c], x = cells[8 * p + c];
+            if (b < 0 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "probe %d corner %d: block %d not in 0..%d", p, c, b, L->n_blocks - 1);
+            if (x < 0 || x >= CELLS) return fail(LUDWIG_ERR_INVALID, "probe %d corner %d: cell %d not in 0..511", p, c, x);
+        }
+        for (int a = 0; a < 3; ++a) {
+            const float w = weights[3 * p + a];
+            if (!(w >= 0.0f && w <= 1.0f)) return fail(LUDWIG_ERR_INVALID, "probe %d: weight %d = %g not in [0, 1]", p, a, (double)w);
+        }
+    }
+    for (int li = 0; li < n_levels; ++li)
+        if (levels[li] && levels[li]->device != first->device) return fail(LUDWIG_ERR_INVALID, "probes: levels on different devices");
+    LudwigProbes *P = new (std::nothrow) LudwigProbes;
+    if (!P) return fail(LUDWIG_ERR_ALLOC, "probes: out of host memory");
+    P->device = first->device;
+    P->n_levels = n_levels;
+    P->n_probes = n_probes;
+    P->capacity = capacity;
+    P->levels.assign(levels, levels + n_levels);
+    P->per.resize(n_levels);
+    LW_HIP(hipSetDevice(P->device));
+    int r = LUDWIG_OK;
+    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
+        std::vector<int32_t> hc, hcol;
+        std::vector<float> hw;
+        const LudwigLevel *L = levels[li];
+        for (int32_t p = 0; p < n_probes; ++p) {
+            if (level_index[p] != li) continue;
+            for (int c = 0; c < 8; ++c) {
+                const int32_t b = blocks[8 * p + c];
+                hc.push_back((L->ref2int.empty() ? b : L->ref2int[b]) * CELLS + cells[8 * p + c]);
+            }
+            for (int a = 0; a < 3; ++a) hw.push_back(weights[3 * p + a]);
+            hcol.push_back(p);
+        }
+        LudwigProbes::PerLevel &q = P->per[li];
+        q.n = (int)hcol.size();
+        if (q.n == 0) continue;
+        hipError_t e = hipMalloc((void **)&q.cell, hc.size() * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&q.w, hw.size() * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&q.col, hcol.size() * 4);
+        if (e == hipSuccess) e = hipMemcpy(q.cell, hc.data(), hc.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(q.w, hw.data(), hw.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(q.col, hcol.data(), hcol.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "probes: level %d tables: %s", li, hipGetErrorString(e));
+        // a probe reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now
+        // on (+4 of 216 B per cell where the store was elided), so a batch never replays it
+        if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(levels[li], 1);
+    }
+    if (r == LUDWIG_OK) {
+        const hipError_t e = hipMalloc((void **)&P->ring, (size_t)capacity * n_probes * 4 * sizeof(float));
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "probes: ring of %d samples: %s", capacity, hipGetErrorString(e));
+    }
+    if (r != LUDWIG_OK) {
+        ludwig_probes_destroy(P);
+        return r;
+    }
+    *out = P;
+    return LUDWIG_OK;
+}
+
+int ludwig_probes_sample(LudwigProbes *P, int32_t level_index, int64_t t_sub)
+{
+    if (!P) return fail(LUDWIG_ERR_INVALID, "null probe set");
+    if (level_index < 0 || level_index >= P->n_levels) return fail(LUDWIG_ERR_INVALID, "probes: level index %d not in 0..%d", level_index, P->n_levels - 1);
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "probes: t_sub %lld < 0", (long long)t_sub);
+    if (P->per[level_index].n == 0) return LUDWIG_OK;
+    // the coarse step sub-step t_sub of level index li belongs to: t_sub >> li. Its slot is the newest one when that is for the same
+    // step and this level has not written it yet; else a new slot, filled with NaN until every probed level has written its part
+    const int64_t step = t_sub >> level_index;
+    const uint64_t bit = (uint64_t)1 << level_index;
+    LudwigLevel *L = P->levels[level_index];
+    // a new slot is NaN-filled on this level's stream and the other levels write their columns of it on theirs: one stream orders both
+    for (int li = 0; li < P->n_levels; ++li)
+        if (P->per[li].n > 0 && P->levels[li]->stream != L->stream)
+            return fail(LUDWIG_ERR_STATE, "probes: levels %d and %d sample on different streams", level_index, li);
+    LW_HIP(hipSetDevice(P->device));
+    int slot = (int)P->slot_step.size() - 1;
+    if (slot < 0 || P->slot_step[slot] != step || (P->slot_levels[slot] & bit)) {
+        if ((int)P->slot_step.size() >= P->capacity)
+            return fail(LUDWIG_ERR_STATE, "probes: ring full (%d samples): download first", P->capacity);
+        slot = (int)P->slot_step.size();
+        LW_HIP(hipMemsetAsync(P->ring + (size_t)slot * P->n_probes * 4, 0xff, (size_t)P->n_probes * 16, L->stream));
+        P->slot_step.push_back(step);
+        P->slot_levels.push_back(0);
+    }
+    const int r = probes_launch(P, level_index, slot, t_sub);
+    if (r) return r;
+    P->slot_levels[slot] |= bit;
+    return LUDWIG_OK;
+}
+
+int ludwig_probes_download(LudwigProbes *P, float *values, int64_t *steps, int32_t max_samples, int32_t *n_samples)
+{
+    if (!P || !n_samples || max_samples < 0 || (max_samples > 0 && (!values || !steps))) return fail(LUDWIG_ERR_INVALID, "null argument");
+    const int n = (int)P->slot_step.size();
+    if (n > max_samples) return fail(LUDWIG_ERR_INVALID, "probes: %d samples waiting, room for %d", n, max_samples);
+    *n_samples = n;
+    if (n == 0) return LUDWIG_OK;
+    LW_HIP(hipSetDevice(P->device));
+    for (int li = 0; li < P->n_levels; ++li)
+        if (P->per[li].n > 0) LW_HIP(hipStreamSynchronize(P->levels[li]->stream));
+    LW_HIP(hipMemcpy(values, P->ring, (size_t)n * P->n_probes * 16, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) steps[i] = P->slot_step[i];
+    P->slot_step.clear();
+    P->slot_levels.clear();
+    return LUDWIG_OK;
+}
+
+int ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                         const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval)
+{
+    int r = check_batch_levels(levels, n_levels, batch_size, flags);
+    if (r) return r;
+    if (!probes) return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr, 0, 1);
+    if (interval < 1) return fail(LUDWIG_ERR_INVALID, "probes: interval %d < 1", interval);
+    if (probes->n_levels != n_levels) return fail(LUDWIG_ERR_INVALID, "probes: set made over %d levels, batch of %d", probes->n_levels, n_levels);
+    for (int i = 0; i < n_levels; ++i)
+        if (probes->levels[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "probes: set made over other levels (level %d)", i + 1);
+    // nothing is stepped when the batch's samples would not fit
+    const int64_t k = batch_size > 0 ? probe_samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
+    if ((int64_t)probes->slot_step.size() + k > probes->capacity)
+        return fail(LUDWIG_ERR_STATE, "probes: %lld samples of this batch overflow the ring (%d of %d used): download first", (long long)k,
+                    (int)probes->slot_step.size(), probes->capacity);
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, probes, start_step, interval);
 }
 
 int ludwig_halo_pack(const LudwigLevel *L, int field, const int64_t *index_dev, int64_t n, float *dst_dev, void *hip_stream)

@@ -936,6 +936,20 @@ def interpolation_needs(child: LocalView, parent: LocalView, domain_cells: Tuple
     return {k: (np.unique(np.concatenate(v)) if v else np.zeros(0, np.int64)) for k, v in out.items()}
 
 
+def probe_needs(view: LocalView, n_global: int, cells: np.ndarray) -> Dict[str, np.ndarray]:
+    """'rho' and 'vel' needs (local element offsets) of the probe stencil cells `cells` (global block id * 512 + cell) that lie in
+    ghost blocks: a probe's corners are its base cell's block or one of its 26 neighbours, all held here as ghosts"""
+    c = np.unique(np.asarray(cells, dtype=np.int64))
+    g2l = np.full(n_global, -1, dtype=np.int64)
+    g2l[view.local_to_global] = np.arange(len(view.local_to_global))
+    lb = g2l[c // CELLS]
+    assert (lb >= 0).all(), "a probe corner in a block this rank holds no copy of"
+    gh = lb >= view.n_owned
+    loc = lb[gh] * CELLS + c[gh] % CELLS
+    sk = view.level.n_blocks * CELLS
+    return {"rho": loc, "vel": np.concatenate([loc + k * sk for k in range(3)])}
+
+
 class MultiLevelRunner:
     """Distributed recursive_step! (src/solver_control.jl:21-143) for nested levels: same call order and A/B parity as
     the single-device driver, plus after every level step the halo exchange of that level (same-level ghosts AND the
@@ -946,9 +960,12 @@ class MultiLevelRunner:
 
     def __init__(self, grids: Sequence[BlockLevel], owners, params, rank: int, world: int, device: int,
                  stage_through_host: bool = False, overlap: bool = True, transport: Optional[str] = None, comm=None,
-                 wire_ranks: Optional[List[Dict[int, int]]] = None, requests_to_me: Optional[Callable] = None, upload_state: bool = True):
+                 wire_ranks: Optional[List[Dict[int, int]]] = None, requests_to_me: Optional[Callable] = None, upload_state: bool = True,
+                 probe_cells: Optional[Sequence[np.ndarray]] = None):
         """upload_state=False: the host levels' f / rho / vel arrays are neither sliced nor uploaded - the caller initialises the state
-        on the device right away (DistributedStepper: init_eq!); on the shipped Wing_5_deg that is 25 GB of zeros per rank otherwise"""
+        on the device right away (DistributedStepper: init_eq!); on the shipped Wing_5_deg that is 25 GB of zeros per rank otherwise.
+        probe_cells: per level, the cells (global block id * 512 + cell) the probes this rank owns read; those in ghost blocks join the
+        level's 'rho' and 'vel' halo (None: every plan as without probes)"""
         import ctypes as C
         import torch
         from . import _lib
@@ -985,6 +1002,10 @@ class MultiLevelRunner:
             if i + 1 < len(grids) and self.views[i + 1].n_owned > 0:
                 extra = interpolation_needs(self.views[i + 1], v, dims)
                 for name in ("f", "rho", "vel"):
+                    needs[name] = np.unique(np.concatenate([needs[name], extra[name]]))
+            if probe_cells is not None and len(probe_cells[i]):
+                extra = probe_needs(v, g.n_blocks, probe_cells[i])
+                for name in ("rho", "vel"):
                     needs[name] = np.unique(np.concatenate([needs[name], extra[name]]))
             mine = make_requests(v, g.n_blocks, needs)
             if requests_to_me is not None:          # loop-back tests: what the peers would ask, supplied by the caller (level index, own requests)

@@ -98,6 +98,13 @@ class CaseConfig:
     statistics_enabled: bool = False
     statistics_start_step: int = 1      # first sampled coarse step (the sums are reset there); YAML default: ramp_steps
     statistics_interval: int = 10       # coarse steps between samples
+    # probes, advanced.probes (no reference counterpart): rho, u at points every `interval` coarse steps from `start_step`, written to
+    # probes.csv / probes_points.csv; points in the STL's frame after stl_scale (probes.py)
+    probes_enabled: bool = False
+    probes_start_step: int = 1
+    probes_interval: int = 1
+    probes_points: Tuple[Tuple[float, float, float], ...] = ()
+    probes_names: Tuple[str, ...] = ()
 
     @property
     def reference_area_config(self) -> float:
@@ -126,6 +133,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     stats_interval = int(g("advanced", "statistics", "interval", default=10))
     if stats_interval < 1:
         raise ValueError(f"advanced.statistics.interval must be >= 1, got {stats_interval}")
+    probes = _probes_config(g("advanced", "probes", default=None))
     return CaseConfig(
         stl_file=g("basic", "stl_file", required=True), stl_scale=float(g("basic", "stl_scale", required=True)),
         surface_resolution=int(g("basic", "surface_resolution", required=True)), num_levels=int(g("basic", "num_levels", required=True)),
@@ -172,7 +180,46 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
                               if bool(g("basic", "simulation", "output_fields", key, default=False))),
         statistics_enabled=bool(g("advanced", "statistics", "enabled", default=False)),
         statistics_start_step=max(stats_start, 1), statistics_interval=stats_interval,
+        **probes,
     )
+
+
+def _probes_config(pc) -> dict:
+    """advanced.probes: {enabled: false, start_step: 1, interval: 1, points: [[x, y, z], ...], names: [...]} -> CaseConfig fields.
+    Absent or disabled: the defaults (nothing is planned, allocated or written)."""
+    if pc is None:
+        return {}
+    if not isinstance(pc, dict):
+        raise ValueError("advanced.probes must be a mapping")
+    if not bool(pc.get("enabled", False)):
+        return {}
+    start, interval = int(pc.get("start_step", 1)), int(pc.get("interval", 1))
+    if interval < 1:
+        raise ValueError(f"advanced.probes.interval must be >= 1, got {interval}")
+    if start < 1:
+        raise ValueError(f"advanced.probes.start_step must be >= 1, got {start}")
+    raw = pc.get("points") or []
+    pts = []
+    for i, p in enumerate(raw):
+        if not isinstance(p, (list, tuple)) or len(p) != 3:
+            raise ValueError(f"advanced.probes.points[{i}] must be [x, y, z], got {p!r}")
+        v = tuple(float(c) for c in p)
+        if not all(math.isfinite(c) for c in v):
+            raise ValueError(f"advanced.probes.points[{i}] is not finite: {p!r}")
+        pts.append(v)
+    if not pts:
+        raise ValueError("advanced.probes.enabled needs at least one point")
+    names = pc.get("names")
+    names = [f"p{i}" for i in range(len(pts))] if names is None else [str(n) for n in names]
+    if len(names) != len(pts):
+        raise ValueError(f"advanced.probes: {len(names)} names for {len(pts)} points")
+    for n in names:
+        if not n or any(ch in n for ch in ',"\'\n\r') or n != n.strip():
+            raise ValueError(f"advanced.probes.names: {n!r} is not a plain CSV column name")
+    if len(set(names)) != len(names):
+        raise ValueError("advanced.probes.names must be unique")
+    return dict(probes_enabled=True, probes_start_step=start, probes_interval=interval, probes_points=tuple(pts),
+                probes_names=tuple(names))
 
 
 # ----------------------------------------------------------------------------------------------------------------
