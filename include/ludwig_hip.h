@@ -317,6 +317,45 @@ int  ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_
                                           float u_curr, const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step,
                                           int32_t interval);
 
+/* ---- surface statistics: time-averaged wall loads per triangle (no reference counterpart) ----
+ * A surface set lives on one level (the finest). Triangle i reads its nearest fluid cell (reference block index blocks[i], 0-based,
+ * -1 = none found; cell cells[i] = x + 8 y + 64 z), with wall distance wall_dist[i] in lattice units and normal normals[3i + 0..2].
+ * A sample evaluates p, tau_x, tau_y, tau_z exactly as ludwig_map_surface_stresses does for that cell (sp->tau, pressure_scale,
+ * stress_scale; the other fields of sp are ignored), |tau| = sqrt((tau_x^2 + tau_y^2) + tau_z^2) in float32, and adds to 7 float64
+ * sums per triangle, [7][n_tri]: S_p, S_pp, S_tau_x, S_tau_y, S_tau_z, S_|tau|, S_|tau|^2 - each a plain sequential addition of the
+ * float32 value (squares of it, exact in float64) in sample order. A triangle with no cell adds zeros. The sums start at zero.
+ * Creating the set makes the level store rho after every step (see ludwig_level_set_rho_store). n_tri = 0 is allowed (a rank that
+ * owns none of the triangles): samples are counted, nothing is launched. The level may hold at most 2^31 / 512 blocks. */
+typedef struct LudwigSurfaceStats LudwigSurfaceStats;   /* opaque */
+int  ludwig_surface_stats_create(LudwigLevel *level, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *wall_dist,
+                                 const float *normals, const LudwigSurfaceParams *sp, LudwigSurfaceStats **out);
+/* frees the set, not the level; it does not touch the level, so it may come before or after its destruction */
+void ludwig_surface_stats_destroy(LudwigSurfaceStats *stats);
+/* zero the sums and the sample count, queued on the level's stream */
+int  ludwig_surface_stats_reset(LudwigSurfaceStats *stats);
+/* one sample of the state sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd; rho as a download would return it), queued on
+ * the level's stream, no host synchronisation */
+int  ludwig_surface_stats_accumulate(LudwigSurfaceStats *stats, int64_t t_sub);
+/* the sums [7][n_tri] in the caller's triangle order (bytes must be 7 * n_tri * 8) and the number of samples; synchronizes the
+ * level's stream */
+int  ludwig_surface_stats_download(LudwigSurfaceStats *stats, double *sums, size_t bytes, int64_t *n_samples);
+
+/* what a batch samples: each set at coarse steps start + k interval (k >= 0); a null set is not sampled */
+typedef struct LudwigBatchSamplers {
+    LudwigProbes       *probes;
+    int64_t             probes_start_step;
+    int32_t             probes_interval;
+    LudwigSurfaceStats *surface;
+    int64_t             surface_start_step;
+    int32_t             surface_interval;
+} LudwigBatchSamplers;
+/* ludwig_execute_timestep_batch with the samplers of s sampled inside the batch: the probes as ludwig_execute_timestep_batch_probes
+ * does, the surface set with one launch on its level's own stream, right after that level's last sub-step of a sampled coarse step.
+ * s = NULL, or both sets null, is ludwig_execute_timestep_batch itself. Fails before stepping anything with LUDWIG_ERR_INVALID if
+ * the surface set's level is not in `levels` or its interval < 1, and as ludwig_execute_timestep_batch_probes for the probes. */
+int  ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
+                                           float u_curr, const LudwigStepFlags *flags, const LudwigBatchSamplers *s);
+
 /* ---- halo exchange helpers (no reference counterpart: the reference is single-device) ---- */
 /* dst[i] = field[index[i]] / field[index[i]] = src[i]; index, dst, src are DEVICE pointers, index holds element
  * offsets into the field in the reference layout. hip_stream: the stream to queue on (hipStream_t), NULL = the

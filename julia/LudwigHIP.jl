@@ -33,6 +33,18 @@ struct StepFlags               # LudwigStepFlags
     c_wale::Float32; nu_sgs_background::Float32; inlet_turbulence::Float32; q_min_threshold::Float32
 end
 
+struct SurfaceParams           # LudwigSurfaceParams
+    dx::Float32; tau::Float32
+    offset_x::Float32; offset_y::Float32; offset_z::Float32
+    pressure_scale::Float32; stress_scale::Float32
+    search_radius::Int32
+end
+
+struct BatchSamplers           # LudwigBatchSamplers
+    probes::Ptr{Cvoid}; probes_start_step::Int64; probes_interval::Int32
+    surface::Ptr{Cvoid}; surface_start_step::Int64; surface_interval::Int32
+end
+
 mutable struct DeviceLevel
     handle::Ptr{Cvoid}
     level_id::Int; tau::Float32; n_blocks::Int
@@ -154,6 +166,30 @@ function probes_download!(values::Array{Float32,3}, steps::Vector{Int64}, p::Ptr
     return Int(n[])
 end
 
+# surface statistics (no reference counterpart): 7 float64 sums per triangle of p, p^2, tau, |tau|, |tau|^2 at its nearest fluid cell
+"""a surface set on `grid`: per triangle its nearest fluid cell (0-based reference block index, -1 = none; cell x + 8y + 64z), wall
+distance in lattice units and normal (3 x n); tau and the two scales from `sp`. Free it with `surface_stats_destroy`."""
+function surface_stats_create(grid::DeviceLevel, blocks::Vector{Int32}, cells::Vector{Int32}, wall_dist::Vector{Float32},
+                              normals::Matrix{Float32}, sp::SurfaceParams)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve blocks cells wall_dist normals check(ccall((:ludwig_surface_stats_create, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ref{SurfaceParams}, Ref{Ptr{Cvoid}}),
+        grid.handle, Int32(length(blocks)), blocks, cells, wall_dist, normals, sp, out))
+    return out[]
+end
+surface_stats_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_surface_stats_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+surface_stats_reset!(s::Ptr{Cvoid}) = check(ccall((:ludwig_surface_stats_reset, LIB), Cint, (Ptr{Cvoid},), s))
+"""one sample of the state the level's sub-step `timestep` wrote (queued on the level's stream)"""
+surface_stats_accumulate!(s::Ptr{Cvoid}, timestep::Integer) =
+    check(ccall((:ludwig_surface_stats_accumulate, LIB), Cint, (Ptr{Cvoid}, Int64), s, Int64(timestep)))
+"""the sums into `sums` (n_tri x 7: S_p, S_pp, S_tau_x, S_tau_y, S_tau_z, S_|tau|, S_|tau|^2); returns the number of samples"""
+function surface_stats_download!(sums::Matrix{Float64}, s::Ptr{Cvoid})
+    n = Ref{Int64}(0)
+    GC.@preserve sums check(ccall((:ludwig_surface_stats_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Csize_t, Ref{Int64}),
+                                  s, sums, sizeof(sums), n))
+    return Int(n[])
+end
+
 """
 Multi-GPU hosts only: a HIP stream for the stepping kernels that leaves `reserved_cus` compute units to the halo exchange
 (`ludwig_stream_create`, include/ludwig_hip.h); hand it to `ludwig_level_set_stream`. No counterpart in the reference.
@@ -272,6 +308,15 @@ function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch
                                      (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{Cvoid}, Int64, Int32),
                                      handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, probes,
                                      Int64(start_step), Int32(interval)))
+end
+
+"""execute_timestep_batch! with the probe set and the surface set of `s` sampled inside the batch (either may be C_NULL)"""
+function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                                 s::BatchSamplers)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    GC.@preserve handles check(ccall((:ludwig_execute_timestep_batch_sampled, LIB), Cint,
+                                     (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ref{BatchSamplers}),
+                                     handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, s))
 end
 
 end # module

@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "ludwig_level_gradient_fields_compute", "ludwig_level_gradient_fields_download",
     "ludwig_probes_create", "ludwig_probes_destroy", "ludwig_probes_sample", "ludwig_probes_download",
     "ludwig_execute_timestep_batch_probes",
+    "ludwig_surface_stats_create", "ludwig_surface_stats_destroy", "ludwig_surface_stats_reset", "ludwig_surface_stats_accumulate",
+    "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -83,6 +85,13 @@ class SurfaceParams(C.Structure):
     _fields_ = [
         ("dx", C.c_float), ("tau", C.c_float), ("offset_x", C.c_float), ("offset_y", C.c_float), ("offset_z", C.c_float),
         ("pressure_scale", C.c_float), ("stress_scale", C.c_float), ("search_radius", C.c_int32),
+    ]
+
+
+class BatchSamplers(C.Structure):
+    _fields_ = [
+        ("probes", C.c_void_p), ("probes_start_step", C.c_int64), ("probes_interval", C.c_int32),
+        ("surface", C.c_void_p), ("surface_start_step", C.c_int64), ("surface_interval", C.c_int32),
     ]
 
 
@@ -170,6 +179,12 @@ def load() -> C.CDLL:
         "ludwig_probes_sample": (C.c_int, [vp, i32, i64]),
         "ludwig_probes_download": (C.c_int, [vp, vp, vp, i32, C.POINTER(C.c_int32)]),
         "ludwig_execute_timestep_batch_probes": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), vp, i64, i32]),
+        "ludwig_surface_stats_create": (C.c_int, [vp, i32, vp, vp, vp, vp, C.POINTER(SurfaceParams), C.POINTER(vp)]),
+        "ludwig_surface_stats_destroy": (None, [vp]),
+        "ludwig_surface_stats_reset": (C.c_int, [vp]),
+        "ludwig_surface_stats_accumulate": (C.c_int, [vp, i64]),
+        "ludwig_surface_stats_download": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int64)]),
+        "ludwig_execute_timestep_batch_sampled": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

@@ -19,6 +19,7 @@ import numpy as np
 from . import forces as forces_mod
 from . import probes as probes_mod
 from . import statistics as stats_mod
+from . import surface_stats as surface_mod
 from .blocks import adapt
 from .preprocess import CaseConfig, DomainParameters, setup_multilevel_domain, solver_params
 from .solver_control import execute_timestep_batch, ramp_velocity
@@ -45,10 +46,11 @@ class HipStepper:
             d.init_equilibrium()               # src/main.jl:126-135 (every state array: nothing of the host's to upload first)
         self.probes = None                     # probes_setup
         self._series = None
+        self.surface = None                    # surface_stats_setup
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.probes is None:
-            execute_timestep_batch(self.dev, t_start, n, u_curr, params)
+            execute_timestep_batch(self.dev, t_start, n, u_curr, params, surface=self.surface)
             return
         # sampled inside the C batch, the ring drained after it; a batch with more samples than the ring holds is cut where it fills
         # (the same inlet speed: the same steps, the same bits)
@@ -58,7 +60,7 @@ class HipStepper:
             if probes_mod.samples_in(t, end, P.start_step, P.interval) > P.capacity:
                 first = P.start_step + max(0, -(-(t - P.start_step) // P.interval)) * P.interval
                 seg_end = first + (P.capacity - 1) * P.interval
-            execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P)
+            execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P, surface=self.surface)
             self._series.append(*P.download())
             t = seg_end + 1
 
@@ -73,6 +75,21 @@ class HipStepper:
     def probes_series(self):
         """(coarse steps [n] int64, values [n, n_probes, 4] float32: rho, ux, uy, uz) of every sample so far"""
         return self._series.arrays()
+
+    # -- surface statistics (no reference counterpart) --
+    def surface_stats_setup(self, mesh, params, start_step: int = 1, interval: int = 1):
+        """accumulate the wall loads of `mesh` on the finest level at coarse steps start_step + k interval, inside every batch; returns
+        the surface_stats.SurfacePlan"""
+        fin = len(self.host) - 1
+        plan = surface_mod.plan_surface(mesh, self.host[fin], params)
+        if self.surface is not None:
+            self.surface.close()
+        self.surface = surface_mod.DeviceSurfaceStats(plan, self.dev[fin], fin, self.host[fin].tau, params, max(int(start_step), 1), interval)
+        return plan
+
+    def surface_stats_sums(self):
+        """(sums [7, n_tri] Float64, samples) of the surface set"""
+        return self.surface.download()
 
     def field(self, level: int, name: str) -> np.ndarray:
         return self.dev[level].download(name)
@@ -115,6 +132,9 @@ class HipStepper:
         if self.probes is not None:
             self.probes.close()
             self.probes = None
+        if self.surface is not None:
+            self.surface.close()
+            self.surface = None
         for d in self.dev:
             d.close()
 
@@ -156,6 +176,8 @@ class DistributedStepper:
         self._tri = {}                         # level -> static triangle map (see surface_forces)
         self._probe_cfg = None                 # probes_setup: (plan, start_step, interval, capacity)
         self.probes = None                     # this rank's probe set (None: it owns no probe)
+        self._surface_cfg = None               # surface_stats_setup: (plan, params, start_step, interval)
+        self.surface = None                    # this rank's surface set (None: it holds no copy of the finest level)
 
     def _level_owner(self, level: int) -> np.ndarray:
         g = self.host[level]
@@ -190,14 +212,20 @@ class DistributedStepper:
             self._probe_cols = mine
             self._probe_pending = 0
             self._series = probes_mod.Series(local.n)          # this rank's probes, in the order of _probe_cols
+        if self._surface_cfg is not None:
+            self._surface_create()
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.runner is None:
             self._start(params)
         self.runner.params = params
-        P = self.probes
+        P, S = self.probes, self.surface
+        fin = len(self.host) - 1
         for t in range(t_start, t_start + n):
             self.runner.step(t, u_curr)
+            if S is not None and S.is_sample_step(t):
+                self.runner._join(fin)
+                S.accumulate(stats_mod.t_sub_after(fin, t))
             if P is not None and probes_mod.is_sample_step(t, P.start_step, P.interval):
                 if self._probe_pending == P.capacity:
                     self._series.append(*P.download())
@@ -238,6 +266,57 @@ class DistributedStepper:
             assert vals.shape == (steps.size, len(cols), 4)
             out[:, cols] = vals
         return steps, out
+
+    # -- surface statistics: each rank accumulates the triangles whose cell it owns (the rule of _triangle_map); per-triangle sums do
+    # not depend on the partition, so the gathered sums are one device's bit for bit --
+    def surface_stats_setup(self, mesh, params, start_step: int = 1, interval: int = 1):
+        """returns the global surface_stats.SurfacePlan; the rank's set is made with the first batch (or now, after it)"""
+        if int(interval) < 1:
+            raise ValueError(f"surface statistics: interval {interval} < 1")
+        fin = len(self.host) - 1
+        plan = surface_mod.plan_surface(mesh, self.host[fin], params)
+        if self.surface is not None:
+            self.surface.close()
+            self.surface = None
+        self._surface_cfg = (plan, params, max(int(start_step), 1), int(interval))
+        if self.runner is not None:
+            self._surface_create()
+        return plan
+
+    def _surface_create(self) -> None:
+        plan, params, start, interval = self._surface_cfg
+        fin = len(self.host) - 1
+        owner = self._level_owner(fin)
+        self._surface_sel = np.flatnonzero(plan.found & (owner[np.maximum(plan.blocks, 0)] == self.rank))
+        lv, view = self.runner.levels[fin], self.runner.views[fin]
+        if lv is None:
+            assert self._surface_sel.size == 0
+            return
+        g2l = np.full(self.host[fin].n_blocks, -1, dtype=np.int64)
+        g2l[view.local_to_global[: view.n_owned]] = np.arange(view.n_owned)
+        local = plan.subset(self._surface_sel)
+        local.blocks = g2l[local.blocks].astype(np.int32)
+        assert (local.blocks >= 0).all()
+        self.surface = surface_mod.DeviceSurfaceStats(local, lv, fin, self.host[fin].tau, params, start, interval)
+
+    def surface_stats_sums(self):
+        """(sums [7, n_tri] Float64 in triangle order, samples) on rank 0 (None elsewhere); collective"""
+        plan = self._surface_cfg[0]
+        mine = None
+        if self.surface is not None:
+            sums, n = self.surface.download()
+            mine = (self._surface_sel, sums, n)
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        if self.rank != 0:
+            return None
+        out = np.zeros((len(surface_mod.COMPONENTS), plan.n), dtype=np.float64)
+        n = 0
+        for part in parts:
+            if part is not None:
+                sel, sums, n = part
+                out[:, sel] = sums
+        return out, n
 
     # -- collectives of a few scalars --
     def _comm_device(self):
@@ -390,6 +469,9 @@ class DistributedStepper:
         if self.probes is not None:
             self.probes.close()
             self.probes = None
+        if self.surface is not None:
+            self.surface.close()
+            self.surface = None
         if self.runner is not None:
             self.runner.close()          # plans, communicator, levels; the views and plans stay readable (statistics)
 
@@ -426,7 +508,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     derivatives per unit length of the file's coordinates (scale 1/dx). Unlike the reference (main.jl:79) an
     existing directory is NOT emptied first. write_files=False on all ranks but one of a distributed run.
     With cfg.probes_enabled, probes_points.csv is written once and probes.csv gains the new samples at every diagnostics step and at
-    the end of the run (probes.py); batches are not cut for probes."""
+    the end of the run (probes.py); batches are not cut for probes.
+    With cfg.surface_statistics_enabled, the finest level's wall loads are accumulated per triangle (surface_stats.py) - inside the
+    batches where the stepper offers surface_stats_setup, else on the host from downloaded fields with batches cut at the sampled
+    steps - and every output step once a sample exists writes surface_mean_%06d.vtu and a forces_mean.csv row."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
@@ -442,12 +527,25 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     writing = out_dir is not None and write_files
     if probes_on:
         st.probes_setup(pplan, cfg.probes_start_step, cfg.probes_interval, max(batch, 1))
+    surf_on = bool(cfg.surface_statistics_enabled)
+    surf_start, surf_interval = cfg.surface_statistics_start_step, cfg.surface_statistics_interval
+    fin = len(grids) - 1
+    surf_host = None                     # the host fallback (a stepper without surface_stats_setup)
+    if surf_on:
+        if hasattr(st, "surface_stats_setup"):
+            splan = st.surface_stats_setup(mesh, params, surf_start, surf_interval)
+        else:
+            splan = surface_mod.plan_surface(mesh, grids[fin], params)
+            surf_host = surface_mod.HostSurfaceStats(splan, grids[fin].tau, params, surf_start, surf_interval)
     if writing:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "convergence.csv"), "w") as io:
             io.write(out_mod.CONVERGENCE_CSV_HEADER + "\n")
         if cfg.forces_enabled:
             out_mod.write_force_csv_header(os.path.join(out_dir, "forces.csv"))
+        if surf_on:
+            with open(os.path.join(out_dir, "forces_mean.csv"), "w") as io:
+                io.write(surface_mod.FORCES_MEAN_CSV_HEADER + "\n")
         if probes_on:
             probes_mod.write_points_csv(os.path.join(out_dir, "probes_points.csv"), pplan, grids)
             with open(os.path.join(out_dir, "probes.csv"), "w") as io:
@@ -475,17 +573,26 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if stats_on:
+            if stats_on or surf_host is not None:
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
+                cuts = set()
+                if stats_on:
+                    cuts.update(stats_mod.sample_steps(t, batch_end, cfg.statistics_start_step, cfg.statistics_interval))
+                if surf_host is not None:
+                    cuts.update(stats_mod.sample_steps(t, batch_end, surf_start, surf_interval))
                 seg = t
-                for s_step in stats_mod.sample_steps(t, batch_end, cfg.statistics_start_step, cfg.statistics_interval):
+                for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
-                    if s_step == cfg.statistics_start_step:
-                        st.stats_reset()
-                        stats_window = [0, s_step, s_step]
-                    st.stats_sample(s_step)
-                    stats_window[0] += 1
-                    stats_window[2] = s_step
+                    if stats_on and stats_mod.is_sample_step(s_step, cfg.statistics_start_step, cfg.statistics_interval):
+                        if s_step == cfg.statistics_start_step:
+                            st.stats_reset()
+                            stats_window = [0, s_step, s_step]
+                        st.stats_sample(s_step)
+                        stats_window[0] += 1
+                        stats_window[2] = s_step
+                    if surf_host is not None and stats_mod.is_sample_step(s_step, surf_start, surf_interval):
+                        t_sub = stats_mod.t_sub_after(fin, s_step)
+                        surf_host.accumulate(st.field(fin, "rho"), st.field(fin, "vel_temp" if t_sub % 2 == 0 else "vel"))
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)
@@ -551,6 +658,16 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         finals = {lvl: st.statistics(lvl) for lvl in sorted({l for l, _ in mesh_arrays_needed})}   # collective
                         if writing:
                             out_mod.export_mean_mesh(out_step, grids, finals.__getitem__, tuple(stats_window), out_dir)
+                    if surf_on:
+                        got = surf_host.download() if surf_host is not None else st.surface_stats_sums()        # collective
+                        if writing and got is not None and got[1] > 0:
+                            window = surface_mod.window_of(got[1], surf_start, surf_interval)
+                            fin_stats = surface_mod.finalize(got[0], got[1], params)
+                            surface_mod.save_surface_mean_vtk(os.path.join(out_dir, "surface_mean_%06d" % out_step), mesh, fin_stats,
+                                                              splan.found, window)
+                            fr_mean = surface_mod.mean_forces(mesh, fin_stats, params, cfg.symmetric_analysis)
+                            with open(os.path.join(out_dir, "forces_mean.csv"), "a") as io:
+                                io.write(surface_mod.forces_mean_csv_row(out_step, window, fr_mean) + "\n")
             t = batch_end + 1
         if probes_on:
             flush_probes()

@@ -1728,17 +1728,50 @@ static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub)
     return LUDWIG_OK;
 }
 
-// Probe sampling inside a batch (ludwig_execute_timestep_batch_probes): the coarse step being run and its ring slot, -1 = not sampled.
-struct ProbeHook {
+// ---- surface statistics (ludwig_surface_stats_*; no reference counterpart) ----
+// Per triangle, in the caller's order: the nearest fluid cell in the internal block order (-1: none), and [4][n] floats of wall distance
+// and normal; [SURFACE_STAT_COMPONENTS][n] float64 sums. The set does not own its level.
+struct LudwigSurfaceStats {
+    LudwigLevel *level = nullptr;
+    int device = 0, n_tri = 0;
+    float tau = 0.0f, pressure_scale = 0.0f, stress_scale = 0.0f;
+    int32_t *cell = nullptr;
+    float *rec = nullptr;
+    double *sums = nullptr;
+    int64_t n_samples = 0;
+};
+
+static int surface_stats_launch(LudwigSurfaceStats *S, int64_t t_sub)
+{
+    LudwigLevel *L = S->level;
+    if (S->n_tri > 0) {
+        {   // rho as a download would return it now; a no-op on the level, which stores it every step since the set was made
+            const int r = ensure_rho(L);
+            if (r) return r;
+        }
+        const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];  // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+        hipLaunchKernelGGL(k_accumulate_surface_stats, dim3((unsigned)((S->n_tri + 255) / 256)), dim3(256), 0, L->stream, S->sums, S->cell,
+                           S->rec, S->n_tri, L->rho, vel, S->tau, S->pressure_scale, S->stress_scale);
+        LW_HIP(hipGetLastError());
+    }
+    ++S->n_samples;
+    return LUDWIG_OK;
+}
+
+// Sampling inside a batch (ludwig_execute_timestep_batch_sampled): the coarse step being run, the probes' ring slot (-1 = not sampled)
+// and whether the surface set samples this step.
+struct BatchHook {
     LudwigProbes *P = nullptr;
+    LudwigSurfaceStats *S = nullptr;
     int64_t t = 0;
     int slot = -1;
+    bool surface = false;
 };
 static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub);
 
 static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-based*/, int64_t t_sub, const LudwigLevel *parent,
                           float parent_tau, float temporal_weight, float u_vel, const LudwigStepFlags *fl, bool concurrent,
-                          const ProbeHook *ph = nullptr)
+                          const BatchHook *ph = nullptr)
 {
     // recursive_step! / recursive_step_temporal!, reference src/solver_control.jl:21-143
     if (lvl > n_levels) return LUDWIG_OK;
@@ -1790,11 +1823,14 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         LW_HIP(hipEventRecord(L->ev_stepped, L->stream));
         ++L->stepped_gen;
     }
-    if (ph && ph->slot >= 0) {
-        // the level's last sub-step of a sampled coarse step: the probes of this level read its newest rho / vel on its own stream,
-        // behind the step (and behind the event its children wait for) and ahead of the next write to either
+    if (ph && (ph->slot >= 0 || ph->surface)) {
+        // the level's last sub-step of a sampled coarse step: the probes and the surface set of this level read its newest rho / vel
+        // on its own stream, behind the step (and behind the event its children wait for) and ahead of the next write to either
         const int64_t m = (int64_t)1 << (lvl - 1);
-        if (t_sub == m * ph->t + m - 1 && (rc = probes_launch(ph->P, lvl - 1, ph->slot, t_sub))) return rc;
+        if (t_sub == m * ph->t + m - 1) {
+            if (ph->slot >= 0 && (rc = probes_launch(ph->P, lvl - 1, ph->slot, t_sub))) return rc;
+            if (ph->surface && ph->S->level == L && (rc = surface_stats_launch(ph->S, t_sub))) return rc;
+        }
     }
     if (has_children) {
         if ((rc = recursive_step(levels, n_levels, lvl + 1, 2 * t_sub, L, L->tau, 0.0f, u_vel, fl, concurrent, ph))) return rc;
@@ -1815,19 +1851,21 @@ static int check_batch_levels(LudwigLevel *const *levels, int32_t n_levels, int3
 }
 
 static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval);
+                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s);
 
 int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                                   const LudwigStepFlags *flags)
 {
     const int r = check_batch_levels(levels, n_levels, batch_size, flags);
     if (r) return r;
-    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr, 0, 1);
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr);
 }
 
 static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval)
+                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s)
 {
+    LudwigProbes *probes = s ? s->probes : nullptr;
+    LudwigSurfaceStats *surface = s ? s->surface : nullptr;
     const bool concurrent = n_levels > 1 && level_streams();
     hipStream_t user_stream = levels[0]->stream;
     if (concurrent) {
@@ -1888,14 +1926,16 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
     int rc = LUDWIG_OK;
     for (int32_t o = 0; o < batch_size && rc == LUDWIG_OK; ++o) {
         const int64_t t = t_start + o;
-        if (!probes) {
+        if (!probes && !surface) {
             rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent);
             continue;
         }
-        ProbeHook ph;
+        BatchHook ph;
         ph.P = probes;
+        ph.S = surface;
         ph.t = t;
-        if (probe_step_sampled(t, start_step, interval)) ph.slot = probes_open_slot(probes, t);
+        if (probes && probe_step_sampled(t, s->probes_start_step, s->probes_interval)) ph.slot = probes_open_slot(probes, t);
+        ph.surface = surface && probe_step_sampled(t, s->surface_start_step, s->surface_interval);
         rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
     }
     if (concurrent) {
@@ -2260,19 +2300,132 @@ int ludwig_probes_download(LudwigProbes *P, float *values, int64_t *steps, int32
 int ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                                          const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval)
 {
+    LudwigBatchSamplers s{};
+    s.probes = probes;
+    s.probes_start_step = start_step;
+    s.probes_interval = interval;
+    return ludwig_execute_timestep_batch_sampled(levels, n_levels, t_start, batch_size, u_curr, flags, &s);
+}
+
+int ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                          const LudwigStepFlags *flags, const LudwigBatchSamplers *s)
+{
     int r = check_batch_levels(levels, n_levels, batch_size, flags);
     if (r) return r;
-    if (!probes) return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr, 0, 1);
-    if (interval < 1) return fail(LUDWIG_ERR_INVALID, "probes: interval %d < 1", interval);
-    if (probes->n_levels != n_levels) return fail(LUDWIG_ERR_INVALID, "probes: set made over %d levels, batch of %d", probes->n_levels, n_levels);
-    for (int i = 0; i < n_levels; ++i)
-        if (probes->levels[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "probes: set made over other levels (level %d)", i + 1);
-    // nothing is stepped when the batch's samples would not fit
-    const int64_t k = batch_size > 0 ? probe_samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
-    if ((int64_t)probes->slot_step.size() + k > probes->capacity)
-        return fail(LUDWIG_ERR_STATE, "probes: %lld samples of this batch overflow the ring (%d of %d used): download first", (long long)k,
-                    (int)probes->slot_step.size(), probes->capacity);
-    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, probes, start_step, interval);
+    if (!s || (!s->probes && !s->surface)) return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr);
+    if (LudwigProbes *probes = s->probes) {
+        const int32_t interval = s->probes_interval;
+        const int64_t start_step = s->probes_start_step;
+        if (interval < 1) return fail(LUDWIG_ERR_INVALID, "probes: interval %d < 1", interval);
+        if (probes->n_levels != n_levels) return fail(LUDWIG_ERR_INVALID, "probes: set made over %d levels, batch of %d", probes->n_levels, n_levels);
+        for (int i = 0; i < n_levels; ++i)
+            if (probes->levels[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "probes: set made over other levels (level %d)", i + 1);
+        // nothing is stepped when the batch's samples would not fit
+        const int64_t k = batch_size > 0 ? probe_samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
+        if ((int64_t)probes->slot_step.size() + k > probes->capacity)
+            return fail(LUDWIG_ERR_STATE, "probes: %lld samples of this batch overflow the ring (%d of %d used): download first", (long long)k,
+                        (int)probes->slot_step.size(), probes->capacity);
+    }
+    if (const LudwigSurfaceStats *S = s->surface) {
+        if (s->surface_interval < 1) return fail(LUDWIG_ERR_INVALID, "surface statistics: interval %d < 1", s->surface_interval);
+        bool in_batch = false;
+        for (int i = 0; i < n_levels; ++i) in_batch = in_batch || levels[i] == S->level;
+        if (!in_batch) return fail(LUDWIG_ERR_INVALID, "surface statistics: the set's level is not in the batch");
+    }
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s);
+}
+
+void ludwig_surface_stats_destroy(LudwigSurfaceStats *S)
+{
+    if (!S) return;
+    (void)hipSetDevice(S->device);
+    if (S->cell) (void)hipFree(S->cell);
+    if (S->rec) (void)hipFree(S->rec);
+    if (S->sums) (void)hipFree(S->sums);
+    delete S;
+}
+
+int ludwig_surface_stats_create(LudwigLevel *L, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *wall_dist,
+                                const float *normals, const LudwigSurfaceParams *sp, LudwigSurfaceStats **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!L || !sp || n_tri < 0 || (n_tri > 0 && (!blocks || !cells || !wall_dist || !normals))) return fail(LUDWIG_ERR_INVALID, "null argument");
+    // the kernel indexes cells as internal block * 512 + cell in 32 bits
+    if (n_tri > 0 && (int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "surface statistics: level has %d blocks, more than 32-bit cell indices reach", L->n_blocks);
+    // everything is checked before anything is allocated
+    std::vector<int32_t> hc((size_t)n_tri);
+    std::vector<float> hr((size_t)n_tri * 4);
+    for (int32_t i = 0; i < n_tri; ++i) {
+        const int32_t b = blocks[i], x = cells[i];
+        if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "surface statistics: triangle %d: block %d not in -1..%d", i, b, L->n_blocks - 1);
+        if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "surface statistics: triangle %d: cell %d not in 0..511", i, x);
+        hc[i] = b < 0 ? -1 : (L->ref2int.empty() ? b : L->ref2int[b]) * CELLS + x;
+        hr[i] = wall_dist[i];
+        for (int a = 0; a < 3; ++a) hr[(size_t)(a + 1) * n_tri + i] = normals[3 * i + a];
+    }
+    LudwigSurfaceStats *S = new (std::nothrow) LudwigSurfaceStats;
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "surface statistics: out of host memory");
+    S->level = L;
+    S->device = L->device;
+    S->n_tri = n_tri;
+    S->tau = sp->tau;
+    S->pressure_scale = sp->pressure_scale;
+    S->stress_scale = sp->stress_scale;
+    LW_HIP(hipSetDevice(S->device));
+    int r = LUDWIG_OK;
+    if (n_tri > 0) {
+        const size_t n = (size_t)n_tri;
+        hipError_t e = hipMalloc((void **)&S->cell, n * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&S->rec, n * 16);
+        if (e == hipSuccess) e = hipMalloc((void **)&S->sums, n * SURFACE_STAT_COMPONENTS * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(S->cell, hc.data(), n * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S->rec, hr.data(), n * 16, hipMemcpyHostToDevice);
+        // zeroed on the level's stream: ahead of every sample, which is queued there (or on a batch's level stream, which starts behind it)
+        if (e == hipSuccess) e = hipMemsetAsync(S->sums, 0, n * SURFACE_STAT_COMPONENTS * sizeof(double), L->stream);
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "surface statistics: %d triangles: %s", n_tri, hipGetErrorString(e));
+    }
+    // a sample reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now on
+    // (+4 of 216 B per cell where the store was elided), so a batch never replays it
+    if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(L, 1);
+    if (r != LUDWIG_OK) {
+        ludwig_surface_stats_destroy(S);
+        return r;
+    }
+    *out = S;
+    return LUDWIG_OK;
+}
+
+int ludwig_surface_stats_reset(LudwigSurfaceStats *S)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null surface statistics set");
+    S->n_samples = 0;
+    if (S->n_tri == 0) return LUDWIG_OK;
+    LW_HIP(hipSetDevice(S->device));
+    LW_HIP(hipMemsetAsync(S->sums, 0, (size_t)S->n_tri * SURFACE_STAT_COMPONENTS * sizeof(double), S->level->stream));
+    return LUDWIG_OK;
+}
+
+int ludwig_surface_stats_accumulate(LudwigSurfaceStats *S, int64_t t_sub)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null surface statistics set");
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "surface statistics: t_sub %lld < 0", (long long)t_sub);
+    LW_HIP(hipSetDevice(S->device));
+    return surface_stats_launch(S, t_sub);
+}
+
+int ludwig_surface_stats_download(LudwigSurfaceStats *S, double *sums, size_t bytes, int64_t *n_samples)
+{
+    if (!S || (!sums && bytes > 0)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    const size_t want = (size_t)S->n_tri * SURFACE_STAT_COMPONENTS * sizeof(double);
+    if (bytes != want) return fail(LUDWIG_ERR_INVALID, "surface statistics: got %zu bytes, expected %zu", bytes, want);
+    if (n_samples) *n_samples = S->n_samples;
+    if (want == 0) return LUDWIG_OK;
+    LW_HIP(hipSetDevice(S->device));
+    LW_HIP(hipStreamSynchronize(S->level->stream));
+    LW_HIP(hipMemcpy(sums, S->sums, want, hipMemcpyDeviceToHost));
+    return LUDWIG_OK;
 }
 
 int ludwig_halo_pack(const LudwigLevel *L, int field, const int64_t *index_dev, int64_t n, float *dst_dev, void *hip_stream)

@@ -98,6 +98,11 @@ class CaseConfig:
     statistics_enabled: bool = False
     statistics_start_step: int = 1      # first sampled coarse step (the sums are reset there); YAML default: ramp_steps
     statistics_interval: int = 10       # coarse steps between samples
+    # surface statistics, advanced.surface_statistics (no reference counterpart): per-triangle mean / rms wall loads of the finest level,
+    # written to surface_mean_%06d.vtu and forces_mean.csv on output steps (surface_stats.py)
+    surface_statistics_enabled: bool = False
+    surface_statistics_start_step: int = 1      # first sampled coarse step; YAML default: ramp_steps
+    surface_statistics_interval: int = 1        # coarse steps between samples
     # probes, advanced.probes (no reference counterpart): rho, u at points every `interval` coarse steps from `start_step`, written to
     # probes.csv / probes_points.csv; points in the STL's frame after stl_scale (probes.py)
     probes_enabled: bool = False
@@ -133,6 +138,10 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     stats_interval = int(g("advanced", "statistics", "interval", default=10))
     if stats_interval < 1:
         raise ValueError(f"advanced.statistics.interval must be >= 1, got {stats_interval}")
+    surf_start = int(g("advanced", "surface_statistics", "start_step", default=ramp_steps))
+    surf_interval = int(g("advanced", "surface_statistics", "interval", default=1))
+    if surf_interval < 1:
+        raise ValueError(f"advanced.surface_statistics.interval must be >= 1, got {surf_interval}")
     probes = _probes_config(g("advanced", "probes", default=None))
     return CaseConfig(
         stl_file=g("basic", "stl_file", required=True), stl_scale=float(g("basic", "stl_scale", required=True)),
@@ -180,6 +189,8 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
                               if bool(g("basic", "simulation", "output_fields", key, default=False))),
         statistics_enabled=bool(g("advanced", "statistics", "enabled", default=False)),
         statistics_start_step=max(stats_start, 1), statistics_interval=stats_interval,
+        surface_statistics_enabled=bool(g("advanced", "surface_statistics", "enabled", default=False)),
+        surface_statistics_start_step=max(surf_start, 1), surface_statistics_interval=surf_interval,
         **probes,
     )
 
