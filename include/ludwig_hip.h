@@ -356,6 +356,28 @@ typedef struct LudwigBatchSamplers {
 int  ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                            float u_curr, const LudwigStepFlags *flags, const LudwigBatchSamplers *s);
 
+/* ---- slices: planar grids of points sampled after a coarse step (no reference counterpart) ----
+ * A slice set is made over a level array. Point p with valid[p] != 0 lives on level level_index[p] (0-based) and has the probes'
+ * stencil: 8 corners c = dx + 2 dy + 4 dz (reference block index blocks[8p + c], cell cells[8p + c] = x + 8 y + 64 z), corner 0 the
+ * base cell, every corner that is no fluid cell of the level already replaced by the base cell, and weights[3p + 0..2] in [0, 1].
+ * The base cell's block must be owned (its neighbour row reaches every cell a point reads: the corners and their face neighbours).
+ * Points with valid[p] == 0 are not read and sample as 0. A sample is rows [n_rows][n_points] floats: rho, ux, uy, uz, |u| =
+ * sqrt((ux^2 + uy^2) + uz^2), and with LUDWIG_SLICE_GRADIENT in flags vorticity x, y, z and Q - the trilinear interpolation of the
+ * cell values ludwig_level_gradient_fields_compute gives with scales[level]. Interpolation is ludwig_probes_*'s, bit for bit.
+ * Entries of `levels` no valid point refers to may be null. */
+typedef struct LudwigSlices LudwigSlices;   /* opaque */
+enum { LUDWIG_SLICE_GRADIENT = 1 };
+int  ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_points, const int32_t *level_index,
+                          const int32_t *blocks, const int32_t *cells, const float *weights, const uint8_t *valid,
+                          const float *scales, int32_t flags, LudwigSlices **out);
+/* frees the set, not the levels */
+void ludwig_slices_destroy(LudwigSlices *slices);
+/* sample every point on its level's newest state after coarse step t_coarse: level index li has then finished sub-step
+ * t_sub = 2^li (t_coarse + 1) - 1, whose velocity is vel_temp if t_sub is even, vel if odd. One launch per level, on its stream. */
+int  ludwig_slices_sample(LudwigSlices *slices, int64_t t_coarse);
+/* the last sample: bytes = n_rows * n_points * 4 (n_rows 5, or 9 with LUDWIG_SLICE_GRADIENT). Synchronizes the levels' streams. */
+int  ludwig_slices_download(LudwigSlices *slices, float *values, size_t bytes);
+
 /* ---- halo exchange helpers (no reference counterpart: the reference is single-device) ---- */
 /* dst[i] = field[index[i]] / field[index[i]] = src[i]; index, dst, src are DEVICE pointers, index holds element
  * offsets into the field in the reference layout. hip_stream: the stream to queue on (hipStream_t), NULL = the

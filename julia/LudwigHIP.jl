@@ -166,6 +166,27 @@ function probes_download!(values::Array{Float32,3}, steps::Vector{Int64}, p::Ptr
     return Int(n[])
 end
 
+# slices (no reference counterpart): planar grids of points, the probes' stencil and trilinear, plus |u|, vorticity and Q
+const SLICE_GRADIENT = Int32(1)
+"""a slice set over `grids`: per point its 0-based level, 8 stencil corners as probes_create takes them, weights 3 x n Float32, valid
+(UInt8, 0: not read, sampled as 0), per level the gradient scale (1/dx), flags (SLICE_GRADIENT adds vorticity and Q). Free it with
+`slices_destroy`."""
+function slices_create(grids::Vector{DeviceLevel}, level::Vector{Int32}, blocks::Matrix{Int32}, cells::Matrix{Int32},
+                       weights::Matrix{Float32}, valid::Vector{UInt8}, scales::Vector{Float32}, flags::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles level blocks cells weights valid scales check(ccall((:ludwig_slices_create, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{UInt8}, Ptr{Float32}, Int32, Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int32(length(level)), level, blocks, cells, weights, valid, scales, Int32(flags), out))
+    return out[]
+end
+slices_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_slices_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""sample every point on its level's newest state after coarse step `t_coarse` (queued on the levels' streams)"""
+slices_sample!(s::Ptr{Cvoid}, t_coarse::Integer) = check(ccall((:ludwig_slices_sample, LIB), Cint, (Ptr{Cvoid}, Int64), s, Int64(t_coarse)))
+"""the last sample into values (n_points x rows: 5, or 9 with SLICE_GRADIENT)"""
+slices_download!(values::Matrix{Float32}, s::Ptr{Cvoid}) =
+    GC.@preserve values check(ccall((:ludwig_slices_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), s, values, sizeof(values)))
+
 # surface statistics (no reference counterpart): 7 float64 sums per triangle of p, p^2, tau, |tau|, |tau|^2 at its nearest fluid cell
 """a surface set on `grid`: per triangle its nearest fluid cell (0-based reference block index, -1 = none; cell x + 8y + 64z), wall
 distance in lattice units and normal (3 x n); tau and the two scales from `sp`. Free it with `surface_stats_destroy`."""

@@ -24,6 +24,8 @@ STAT_NAMES = {"rho": (STAT_RHO, 1), "vel": (STAT_VEL, 3), "vel2": (STAT_VEL2, 6)
 # enum LudwigGradField: velocity-gradient field -> (id, components)
 GRAD_VORTICITY, GRAD_Q = range(2)
 GRAD_NAMES = {"vorticity": (GRAD_VORTICITY, 3), "q": (GRAD_Q, 1)}
+# ludwig_slices_create flags
+SLICE_GRADIENT = 1
 # enum LudwigPart
 PART_ALL, PART_BOUNDARY, PART_INTERIOR = 0, 1, 2
 
@@ -46,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_execute_timestep_batch_probes",
     "ludwig_surface_stats_create", "ludwig_surface_stats_destroy", "ludwig_surface_stats_reset", "ludwig_surface_stats_accumulate",
     "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
+    "ludwig_slices_create", "ludwig_slices_destroy", "ludwig_slices_sample", "ludwig_slices_download",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -185,6 +188,10 @@ def load() -> C.CDLL:
         "ludwig_surface_stats_accumulate": (C.c_int, [vp, i64]),
         "ludwig_surface_stats_download": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int64)]),
         "ludwig_execute_timestep_batch_sampled": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers)]),
+        "ludwig_slices_create": (C.c_int, [C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)]),
+        "ludwig_slices_destroy": (None, [vp]),
+        "ludwig_slices_sample": (C.c_int, [vp, i64]),
+        "ludwig_slices_download": (C.c_int, [vp, vp, C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

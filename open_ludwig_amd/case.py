@@ -18,6 +18,7 @@ import numpy as np
 
 from . import forces as forces_mod
 from . import probes as probes_mod
+from . import slices as slices_mod
 from . import statistics as stats_mod
 from . import surface_stats as surface_mod
 from .blocks import adapt
@@ -47,6 +48,7 @@ class HipStepper:
         self.probes = None                     # probes_setup
         self._series = None
         self.surface = None                    # surface_stats_setup
+        self.slices = None                     # slices_setup
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.probes is None:
@@ -90,6 +92,22 @@ class HipStepper:
     def surface_stats_sums(self):
         """(sums [7, n_tri] Float64, samples) of the surface set"""
         return self.surface.download()
+
+    # -- slices (no reference counterpart) --
+    def slices_setup(self, plans, start_step: int = 1, interval: int = 1) -> None:
+        """one device set over the planes of `plans` (slices.plan_slice over this stepper's grids); the caller samples after the
+        coarse steps start_step + k interval (run_case cuts its batches there)"""
+        self._slice_steps = slices_mod.check_schedule(start_step, interval)
+        if self.slices is not None:
+            self.slices.close()
+        self.slices = slices_mod.DeviceSlices(plans, self.dev, self.host)
+
+    def slices_sample(self, t_coarse: int):
+        """sample every plane on the newest state after coarse step t_coarse (the last batch must have ended there; ValueError if
+        t_coarse is no sampled step): one [rows, n] float32 array per plane (slices.ROWS)"""
+        slices_mod.check_sample_step(t_coarse, *self._slice_steps)
+        self.slices.sample(t_coarse)
+        return self.slices.download()
 
     def field(self, level: int, name: str) -> np.ndarray:
         return self.dev[level].download(name)
@@ -135,6 +153,9 @@ class HipStepper:
         if self.surface is not None:
             self.surface.close()
             self.surface = None
+        if self.slices is not None:
+            self.slices.close()
+            self.slices = None
         for d in self.dev:
             d.close()
 
@@ -178,6 +199,8 @@ class DistributedStepper:
         self.probes = None                     # this rank's probe set (None: it owns no probe)
         self._surface_cfg = None               # surface_stats_setup: (plan, params, start_step, interval)
         self.surface = None                    # this rank's surface set (None: it holds no copy of the finest level)
+        self._slice_plans = None               # slices_setup: the global plans
+        self.slices = None                     # this rank's slice set (None: it owns no base block of a valid point)
 
     def _level_owner(self, level: int) -> np.ndarray:
         g = self.host[level]
@@ -196,6 +219,11 @@ class DistributedStepper:
             for p in mine:
                 li = int(plan.level[p])
                 probe_cells[li] = np.concatenate([probe_cells[li], plan.blocks[p].astype(np.int64) * 512 + plan.cells[p]])
+        if self._slice_plans is not None:
+            # the same halo rule for slice points: their stencil cells (and face neighbours) in ghost blocks join 'rho' and 'vel'
+            self._slice_mine_cache = self._slice_mine()
+            extra = self._slice_cells()
+            probe_cells = extra if probe_cells is None else [np.concatenate([a, b]) for a, b in zip(probe_cells, extra)]
         self.runner = self.partition.MultiLevelRunner(self.host, self.owners, params, self.rank, self.world, self.device, self.stage,
                                                       overlap=self.overlap, transport=self.transport, upload_state=False,
                                                       probe_cells=probe_cells)
@@ -214,6 +242,8 @@ class DistributedStepper:
             self._series = probes_mod.Series(local.n)          # this rank's probes, in the order of _probe_cols
         if self._surface_cfg is not None:
             self._surface_create()
+        if self._slice_plans is not None:
+            self._slices_create()
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.runner is None:
@@ -266,6 +296,70 @@ class DistributedStepper:
             assert vals.shape == (steps.size, len(cols), 4)
             out[:, cols] = vals
         return steps, out
+
+    # -- slices: each rank samples the points whose base cell's block it owns; corners and their face neighbours in a peer's blocks are
+    # read from the ghost copies, which the 'rho' / 'vel' halo refreshes; the samples are gathered to rank 0 in plane order --
+    def slices_setup(self, plans, start_step: int = 1, interval: int = 1) -> None:
+        """before the first batch: the stencil cells change the halo plans, which the first batch builds"""
+        if self.runner is not None:
+            raise RuntimeError("DistributedStepper.slices_setup must come before the first batch")
+        self._slice_steps = slices_mod.check_schedule(start_step, interval)
+        self._slice_plans = list(plans)
+
+    def _slice_mine(self):
+        """per plan: bool [n], the valid points whose base block this rank owns"""
+        out = []
+        for plan in self._slice_plans:
+            mine = np.zeros(plan.n, bool)
+            for li in np.unique(plan.level[plan.valid]):
+                sel = np.flatnonzero(plan.valid & (plan.level == li))
+                mine[sel] = self._level_owner(int(li))[plan.blocks[sel, 0]] == self.rank
+            out.append(mine)
+        return out
+
+    def _slice_cells(self):
+        """per level, the global cells (block * 512 + cell) this rank's slice points read"""
+        cells = [[] for _ in self.host]
+        for plan, mine in zip(self._slice_plans, self._slice_mine_cache):
+            for li in np.unique(plan.level[mine]):
+                cells[int(li)].append(slices_mod.stencil_cells(plan, np.flatnonzero(mine & (plan.level == li)), self.host[int(li)]))
+        return [np.concatenate(c) if c else np.zeros(0, np.int64) for c in cells]
+
+    def _slices_create(self) -> None:
+        g2l = []
+        for g, v in zip(self.host, self.runner.views):
+            a = np.full(g.n_blocks, -1, dtype=np.int64)
+            if v is not None:
+                a[np.asarray(v.local_to_global)] = np.arange(len(v.local_to_global))
+            g2l.append(a)
+        local = [slices_mod.local_plan(p, m, g2l) for p, m in zip(self._slice_plans, self._slice_mine_cache)]
+        if not any(p.valid.any() for p in local):
+            return
+        # as with probes: the sampled levels store rho every step, so a sample never replays an elided store over the ghost rho the
+        # halo has just refreshed
+        for li in sorted({int(l) for p in local for l in p.level[p.valid]}):
+            self.runner.levels[li].set_rho_store(True)
+        self.slices = slices_mod.DeviceSlices(local, self.runner.levels, self.host)
+
+    def slices_sample(self, t_coarse: int):
+        """every plane sampled after coarse step t_coarse (the last batch must have ended there), one [rows, n] float32 array per plane
+        on rank 0 (None elsewhere); collective"""
+        slices_mod.check_sample_step(t_coarse, *self._slice_steps)
+        mine = None
+        if self.slices is not None:
+            self.slices.sample(t_coarse)
+            vals = self.slices.download()
+            mine = [(np.flatnonzero(m), v[:, m]) for m, v in zip(self._slice_mine_cache, vals)]
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        if self.rank != 0:
+            return None
+        rows = slices_mod.ROWS_GRAD if any(p.gradient for p in self._slice_plans) else slices_mod.ROWS_BASIC
+        out = [np.zeros((rows, p.n), dtype=np.float32) for p in self._slice_plans]
+        for part in parts:
+            for k, (cols, v) in enumerate(part or ()):
+                out[k][:, cols] = v
+        return out
 
     # -- surface statistics: each rank accumulates the triangles whose cell it owns (the rule of _triangle_map); per-triangle sums do
     # not depend on the partition, so the gathered sums are one device's bit for bit --
@@ -472,6 +566,9 @@ class DistributedStepper:
         if self.surface is not None:
             self.surface.close()
             self.surface = None
+        if self.slices is not None:
+            self.slices.close()
+            self.slices = None
         if self.runner is not None:
             self.runner.close()          # plans, communicator, levels; the views and plans stay readable (statistics)
 
@@ -511,7 +608,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     the end of the run (probes.py); batches are not cut for probes.
     With cfg.surface_statistics_enabled, the finest level's wall loads are accumulated per triangle (surface_stats.py) - inside the
     batches where the stepper offers surface_stats_setup, else on the host from downloaded fields with batches cut at the sampled
-    steps - and every output step once a sample exists writes surface_mean_%06d.vtu and a forces_mean.csv row."""
+    steps - and every output step once a sample exists writes surface_mean_%06d.vtu and a forces_mean.csv row.
+    With cfg.slices_enabled, every plane is sampled after the coarse steps start_step + k interval - batches are cut there with the
+    batch's own inlet speed - on the device where the stepper offers slices_setup, else from downloaded fields (slices.host_sample);
+    each sample is written to slice_<name>_%06d.vti and listed in slice_<name>.pvd (slices.py)."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
@@ -519,6 +619,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     probes_on = bool(cfg.probes_enabled)
     # points are refused (outside the domain, inside the body) before anything is allocated on a device
     pplan = probes_mod.plan_probes(cfg.probes_points, grids, params.mesh_offset, cfg.probes_names) if probes_on else None
+    slices_on = bool(cfg.slices_enabled)
+    sl_start, sl_interval = cfg.slices_start_step, cfg.slices_interval
+    # a plane outside the domain is refused before anything is allocated on a device
+    splans = [slices_mod.plan_slice(spec, grids, params.mesh_offset) for spec in cfg.slices_planes] if slices_on else []
     st = stepper_factory(grids)
     total_steps = steps if steps is not None else cfg.steps
     rows: List[DiagRow] = []
@@ -527,6 +631,9 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     writing = out_dir is not None and write_files
     if probes_on:
         st.probes_setup(pplan, cfg.probes_start_step, cfg.probes_interval, max(batch, 1))
+    dev_slices = slices_on and hasattr(st, "slices_setup")
+    if dev_slices:
+        st.slices_setup(splans, sl_start, sl_interval)
     surf_on = bool(cfg.surface_statistics_enabled)
     surf_start, surf_interval = cfg.surface_statistics_start_step, cfg.surface_statistics_interval
     fin = len(grids) - 1
@@ -546,6 +653,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         if surf_on:
             with open(os.path.join(out_dir, "forces_mean.csv"), "w") as io:
                 io.write(surface_mod.FORCES_MEAN_CSV_HEADER + "\n")
+        if slices_on:
+            slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
         if probes_on:
             probes_mod.write_points_csv(os.path.join(out_dir, "probes_points.csv"), pplan, grids)
             with open(os.path.join(out_dir, "probes.csv"), "w") as io:
@@ -573,13 +682,15 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if stats_on or surf_host is not None:
+            if stats_on or surf_host is not None or slices_on:
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
                     cuts.update(stats_mod.sample_steps(t, batch_end, cfg.statistics_start_step, cfg.statistics_interval))
                 if surf_host is not None:
                     cuts.update(stats_mod.sample_steps(t, batch_end, surf_start, surf_interval))
+                if slices_on:
+                    cuts.update(stats_mod.sample_steps(t, batch_end, sl_start, sl_interval))
                 seg = t
                 for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
@@ -593,6 +704,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     if surf_host is not None and stats_mod.is_sample_step(s_step, surf_start, surf_interval):
                         t_sub = stats_mod.t_sub_after(fin, s_step)
                         surf_host.accumulate(st.field(fin, "rho"), st.field(fin, "vel_temp" if t_sub % 2 == 0 else "vel"))
+                    if slices_on and stats_mod.is_sample_step(s_step, sl_start, sl_interval):
+                        got = st.slices_sample(s_step) if dev_slices else slices_mod.host_sample(st, splans, grids, s_step)
+                        if writing:
+                            slice_writer.write(s_step, got)
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)

@@ -1251,6 +1251,96 @@ __global__ __launch_bounds__(64) void k_probe_sample(float *__restrict__ out, co
     *(float4 *)(out + 4 * (int64_t)col[p]) = make_float4(res[0], res[1], res[2], res[3]);
 }
 
+// ---- slices (ludwig_slices_*; no reference counterpart) ----
+// One lane per point of one level; lanes run in the order of their base cells (the host sorts them), the output index is col[p].
+// base[p] = internal block * 512 + (x + 8 y + 64 z) of the base cell; its block is OWNED, so its neighbour row is complete, and every
+// cell the point reads - the 8 corners i0 + {0,1}^3 and their 6 face neighbours, i0 - 1 .. i0 + 2 per axis - lies in that block's
+// 3 x 3 x 3 neighbourhood: slice_locate finds it through meta[base block][DIR] (-1: no block there). rep[p] bit c: corner c was
+// replaced by the base cell (the probes' rule). w[3 p + a]: weights along x, y, z. Rows of out, [row][n_set]: rho, ux, uy, uz, |u|,
+// and with GRAD vorticity x, y, z, Q. |u| = sqrt((ux^2 + uy^2) + uz^2) of the interpolated components. Vorticity and Q at a
+// corner are k_velocity_gradient_fields' cell values, computed here from the same six neighbours (a missing neighbour block: the
+// corner's own value) in the same expressions; the corners are fluid cells, so its obstacle rule never applies. Then the probes'
+// trilinear (probe_lerp, x, y, z) of every quantity. -ffp-contract=off: open_ludwig_amd/slices.py restates it bit for bit.
+constexpr int SLICE_ROWS_BASIC = 5, SLICE_ROWS_GRAD = 9;
+
+__device__ __forceinline__ int64_t slice_locate(const int32_t *__restrict__ meta, int64_t b0, int x, int y, int z)
+{
+    // x, y, z relative to the base block's origin, -1 .. 9
+    const int ox = x >> 3, oy = y >> 3, oz = z >> 3;   // arithmetic shift: -1, 0 or 1
+    int64_t b = b0;
+    if (ox | oy | oz) {
+        b = meta[b0 * NBR_STRIDE + DIR(ox, oy, oz)];
+        if (b < 0) return -1;
+    }
+    return b * CELLS + ((x & 7) + 8 * (y & 7) + 64 * (z & 7));
+}
+
+__device__ __forceinline__ float slice_vel(const float *__restrict__ vel, int64_t e, int k)
+{
+    return vel[((e >> 9) * 3 + k) * CELLS + (e & 511)];
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(64) void k_slice_sample(float *__restrict__ out, int64_t n_set, const int32_t *__restrict__ base,
+                                                     const float *__restrict__ w, const uint8_t *__restrict__ rep,
+                                                     const int32_t *__restrict__ col, int n, const float *__restrict__ rho,
+                                                     const float *__restrict__ vel, const int32_t *__restrict__ meta, float scale)
+{
+    const int p = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (p >= n) return;
+    const int64_t e0 = base[p], b0 = e0 >> 9;
+    const int x0 = (int)(e0 & 7), y0 = (int)((e0 >> 3) & 7), z0 = (int)((e0 >> 6) & 7);
+    const unsigned r = rep[p];
+    const float wx = w[3 * p], wy = w[3 * p + 1], wz = w[3 * p + 2];
+    constexpr int NQ = GRAD ? 8 : 4;           // rho, ux, uy, uz (+ wx, wy, wz, Q) at the corners
+    float v[NQ][8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const bool keep = !((r >> c) & 1u);
+        const int cx = x0 + (keep ? (c & 1) : 0), cy = y0 + (keep ? ((c >> 1) & 1) : 0), cz = z0 + (keep ? (c >> 2) : 0);
+        int64_t e = slice_locate(meta, b0, cx, cy, cz);
+        if (e < 0) e = e0;                     // (the set's creation has checked that a kept corner exists)
+        v[0][c] = rho[e];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[1 + k][c] = slice_vel(vel, e, k);
+        if constexpr (GRAD) {
+            float g[3][3];                     // g[i][j] = du_i/dx_j
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                int64_t hi = slice_locate(meta, b0, cx + (j == 0), cy + (j == 1), cz + (j == 2));
+                int64_t lo = slice_locate(meta, b0, cx - (j == 0), cy - (j == 1), cz - (j == 2));
+                if (hi < 0) hi = e;
+                if (lo < 0) lo = e;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) g[i][j] = (0.5f * (slice_vel(vel, hi, i) - slice_vel(vel, lo, i))) * scale;
+            }
+            v[4][c] = g[2][1] - g[1][2];
+            v[5][c] = g[0][2] - g[2][0];
+            v[6][c] = g[1][0] - g[0][1];
+            v[7][c] = -0.5f * (((g[0][0] * g[0][0] + g[1][1] * g[1][1]) + g[2][2] * g[2][2]) +
+                               2.0f * ((g[0][1] * g[1][0] + g[0][2] * g[2][0]) + g[1][2] * g[2][1]));
+        }
+    }
+    float res[NQ];
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        const float x00 = probe_lerp(v[k][0], v[k][1], wx), x10 = probe_lerp(v[k][2], v[k][3], wx);
+        const float x01 = probe_lerp(v[k][4], v[k][5], wx), x11 = probe_lerp(v[k][6], v[k][7], wx);
+        const float y0 = probe_lerp(x00, x10, wy), y1 = probe_lerp(x01, x11, wy);
+        res[k] = probe_lerp(y0, y1, wz);
+    }
+    const int64_t o = col[p];
+    out[o] = res[0];
+    out[n_set + o] = res[1];
+    out[2 * n_set + o] = res[2];
+    out[3 * n_set + o] = res[3];
+    out[4 * n_set + o] = sqrtf((res[1] * res[1] + res[2] * res[2]) + res[3] * res[3]);
+    if constexpr (GRAD) {
+#pragma unroll
+        for (int k = 4; k < 8; ++k) out[(k + 1) * n_set + o] = res[k];
+    }
+}
+
 // ---- internal storage (ludwig_hip.hip "block order", "block-major"): the caller's arrays keep the reference's layout,
 // [8,8,8,n_blocks,K] with the reference's block order; the device arrays hold the blocks in the library's own order, block-major.
 // ref2int[b_reference] = b_internal (nullptr = same order) ----

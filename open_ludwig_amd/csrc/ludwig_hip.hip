@@ -2428,6 +2428,199 @@ int ludwig_surface_stats_download(LudwigSurfaceStats *S, double *sums, size_t by
     return LUDWIG_OK;
 }
 
+// ---- slices (ludwig_slices_*; no reference counterpart) ----
+// Per level: its points in the order of their base cells (lanes of one wave read neighbouring cells), each with its base cell
+// (internal block * 512 + cell), weights, replaced-corner mask and place in the set. One device result [n_rows][n_points], zero
+// where no valid point writes.
+struct LudwigSlices {
+    int device = 0;
+    int n_levels = 0, n_points = 0, n_rows = 0;
+    bool grad = false;
+    std::vector<LudwigLevel *> levels;
+    std::vector<float> scales;
+    struct PerLevel {
+        int n = 0;
+        int32_t *base = nullptr;                // [n]
+        float *w = nullptr;                     // [n][3]
+        uint8_t *rep = nullptr;                 // [n] bit c: corner c replaced by the base cell
+        int32_t *col = nullptr;                 // [n] place in the set
+    };
+    std::vector<PerLevel> per;
+    float *out = nullptr;
+};
+
+void ludwig_slices_destroy(LudwigSlices *S)
+{
+    if (!S) return;
+    (void)hipSetDevice(S->device);
+    for (LudwigSlices::PerLevel &q : S->per) {
+        if (q.base) (void)hipFree(q.base);
+        if (q.w) (void)hipFree(q.w);
+        if (q.rep) (void)hipFree(q.rep);
+        if (q.col) (void)hipFree(q.col);
+    }
+    if (S->out) (void)hipFree(S->out);
+    delete S;
+}
+
+int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_points, const int32_t *level_index,
+                         const int32_t *blocks, const int32_t *cells, const float *weights, const uint8_t *valid,
+                         const float *scales, int32_t flags, LudwigSlices **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels || !level_index || !blocks || !cells || !weights || !valid || !scales) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > 64) return fail(LUDWIG_ERR_INVALID, "slices: n_levels %d not in 1..64", n_levels);
+    if (n_points < 1) return fail(LUDWIG_ERR_INVALID, "slices: n_points %d < 1", n_points);
+    if (flags & ~LUDWIG_SLICE_GRADIENT) return fail(LUDWIG_ERR_INVALID, "slices: unknown flags %d", flags);
+    const bool grad = (flags & LUDWIG_SLICE_GRADIENT) != 0;
+    const int n_rows = grad ? SLICE_ROWS_GRAD : SLICE_ROWS_BASIC;
+    if ((int64_t)n_rows * n_points > (int64_t)INT32_MAX) return fail(LUDWIG_ERR_INVALID, "slices: %d points too many", n_points);
+    // everything is checked before anything is allocated: every cell a point reads is found here, through the host copy of the
+    // neighbour rows the kernel reads, so the kernel never needs a bounds check of its own
+    const LudwigLevel *first = nullptr;
+    std::vector<std::vector<int32_t>> hb(n_levels), hcol(n_levels);
+    std::vector<std::vector<float>> hw(n_levels);
+    std::vector<std::vector<uint8_t>> hr(n_levels);
+    for (int32_t p = 0; p < n_points; ++p) {
+        if (!valid[p]) continue;
+        const int li = level_index[p];
+        if (li < 0 || li >= n_levels) return fail(LUDWIG_ERR_INVALID, "slice point %d: level index %d not in 0..%d", p, li, n_levels - 1);
+        const LudwigLevel *L = levels[li];
+        if (!L) return fail(LUDWIG_ERR_INVALID, "slice point %d: level %d is null", p, li);
+        if (first && L->device != first->device) return fail(LUDWIG_ERR_INVALID, "slices: levels on different devices");
+        if (!first) first = L;
+        if ((int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+            return fail(LUDWIG_ERR_INVALID, "slice point %d: level %d has %d blocks, more than 32-bit cell indices reach", p, li, L->n_blocks);
+        if (!std::isfinite(scales[li]) || scales[li] == 0.0f)
+            return fail(LUDWIG_ERR_INVALID, "slices: scale %g of level %d must be finite and non-zero", (double)scales[li], li);
+        int32_t e[8];
+        for (int c = 0; c < 8; ++c) {
+            const int32_t b = blocks[8 * p + c], x = cells[8 * p + c];
+            if (b < 0 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "slice point %d corner %d: block %d not in 0..%d", p, c, b, L->n_blocks - 1);
+            if (x < 0 || x >= CELLS) return fail(LUDWIG_ERR_INVALID, "slice point %d corner %d: cell %d not in 0..511", p, c, x);
+            e[c] = (L->ref2int.empty() ? b : L->ref2int[b]) * CELLS + x;
+        }
+        const int32_t b0 = e[0] / CELLS;
+        if (b0 >= L->n_owned) return fail(LUDWIG_ERR_INVALID, "slice point %d: base block %d is not owned by this level", p, blocks[8 * p]);
+        const int x0 = e[0] & 7, y0 = (e[0] >> 3) & 7, z0 = e[0] >> 6 & 7;
+        auto locate = [&](int x, int y, int z) -> int64_t {
+            const int ox = x >> 3, oy = y >> 3, oz = z >> 3;
+            int64_t b = b0;
+            if (ox | oy | oz) b = L->h_meta[(size_t)b0 * NBR_STRIDE + DIR(ox, oy, oz)];
+            return b < 0 ? -1 : b * CELLS + ((x & 7) + 8 * (y & 7) + 64 * (z & 7));
+        };
+        uint8_t rep = 0;
+        for (int c = 1; c < 8; ++c) {
+            const int cx = x0 + (c & 1), cy = y0 + ((c >> 1) & 1), cz = z0 + (c >> 2);
+            if (e[c] == e[0]) rep |= (uint8_t)(1u << c);
+            else if (locate(cx, cy, cz) != e[c])
+                return fail(LUDWIG_ERR_INVALID, "slice point %d corner %d: neither the cell next to the base cell nor the base cell", p, c);
+        }
+        for (int a = 0; a < 3; ++a) {
+            const float w = weights[3 * p + a];
+            if (!(w >= 0.0f && w <= 1.0f)) return fail(LUDWIG_ERR_INVALID, "slice point %d: weight %d = %g not in [0, 1]", p, a, (double)w);
+            hw[li].push_back(w);
+        }
+        hb[li].push_back(e[0]);
+        hr[li].push_back(rep);
+        hcol[li].push_back(p);
+    }
+    if (!first) return fail(LUDWIG_ERR_INVALID, "slices: no valid point");
+    for (int li = 0; li < n_levels; ++li)
+        if (levels[li] && levels[li]->device != first->device) return fail(LUDWIG_ERR_INVALID, "slices: levels on different devices");
+    LudwigSlices *S = new (std::nothrow) LudwigSlices;
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "slices: out of host memory");
+    S->device = first->device;
+    S->n_levels = n_levels;
+    S->n_points = n_points;
+    S->n_rows = n_rows;
+    S->grad = grad;
+    S->levels.assign(levels, levels + n_levels);
+    S->scales.assign(scales, scales + n_levels);
+    S->per.resize(n_levels);
+    LW_HIP(hipSetDevice(S->device));
+    int r = LUDWIG_OK;
+    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
+        const size_t n = hcol[li].size();
+        LudwigSlices::PerLevel &q = S->per[li];
+        q.n = (int)n;
+        if (n == 0) continue;
+        // launch order: by base cell (stable, so points of one cell keep the set's order)
+        std::vector<int32_t> ord(n);
+        for (size_t i = 0; i < n; ++i) ord[i] = (int32_t)i;
+        std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return hb[li][a] < hb[li][b]; });
+        std::vector<int32_t> sb(n), sc(n);
+        std::vector<float> sw(3 * n);
+        std::vector<uint8_t> sr(n);
+        for (size_t i = 0; i < n; ++i) {
+            const int32_t j = ord[i];
+            sb[i] = hb[li][j];
+            sc[i] = hcol[li][j];
+            sr[i] = hr[li][j];
+            for (int a = 0; a < 3; ++a) sw[3 * i + a] = hw[li][3 * j + a];
+        }
+        hipError_t e = hipMalloc((void **)&q.base, n * 4);
+        if (e == hipSuccess) e = hipMalloc((void **)&q.w, n * 12);
+        if (e == hipSuccess) e = hipMalloc((void **)&q.rep, n);
+        if (e == hipSuccess) e = hipMalloc((void **)&q.col, n * 4);
+        if (e == hipSuccess) e = hipMemcpy(q.base, sb.data(), n * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(q.w, sw.data(), n * 12, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(q.rep, sr.data(), n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(q.col, sc.data(), n * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "slices: level %d tables: %s", li, hipGetErrorString(e));
+    }
+    if (r == LUDWIG_OK) {
+        const size_t bytes = (size_t)n_rows * n_points * sizeof(float);
+        hipError_t e = hipMalloc((void **)&S->out, bytes);
+        if (e == hipSuccess) e = hipMemset(S->out, 0, bytes);           // invalid points stay 0
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "slices: result of %d points: %s", n_points, hipGetErrorString(e));
+    }
+    if (r != LUDWIG_OK) {
+        ludwig_slices_destroy(S);
+        return r;
+    }
+    *out = S;
+    return LUDWIG_OK;
+}
+
+int ludwig_slices_sample(LudwigSlices *S, int64_t t_coarse)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null slice set");
+    if (t_coarse < 0) return fail(LUDWIG_ERR_INVALID, "slices: t_coarse %lld < 0", (long long)t_coarse);
+    LW_HIP(hipSetDevice(S->device));
+    for (int li = 0; li < S->n_levels; ++li) {
+        const LudwigSlices::PerLevel &q = S->per[li];
+        if (q.n == 0) continue;
+        LudwigLevel *L = S->levels[li];
+        const int r = ensure_rho(L);                     // rho as a download would return it now
+        if (r) return r;
+        const int64_t t_sub = (t_coarse + 1) * ((int64_t)1 << li) - 1;
+        const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];     // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+        const dim3 grid((unsigned)((q.n + 63) / 64)), block(64);
+        if (S->grad)
+            hipLaunchKernelGGL(k_slice_sample<true>, grid, block, 0, L->stream, S->out, (int64_t)S->n_points, q.base, q.w, q.rep, q.col,
+                               q.n, L->rho, vel, (const int32_t *)L->meta, S->scales[li]);
+        else
+            hipLaunchKernelGGL(k_slice_sample<false>, grid, block, 0, L->stream, S->out, (int64_t)S->n_points, q.base, q.w, q.rep, q.col,
+                               q.n, L->rho, vel, (const int32_t *)L->meta, S->scales[li]);
+        LW_HIP(hipGetLastError());
+    }
+    return LUDWIG_OK;
+}
+
+int ludwig_slices_download(LudwigSlices *S, float *values, size_t bytes)
+{
+    if (!S || !values) return fail(LUDWIG_ERR_INVALID, "null argument");
+    const size_t want = (size_t)S->n_rows * S->n_points * sizeof(float);
+    if (bytes != want) return fail(LUDWIG_ERR_INVALID, "slices: got %zu bytes, expected %zu", bytes, want);
+    LW_HIP(hipSetDevice(S->device));
+    for (int li = 0; li < S->n_levels; ++li)
+        if (S->per[li].n > 0) LW_HIP(hipStreamSynchronize(S->levels[li]->stream));
+    LW_HIP(hipMemcpy(values, S->out, want, hipMemcpyDeviceToHost));
+    return LUDWIG_OK;
+}
+
 int ludwig_halo_pack(const LudwigLevel *L, int field, const int64_t *index_dev, int64_t n, float *dst_dev, void *hip_stream)
 {
     if (!L || (n > 0 && (!index_dev || !dst_dev))) return fail(LUDWIG_ERR_INVALID, "null argument");

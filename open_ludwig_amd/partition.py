@@ -937,8 +937,9 @@ def interpolation_needs(child: LocalView, parent: LocalView, domain_cells: Tuple
 
 
 def probe_needs(view: LocalView, n_global: int, cells: np.ndarray) -> Dict[str, np.ndarray]:
-    """'rho' and 'vel' needs (local element offsets) of the probe stencil cells `cells` (global block id * 512 + cell) that lie in
-    ghost blocks: a probe's corners are its base cell's block or one of its 26 neighbours, all held here as ghosts"""
+    """'rho' and 'vel' needs (local element offsets) of the probe and slice stencil cells `cells` (global block id * 512 + cell) that
+    lie in ghost blocks: a point's corners - and, for a slice with the gradient, their face neighbours - are in its base cell's block
+    or one of its 26 neighbours, all held here as ghosts"""
     c = np.unique(np.asarray(cells, dtype=np.int64))
     g2l = np.full(n_global, -1, dtype=np.int64)
     g2l[view.local_to_global] = np.arange(len(view.local_to_global))
@@ -964,8 +965,8 @@ class MultiLevelRunner:
                  probe_cells: Optional[Sequence[np.ndarray]] = None):
         """upload_state=False: the host levels' f / rho / vel arrays are neither sliced nor uploaded - the caller initialises the state
         on the device right away (DistributedStepper: init_eq!); on the shipped Wing_5_deg that is 25 GB of zeros per rank otherwise.
-        probe_cells: per level, the cells (global block id * 512 + cell) the probes this rank owns read; those in ghost blocks join the
-        level's 'rho' and 'vel' halo (None: every plan as without probes)"""
+        probe_cells: per level, the cells (global block id * 512 + cell) the probes and slice points this rank owns read; those in ghost
+        blocks join the level's 'rho' and 'vel' halo (None: every plan as without probes and slices)"""
         import ctypes as C
         import torch
         from . import _lib

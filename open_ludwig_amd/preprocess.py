@@ -110,6 +110,12 @@ class CaseConfig:
     probes_interval: int = 1
     probes_points: Tuple[Tuple[float, float, float], ...] = ()
     probes_names: Tuple[str, ...] = ()
+    # slices, advanced.slices (no reference counterpart): planar grids of points sampled every `interval` coarse steps from
+    # `start_step`, written to slice_<name>_%06d.vti and slice_<name>.pvd (slices.py)
+    slices_enabled: bool = False
+    slices_start_step: int = 1
+    slices_interval: int = 1
+    slices_planes: Tuple["SlicePlane", ...] = ()
 
     @property
     def reference_area_config(self) -> float:
@@ -143,6 +149,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     if surf_interval < 1:
         raise ValueError(f"advanced.surface_statistics.interval must be >= 1, got {surf_interval}")
     probes = _probes_config(g("advanced", "probes", default=None))
+    slices = _slices_config(g("advanced", "slices", default=None))
     return CaseConfig(
         stl_file=g("basic", "stl_file", required=True), stl_scale=float(g("basic", "stl_scale", required=True)),
         surface_resolution=int(g("basic", "surface_resolution", required=True)), num_levels=int(g("basic", "num_levels", required=True)),
@@ -192,6 +199,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         surface_statistics_enabled=bool(g("advanced", "surface_statistics", "enabled", default=False)),
         surface_statistics_start_step=max(surf_start, 1), surface_statistics_interval=surf_interval,
         **probes,
+        **slices,
     )
 
 
@@ -231,6 +239,93 @@ def _probes_config(pc) -> dict:
         raise ValueError("advanced.probes.names must be unique")
     return dict(probes_enabled=True, probes_start_step=start, probes_interval=interval, probes_points=tuple(pts),
                 probes_names=tuple(names))
+
+
+SLICE_FIELDS = ("density", "velocity", "velocity_magnitude", "vorticity", "q_criterion")   # basic.simulation.output_fields keys
+SLICE_MAX_POINTS = 1 << 24                                  # per plane
+
+
+@dataclass(frozen=True)
+class SlicePlane:
+    """one plane of advanced.slices.planes (semantics: slices.py)"""
+    name: str
+    normal: int                                             # axis: 0 = x, 1 = y, 2 = z
+    position: float                                         # STL frame after stl_scale
+    bounds: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None   # the two in-plane axes in x, y, z order; None: the domain
+    spacing: Optional[float] = None                         # None: dx of the finest level
+    fields: Tuple[str, ...] = ("density", "velocity", "velocity_magnitude")
+
+
+def slice_axis_points(lo: float, hi: float, h: float) -> int:
+    """points along one in-plane axis: floor((hi - lo) / h) + 1"""
+    return int(math.floor((hi - lo) / h)) + 1
+
+
+def _slices_config(sc) -> dict:
+    """advanced.slices: {enabled: false, start_step: 1, interval: 1, planes: [{name, normal, position, bounds?, spacing?, fields?}]}
+    -> CaseConfig fields. Absent or disabled: the defaults. What needs the domain (a plane outside it, the default bounds' point count)
+    is checked when the plane is planned (slices.plane_grid)."""
+    if sc is None:
+        return {}
+    if not isinstance(sc, dict):
+        raise ValueError("advanced.slices must be a mapping")
+    if not bool(sc.get("enabled", False)):
+        return {}
+    start, interval = int(sc.get("start_step", 1)), int(sc.get("interval", 1))
+    if interval < 1:
+        raise ValueError(f"advanced.slices.interval must be >= 1, got {interval}")
+    if start < 1:
+        raise ValueError(f"advanced.slices.start_step must be >= 1, got {start}")
+    raw = sc.get("planes") or []
+    if not isinstance(raw, (list, tuple)) or not raw:
+        raise ValueError("advanced.slices.enabled needs at least one plane")
+    planes, seen = [], set()
+    for i, pc in enumerate(raw):
+        where = f"advanced.slices.planes[{i}]"
+        if not isinstance(pc, dict):
+            raise ValueError(f"{where} must be a mapping")
+        name = str(pc.get("name", ""))
+        if not name or not all(ch.isalnum() or ch in "_-." for ch in name) or name.startswith("."):
+            raise ValueError(f"{where}.name {name!r} is not a plain file-name stem")
+        if name in seen:
+            raise ValueError(f"{where}.name {name!r} is not unique")
+        seen.add(name)
+        where = f"advanced.slices plane {name!r}"
+        normal = str(pc.get("normal", "")).lower()
+        if normal not in ("x", "y", "z"):
+            raise ValueError(f"{where}: normal {pc.get('normal')!r} is not x, y or z")
+        if "position" not in pc:
+            raise ValueError(f"{where}: position is required")
+        position = float(pc["position"])
+        if not math.isfinite(position):
+            raise ValueError(f"{where}: position {position} is not finite")
+        bounds = pc.get("bounds")
+        if bounds is not None:
+            ok = isinstance(bounds, (list, tuple)) and len(bounds) == 2 and all(isinstance(b, (list, tuple)) and len(b) == 2 for b in bounds)
+            if not ok:
+                raise ValueError(f"{where}: bounds must be [[a0, a1], [b0, b1]], got {bounds!r}")
+            bounds = tuple((float(b[0]), float(b[1])) for b in bounds)
+            for lo, hi in bounds:
+                if not (math.isfinite(lo) and math.isfinite(hi)) or not lo < hi:
+                    raise ValueError(f"{where}: bounds {list(map(list, bounds))} must be finite with lower < upper")
+        spacing = pc.get("spacing")
+        if spacing is not None:
+            spacing = float(spacing)
+            if not (math.isfinite(spacing) and spacing > 0):
+                raise ValueError(f"{where}: spacing {spacing} must be > 0")
+        fields = pc.get("fields")
+        fields = ("density", "velocity", "velocity_magnitude") if fields is None else tuple(str(f) for f in fields)
+        for f in fields:
+            if f not in SLICE_FIELDS:
+                raise ValueError(f"{where}: unknown field {f!r} (one of {', '.join(SLICE_FIELDS)})")
+        if not fields or len(set(fields)) != len(fields):
+            raise ValueError(f"{where}: fields must be a non-empty list without repeats")
+        if bounds is not None and spacing is not None:
+            n = slice_axis_points(*bounds[0], spacing) * slice_axis_points(*bounds[1], spacing)
+            if n > SLICE_MAX_POINTS:
+                raise ValueError(f"{where}: {n} points, more than {SLICE_MAX_POINTS} per plane")
+        planes.append(SlicePlane(name, "xyz".index(normal), position, bounds, spacing, tuple(f for f in SLICE_FIELDS if f in fields)))
+    return dict(slices_enabled=True, slices_start_step=start, slices_interval=interval, slices_planes=tuple(planes))
 
 
 # ----------------------------------------------------------------------------------------------------------------
