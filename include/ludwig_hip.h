@@ -271,6 +271,23 @@ int  ludwig_level_stats_accumulate(LudwigLevel *level, int64_t t_sub);
  * 4096 n_blocks K; *n_samples (may be NULL) = samples since the last reset. Synchronizes the stream. LUDWIG_ERR_STATE before the first reset. */
 int  ludwig_level_stats_download(const LudwigLevel *level, int stat, double *host, size_t bytes, int64_t *n_samples);
 
+/* ---- flow monitor: compute_flow_stats of a level plus where (src/diagnostics.jl:56-94; the locations, the non-finite count and
+ * the fixed summation order have no reference counterpart) ----
+ * One record from one pass over the blocks this device owns: rho as ludwig_level_download(LUDWIG_RHO) would return it now (an elided
+ * store is replayed first), the velocity buffer sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd) and obstacle. Per
+ * non-obstacle cell v2 = (ux ux + uy uy) + uz uz in float32; the cell is counted iff rho, ux, uy, uz and v2 are all finite, else bad.
+ *   counts[2]    non-obstacle cells, bad cells
+ *   extremes[3]  min rho, max rho, max v2 over the counted cells (IEEE < and >); +inf, -inf, -inf without a counted cell
+ *   cells[4][4]  (bx, by, bz, x + 8 y + 64 z) of the min-rho, max-rho, max-v2 cell - among equal values the lowest in
+ *                (bx, by, bz, z, y, x) order, whatever the block order - and of the lowest bad cell; -1 four times where absent.
+ *                Block coordinates are the level's map_x/y/z (at most 2^18 - 1 per axis, LUDWIG_ERR_INVALID otherwise)
+ *   sums[2]      Float64 sums of rho and of rho v2 over the counted cells (every other cell adds +0.0) in one fixed balanced tree:
+ *                adjacent pairs halved, x = x[0::2] + x[1::2], over the 512 cells of a block in cell order, then over the per-block
+ *                results in the caller's block order with +0.0 appended wherever a length is odd.
+ * The per-block scratch (80 B per owned block) is allocated by the first call; a level never monitored allocates and launches nothing.
+ * Runs on the level's stream: one small download, one synchronisation. A level created with n_owned < 0 returns the empty record. */
+int  ludwig_level_monitor(LudwigLevel *level, int64_t t_sub, int64_t *counts, int64_t *cells, float *extremes, double *sums);
+
 /* ---- velocity-gradient fields (no reference counterpart for the output; the gradient is compute_velocity_gradients,
  * src/physics_utils.jl:44-82, the one WALE uses) ----
  * Per cell of the blocks this device owns, from one velocity buffer u: g_ij = (0.5f (u_i(+e_j) - u_i(-e_j))) * scale with the

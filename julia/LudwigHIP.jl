@@ -131,6 +131,20 @@ function stats_download!(a::Array{Float64}, d::DeviceLevel, stat::Int32)
     return n[]
 end
 
+# flow monitor: compute_flow_stats (src/diagnostics.jl:56-94) of the owned cells plus the non-finite count and where each extreme sits
+"""the health record of the level's newest state after sub-step `timestep` (vel_temp if even, vel if odd; rho as stored):
+(counts = [non-obstacle cells, non-finite cells], cells = 4 x 4 Int64 with one column (bx, by, bz, x + 8y + 64z) each for min rho,
+max rho, max v2 and the first non-finite cell (-1 where absent), extremes = Float32[min rho, max rho, max v2],
+sums = Float64[sum rho, sum rho v2] in the fixed balanced tree of include/ludwig_hip.h)"""
+function monitor(d::DeviceLevel, timestep::Integer)
+    counts, cells = zeros(Int64, 2), fill(Int64(-1), 4, 4)
+    extremes, sums = zeros(Float32, 3), zeros(Float64, 2)
+    GC.@preserve counts cells extremes sums check(ccall((:ludwig_level_monitor, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float32}, Ptr{Float64}),
+        d.handle, Int64(timestep), pointer(counts), pointer(cells), pointer(extremes), pointer(sums)))
+    return (counts = counts, cells = cells, extremes = extremes, sums = sums)
+end
+
 # velocity-gradient fields (no reference counterpart for the output; the gradient is compute_velocity_gradients, the one WALE uses)
 const GRAD_VORTICITY, GRAD_Q = Int32(0), Int32(1)                       # K = 3, 1
 """vorticity and Q-criterion of the owned cells from `vel_field` (VEL or VEL_TEMP), derivatives times `scale` (1/dx)"""

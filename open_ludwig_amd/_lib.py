@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_surface_stats_create", "ludwig_surface_stats_destroy", "ludwig_surface_stats_reset", "ludwig_surface_stats_accumulate",
     "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
     "ludwig_slices_create", "ludwig_slices_destroy", "ludwig_slices_sample", "ludwig_slices_download",
+    "ludwig_level_monitor",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -174,6 +175,7 @@ def load() -> C.CDLL:
         "ludwig_step_distributed": (C.c_int, [vp, vp, vp, i64, f32, f32, f32, C.POINTER(StepFlags)]),
         "ludwig_level_stats_reset": (C.c_int, [vp]),
         "ludwig_level_stats_accumulate": (C.c_int, [vp, i64]),
+        "ludwig_level_monitor": (C.c_int, [vp, i64, vp, vp, vp, vp]),
         "ludwig_level_stats_download": (C.c_int, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int64)]),
         "ludwig_level_gradient_fields_compute": (C.c_int, [vp, i32, f32]),
         "ludwig_level_gradient_fields_download": (C.c_int, [vp, i32, vp, C.c_size_t]),

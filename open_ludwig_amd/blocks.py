@@ -357,6 +357,17 @@ class DeviceLevel:
         _lib.check(self._lib.ludwig_level_stats_download(self.handle, sid, a.ctypes.data if a.size else None, a.nbytes, C.byref(n)))
         return a, int(n.value)
 
+    # -- flow monitor (monitor.py) --
+    def monitor(self, t_sub: int):
+        """the monitor.Record of the owned blocks from the newest state after sub-step t_sub (vel_temp if t_sub is even, vel if odd;
+        rho as download('rho') gives it), reduced on the device: one small download, one synchronisation"""
+        from . import monitor as monitor_mod
+        counts, cells = np.zeros(2, np.int64), np.zeros(16, np.int64)
+        extremes, sums = np.zeros(3, np.float32), np.zeros(2, np.float64)
+        _lib.check(self._lib.ludwig_level_monitor(self.handle, int(t_sub), counts.ctypes.data, cells.ctypes.data, extremes.ctypes.data,
+                                                  sums.ctypes.data))
+        return monitor_mod.from_arrays(counts, cells, extremes, sums)
+
     # -- velocity-gradient fields (no reference counterpart for the output; the gradient is the WALE one) --
     def gradient_fields(self, vel_name: str, scale) -> Tuple[np.ndarray, np.ndarray]:
         """vorticity [8,8,8,n_blocks,3] and Q-criterion [8,8,8,n_blocks] (Float32, reference layout, ghost blocks 0) of the owned

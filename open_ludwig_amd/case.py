@@ -17,6 +17,7 @@ from typing import Callable, List, Optional
 import numpy as np
 
 from . import forces as forces_mod
+from . import monitor as monitor_mod
 from . import probes as probes_mod
 from . import slices as slices_mod
 from . import statistics as stats_mod
@@ -120,6 +121,11 @@ class HipStepper:
     def rho_min(self, level: int) -> float:
         """compute_flow_stats (src/diagnostics.jl:56-94), reduced on the device"""
         return self.dev[level].rho_min()
+
+    def monitor(self, level: int, t_coarse: int):
+        """the monitor.Record of a level's newest state after coarse step t_coarse (the last batch must have ended there), reduced on
+        the device"""
+        return self.dev[level].monitor(stats_mod.t_sub_after(level, t_coarse))
 
     # -- time-averaged statistics (no reference counterpart) --
     def stats_reset(self) -> None:
@@ -426,6 +432,19 @@ class DistributedStepper:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.MIN)
         return float("nan") if float(t[1].item()) < 0 else float(t[0].item())
 
+    def monitor(self, level: int, t_coarse: int):
+        """the monitor.Record of the GLOBAL level after coarse step t_coarse, on every rank: each rank reduces its owned blocks on its
+        device, the small records are gathered and merged on rank 0 (monitor.merge) and the result is sent back; collective"""
+        lv, view = self.runner.levels[level], self.runner.views[level]
+        mine = None
+        if lv is not None and view.n_owned > 0:
+            mine = lv.monitor(stats_mod.t_sub_after(level, t_coarse))
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        out = [monitor_mod.merge(parts) if self.rank == 0 else None]
+        self.dist.broadcast_object_list(out, src=0)
+        return out[0]
+
     def _triangle_map(self, level: int, mesh, params, search_radius: int):
         key = (level, search_radius)
         if key not in self._tri:
@@ -611,7 +630,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     steps - and every output step once a sample exists writes surface_mean_%06d.vtu and a forces_mean.csv row.
     With cfg.slices_enabled, every plane is sampled after the coarse steps start_step + k interval - batches are cut there with the
     batch's own inlet speed - on the device where the stepper offers slices_setup, else from downloaded fields (slices.host_sample);
-    each sample is written to slice_<name>_%06d.vti and listed in slice_<name>.pvd (slices.py)."""
+    each sample is written to slice_<name>_%06d.vti and listed in slice_<name>.pvd (slices.py).
+    With cfg.flow_monitor_enabled, a monitor.Record of every level is taken at every diagnostics step and after the last step, from the
+    state at batch end (where rho_min is taken; no batch is cut) - on the device where the stepper offers monitor, else from downloaded
+    fields (monitor.host_monitor); flow_monitor.csv gains one row per level and the warnings go to `log`. With
+    cfg.flow_monitor_stop_on_divergence the run ends once a level holds non-finite fluid cells: that step's rows and files are
+    written, then monitor.FlowDiverged is raised (on every rank of a distributed run)."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
@@ -659,7 +683,34 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             probes_mod.write_points_csv(os.path.join(out_dir, "probes_points.csv"), pplan, grids)
             with open(os.path.join(out_dir, "probes.csv"), "w") as io:
                 io.write(probes_mod.series_csv_header(pplan.names) + "\n")
+        if cfg.flow_monitor_enabled:
+            with open(os.path.join(out_dir, "flow_monitor.csv"), "w") as io:
+                io.write(monitor_mod.CSV_HEADER + "\n")
     probes_written = [0]
+
+    def take_monitor(step, state_step):
+        """a record of every level from the state after coarse step state_step; rows and warnings out; the first diverged level's
+        FlowDiverged or None (collective in a distributed run)"""
+        diverged = None
+        for lvl, g in enumerate(grids):
+            if hasattr(st, "monitor"):
+                rec = st.monitor(lvl, state_step)
+            else:
+                vel_name = "vel_temp" if stats_mod.t_sub_after(lvl, state_step) % 2 == 0 else "vel"
+                rho_l, vel_l = st.field(lvl, "rho"), st.field(lvl, vel_name)
+                rec = monitor_mod.host_monitor(rho_l, vel_l, g.obstacle, g.active_block_coords) if rho_l is not None else None
+            if rec is None:
+                continue
+            if writing:
+                with open(os.path.join(out_dir, "flow_monitor.csv"), "a") as io:
+                    io.write(monitor_mod.csv_row(step, state_step, g.level_id, rec, g.dx, params.mesh_offset) + "\n")
+            if log:
+                for line in monitor_mod.warnings_of(rec, step, g.level_id, g.dx, params.mesh_offset):
+                    log(line)
+            if rec.n_bad > 0 and diverged is None:
+                diverged = monitor_mod.FlowDiverged(step, g.level_id, rec.first_bad,
+                                                    monitor_mod.cell_coordinates(rec.first_bad, g.dx, params.mesh_offset), rec.n_bad)
+        return diverged
 
     def flush_probes():
         """append the samples not yet in probes.csv (collective in a distributed run)"""
@@ -677,6 +728,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     stats_window = [0, 0, 0]             # samples, first and last sampled step
     # derived flow arrays on output steps: (VTU name, index into gradient_fields' result, components)
     grad_names = [g for g in (("Vorticity", 0, 3), ("QCriterion", 1, 1)) if g[0] in cfg.output_fields]
+    monitor_on = bool(cfg.flow_monitor_enabled)
+    diverged = None
     try:
         while t <= total_steps:
             batch_end = min(t + batch - 1, total_steps)
@@ -713,6 +766,7 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)
             else:
                 st.batch(t, actual, u_curr, sp)
+            monitored = False
             if batch_end % cfg.diag_freq < actual or batch_end == total_steps:
                 diag_step = (batch_end // cfg.diag_freq) * cfg.diag_freq
                 if t <= diag_step <= batch_end:
@@ -741,6 +795,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         log(f"{diag_step:8d} | {float(u_curr):.4f} | {rho_min:.4f} | {cd:8.4f} | {cl:8.4f}")
                     if probes_on:
                         flush_probes()
+                    if monitor_on:
+                        diverged = take_monitor(diag_step, batch_end)
+                        monitored = True
+            if monitor_on and batch_end == total_steps and not monitored:
+                diverged = take_monitor(batch_end, batch_end)          # the last step is no diagnostics step: a record of the end state
             if out_dir is not None and batch_end % cfg.output_freq < actual:                      # src/main.jl:213-231
                 out_step = (batch_end // cfg.output_freq) * cfg.output_freq
                 if t <= out_step <= batch_end:
@@ -783,6 +842,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                             fr_mean = surface_mod.mean_forces(mesh, fin_stats, params, cfg.symmetric_analysis)
                             with open(os.path.join(out_dir, "forces_mean.csv"), "a") as io:
                                 io.write(surface_mod.forces_mean_csv_row(out_step, window, fr_mean) + "\n")
+            if diverged is not None and cfg.flow_monitor_stop_on_divergence:
+                if probes_on:
+                    flush_probes()
+                raise diverged
             t = batch_end + 1
         if probes_on:
             flush_probes()

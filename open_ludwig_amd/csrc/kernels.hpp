@@ -1417,4 +1417,203 @@ __global__ __launch_bounds__(256) void k_unpack_octets(float *__restrict__ field
     }
 }
 
+// ---- flow monitor (ludwig_level_monitor; compute_flow_stats of every level plus where, reference src/diagnostics.jl:56-94) ----
+// One record per level from one streaming pass over rho, one velocity buffer and obstacle (17 B per cell). Per non-obstacle cell
+// v2 = (ux ux + uy uy) + uz uz in float32 (-ffp-contract=off); the cell is COUNTED iff rho, ux, uy, uz and v2 are all finite, else
+// BAD. Over the counted cells: min / max of rho and max of v2, IEEE < and >, among equal values the cell lowest in
+// (bx, by, bz, cell) order - a key built from the block's own coordinates (meta), so neither the internal block order nor a rank's
+// block list can show; over the bad cells the lowest such key. Two Float64 sums, rho and rho v2 (a product of two floats is exact in
+// double), every other cell adding +0.0, in one fixed balanced tree: inside a block over the 512 cells in cell order, adjacent pairs
+// halved nine times (the lane's two cells, an xor-butterfly over the wave, the four waves through LDS); across blocks the same
+// halving over the per-block records in the reference block order, 512 records per workgroup and launch - missing records are +0.0,
+// and adding +0.0 is exact, so the chunks give the bits of the one tree. open_ludwig_amd/monitor.py (host_monitor) restates all of it.
+// k_monitor_blocks: workgroup r = reference block r of the owned ones, two x-consecutive cells per lane, one MonitorRecord per block
+// into a slab with plain stores. k_monitor_combine: 512 records -> 1, until one is left. No atomics.
+struct MonitorRecord {
+    double sum_rho, sum_rho_v2;
+    long long n_fluid, n_bad;
+    unsigned long long key_rho_min, key_rho_max, key_v2_max, key_bad;   // MONITOR_NO_KEY: absent
+    float rho_min, rho_max, v2_max, pad;
+};
+constexpr unsigned long long MONITOR_NO_KEY = ~0ull;
+constexpr int MONITOR_COORD_BITS = 18;                         // block coordinates 1 .. 2^18 - 1 per axis, 9 bits of cell
+__device__ __forceinline__ unsigned long long monitor_block_key(int bx, int by, int bz)
+{
+    return ((((unsigned long long)(unsigned)bx << MONITOR_COORD_BITS | (unsigned)by) << MONITOR_COORD_BITS) | (unsigned)bz) << 9;
+}
+__device__ __forceinline__ bool monitor_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+__device__ __forceinline__ double monitor_wave_sum(double x)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) x += __shfl_xor(x, o, 64);      // adjacent pairs first: the halving tree, every lane ends with the sum
+    return x;
+}
+// the lowest lane whose flag is set, -1 if none (wave-uniform)
+__device__ __forceinline__ int monitor_first_lane(bool flag)
+{
+    const unsigned long long m = __ballot(flag);
+    return m ? (int)__builtin_ctzll(m) : -1;
+}
+// one extreme of a block's wave: every lane brings its better cell (has, v, cell; lanes hold cells in order, so the lowest lane among
+// equal values holds the lowest cell). MIN: IEEE <, else >. Returns the winning lane or -1; v and cell become the winner's.
+template <bool MIN>
+__device__ __forceinline__ int monitor_wave_extreme(bool has, float &v, int &cell)
+{
+    float w = has ? v : (MIN ? __int_as_float(0x7f800000) : __int_as_float(0xff800000));
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float q = __shfl_xor(w, o, 64);
+        w = MIN ? (q < w ? q : w) : (q > w ? q : w);
+    }
+    const int lane = monitor_first_lane(has && v == w);              // == : -0.0 and +0.0 tie, the lowest cell takes it
+    if (lane >= 0) {
+        v = __shfl(v, lane, 64);
+        cell = __shfl(cell, lane, 64);
+    }
+    return lane;
+}
+
+__global__ __launch_bounds__(256) void k_monitor_blocks(MonitorRecord *__restrict__ slab, const float *__restrict__ rho,
+                                                        const float *__restrict__ vel, const uint8_t *__restrict__ obstacle,
+                                                        const int32_t *__restrict__ meta, const int32_t *__restrict__ ref2int)
+{
+    struct WaveOut { double s0, s1; float lo, hi, v2; int c_lo, c_hi, c_v2, c_bad, n_fluid, n_bad; };
+    __shared__ WaveOut part[4];
+    const int r = (int)blockIdx.x;
+    const int64_t b = ref2int ? ref2int[r] : r;
+    const int t = (int)threadIdx.x, c = 2 * t;
+    const float2 rh = *(const float2 *)(rho + b * CELLS + c);
+    const float *v = vel + b * 3 * CELLS + c;
+    const float2 vx = *(const float2 *)v, vy = *(const float2 *)(v + CELLS), vz = *(const float2 *)(v + 2 * CELLS);
+    const uchar2 ob = *(const uchar2 *)(obstacle + b * CELLS + c);
+    const float q0 = (vx.x * vx.x + vy.x * vy.x) + vz.x * vz.x, q1 = (vx.y * vx.y + vy.y * vy.y) + vz.y * vz.y;
+    const bool f0 = ob.x == 0, f1 = ob.y == 0;
+    const bool k0 = f0 && monitor_finite(rh.x) && monitor_finite(vx.x) && monitor_finite(vy.x) && monitor_finite(vz.x) && monitor_finite(q0);
+    const bool k1 = f1 && monitor_finite(rh.y) && monitor_finite(vx.y) && monitor_finite(vy.y) && monitor_finite(vz.y) && monitor_finite(q1);
+    const bool bad0 = f0 && !k0, bad1 = f1 && !k1, has = k0 || k1;
+    // the lane's own pair: the first halving of the sums, the better of its two cells (the first one on a tie)
+    const double s0 = monitor_wave_sum((k0 ? (double)rh.x : 0.0) + (k1 ? (double)rh.y : 0.0));
+    const double s1 = monitor_wave_sum((k0 ? (double)rh.x * (double)q0 : 0.0) + (k1 ? (double)rh.y * (double)q1 : 0.0));
+    const bool lo1 = k1 && (!k0 || rh.y < rh.x), hi1 = k1 && (!k0 || rh.y > rh.x), v21 = k1 && (!k0 || q1 > q0);
+    float lo = lo1 ? rh.y : rh.x, hi = hi1 ? rh.y : rh.x, v2 = v21 ? q1 : q0;
+    int c_lo = c + (lo1 ? 1 : 0), c_hi = c + (hi1 ? 1 : 0), c_v2 = c + (v21 ? 1 : 0);
+    const int l_lo = monitor_wave_extreme<true>(has, lo, c_lo);
+    monitor_wave_extreme<false>(has, hi, c_hi);
+    monitor_wave_extreme<false>(has, v2, c_v2);
+    const int l_bad = monitor_first_lane(bad0 || bad1);
+    int c_bad = c + (bad0 ? 0 : 1);
+    if (l_bad >= 0) c_bad = __shfl(c_bad, l_bad, 64);
+    const int n_fluid = __popcll(__ballot(f0)) + __popcll(__ballot(f1)), n_bad = __popcll(__ballot(bad0)) + __popcll(__ballot(bad1));
+    if ((t & 63) == 0) {
+        WaveOut &w = part[t >> 6];
+        w.s0 = s0; w.s1 = s1; w.lo = lo; w.hi = hi; w.v2 = v2;
+        w.c_lo = l_lo >= 0 ? c_lo : -1; w.c_hi = l_lo >= 0 ? c_hi : -1; w.c_v2 = l_lo >= 0 ? c_v2 : -1;   // one `has` for all three
+        w.c_bad = l_bad >= 0 ? c_bad : -1;
+        w.n_fluid = n_fluid; w.n_bad = n_bad;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    const int32_t *row = meta + b * NBR_STRIDE;
+    const unsigned long long base = monitor_block_key(row[NBR_BX], row[NBR_BY], row[NBR_BZ]);
+    MonitorRecord o;
+    o.sum_rho = (part[0].s0 + part[1].s0) + (part[2].s0 + part[3].s0);
+    o.sum_rho_v2 = (part[0].s1 + part[1].s1) + (part[2].s1 + part[3].s1);
+    o.n_fluid = o.n_bad = 0;
+    o.rho_min = __int_as_float(0x7f800000); o.rho_max = o.v2_max = __int_as_float(0xff800000); o.pad = 0.0f;
+    int c0 = -1, c1 = -1, c2 = -1, cb = -1;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {                                    // waves in cell order: a strict comparison keeps the lowest cell
+        const WaveOut &p = part[w];
+        o.n_fluid += p.n_fluid; o.n_bad += p.n_bad;
+        if (p.c_lo >= 0) {
+            if (c0 < 0 || p.lo < o.rho_min) { o.rho_min = p.lo; c0 = p.c_lo; }
+            if (c1 < 0 || p.hi > o.rho_max) { o.rho_max = p.hi; c1 = p.c_hi; }
+            if (c2 < 0 || p.v2 > o.v2_max) { o.v2_max = p.v2; c2 = p.c_v2; }
+        }
+        if (cb < 0) cb = p.c_bad;
+    }
+    o.key_rho_min = c0 >= 0 ? base + (unsigned)c0 : MONITOR_NO_KEY;
+    o.key_rho_max = c1 >= 0 ? base + (unsigned)c1 : MONITOR_NO_KEY;
+    o.key_v2_max = c2 >= 0 ? base + (unsigned)c2 : MONITOR_NO_KEY;
+    o.key_bad = cb >= 0 ? base + (unsigned)cb : MONITOR_NO_KEY;
+    slab[r] = o;
+}
+
+// one extreme over the records of a wave: the value by IEEE < / >, among equal values the lowest key
+template <bool MIN>
+__device__ __forceinline__ void monitor_wave_extreme_keyed(float &v, unsigned long long &key)
+{
+    const bool has = key != MONITOR_NO_KEY;
+    float w = has ? v : (MIN ? __int_as_float(0x7f800000) : __int_as_float(0xff800000));
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float q = __shfl_xor(w, o, 64);
+        w = MIN ? (q < w ? q : w) : (q > w ? q : w);
+    }
+    unsigned long long k = (has && v == w) ? key : MONITOR_NO_KEY;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long q = __shfl_xor(k, o, 64);
+        k = q < k ? q : k;
+    }
+    const int lane = monitor_first_lane(has && key == k);
+    if (lane >= 0) v = __shfl(v, lane, 64);                          // the winner's own value (the sign of a zero)
+    else v = w;
+    key = k;
+}
+template <bool MIN>
+__device__ __forceinline__ void monitor_take(float &v, unsigned long long &key, float v2, unsigned long long key2)
+{
+    if (key2 == MONITOR_NO_KEY) return;
+    if (key == MONITOR_NO_KEY || (MIN ? v2 < v : v2 > v) || (v2 == v && key2 < key)) { v = v2; key = key2; }
+}
+
+__global__ __launch_bounds__(256) void k_monitor_combine(MonitorRecord *__restrict__ out, const MonitorRecord *__restrict__ in, int64_t n)
+{
+    __shared__ MonitorRecord part[4];
+    const int t = (int)threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * CELLS + 2 * t;
+    MonitorRecord a;
+    a.sum_rho = a.sum_rho_v2 = 0.0;
+    a.n_fluid = a.n_bad = 0;
+    a.key_rho_min = a.key_rho_max = a.key_v2_max = a.key_bad = MONITOR_NO_KEY;
+    a.rho_min = __int_as_float(0x7f800000); a.rho_max = a.v2_max = __int_as_float(0xff800000); a.pad = 0.0f;
+    MonitorRecord b = a;
+    if (i < n) a = in[i];
+    if (i + 1 < n) b = in[i + 1];
+    a.sum_rho = monitor_wave_sum(a.sum_rho + b.sum_rho);
+    a.sum_rho_v2 = monitor_wave_sum(a.sum_rho_v2 + b.sum_rho_v2);
+    a.n_fluid += b.n_fluid; a.n_bad += b.n_bad;
+    a.key_bad = b.key_bad < a.key_bad ? b.key_bad : a.key_bad;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        a.n_fluid += __shfl_xor(a.n_fluid, o, 64);
+        a.n_bad += __shfl_xor(a.n_bad, o, 64);
+        const unsigned long long q = __shfl_xor(a.key_bad, o, 64);
+        a.key_bad = q < a.key_bad ? q : a.key_bad;
+    }
+    monitor_take<true>(a.rho_min, a.key_rho_min, b.rho_min, b.key_rho_min);
+    monitor_take<false>(a.rho_max, a.key_rho_max, b.rho_max, b.key_rho_max);
+    monitor_take<false>(a.v2_max, a.key_v2_max, b.v2_max, b.key_v2_max);
+    monitor_wave_extreme_keyed<true>(a.rho_min, a.key_rho_min);
+    monitor_wave_extreme_keyed<false>(a.rho_max, a.key_rho_max);
+    monitor_wave_extreme_keyed<false>(a.v2_max, a.key_v2_max);
+    if ((t & 63) == 0) part[t >> 6] = a;
+    __syncthreads();
+    if (t != 0) return;
+    MonitorRecord o = part[0];
+    o.sum_rho = (part[0].sum_rho + part[1].sum_rho) + (part[2].sum_rho + part[3].sum_rho);
+    o.sum_rho_v2 = (part[0].sum_rho_v2 + part[1].sum_rho_v2) + (part[2].sum_rho_v2 + part[3].sum_rho_v2);
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+        const MonitorRecord &p = part[w];
+        o.n_fluid += p.n_fluid; o.n_bad += p.n_bad;
+        o.key_bad = p.key_bad < o.key_bad ? p.key_bad : o.key_bad;
+        monitor_take<true>(o.rho_min, o.key_rho_min, p.rho_min, p.key_rho_min);
+        monitor_take<false>(o.rho_max, o.key_rho_max, p.rho_max, p.key_rho_max);
+        monitor_take<false>(o.v2_max, o.key_v2_max, p.v2_max, p.key_v2_max);
+    }
+    out[blockIdx.x] = o;
+}
+
 }  // namespace lw

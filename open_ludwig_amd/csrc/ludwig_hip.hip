@@ -190,6 +190,9 @@ struct LudwigLevel {
     // allocated (and zeroed) by the first compute; only the owned blocks are ever written, the ghost blocks stay zero
     float *grad = nullptr;
     bool grad_ready = false;            // compute has been called
+    // flow monitor (ludwig_level_monitor): one MonitorRecord per owned block in the reference block order, then the records of every
+    // combine stage (512 -> 1) behind them; allocated by the first call
+    MonitorRecord *monitor_slab = nullptr;
 };
 
 namespace {
@@ -1058,6 +1061,7 @@ void ludwig_level_destroy(LudwigLevel *L)
     if (L->f_iface) (void)hipFree(L->f_iface);
     if (L->stats) (void)hipFree(L->stats);
     if (L->grad) (void)hipFree(L->grad);
+    if (L->monitor_slab) (void)hipFree(L->monitor_slab);
     if (L->d_ref2int) (void)hipFree(L->d_ref2int);
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->own_stream) (void)hipStreamDestroy(L->own_stream);
@@ -2066,6 +2070,66 @@ int ludwig_level_stats_accumulate(LudwigLevel *L, int64_t t_sub)
     hipLaunchKernelGGL(k_accumulate_stats, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->stats, L->rho, vel);
     LW_HIP(hipGetLastError());
     ++L->stats_n;
+    return LUDWIG_OK;
+}
+
+int ludwig_level_monitor(LudwigLevel *L, int64_t t_sub, int64_t *counts, int64_t *cells, float *extremes, double *sums)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    if (!counts || !cells || !extremes || !sums) return fail(LUDWIG_ERR_INVALID, "monitor: null output");
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "monitor: t_sub %lld < 0", (long long)t_sub);
+    counts[0] = counts[1] = 0;
+    for (int i = 0; i < 16; ++i) cells[i] = -1;
+    extremes[0] = __builtin_inff(); extremes[1] = extremes[2] = -__builtin_inff();
+    sums[0] = sums[1] = 0.0;
+    if (L->n_owned == 0) return LUDWIG_OK;            // no owned blocks: the empty record, nothing allocated
+    LW_HIP(hipSetDevice(L->device));
+    size_t total = 0;                                  // records of every stage: n_owned, then ceil(n / 512) until one is left
+    for (size_t n = (size_t)L->n_owned;; n = (n + CELLS - 1) / CELLS) {
+        total += n;
+        if (n == 1) break;
+    }
+    if (!L->monitor_slab) {
+        constexpr int32_t limit = 1 << MONITOR_COORD_BITS;
+        for (int b = 0; b < L->n_owned; ++b) {
+            const int32_t *row = &L->h_meta[(size_t)b * NBR_STRIDE];
+            if (row[NBR_BX] < 0 || row[NBR_BX] >= limit || row[NBR_BY] < 0 || row[NBR_BY] >= limit || row[NBR_BZ] < 0 || row[NBR_BZ] >= limit)
+                return fail(LUDWIG_ERR_INVALID, "monitor: block coordinates (%d, %d, %d) not in 0..%d", row[NBR_BX], row[NBR_BY], row[NBR_BZ], limit - 1);
+        }
+        const int r = dev_alloc(L, &L->monitor_slab, total);
+        if (r) return r;
+    }
+    {   // rho as ludwig_level_download(LUDWIG_RHO) would return it now: an elided store is replayed first, on the level's stream
+        const int r = ensure_rho(L);
+        if (r) return r;
+    }
+    const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];    // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+    MonitorRecord *in = L->monitor_slab;
+    hipLaunchKernelGGL(k_monitor_blocks, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, in, L->rho, vel,
+                       (const uint8_t *)L->obstacle, (const int32_t *)L->meta, (const int32_t *)L->d_ref2int);
+    LW_HIP(hipGetLastError());
+    for (int64_t n = L->n_owned; n > 1;) {
+        const int64_t m = (n + CELLS - 1) / CELLS;
+        hipLaunchKernelGGL(k_monitor_combine, dim3((unsigned)m), dim3(CELLS / 2), 0, L->stream, in + n, in, n);
+        LW_HIP(hipGetLastError());
+        in += n;
+        n = m;
+    }
+    MonitorRecord rec;
+    LW_HIP(hipMemcpyAsync(&rec, in, sizeof rec, hipMemcpyDeviceToHost, L->stream));
+    LW_HIP(hipStreamSynchronize(L->stream));
+    counts[0] = rec.n_fluid; counts[1] = rec.n_bad;
+    extremes[0] = rec.rho_min; extremes[1] = rec.rho_max; extremes[2] = rec.v2_max;
+    sums[0] = rec.sum_rho; sums[1] = rec.sum_rho_v2;
+    const unsigned long long keys[4] = {rec.key_rho_min, rec.key_rho_max, rec.key_v2_max, rec.key_bad};
+    const unsigned long long mask = (1ull << MONITOR_COORD_BITS) - 1;
+    for (int i = 0; i < 4; ++i) {
+        if (keys[i] == MONITOR_NO_KEY) continue;
+        cells[4 * i + 0] = (int64_t)((keys[i] >> (9 + 2 * MONITOR_COORD_BITS)) & mask);
+        cells[4 * i + 1] = (int64_t)((keys[i] >> (9 + MONITOR_COORD_BITS)) & mask);
+        cells[4 * i + 2] = (int64_t)((keys[i] >> 9) & mask);
+        cells[4 * i + 3] = (int64_t)(keys[i] & 511);
+    }
     return LUDWIG_OK;
 }
 

@@ -116,6 +116,10 @@ class CaseConfig:
     slices_start_step: int = 1
     slices_interval: int = 1
     slices_planes: Tuple["SlicePlane", ...] = ()
+    # flow monitor, advanced.flow_monitor (no reference counterpart; its advanced.diagnostics.stability_check is read by nobody, there or
+    # here): a health record of every level at every diagnostics step, written to flow_monitor.csv (monitor.py)
+    flow_monitor_enabled: bool = False
+    flow_monitor_stop_on_divergence: bool = False       # end the run with monitor.FlowDiverged once a level holds non-finite fluid cells
 
     @property
     def reference_area_config(self) -> float:
@@ -150,6 +154,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         raise ValueError(f"advanced.surface_statistics.interval must be >= 1, got {surf_interval}")
     probes = _probes_config(g("advanced", "probes", default=None))
     slices = _slices_config(g("advanced", "slices", default=None))
+    flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
     return CaseConfig(
         stl_file=g("basic", "stl_file", required=True), stl_scale=float(g("basic", "stl_scale", required=True)),
         surface_resolution=int(g("basic", "surface_resolution", required=True)), num_levels=int(g("basic", "num_levels", required=True)),
@@ -200,6 +205,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         surface_statistics_start_step=max(surf_start, 1), surface_statistics_interval=surf_interval,
         **probes,
         **slices,
+        **flow_monitor,
     )
 
 
@@ -239,6 +245,21 @@ def _probes_config(pc) -> dict:
         raise ValueError("advanced.probes.names must be unique")
     return dict(probes_enabled=True, probes_start_step=start, probes_interval=interval, probes_points=tuple(pts),
                 probes_names=tuple(names))
+
+
+def _flow_monitor_config(mc) -> dict:
+    """advanced.flow_monitor: {enabled: false, stop_on_divergence: false} -> CaseConfig fields. Absent: the defaults."""
+    if mc is None:
+        return {}
+    if not isinstance(mc, dict):
+        raise ValueError("advanced.flow_monitor must be a mapping")
+    vals = {}
+    for key in ("enabled", "stop_on_divergence"):
+        v = mc.get(key, False)
+        if not isinstance(v, bool):
+            raise ValueError(f"advanced.flow_monitor.{key} must be true or false, got {v!r}")
+        vals[key] = v
+    return dict(flow_monitor_enabled=vals["enabled"], flow_monitor_stop_on_divergence=vals["stop_on_divergence"])
 
 
 SLICE_FIELDS = ("density", "velocity", "velocity_magnitude", "vorticity", "q_criterion")   # basic.simulation.output_fields keys
