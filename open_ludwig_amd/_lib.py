@@ -211,6 +211,31 @@ def check(rc: int) -> None:
         raise LudwigError(rc, msg.decode("utf-8", "replace") if msg else "")
 
 
+class Handle:
+    """An object of the library behind a ctypes handle `_h`, made by the subclass's constructor (which also sets `_lib`): `handle`
+    raises once it is closed, close() destroys it once, and a failing __del__ stays silent."""
+    _destroy = ""       # the library's destroy function
+    _closed = ""        # what `handle` raises after close()
+    _h = None
+
+    @property
+    def handle(self):
+        if not self._h:                        # None, or a NULL c_void_p
+            raise RuntimeError(self._closed)
+        return self._h
+
+    def close(self) -> None:
+        if self._h:
+            getattr(self._lib, self._destroy)(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_count() -> int:
     n = C.c_int(0)
     rc = load().ludwig_device_count(C.byref(n))

@@ -170,12 +170,13 @@ def copy_to_old(level, f_current_name: str, vel_current_name: str, t_sub: Option
 _FIELD_DTYPES = {"obstacle": np.uint8}
 
 
-class DeviceLevel:
+class DeviceLevel(_lib.Handle):
     """`adapt(backend, level)` (src/blocks.jl:67-87): a BlockLevel whose arrays live in MI355X HBM.
 
     Owns an opaque LudwigLevel handle. Field access goes through download()/upload() (`Array(level.f)` /
     `copyto!(level.f, host)` in the reference); there is no host shadow copy.
     """
+    _destroy, _closed = "ludwig_level_destroy", "DeviceLevel is closed"
 
     def __init__(self, host: BlockLevel, device: int = 0, upload_state: bool = True):
         """upload_state=False: skip copying the host level's f / rho / vel arrays (the caller initialises the state on the device,
@@ -244,24 +245,6 @@ class DeviceLevel:
                 self.upload(name, getattr(host, name))
         if host.n_boundary_cells > 0:
             self.upload("f_post_collision", host.f_post_collision)
-
-    # -- life cycle --
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.ludwig_level_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        if not self._h:
-            raise RuntimeError("DeviceLevel is closed")
-        return self._h
 
     def info(self) -> _lib.LevelInfo:
         info = _lib.LevelInfo()

@@ -38,6 +38,15 @@ class DiagRow:
     cmy: float = 0.0
 
 
+def _close_observers(st) -> None:
+    """close a stepper's probe, surface and slice sets (each may be None)"""
+    for name in ("probes", "surface", "slices"):
+        obs = getattr(st, name)
+        if obs is not None:
+            obs.close()
+            setattr(st, name, None)
+
+
 class HipStepper:
     """grids on one MI355X behind libludwig_hip.so"""
 
@@ -153,15 +162,7 @@ class HipStepper:
         return self.dev[level].gradient_fields(vel_name, scale)
 
     def close(self):
-        if self.probes is not None:
-            self.probes.close()
-            self.probes = None
-        if self.surface is not None:
-            self.surface.close()
-            self.surface = None
-        if self.slices is not None:
-            self.slices.close()
-            self.slices = None
+        _close_observers(self)
         for d in self.dev:
             d.close()
 
@@ -212,6 +213,38 @@ class DistributedStepper:
         g = self.host[level]
         return np.asarray(self.owners[level] if not isinstance(self.owners, np.ndarray) else
                           self.partition.ancestor_owner(g.level_id, g.active_block_coords, self.host[0].active_block_coords, self.owners))
+
+    def _gather(self, mine):
+        """one object per rank to rank 0: the list of them there, None elsewhere; collective"""
+        parts = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(mine, parts, dst=0)
+        return parts
+
+    def _owned_g2l(self, level: int) -> np.ndarray:
+        """global -> local block index of the blocks this rank OWNS on a level; -1 for every other block, its ghosts included"""
+        view = self.runner.views[level]
+        g2l = np.full(self.host[level].n_blocks, -1, dtype=np.int64)
+        g2l[view.local_to_global[: view.n_owned]] = np.arange(view.n_owned)
+        return g2l
+
+    def _owning(self, level: int):
+        """(device level, view) of a level this rank holds and owns blocks of, else None"""
+        lv, view = self.runner.levels[level], self.runner.views[level]
+        return (lv, view) if lv is not None and view.n_owned > 0 else None
+
+    @staticmethod
+    def _owned_blocks(view, arrays):
+        """(local_to_global of a view's owned blocks, their part of every [8, 8, 8, n_local, ...] array): what _scatter_blocks places"""
+        return view.local_to_global[: view.n_owned], [a[:, :, :, : view.n_owned] for a in arrays]
+
+    @staticmethod
+    def _scatter_blocks(parts, outs) -> None:
+        """the ranks' gathered (local_to_global of the owned blocks, one [8, 8, 8, n_owned, ...] array per output, ...) into the global
+        arrays `outs` (block axis 3); a rank that owns nothing sent None"""
+        for part in parts:
+            if part is not None:
+                for o, a in zip(outs, part[1]):
+                    o[:, :, :, part[0]] = a
 
     def _start(self, params) -> None:
         probe_cells, mine = None, None
@@ -289,9 +322,8 @@ class DistributedStepper:
         if self.probes is not None:
             steps, vals = self._series.arrays()
             mine = (self._probe_cols, steps, vals)
-        parts = [None] * self.world if self.rank == 0 else None
-        self.dist.gather_object(mine, parts, dst=0)
-        if self.rank != 0:
+        parts = self._gather(mine)
+        if parts is None:
             return None
         n_total = self._probe_cfg[0].n
         got = [p for p in parts if p is not None]
@@ -332,6 +364,7 @@ class DistributedStepper:
         return [np.concatenate(c) if c else np.zeros(0, np.int64) for c in cells]
 
     def _slices_create(self) -> None:
+        # on purpose over owned AND ghost blocks (not _owned_g2l): a point's corners may lie in a peer's blocks, read from the ghost copies
         g2l = []
         for g, v in zip(self.host, self.runner.views):
             a = np.full(g.n_blocks, -1, dtype=np.int64)
@@ -356,9 +389,8 @@ class DistributedStepper:
             self.slices.sample(t_coarse)
             vals = self.slices.download()
             mine = [(np.flatnonzero(m), v[:, m]) for m, v in zip(self._slice_mine_cache, vals)]
-        parts = [None] * self.world if self.rank == 0 else None
-        self.dist.gather_object(mine, parts, dst=0)
-        if self.rank != 0:
+        parts = self._gather(mine)
+        if parts is None:
             return None
         rows = slices_mod.ROWS_GRAD if any(p.gradient for p in self._slice_plans) else slices_mod.ROWS_BASIC
         out = [np.zeros((rows, p.n), dtype=np.float32) for p in self._slice_plans]
@@ -388,14 +420,12 @@ class DistributedStepper:
         fin = len(self.host) - 1
         owner = self._level_owner(fin)
         self._surface_sel = np.flatnonzero(plan.found & (owner[np.maximum(plan.blocks, 0)] == self.rank))
-        lv, view = self.runner.levels[fin], self.runner.views[fin]
-        if lv is None:
+        lv = self.runner.levels[fin]
+        if lv is None:                         # (a level held without an owned block still gets its empty set: it counts the samples)
             assert self._surface_sel.size == 0
             return
-        g2l = np.full(self.host[fin].n_blocks, -1, dtype=np.int64)
-        g2l[view.local_to_global[: view.n_owned]] = np.arange(view.n_owned)
         local = plan.subset(self._surface_sel)
-        local.blocks = g2l[local.blocks].astype(np.int32)
+        local.blocks = self._owned_g2l(fin)[local.blocks].astype(np.int32)
         assert (local.blocks >= 0).all()
         self.surface = surface_mod.DeviceSurfaceStats(local, lv, fin, self.host[fin].tau, params, start, interval)
 
@@ -406,9 +436,8 @@ class DistributedStepper:
         if self.surface is not None:
             sums, n = self.surface.download()
             mine = (self._surface_sel, sums, n)
-        parts = [None] * self.world if self.rank == 0 else None
-        self.dist.gather_object(mine, parts, dst=0)
-        if self.rank != 0:
+        parts = self._gather(mine)
+        if parts is None:
             return None
         out = np.zeros((len(surface_mod.COMPONENTS), plan.n), dtype=np.float64)
         n = 0
@@ -423,8 +452,8 @@ class DistributedStepper:
         return self.torch.device("cuda", self.device) if self.dist.get_backend() == "nccl" else self.torch.device("cpu")
 
     def rho_min(self, level: int) -> float:
-        lv = self.runner.levels[level]
-        mine = lv.rho_min() if (lv is not None and self.runner.views[level].n_owned > 0) else float("inf")
+        held = self._owning(level)
+        mine = held[0].rho_min() if held else float("inf")
         # a diverged rank reports NaN (the reference's minimum() propagates it, src/diagnostics.jl:71); what MIN makes of a NaN is
         # the backend's business, so it travels as a flag: [min of the finite values, -1 if any rank saw NaN], one all-reduce MIN
         nan = mine != mine
@@ -435,12 +464,8 @@ class DistributedStepper:
     def monitor(self, level: int, t_coarse: int):
         """the monitor.Record of the GLOBAL level after coarse step t_coarse, on every rank: each rank reduces its owned blocks on its
         device, the small records are gathered and merged on rank 0 (monitor.merge) and the result is sent back; collective"""
-        lv, view = self.runner.levels[level], self.runner.views[level]
-        mine = None
-        if lv is not None and view.n_owned > 0:
-            mine = lv.monitor(stats_mod.t_sub_after(level, t_coarse))
-        parts = [None] * self.world if self.rank == 0 else None
-        self.dist.gather_object(mine, parts, dst=0)
+        held = self._owning(level)
+        parts = self._gather(held[0].monitor(stats_mod.t_sub_after(level, t_coarse)) if held else None)
         out = [monitor_mod.merge(parts) if self.rank == 0 else None]
         self.dist.broadcast_object_list(out, src=0)
         return out[0]
@@ -450,12 +475,8 @@ class DistributedStepper:
         if key not in self._tri:
             g, view = self.host[level], self.runner.views[level]
             nc = forces_mod.nearest_fluid_cells(mesh, g.obstacle, g.block_pointer, g.dx, params, search_radius)
-            owner = np.asarray(self.owners[level] if not isinstance(self.owners, np.ndarray) else
-                               self.partition.ancestor_owner(g.level_id, g.active_block_coords, self.host[0].active_block_coords, self.owners))
-            sel = np.flatnonzero(nc.found & (owner[nc.block] == self.rank))
-            g2l = np.full(g.n_blocks, -1, dtype=np.int64)
-            g2l[view.local_to_global[: view.n_owned]] = np.arange(view.n_owned)
-            lb = g2l[nc.block[sel]]
+            sel = np.flatnonzero(nc.found & (self._level_owner(level)[nc.block] == self.rank))
+            lb = self._owned_g2l(level)[nc.block[sel]]
             assert (lb >= 0).all()
             cell = nc.lx[sel] + 8 * nc.ly[sel] + 64 * nc.lz[sel] + 512 * lb
             sk = 512 * view.level.n_blocks
@@ -490,9 +511,8 @@ class DistributedStepper:
         total, cov = forces_mod.combine_partial_sums(part, self._comm_device())      # fixed order: rank 0, 1, ...
         fr = forces_mod.finish_forces(total, cov, params, symmetric)
         if want_maps:                          # output steps only: per-triangle loads to rank 0 for the surface VTU
-            parts = [None] * self.world if self.rank == 0 else None
-            self.dist.gather_object((sel, p, tx, ty, tz), parts, dst=0)
-            if self.rank == 0:
+            parts = self._gather((sel, p, tx, ty, tz))
+            if parts is not None:
                 n = mesh.centers.shape[0]
                 maps = [np.zeros(n, dtype=np.float32) for _ in range(4)]
                 for s2, *arrs in parts:
@@ -503,22 +523,18 @@ class DistributedStepper:
 
     def field(self, level: int, name: str) -> Optional[np.ndarray]:
         """GLOBAL array of a field, assembled on rank 0 (None elsewhere): result files only, never per diagnostics step."""
-        lv, view = self.runner.levels[level], self.runner.views[level]
-        g = self.host[level]
-        mine = (view.local_to_global[: view.n_owned], lv.download(name)[:, :, :, : view.n_owned] if lv is not None else None)
-        parts = [None] * self.world if self.rank == 0 else None
-        self.dist.gather_object(mine, parts, dst=0)
-        if self.rank != 0:
+        held = self._owning(level)
+        parts = self._gather(self._owned_blocks(held[1], [held[0].download(name)]) if held else None)
+        if parts is None:
             return None
-        out = np.zeros(getattr(g, name).shape, dtype=getattr(g, name).dtype, order="F")
-        for l2g, a in parts:
-            if a is not None and l2g.size:
-                out[:, :, :, l2g] = a
+        ref = getattr(self.host[level], name)
+        out = np.zeros(ref.shape, dtype=ref.dtype, order="F")
+        self._scatter_blocks(parts, [out])
         return out
 
     # -- time-averaged statistics: every rank accumulates its owned blocks; results gathered like field() --
     def _held(self):
-        return [(lvl, lv) for lvl, lv in enumerate(self.runner.levels) if lv is not None and self.runner.views[lvl].n_owned > 0]
+        return [(lvl, self._owning(lvl)[0]) for lvl in range(len(self.host)) if self._owning(lvl)]
 
     def stats_reset(self) -> None:
         for _, lv in self._held():
@@ -530,24 +546,17 @@ class DistributedStepper:
 
     def stats_sums(self, level: int):
         """(S_rho, S_u, S_uu, n) of the GLOBAL level, assembled on rank 0 (None elsewhere); collective"""
-        lv, view = self.runner.levels[level], self.runner.views[level]
-        mine = None
-        if lv is not None and view.n_owned > 0:
-            sums = [lv.stats_download(k) for k in ("rho", "vel", "vel2")]
-            mine = (view.local_to_global[: view.n_owned], [a[:, :, :, : view.n_owned] for a, _ in sums], sums[0][1])
-        parts = [None] * self.world if self.rank == 0 else None
-        self.dist.gather_object(mine, parts, dst=0)
-        if self.rank != 0:
+        held, mine = self._owning(level), None
+        if held:
+            got = [held[0].stats_download(k) for k in ("rho", "vel", "vel2")]
+            mine = self._owned_blocks(held[1], [a for a, _ in got]) + (got[0][1],)
+        parts = self._gather(mine)
+        if parts is None:
             return None
         nb = self.host[level].n_blocks
         out = [np.zeros((8, 8, 8, nb) + ((k,) if k > 1 else ()), dtype=np.float64, order="F") for k in (1, 3, 6)]
-        n = 0
-        for part in parts:
-            if part is None:
-                continue
-            l2g, arrs, n = part
-            for o, a in zip(out, arrs):
-                o[:, :, :, l2g] = a
+        self._scatter_blocks(parts, out)
+        n = ([0] + [part[2] for part in parts if part is not None])[-1]
         return out[0], out[1], out[2], n
 
     def statistics(self, level: int):
@@ -559,35 +568,18 @@ class DistributedStepper:
     # both buffers: each level step exchanges the buffer it wrote, and nothing writes that buffer again before the next such step) --
     def gradient_fields(self, level: int, vel_name: str, scale):
         """(vorticity, Q) of the GLOBAL level, assembled on rank 0 (None elsewhere); collective"""
-        lv, view = self.runner.levels[level], self.runner.views[level]
-        mine = None
-        if lv is not None and view.n_owned > 0:
-            w, q = lv.gradient_fields(vel_name, scale)
-            mine = (view.local_to_global[: view.n_owned], w[:, :, :, : view.n_owned], q[:, :, :, : view.n_owned])
-        parts = [None] * self.world if self.rank == 0 else None
-        self.dist.gather_object(mine, parts, dst=0)
-        if self.rank != 0:
+        held = self._owning(level)
+        parts = self._gather(self._owned_blocks(held[1], held[0].gradient_fields(vel_name, scale)) if held else None)
+        if parts is None:
             return None
         nb = self.host[level].n_blocks
         w_all = np.zeros((8, 8, 8, nb, 3), dtype=np.float32, order="F")
         q_all = np.zeros((8, 8, 8, nb), dtype=np.float32, order="F")
-        for part in parts:
-            if part is not None:
-                l2g, w, q = part
-                w_all[:, :, :, l2g] = w
-                q_all[:, :, :, l2g] = q
+        self._scatter_blocks(parts, [w_all, q_all])
         return w_all, q_all
 
     def close(self):
-        if self.probes is not None:
-            self.probes.close()
-            self.probes = None
-        if self.surface is not None:
-            self.surface.close()
-            self.surface = None
-        if self.slices is not None:
-            self.slices.close()
-            self.slices = None
+        _close_observers(self)
         if self.runner is not None:
             self.runner.close()          # plans, communicator, levels; the views and plans stay readable (statistics)
 

@@ -1022,6 +1022,38 @@ int copy_field(LudwigLevel *L, void *dev, void *host, int K, size_t es, bool to_
     return LUDWIG_OK;
 }
 
+// Components first..first+K-1 of a block-major device array of K_total components (internal block order) into the caller's array in
+// the reference layout: one component at a time into a plane in the reference block order, which is copied out. A result-file call,
+// so the plane is allocated per call. Synchronous on the level's stream.
+template <class T>
+int download_components(const LudwigLevel *L, const T *dev, int K_total, int first, int K, T *host, const char *what)
+{
+    const size_t plane = (size_t)L->sk * sizeof(T);
+    LW_HIP(hipSetDevice(L->device));
+    T *tmp = nullptr;
+    LW_HIP(hipMalloc((void **)&tmp, plane));
+    hipError_t e = hipSuccess;
+    const int64_t n = L->sk;
+    for (int k = 0; k < K && e == hipSuccess; ++k) {
+        hipLaunchKernelGGL(k_component_to_reference<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L->stream, tmp, dev, L->d_ref2int, n,
+                           K_total, first + k);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync((char *)host + (size_t)k * plane, tmp, plane, hipMemcpyDeviceToHost, L->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
+    }
+    (void)hipFree(tmp);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    return LUDWIG_OK;
+}
+
+// A host table onto the device, unless an earlier table of the chain has failed already (e says so).
+template <class T>
+void upload_table(hipError_t &e, const std::vector<T> &h, T *&dev)
+{
+    if (e == hipSuccess) e = hipMalloc((void **)&dev, h.size() * sizeof(T));
+    if (e == hipSuccess) e = hipMemcpy(dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1664,6 +1696,78 @@ static int save_old_impl(LudwigLevel *L, int64_t t_sub, bool defer_rho)
 // LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
 static bool level_streams() { static const bool v = getenv("LUDWIG_BATCH_SERIAL") == nullptr; return v; }
 
+// ---- what the observers share (statistics, gradient fields, monitor, probes, surface statistics, slices) ----
+namespace {
+
+// the output velocity buffer of sub-step t_sub (src/solver_control.jl:35-41)
+const float *vel_out(const LudwigLevel *L, int64_t t_sub) { return L->vel[(t_sub % 2 == 0) ? 1 : 0]; }
+
+// (reference block, cell) as the kernels index it: internal block * 512 + cell
+int32_t internal_cell(const LudwigLevel *L, int32_t b, int32_t x) { return (L->ref2int.empty() ? b : L->ref2int[b]) * CELLS + x; }
+
+// rho as ludwig_level_download(LUDWIG_RHO) would return it now: an elided store is replayed first, on the level's stream
+#define LW_ENSURE_RHO(L)                                                                                  \
+    do {                                                                                                  \
+        const int r_ = ensure_rho(const_cast<LudwigLevel *>(L));                                          \
+        if (r_) return r_;                                                                                \
+    } while (0)
+
+int set_device(int device)
+{
+    LW_HIP(hipSetDevice(device));
+    return LUDWIG_OK;
+}
+
+// One trilinear stencil point p of a probe or slice set ("probe", "slice point"; `set` = "probes", "slices"): its level, which must be
+// on the device of the first one seen, and its 8 corners and 3 weights.
+int check_stencil_point(const char *noun, const char *set, int32_t p, LudwigLevel *const *levels, int32_t n_levels, const int32_t *level_index,
+                        const int32_t *blocks, const int32_t *cells, const float *weights, const LudwigLevel *&first)
+{
+    const int li = level_index[p];
+    if (li < 0 || li >= n_levels) return fail(LUDWIG_ERR_INVALID, "%s %d: level index %d not in 0..%d", noun, p, li, n_levels - 1);
+    const LudwigLevel *L = levels[li];
+    if (!L) return fail(LUDWIG_ERR_INVALID, "%s %d: level %d is null", noun, p, li);
+    if (first && L->device != first->device) return fail(LUDWIG_ERR_INVALID, "%s: levels on different devices", set);
+    if (!first) first = L;
+    // the kernel indexes cells as internal block * 512 + cell in 32 bits
+    if ((int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "%s %d: level %d has %d blocks, more than 32-bit cell indices reach", noun, p, li, L->n_blocks);
+    for (int c = 0; c < 8; ++c) {
+        const int32_t b = blocks[8 * p + c], x = cells[8 * p + c];
+        if (b < 0 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "%s %d corner %d: block %d not in 0..%d", noun, p, c, b, L->n_blocks - 1);
+        if (x < 0 || x >= CELLS) return fail(LUDWIG_ERR_INVALID, "%s %d corner %d: cell %d not in 0..511", noun, p, c, x);
+    }
+    for (int a = 0; a < 3; ++a) {
+        const float w = weights[3 * p + a];
+        if (!(w >= 0.0f && w <= 1.0f)) return fail(LUDWIG_ERR_INVALID, "%s %d: weight %d = %g not in [0, 1]", noun, p, a, (double)w);
+    }
+    return LUDWIG_OK;
+}
+
+// every level of the set, also one that holds none of its points, is on the device of `first`
+int check_one_device(const char *set, LudwigLevel *const *levels, int32_t n_levels, const LudwigLevel *first)
+{
+    for (int li = 0; li < n_levels; ++li)
+        if (levels[li] && levels[li]->device != first->device) return fail(LUDWIG_ERR_INVALID, "%s: levels on different devices", set);
+    return LUDWIG_OK;
+}
+
+// whether coarse step t is one of start_step, start_step + interval, ...; and how many of first..last are
+bool step_sampled(int64_t t, int64_t start_step, int32_t interval)
+{
+    return t >= start_step && (t - start_step) % interval == 0;
+}
+
+int64_t samples_in(int64_t first, int64_t last, int64_t start_step, int32_t interval)
+{
+    const int64_t lo = std::max(first, start_step);
+    if (last < lo) return 0;
+    const int64_t k0 = (lo - start_step + interval - 1) / interval, s0 = start_step + k0 * interval;
+    return s0 > last ? 0 : (last - s0) / interval + 1;
+}
+
+}  // namespace
+
 // ---- probes (ludwig_probes_*; no reference counterpart) ----
 // A probe set over a level array: per level the probes it holds (stencil cells in the internal block order, weights, place in the set)
 // and one device ring [capacity][n_probes][4] of samples. The host keeps the coarse step of every used slot; _download empties it.
@@ -1684,19 +1788,6 @@ struct LudwigProbes {
 };
 
 namespace {
-
-bool probe_step_sampled(int64_t t, int64_t start_step, int32_t interval)
-{
-    return t >= start_step && (t - start_step) % interval == 0;
-}
-
-int64_t probe_samples_in(int64_t first, int64_t last, int64_t start_step, int32_t interval)
-{
-    const int64_t lo = std::max(first, start_step);
-    if (last < lo) return 0;
-    const int64_t k0 = (lo - start_step + interval - 1) / interval, s0 = start_step + k0 * interval;
-    return s0 > last ? 0 : (last - s0) / interval + 1;
-}
 
 uint64_t probed_levels_mask(const LudwigProbes *P)
 {
@@ -1721,13 +1812,10 @@ static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub)
     const LudwigProbes::PerLevel &q = P->per[li];
     if (q.n == 0) return LUDWIG_OK;                       // a level without probes launches nothing
     LudwigLevel *L = P->levels[li];
-    {   // rho as a download would return it now; a no-op on the probed levels, which store it every step
-        const int r = ensure_rho(L);
-        if (r) return r;
-    }
-    const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];  // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+    LW_ENSURE_RHO(L);                                     // a no-op on the probed levels, which store it every step
     float *out = P->ring + (size_t)slot * P->n_probes * 4;
-    hipLaunchKernelGGL(k_probe_sample, dim3((unsigned)((q.n + 63) / 64)), dim3(64), 0, L->stream, out, q.cell, q.w, q.col, q.n, L->rho, vel);
+    hipLaunchKernelGGL(k_probe_sample, dim3((unsigned)((q.n + 63) / 64)), dim3(64), 0, L->stream, out, q.cell, q.w, q.col, q.n, L->rho,
+                       vel_out(L, t_sub));
     LW_HIP(hipGetLastError());
     return LUDWIG_OK;
 }
@@ -1749,13 +1837,9 @@ static int surface_stats_launch(LudwigSurfaceStats *S, int64_t t_sub)
 {
     LudwigLevel *L = S->level;
     if (S->n_tri > 0) {
-        {   // rho as a download would return it now; a no-op on the level, which stores it every step since the set was made
-            const int r = ensure_rho(L);
-            if (r) return r;
-        }
-        const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];  // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+        LW_ENSURE_RHO(L);                                 // a no-op on the level, which stores it every step since the set was made
         hipLaunchKernelGGL(k_accumulate_surface_stats, dim3((unsigned)((S->n_tri + 255) / 256)), dim3(256), 0, L->stream, S->sums, S->cell,
-                           S->rec, S->n_tri, L->rho, vel, S->tau, S->pressure_scale, S->stress_scale);
+                           S->rec, S->n_tri, L->rho, vel_out(L, t_sub), S->tau, S->pressure_scale, S->stress_scale);
         LW_HIP(hipGetLastError());
     }
     ++S->n_samples;
@@ -1938,8 +2022,8 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         ph.P = probes;
         ph.S = surface;
         ph.t = t;
-        if (probes && probe_step_sampled(t, s->probes_start_step, s->probes_interval)) ph.slot = probes_open_slot(probes, t);
-        ph.surface = surface && probe_step_sampled(t, s->surface_start_step, s->surface_interval);
+        if (probes && step_sampled(t, s->probes_start_step, s->probes_interval)) ph.slot = probes_open_slot(probes, t);
+        ph.surface = surface && step_sampled(t, s->surface_start_step, s->surface_interval);
         rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
     }
     if (concurrent) {
@@ -1974,10 +2058,7 @@ int ludwig_map_surface_stresses(const LudwigLevel *L, int vel_field, int32_t n_t
         return fail(LUDWIG_ERR_STATE, "level has no blocks or was created without block_pointer");
     if (!(sp->dx > 0.0f) || sp->search_radius < 0 || sp->search_radius > 16) return fail(LUDWIG_ERR_INVALID, "bad dx or search radius");
     LW_HIP(hipSetDevice(L->device));
-    {
-        const int r = ensure_rho(const_cast<LudwigLevel *>(L));
-        if (r) return r;
-    }
+    LW_ENSURE_RHO(L);
     // scratch: [block_pointer | centers | normals | 4 outputs]; a diagnostics call every few hundred steps, so allocated per call
     const size_t nptr = L->h_block_pointer.size(), n = (size_t)n_tri;
     char *buf = nullptr;
@@ -2016,10 +2097,7 @@ int ludwig_level_rho_min(const LudwigLevel *L, float *rho_min)
     *rho_min = __builtin_inff();
     if (L->n_owned == 0) return LUDWIG_OK;
     LW_HIP(hipSetDevice(L->device));
-    {
-        const int r = ensure_rho(const_cast<LudwigLevel *>(L));
-        if (r) return r;
-    }
+    LW_ENSURE_RHO(L);
     int *d = nullptr;
     LW_HIP(hipMalloc((void **)&d, 2 * sizeof(int)));
     const int init[2] = {0x7f800000, 0};                  // +inf, "no NaN seen"
@@ -2062,12 +2140,8 @@ int ludwig_level_stats_accumulate(LudwigLevel *L, int64_t t_sub)
     if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "statistics: t_sub %lld < 0", (long long)t_sub);
     if (L->n_owned == 0) return LUDWIG_OK;
     LW_HIP(hipSetDevice(L->device));
-    {   // rho as ludwig_level_download(LUDWIG_RHO) would return it now: an elided store is replayed first, on the level's stream
-        const int r = ensure_rho(L);
-        if (r) return r;
-    }
-    const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];    // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
-    hipLaunchKernelGGL(k_accumulate_stats, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->stats, L->rho, vel);
+    LW_ENSURE_RHO(L);
+    hipLaunchKernelGGL(k_accumulate_stats, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->stats, L->rho, vel_out(L, t_sub));
     LW_HIP(hipGetLastError());
     ++L->stats_n;
     return LUDWIG_OK;
@@ -2099,13 +2173,9 @@ int ludwig_level_monitor(LudwigLevel *L, int64_t t_sub, int64_t *counts, int64_t
         const int r = dev_alloc(L, &L->monitor_slab, total);
         if (r) return r;
     }
-    {   // rho as ludwig_level_download(LUDWIG_RHO) would return it now: an elided store is replayed first, on the level's stream
-        const int r = ensure_rho(L);
-        if (r) return r;
-    }
-    const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];    // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+    LW_ENSURE_RHO(L);
     MonitorRecord *in = L->monitor_slab;
-    hipLaunchKernelGGL(k_monitor_blocks, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, in, L->rho, vel,
+    hipLaunchKernelGGL(k_monitor_blocks, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, in, L->rho, vel_out(L, t_sub),
                        (const uint8_t *)L->obstacle, (const int32_t *)L->meta, (const int32_t *)L->d_ref2int);
     LW_HIP(hipGetLastError());
     for (int64_t n = L->n_owned; n > 1;) {
@@ -2147,21 +2217,7 @@ int ludwig_level_stats_download(const LudwigLevel *L, int stat, double *host, si
         memset(host, 0, bytes);
         return LUDWIG_OK;
     }
-    LW_HIP(hipSetDevice(L->device));
-    double *tmp = nullptr;                            // one component in the reference order; a result-file call, allocated per call
-    LW_HIP(hipMalloc((void **)&tmp, plane));
-    hipError_t e = hipSuccess;
-    const int64_t n = L->sk;
-    for (int k = 0; k < K && e == hipSuccess; ++k) {
-        hipLaunchKernelGGL(k_component_to_reference<double>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L->stream, tmp,
-                           (const double *)L->stats, L->d_ref2int, n, STAT_COMPONENTS, first + k);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync((char *)host + (size_t)k * plane, tmp, plane, hipMemcpyDeviceToHost, L->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
-    }
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "statistics download: %s", hipGetErrorString(e));
-    return LUDWIG_OK;
+    return download_components(L, (const double *)L->stats, STAT_COMPONENTS, first, K, host, "statistics download");
 }
 
 int ludwig_level_gradient_fields_compute(LudwigLevel *L, int vel_field, float scale)
@@ -2200,21 +2256,7 @@ int ludwig_level_gradient_fields_download(const LudwigLevel *L, int which, float
         memset(host, 0, bytes);
         return LUDWIG_OK;
     }
-    LW_HIP(hipSetDevice(L->device));
-    float *tmp = nullptr;                             // one component in the reference order; a result-file call, allocated per call
-    LW_HIP(hipMalloc((void **)&tmp, plane));
-    hipError_t e = hipSuccess;
-    const int64_t n = L->sk;
-    for (int k = 0; k < K && e == hipSuccess; ++k) {
-        hipLaunchKernelGGL(k_component_to_reference<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L->stream, tmp,
-                           (const float *)L->grad, L->d_ref2int, n, GRAD_COMPONENTS, first + k);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync((char *)host + (size_t)k * plane, tmp, plane, hipMemcpyDeviceToHost, L->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
-    }
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "gradient fields download: %s", hipGetErrorString(e));
-    return LUDWIG_OK;
+    return download_components(L, (const float *)L->grad, GRAD_COMPONENTS, first, K, host, "gradient fields download");
 }
 
 void ludwig_probes_destroy(LudwigProbes *P)
@@ -2243,27 +2285,10 @@ int ludwig_probes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
     // everything is checked before anything is allocated
     const LudwigLevel *first = nullptr;
     for (int32_t p = 0; p < n_probes; ++p) {
-        const int li = level_index[p];
-        if (li < 0 || li >= n_levels) return fail(LUDWIG_ERR_INVALID, "probe %d: level index %d not in 0..%d", p, li, n_levels - 1);
-        const LudwigLevel *L = levels[li];
-        if (!L) return fail(LUDWIG_ERR_INVALID, "probe %d: level %d is null", p, li);
-        if (first && L->device != first->device) return fail(LUDWIG_ERR_INVALID, "probes: levels on different devices");
-        if (!first) first = L;
-        // the kernel indexes cells as internal block * 512 + cell in 32 bits
-        if ((int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
-            return fail(LUDWIG_ERR_INVALID, "probe %d: level %d has %d blocks, more than 32-bit cell indices reach", p, li, L->n_blocks);
-        for (int c = 0; c < 8; ++c) {
-            const int32_t b = blocks[8 * p + c], x = cells[8 * p + c];
-            if (b < 0 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "probe %d corner %d: block %d not in 0..%d", p, c, b, L->n_blocks - 1);
-            if (x < 0 || x >= CELLS) return fail(LUDWIG_ERR_INVALID, "probe %d corner %d: cell %d not in 0..511", p, c, x);
-        }
-        for (int a = 0; a < 3; ++a) {
-            const float w = weights[3 * p + a];
-            if (!(w >= 0.0f && w <= 1.0f)) return fail(LUDWIG_ERR_INVALID, "probe %d: weight %d = %g not in [0, 1]", p, a, (double)w);
-        }
+        const int r = check_stencil_point("probe", "probes", p, levels, n_levels, level_index, blocks, cells, weights, first);
+        if (r) return r;
     }
-    for (int li = 0; li < n_levels; ++li)
-        if (levels[li] && levels[li]->device != first->device) return fail(LUDWIG_ERR_INVALID, "probes: levels on different devices");
+    if (const int r = check_one_device("probes", levels, n_levels, first)) return r;
     LudwigProbes *P = new (std::nothrow) LudwigProbes;
     if (!P) return fail(LUDWIG_ERR_ALLOC, "probes: out of host memory");
     P->device = first->device;
@@ -2272,30 +2297,24 @@ int ludwig_probes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
     P->capacity = capacity;
     P->levels.assign(levels, levels + n_levels);
     P->per.resize(n_levels);
-    LW_HIP(hipSetDevice(P->device));
-    int r = LUDWIG_OK;
+    int r = set_device(P->device);
     for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
         std::vector<int32_t> hc, hcol;
         std::vector<float> hw;
         const LudwigLevel *L = levels[li];
         for (int32_t p = 0; p < n_probes; ++p) {
             if (level_index[p] != li) continue;
-            for (int c = 0; c < 8; ++c) {
-                const int32_t b = blocks[8 * p + c];
-                hc.push_back((L->ref2int.empty() ? b : L->ref2int[b]) * CELLS + cells[8 * p + c]);
-            }
+            for (int c = 0; c < 8; ++c) hc.push_back(internal_cell(L, blocks[8 * p + c], cells[8 * p + c]));
             for (int a = 0; a < 3; ++a) hw.push_back(weights[3 * p + a]);
             hcol.push_back(p);
         }
         LudwigProbes::PerLevel &q = P->per[li];
         q.n = (int)hcol.size();
         if (q.n == 0) continue;
-        hipError_t e = hipMalloc((void **)&q.cell, hc.size() * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&q.w, hw.size() * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&q.col, hcol.size() * 4);
-        if (e == hipSuccess) e = hipMemcpy(q.cell, hc.data(), hc.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(q.w, hw.data(), hw.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(q.col, hcol.data(), hcol.size() * 4, hipMemcpyHostToDevice);
+        hipError_t e = hipSuccess;
+        upload_table(e, hc, q.cell);
+        upload_table(e, hw, q.w);
+        upload_table(e, hcol, q.col);
         if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "probes: level %d tables: %s", li, hipGetErrorString(e));
         // a probe reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now
         // on (+4 of 216 B per cell where the store was elided), so a batch never replays it
@@ -2385,7 +2404,7 @@ int ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_
         for (int i = 0; i < n_levels; ++i)
             if (probes->levels[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "probes: set made over other levels (level %d)", i + 1);
         // nothing is stepped when the batch's samples would not fit
-        const int64_t k = batch_size > 0 ? probe_samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
+        const int64_t k = batch_size > 0 ? samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
         if ((int64_t)probes->slot_step.size() + k > probes->capacity)
             return fail(LUDWIG_ERR_STATE, "probes: %lld samples of this batch overflow the ring (%d of %d used): download first", (long long)k,
                         (int)probes->slot_step.size(), probes->capacity);
@@ -2425,7 +2444,7 @@ int ludwig_surface_stats_create(LudwigLevel *L, int32_t n_tri, const int32_t *bl
         const int32_t b = blocks[i], x = cells[i];
         if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "surface statistics: triangle %d: block %d not in -1..%d", i, b, L->n_blocks - 1);
         if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "surface statistics: triangle %d: cell %d not in 0..511", i, x);
-        hc[i] = b < 0 ? -1 : (L->ref2int.empty() ? b : L->ref2int[b]) * CELLS + x;
+        hc[i] = b < 0 ? -1 : internal_cell(L, b, x);
         hr[i] = wall_dist[i];
         for (int a = 0; a < 3; ++a) hr[(size_t)(a + 1) * n_tri + i] = normals[3 * i + a];
     }
@@ -2437,15 +2456,13 @@ int ludwig_surface_stats_create(LudwigLevel *L, int32_t n_tri, const int32_t *bl
     S->tau = sp->tau;
     S->pressure_scale = sp->pressure_scale;
     S->stress_scale = sp->stress_scale;
-    LW_HIP(hipSetDevice(S->device));
-    int r = LUDWIG_OK;
-    if (n_tri > 0) {
+    int r = set_device(S->device);
+    if (r == LUDWIG_OK && n_tri > 0) {
         const size_t n = (size_t)n_tri;
-        hipError_t e = hipMalloc((void **)&S->cell, n * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&S->rec, n * 16);
+        hipError_t e = hipSuccess;
+        upload_table(e, hc, S->cell);
+        upload_table(e, hr, S->rec);
         if (e == hipSuccess) e = hipMalloc((void **)&S->sums, n * SURFACE_STAT_COMPONENTS * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy(S->cell, hc.data(), n * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(S->rec, hr.data(), n * 16, hipMemcpyHostToDevice);
         // zeroed on the level's stream: ahead of every sample, which is queued there (or on a batch's level stream, which starts behind it)
         if (e == hipSuccess) e = hipMemsetAsync(S->sums, 0, n * SURFACE_STAT_COMPONENTS * sizeof(double), L->stream);
         if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "surface statistics: %d triangles: %s", n_tri, hipGetErrorString(e));
@@ -2548,23 +2565,14 @@ int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
     std::vector<std::vector<uint8_t>> hr(n_levels);
     for (int32_t p = 0; p < n_points; ++p) {
         if (!valid[p]) continue;
+        const int r = check_stencil_point("slice point", "slices", p, levels, n_levels, level_index, blocks, cells, weights, first);
+        if (r) return r;
         const int li = level_index[p];
-        if (li < 0 || li >= n_levels) return fail(LUDWIG_ERR_INVALID, "slice point %d: level index %d not in 0..%d", p, li, n_levels - 1);
         const LudwigLevel *L = levels[li];
-        if (!L) return fail(LUDWIG_ERR_INVALID, "slice point %d: level %d is null", p, li);
-        if (first && L->device != first->device) return fail(LUDWIG_ERR_INVALID, "slices: levels on different devices");
-        if (!first) first = L;
-        if ((int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
-            return fail(LUDWIG_ERR_INVALID, "slice point %d: level %d has %d blocks, more than 32-bit cell indices reach", p, li, L->n_blocks);
         if (!std::isfinite(scales[li]) || scales[li] == 0.0f)
             return fail(LUDWIG_ERR_INVALID, "slices: scale %g of level %d must be finite and non-zero", (double)scales[li], li);
         int32_t e[8];
-        for (int c = 0; c < 8; ++c) {
-            const int32_t b = blocks[8 * p + c], x = cells[8 * p + c];
-            if (b < 0 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "slice point %d corner %d: block %d not in 0..%d", p, c, b, L->n_blocks - 1);
-            if (x < 0 || x >= CELLS) return fail(LUDWIG_ERR_INVALID, "slice point %d corner %d: cell %d not in 0..511", p, c, x);
-            e[c] = (L->ref2int.empty() ? b : L->ref2int[b]) * CELLS + x;
-        }
+        for (int c = 0; c < 8; ++c) e[c] = internal_cell(L, blocks[8 * p + c], cells[8 * p + c]);
         const int32_t b0 = e[0] / CELLS;
         if (b0 >= L->n_owned) return fail(LUDWIG_ERR_INVALID, "slice point %d: base block %d is not owned by this level", p, blocks[8 * p]);
         const int x0 = e[0] & 7, y0 = (e[0] >> 3) & 7, z0 = e[0] >> 6 & 7;
@@ -2581,18 +2589,13 @@ int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
             else if (locate(cx, cy, cz) != e[c])
                 return fail(LUDWIG_ERR_INVALID, "slice point %d corner %d: neither the cell next to the base cell nor the base cell", p, c);
         }
-        for (int a = 0; a < 3; ++a) {
-            const float w = weights[3 * p + a];
-            if (!(w >= 0.0f && w <= 1.0f)) return fail(LUDWIG_ERR_INVALID, "slice point %d: weight %d = %g not in [0, 1]", p, a, (double)w);
-            hw[li].push_back(w);
-        }
+        for (int a = 0; a < 3; ++a) hw[li].push_back(weights[3 * p + a]);
         hb[li].push_back(e[0]);
         hr[li].push_back(rep);
         hcol[li].push_back(p);
     }
     if (!first) return fail(LUDWIG_ERR_INVALID, "slices: no valid point");
-    for (int li = 0; li < n_levels; ++li)
-        if (levels[li] && levels[li]->device != first->device) return fail(LUDWIG_ERR_INVALID, "slices: levels on different devices");
+    if (const int r = check_one_device("slices", levels, n_levels, first)) return r;
     LudwigSlices *S = new (std::nothrow) LudwigSlices;
     if (!S) return fail(LUDWIG_ERR_ALLOC, "slices: out of host memory");
     S->device = first->device;
@@ -2603,8 +2606,7 @@ int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
     S->levels.assign(levels, levels + n_levels);
     S->scales.assign(scales, scales + n_levels);
     S->per.resize(n_levels);
-    LW_HIP(hipSetDevice(S->device));
-    int r = LUDWIG_OK;
+    int r = set_device(S->device);
     for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
         const size_t n = hcol[li].size();
         LudwigSlices::PerLevel &q = S->per[li];
@@ -2624,14 +2626,11 @@ int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
             sr[i] = hr[li][j];
             for (int a = 0; a < 3; ++a) sw[3 * i + a] = hw[li][3 * j + a];
         }
-        hipError_t e = hipMalloc((void **)&q.base, n * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&q.w, n * 12);
-        if (e == hipSuccess) e = hipMalloc((void **)&q.rep, n);
-        if (e == hipSuccess) e = hipMalloc((void **)&q.col, n * 4);
-        if (e == hipSuccess) e = hipMemcpy(q.base, sb.data(), n * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(q.w, sw.data(), n * 12, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(q.rep, sr.data(), n, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(q.col, sc.data(), n * 4, hipMemcpyHostToDevice);
+        hipError_t e = hipSuccess;
+        upload_table(e, sb, q.base);
+        upload_table(e, sw, q.w);
+        upload_table(e, sr, q.rep);
+        upload_table(e, sc, q.col);
         if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "slices: level %d tables: %s", li, hipGetErrorString(e));
     }
     if (r == LUDWIG_OK) {
@@ -2657,10 +2656,8 @@ int ludwig_slices_sample(LudwigSlices *S, int64_t t_coarse)
         const LudwigSlices::PerLevel &q = S->per[li];
         if (q.n == 0) continue;
         LudwigLevel *L = S->levels[li];
-        const int r = ensure_rho(L);                     // rho as a download would return it now
-        if (r) return r;
-        const int64_t t_sub = (t_coarse + 1) * ((int64_t)1 << li) - 1;
-        const float *vel = L->vel[(t_sub % 2 == 0) ? 1 : 0];     // the output buffer of sub-step t_sub (src/solver_control.jl:35-41)
+        LW_ENSURE_RHO(L);
+        const float *vel = vel_out(L, (t_coarse + 1) * ((int64_t)1 << li) - 1);    // the level's last sub-step of coarse step t_coarse
         const dim3 grid((unsigned)((q.n + 63) / 64)), block(64);
         if (S->grad)
             hipLaunchKernelGGL(k_slice_sample<true>, grid, block, 0, L->stream, S->out, (int64_t)S->n_points, q.base, q.w, q.rep, q.col,

@@ -24,7 +24,9 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import Handle
 from .blocks import BLOCK_SIZE
+from .statistics import is_sample_step         # noqa: F401  (one rule for every observer's sampled steps)
 
 F32 = np.float32
 QUANTITIES = ("rho", "ux", "uy", "uz")
@@ -157,9 +159,10 @@ def sample_fields(plan: ProbePlan, fields: Callable[[int], Tuple[np.ndarray, np.
 
 
 # ---- the device probe set (ludwig_probes_*) ----
-class DeviceProbes:
+class DeviceProbes(Handle):
     """a probe set over device levels (DeviceLevel, or None for a level no probe of the plan is on); plan.blocks are the levels' own
     (reference-order) block indices"""
+    _destroy, _closed = "ludwig_probes_destroy", "probe set closed"
 
     def __init__(self, plan: ProbePlan, levels: Sequence, capacity: int, start_step: int = 1, interval: int = 1):
         from . import _lib
@@ -180,12 +183,6 @@ class DeviceProbes:
                                                   self.capacity, C.byref(h)))
         self._h = h
 
-    @property
-    def handle(self):
-        if self._h is None or not self._h.value:
-            raise RuntimeError("probe set closed")
-        return self._h
-
     def sample(self, level_index: int, t_sub: int) -> None:
         from . import _lib
         _lib.check(self._lib.ludwig_probes_sample(self.handle, int(level_index), int(t_sub)))
@@ -198,21 +195,6 @@ class DeviceProbes:
         n = C.c_int32(0)
         _lib.check(self._lib.ludwig_probes_download(self.handle, vals.ctypes.data, steps.ctypes.data, self.capacity, C.byref(n)))
         return steps[: n.value].copy(), vals[: n.value].copy()
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ludwig_probes_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def is_sample_step(step: int, start_step: int, interval: int) -> bool:
-    return step >= start_step and (step - start_step) % interval == 0
 
 
 def samples_in(first: int, last: int, start_step: int, interval: int) -> int:

@@ -37,6 +37,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import Handle
 from .blocks import BLOCK_SIZE
 from .preprocess import SLICE_MAX_POINTS, SlicePlane, slice_axis_points
 from .probes import gather, trilinear
@@ -271,9 +272,10 @@ def local_plan(plan: SlicePlan, mine: np.ndarray, global_to_local: Sequence[Opti
 
 
 # ---- the device slice set (ludwig_slices_*) ----
-class DeviceSlices:
+class DeviceSlices(Handle):
     """one device set over every plane of `plans` on device levels (DeviceLevel, or None for a level no point is on); the plans'
     blocks are the levels' own (reference-order) block indices"""
+    _destroy, _closed = "ludwig_slices_destroy", "slice set closed"
 
     def __init__(self, plans: Sequence[SlicePlan], levels: Sequence, grids: Sequence):
         from . import _lib
@@ -293,12 +295,6 @@ class DeviceSlices:
                                                   _lib.SLICE_GRADIENT if self.gradient else 0, C.byref(h)))
         self._h = h
 
-    @property
-    def handle(self):
-        if self._h is None or not self._h.value:
-            raise RuntimeError("slice set closed")
-        return self._h
-
     def sample(self, t_coarse: int) -> None:
         """queue a sample of every point after coarse step t_coarse"""
         from . import _lib
@@ -311,17 +307,6 @@ class DeviceSlices:
         _lib.check(self._lib.ludwig_slices_download(self.handle, out.ctypes.data, out.nbytes))
         cuts = np.cumsum([0] + self.sizes)
         return [np.ascontiguousarray(out[:, a:b]) for a, b in zip(cuts[:-1], cuts[1:])]
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ludwig_slices_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- files ----

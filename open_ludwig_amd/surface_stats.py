@@ -22,6 +22,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import forces as forces_mod
+from ._lib import Handle
 from .blocks import BLOCK_SIZE
 
 F32 = np.float32
@@ -123,9 +124,10 @@ class HostSurfaceStats:
 
 
 # ---- the device set (ludwig_surface_stats_*) ----
-class DeviceSurfaceStats:
+class DeviceSurfaceStats(Handle):
     """a surface set on device level `device_level` (level index `level_index` of the batch's level array); plan.blocks are that
     level's own (reference-order) block indices"""
+    _destroy, _closed = "ludwig_surface_stats_destroy", "surface statistics set closed"
 
     def __init__(self, plan: SurfacePlan, device_level, level_index: int, tau, params, start_step: int = 1, interval: int = 1):
         from . import _lib
@@ -145,12 +147,6 @@ class DeviceSurfaceStats:
                                                          nr.ctypes.data, C.byref(sp), C.byref(h)))
         self._h = h
 
-    @property
-    def handle(self):
-        if self._h is None or not self._h.value:
-            raise RuntimeError("surface statistics set closed")
-        return self._h
-
     def is_sample_step(self, t: int) -> bool:
         return t >= self.start_step and (t - self.start_step) % self.interval == 0
 
@@ -169,17 +165,6 @@ class DeviceSurfaceStats:
         n = C.c_int64(0)
         _lib.check(self._lib.ludwig_surface_stats_download(self.handle, out.ctypes.data if out.size else None, out.nbytes, C.byref(n)))
         return out, int(n.value)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ludwig_surface_stats_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- results ----

@@ -106,8 +106,40 @@ def test_error_paths_and_reset(gpu):
     d.close()
 
 
+@pytest.mark.gpu
+def test_downloads_do_not_depend_on_the_internal_block_order(gpu, monkeypatch):
+    """The statistics and gradient-field downloads place every block of the internal order back into the reference order. A periodic
+    3 x 2 x 2 block box - block counts that differ per axis, where a wrong permutation shows - stepped twice from a non-uniform state:
+    all three statistics and both gradient fields are bit-identical between a level in the library's own block order and one
+    created under LUDWIG_REFERENCE_BLOCK_ORDER=1 (read when the level is created)."""
+    grids, params = cases.periodic_box((3, 2, 2), init=False)
+    cases.init_perturbed(grids[0], 7)
+    got, orders = [], []
+    for keep_reference_order in (False, True):
+        if keep_reference_order:
+            monkeypatch.setenv("LUDWIG_REFERENCE_BLOCK_ORDER", "1")
+        else:
+            monkeypatch.delenv("LUDWIG_REFERENCE_BLOCK_ORDER", raising=False)
+        d = adapt(grids[0], 0)
+        monkeypatch.undo()                                           # the switch is as it was once the level exists
+        orders.append(d.block_order())
+        execute_timestep_batch([d], 1, 2, np.float32(0.0), params)
+        d.stats_reset()
+        d.stats_accumulate(statistics.t_sub_after(0, 2))
+        arrays = [d.stats_download(name)[0] for name in ("rho", "vel", "vel2")]
+        arrays += list(d.gradient_fields("vel_temp", np.float32(1.0)))  # coarse step 2 is even: its output is vel_temp
+        got.append(arrays)
+        d.close()
+    assert np.array_equal(orders[1], np.arange(12)) and not np.array_equal(orders[0], orders[1]), "the two levels share one block order"
+    for name, a, b in zip(("rho", "vel", "vel2", "vorticity", "q"), *got):
+        assert a.dtype == b.dtype and a.shape == b.shape
+        assert np.array_equal(a.view(np.uint64 if a.dtype == np.float64 else np.uint32),
+                              b.view(np.uint64 if a.dtype == np.float64 else np.uint32)), name
+        assert np.abs(a).max() > 0, name                            # a flow, not a zero field
+
+
 # ---- run_case end to end ----
-_NP = {"Float32": np.float32, "Float64": np.float64, "Int32": np.int32, "Int64": np.int64, "UInt8": np.uint8}
+_NP ={"Float32": np.float32, "Float64": np.float64, "Int32": np.int32, "Int64": np.int64, "UInt8": np.uint8}
 
 
 def _decode(payload, dtype, compressed):

@@ -3,8 +3,6 @@ computes on its owned blocks, whose face stencils reach into ghost blocks the ha
 gathers them like field(). At an odd and an even coarse step, from both velocity buffers (on the finer level the one the flow file
 takes after an even step is the output of the previous sub-step), the gathered fields must be the single-device fields, bit for bit."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -12,26 +10,16 @@ import pytest
 
 from open_ludwig_amd import case, cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _dist_launch import run_ranks  # noqa: E402
 
 
 @pytest.mark.gpu
 def test_two_rank_fields_equal_single_device(gpu, tmp_path):
     import _gradient_dist_worker as w
     levels = 2
-    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_gradient_dist_worker.py"), str(tmp_path), str(levels)]
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    res = run_ranks("_gradient_dist_worker.py", 2, tmp_path, levels)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     got = np.load(os.path.join(tmp_path, "fields.npz"))
     per_rank = [np.load(os.path.join(tmp_path, f"rank{r}.npz")) for r in range(2)]

@@ -5,8 +5,6 @@ because the ranks' trees are added in rank order: a pairwise sum of n <= 2^31 no
 relative, two orders differ by at most twice that - 1e-13 allows it with room; every counted rho is asserted > 0, the bound's premise."""
 import os
 import pickle
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -14,27 +12,17 @@ import pytest
 
 from open_ludwig_amd import case, cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from _dist_launch import run_ranks  # noqa: E402
+
 SUM_RTOL = 1e-13
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 @pytest.mark.gpu
 def test_two_rank_records_equal_single_device(gpu, tmp_path):
     import _monitor_dist_worker as w
-    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_monitor_dist_worker.py"), str(tmp_path)]
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    res = run_ranks("_monitor_dist_worker.py", 2, tmp_path)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     ranks = [pickle.load(open(os.path.join(tmp_path, f"rank{r}.pkl"), "rb")) for r in range(2)]
     for lvl in range(w.LEVELS):

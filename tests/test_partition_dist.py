@@ -2,8 +2,6 @@
 on the one MI355X of the test box and stages messages through the host (RCCL needs one device per rank; the driver
 measures the real RCCL path at round end)."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -12,23 +10,13 @@ import pytest
 from open_ludwig_amd import cases
 from oracle import oracle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _dist_launch import run_ranks  # noqa: E402
 
 
 def _launch(mode, outdir, nbg, steps, world=2, overlap=1):
-    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_dist_worker.py"), mode, str(outdir),
-           str(nbg[0]), str(nbg[1]), str(nbg[2]), str(steps), str(overlap)]
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    res = run_ranks("_dist_worker.py", world, mode, outdir, nbg[0], nbg[1], nbg[2], steps, overlap, timeout=600)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
 
 

@@ -3,8 +3,6 @@ owns its base cell's block, corners in the peer's blocks are read from the ghost
 corners join those halo plans), and DistributedStepper.probes_series gathers to rank 0 in probe order. Most probes' stencils straddle
 the cut, so the gathered series equals the single-device series bit for bit only if those corner ghosts are current."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -12,16 +10,9 @@ import pytest
 
 from open_ludwig_amd import case, cases, partition
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _dist_launch import run_ranks  # noqa: E402
 
 
 def test_straddling_layout_reaches_peer_blocks():
@@ -50,10 +41,7 @@ def test_straddling_layout_reaches_peer_blocks():
 def test_two_rank_series_equals_single_device(gpu, tmp_path):
     import _probes_common as common
     import _probes_dist_worker as w
-    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_probes_dist_worker.py"), str(tmp_path)]
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    res = run_ranks("_probes_dist_worker.py", 2, tmp_path)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     got = np.load(os.path.join(tmp_path, "series.npz"))
     # gathered before any sample: empty series of every probe, not an error

@@ -3,8 +3,6 @@ corners and their face neighbours in the peer's blocks are read from the ghost c
 join the halo plans only when slices are configured), and DistributedStepper.slices_sample gathers to rank 0 in plane order. The
 gathered samples - vorticity and Q included - equal one device's bit for bit only if every one of those ghost cells is current."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -12,16 +10,9 @@ import pytest
 
 from open_ludwig_amd import case, cases, partition, slices as sl
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _dist_launch import run_ranks  # noqa: E402
 
 
 def test_two_rank_layout_reaches_peer_blocks():
@@ -51,10 +42,7 @@ def test_two_rank_layout_reaches_peer_blocks():
 @pytest.mark.gpu
 def test_two_rank_slices_equal_single_device(gpu, tmp_path):
     import _slices_dist_worker as w
-    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_slices_dist_worker.py"), str(tmp_path)]
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    res = run_ranks("_slices_dist_worker.py", 2, tmp_path)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     got = np.load(os.path.join(tmp_path, "slices.npz"))
     mine = [int(np.load(os.path.join(tmp_path, f"rank{r}.npz"))["n_mine"]) for r in range(2)]

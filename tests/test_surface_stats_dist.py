@@ -2,8 +2,6 @@
 fluid cell it owns, DistributedStepper.surface_stats_sums gathers them to rank 0 in triangle order. Per-triangle sums do not depend
 on the partition, so they must be the single-device sums bit for bit."""
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -11,16 +9,9 @@ import pytest
 
 from open_ludwig_amd import case, cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from _dist_launch import run_ranks  # noqa: E402
 
 
 @pytest.mark.gpu
@@ -28,10 +19,7 @@ def test_two_rank_surface_sums_equal_single_device(gpu, tmp_path):
     import _surface_common as common
     import _surface_dist_worker as w
     levels = 2
-    env = dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "_surface_dist_worker.py"), str(tmp_path), str(levels)]
-    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    res = run_ranks("_surface_dist_worker.py", 2, tmp_path, levels)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     n_tri = [int(np.load(os.path.join(tmp_path, f"rank{r}.npz"))["n_tri"]) for r in range(2)]
     assert n_tri[0] > 0 and n_tri[1] > 0, f"the sphere's triangles should be owned on both sides of the cut: {n_tri}"

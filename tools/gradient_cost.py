@@ -12,32 +12,17 @@ what the two arrays cost an output step, device pass, downloads and file include
 BYTES_PER_CELL = 12 (own velocity) + 9 (the six face layers: 6 x 64 cells x 12 B / 512) + 1 (obstacle) + 16 (written) = 38.
 Host clock around work that ends in a device synchronise; the medians of a few repetitions.
 usage: gradient_cost.py [--out FILE]  (default: print only)"""
-import argparse
 import copy
-import json
 import os
 import shutil
-import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
 import numpy as np
 
+from _cost_common import BALL, GOLDEN, add_row, box_case, golden_case, parse_args, timed, write_rows
+
 BYTES_PER_CELL = 12 + 9 + 1 + 16
-
-
-def _timed(fn, sync, reps):
-    out = []
-    for _ in range(reps):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(out))
 
 
 def measure(name, grids, params, u, n_steps=20, n_computes=20, reps=5):
@@ -48,7 +33,7 @@ def measure(name, grids, params, u, n_steps=20, n_computes=20, reps=5):
         d.init_equilibrium()
     sync = dev[0].synchronize
     execute_timestep_batch(dev, 1, 4, np.float32(u), params)            # warm-up: code objects, level streams, a flow
-    step_ms = _timed(lambda: execute_timestep_batch(dev, 5, n_steps, np.float32(u), params), sync, reps) / n_steps
+    step_ms = timed(lambda: execute_timestep_batch(dev, 5, n_steps, np.float32(u), params), sync, reps) / n_steps
     levels = []
     for g, d in zip(grids, dev):
         scale = float(np.float32(1.0 / g.dx))
@@ -57,8 +42,8 @@ def measure(name, grids, params, u, n_steps=20, n_computes=20, reps=5):
             for _ in range(n_computes):
                 _lib.check(lib.ludwig_level_gradient_fields_compute(d.handle, _lib.VEL, scale))
         compute()                                                        # allocation, first launch
-        ms = _timed(compute, sync, reps) / n_computes
-        dl = _timed(lambda: d.gradient_fields("vel", scale), sync, reps)
+        ms = timed(compute, sync, reps) / n_computes
+        dl = timed(lambda: d.gradient_fields("vel", scale), sync, reps)
         cells = 512 * g.n_blocks
         levels.append({"level": g.level_id, "blocks": g.n_blocks, "cells": cells, "compute_ms": round(ms, 4),
                        "compute_GBps": round(BYTES_PER_CELL * cells / (ms * 1e-3) / 1e9, 1),
@@ -72,12 +57,11 @@ def measure(name, grids, params, u, n_steps=20, n_computes=20, reps=5):
 def run_case_output_step(reps=3):
     """one run_case batch of 8 steps with an output step at its end, Vorticity / QCriterion off and on (ball1m, 3 levels)"""
     from open_ludwig_amd import case, preprocess as pp
-    g = os.path.join(ROOT, "tests", "golden")
-    cfg = pp.load_case_configuration(os.path.join(g, "ball1m_config.yaml"), {"basic": {"surface_resolution": 25, "flow": {"velocity": 4.0}}})
+    cfg = pp.load_case_configuration(os.path.join(GOLDEN, "ball1m_config.yaml"), BALL)
     cfg.diag_freq = cfg.output_freq = 8
     on = copy.copy(cfg)
     on.output_fields = cfg.output_fields + ("Vorticity", "QCriterion")
-    setup = pp.setup_multilevel_domain(cfg, os.path.join(g, "ball1m.stl"))
+    setup = pp.setup_multilevel_domain(cfg, os.path.join(GOLDEN, "ball1m.stl"))
     res = {}
     for label, c in (("off", cfg), ("on", on), ("off", cfg), ("on", on)):       # the first pair is the warm-up
         times = []
@@ -93,26 +77,13 @@ def run_case_output_step(reps=3):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from open_ludwig_amd import _lib, cases
-    if _lib.device_count() < 1:
-        raise SystemExit("gradient_cost.py needs a GPU")
+    args = parse_args("gradient_cost.py")
     rows = []
-    grids, params = cases.periodic_box((32, 32, 32), init=False)
-    rows.append(measure("periodic 256^3", grids, params, 0.0))
-    from open_ludwig_amd import preprocess as pp
-    g = os.path.join(ROOT, "tests", "golden")
-    cfg = pp.load_case_configuration(os.path.join(g, "ball1m_config.yaml"), {"basic": {"surface_resolution": 25, "flow": {"velocity": 4.0}}})
-    grids, _, phys, _ = pp.setup_multilevel_domain(cfg, os.path.join(g, "ball1m.stl"))
-    rows.append(measure("ball1m sphere, 3 levels (Re 266k setup)", grids, pp.solver_params(cfg, phys), cfg.u_lattice))
-    rows.append(run_case_output_step())
-    for r in rows:
-        print(json.dumps(r))
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(rows, fh, indent=1)
+    add_row(rows, measure(*box_case()))
+    name, cfg, grids, _, _, params = golden_case()
+    add_row(rows, measure(name, grids, params, cfg.u_lattice))
+    add_row(rows, run_case_output_step())
+    write_rows(rows, args.out)
 
 
 if __name__ == "__main__":

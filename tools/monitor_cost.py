@@ -11,30 +11,15 @@ Per case:
   run_case_added_ms_per_step  monitor_replay_ms / diag_freq of the shipped ball1m case: what advanced.flow_monitor adds to run_case
 TB/s = bytes per cell x owned cells / time. Host clock around work that ends in a device synchronise; the medians of a few repetitions.
 usage: monitor_cost.py [--out FILE]  (default: print only)"""
-import argparse
-import json
 import os
-import sys
 import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 import numpy as np
 
+from _cost_common import GOLDEN, add_row, box_case, golden_case, parse_args, timed, write_rows
+
 STATS_BYTES_PER_CELL = 4 + 12 + 2 * 80
 MONITOR_BYTES_PER_CELL = 4 + 12 + 1
-
-
-def _timed(fn, sync, reps):
-    out = []
-    for _ in range(reps):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(out))
 
 
 def measure(name, grids, params, u, diag_freq, n_steps=20, n_samples=20, reps=5):
@@ -60,10 +45,10 @@ def measure(name, grids, params, u, diag_freq, n_steps=20, n_samples=20, reps=5)
     steps(4)                                                       # warm-up: code objects, level streams, the monitor's slab
     sample_all(t[0] - 1)
     recs = monitor_all(t[0] - 1)
-    step_ms = _timed(lambda: steps(n_steps), sync, reps) / n_steps
-    sample_ms = _timed(lambda: [sample_all(t[0] - 1) for _ in range(n_samples)], sync, reps) / n_samples
-    monitor_ms = _timed(lambda: [monitor_all(t[0] - 1) for _ in range(n_samples)], sync, reps) / n_samples
-    per_level = [_timed(lambda d=d, lvl=lvl: [d.monitor(statistics.t_sub_after(lvl, t[0] - 1)) for _ in range(n_samples)], sync, reps) / n_samples
+    step_ms = timed(lambda: steps(n_steps), sync, reps) / n_steps
+    sample_ms = timed(lambda: [sample_all(t[0] - 1) for _ in range(n_samples)], sync, reps) / n_samples
+    monitor_ms = timed(lambda: [monitor_all(t[0] - 1) for _ in range(n_samples)], sync, reps) / n_samples
+    per_level = [timed(lambda d=d, lvl=lvl: [d.monitor(statistics.t_sub_after(lvl, t[0] - 1)) for _ in range(n_samples)], sync, reps) / n_samples
                  for lvl, d in enumerate(dev)]
     replay = []
     for _ in range(reps):
@@ -94,26 +79,14 @@ def measure(name, grids, params, u, diag_freq, n_steps=20, n_samples=20, reps=5)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from open_ludwig_amd import _lib, cases
-    if _lib.device_count() < 1:
-        raise SystemExit("monitor_cost.py needs a GPU")
+    args = parse_args("monitor_cost.py")
     from open_ludwig_amd import preprocess as pp
-    g = os.path.join(ROOT, "tests", "golden")
-    shipped = pp.load_case_configuration(os.path.join(g, "ball1m_config.yaml"))
+    shipped = pp.load_case_configuration(os.path.join(GOLDEN, "ball1m_config.yaml"))
     rows = []
-    grids, params = cases.periodic_box((32, 32, 32), init=False)
-    rows.append(measure("periodic 256^3", grids, params, 0.0, shipped.diag_freq))
-    cfg = pp.load_case_configuration(os.path.join(g, "ball1m_config.yaml"), {"basic": {"surface_resolution": 25, "flow": {"velocity": 4.0}}})
-    grids, _, phys, _ = pp.setup_multilevel_domain(cfg, os.path.join(g, "ball1m.stl"))
-    rows.append(measure("ball1m sphere, 3 levels (Re 266k setup)", grids, pp.solver_params(cfg, phys), cfg.u_lattice, shipped.diag_freq))
-    for r in rows:
-        print(json.dumps(r))
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(rows, fh, indent=1)
+    add_row(rows, measure(*box_case(), shipped.diag_freq))
+    name, cfg, grids, _, _, params = golden_case()
+    add_row(rows, measure(name, grids, params, cfg.u_lattice, shipped.diag_freq))
+    write_rows(rows, args.out)
 
 
 if __name__ == "__main__":

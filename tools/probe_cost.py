@@ -12,16 +12,11 @@ see the host time between the synchronised batches too, as a run does). The medi
 and the overhead of each against `off`; drain_ms_per_coarse_step is the host clock around the ring downloads alone (inside the
 bracket).
 usage: probe_cost.py [--out FILE] [--reps N]"""
-import argparse
-import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
 import numpy as np
+
+from _cost_common import HipEvent, add_row, box_case, golden_case, parse_args, write_rows
 
 BATCH, BATCHES = 8, 8
 
@@ -34,28 +29,6 @@ def ball1m_points():
     return np.array(pts)
 
 
-class _HipEvent:
-    """a hipEvent_t of the HIP runtime libludwig_hip.so runs on, recorded on the null stream (the levels' stream here)"""
-
-    def __init__(self):
-        import ctypes as C
-        from open_ludwig_amd import _lib
-        _lib.load()
-        path = next(l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l)   # the runtime the library loaded
-        self.C, self.hip = C, C.CDLL(path)
-        self.ev = C.c_void_p()
-        assert self.hip.hipEventCreate(C.byref(self.ev)) == 0
-
-    def record(self):
-        assert self.hip.hipEventRecord(self.ev, None) == 0
-
-    def elapsed_ms(self, end) -> float:
-        assert self.hip.hipEventSynchronize(end.ev) == 0
-        ms = self.C.c_float()
-        assert self.hip.hipEventElapsedTime(self.C.byref(ms), self.ev, end.ev) == 0
-        return float(ms.value)
-
-
 def measure(name, grids, params, u, plan, reps):
     from open_ludwig_amd import adapt, execute_timestep_batch, probes as pm
     # ONE copy of the levels for every configuration: separate copies differ by a few % on their own (allocation placement)
@@ -66,7 +39,7 @@ def measure(name, grids, params, u, plan, reps):
             "probes_10": [pm.DeviceProbes(plan, dev, BATCH, 1, 10), True]}
     t_next = [1]
 
-    ev0, ev1 = _HipEvent(), _HipEvent()
+    ev0, ev1 = HipEvent(), HipEvent()
 
     def run(key):
         """(device ms per coarse step, host ms per coarse step spent draining the ring)"""
@@ -114,28 +87,17 @@ def measure(name, grids, params, u, plan, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=9)
-    args = ap.parse_args()
-    from open_ludwig_amd import _lib, cases, preprocess as pp, probes as pm
-    if _lib.device_count() < 1:
-        raise SystemExit("probe_cost.py needs a GPU")
+    args = parse_args("probe_cost.py", ("--reps", dict(type=int, default=9)))
+    from open_ludwig_amd import probes as pm
     rows = []
-    g = os.path.join(ROOT, "tests", "golden")
-    cfg = pp.load_case_configuration(os.path.join(g, "ball1m_config.yaml"), {"basic": {"surface_resolution": 25, "flow": {"velocity": 4.0}}})
-    grids, _, phys, _ = pp.setup_multilevel_domain(cfg, os.path.join(g, "ball1m.stl"))
+    name, cfg, grids, _, phys, params = golden_case()
     plan = pm.plan_probes(ball1m_points(), grids, phys.mesh_offset)
-    rows.append(measure("ball1m sphere, 3 levels (Re 266k setup)", grids, pp.solver_params(cfg, phys), cfg.u_lattice, plan, args.reps))
-    print(json.dumps(rows[-1]), flush=True)
-    grids, params = cases.periodic_box((32, 32, 32), init=False)
+    add_row(rows, measure(name, grids, params, cfg.u_lattice, plan, args.reps))
+    name, grids, params, u = box_case()
     rng = np.random.default_rng(5)
     plan = pm.plan_probes(rng.uniform(8.0, 248.0, (64, 3)), grids)
-    rows.append(measure("periodic 256^3", grids, params, 0.0, plan, args.reps))
-    print(json.dumps(rows[-1]), flush=True)
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(rows, fh, indent=1)
+    add_row(rows, measure(name, grids, params, u, plan, args.reps))
+    write_rows(rows, args.out)
 
 
 if __name__ == "__main__":

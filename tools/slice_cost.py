@@ -14,25 +14,15 @@ run_case (ball1m, 8 coarse steps, one batch, forces and diagnostics on): wall ti
 (flow_%06d.vtu + surface_%06d.vtu at step 8), and with one slice output step (the plane above at step 8); the differences against no
 output are the cost of each output step.
 usage: slice_cost.py [--out FILE] [--reps N] [--cases ball1m,wing] [--run-case 0|1]"""
-import argparse
-import json
 import os
-import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
 import numpy as np
 
+from _cost_common import BALL, GOLDEN, add_row, golden_case, parse_args, write_rows
+
 STEPS = 40
-
-
-BALL = {"basic": {"surface_resolution": 25, "flow": {"velocity": 4.0}}}
-CASES = {"ball1m": ("ball1m sphere, 3 levels (Re 266k setup)", "ball1m", "ball1m.stl", BALL),
-         "wing": ("wing5deg, surface resolution 200, 3 levels", "wing5deg", "wing5deg_model.stl",
-                  {"basic": {"surface_resolution": 200, "num_levels": 3}})}
 
 
 def plane_of(key, grids, phys):
@@ -47,9 +37,8 @@ def plane_of(key, grids, phys):
 
 def run_case_cost(reps):
     """(seconds without output, with one flow-file output step, with one slice output step), medians of reps runs of ball1m"""
-    import tempfile
     from open_ludwig_amd import case, preprocess as pp
-    g = os.path.join(ROOT, "tests", "golden")
+    g = GOLDEN
     plane = {"name": "wake", "normal": "y", "position": 0.0, "bounds": [[-1.0, 4.0], [-1.25, 1.25]], "spacing": 5.0 / 1023,
              "fields": ["density", "velocity", "velocity_magnitude", "vorticity", "q_criterion"]}
     runs = {"none": (10**6, False), "flow": (8, False), "slice": (10**6, True)}
@@ -69,12 +58,8 @@ def run_case_cost(reps):
 
 
 def measure(key, reps):
-    from open_ludwig_amd import case, preprocess as pp, slices as sl
-    g = os.path.join(ROOT, "tests", "golden")
-    name, cfg_name, stl, over = CASES[key]
-    cfg = pp.load_case_configuration(os.path.join(g, cfg_name + "_config.yaml"), over)
-    grids, _, phys, _ = pp.setup_multilevel_domain(cfg, os.path.join(g, stl))
-    params = pp.solver_params(cfg, phys)
+    from open_ludwig_amd import case, slices as sl
+    name, cfg, grids, _, phys, params = golden_case(key)
     spec = plane_of(key, grids, phys)
     t0 = time.perf_counter()
     plan = sl.plan_slice(spec, grids, phys.mesh_offset)
@@ -129,27 +114,16 @@ def measure(key, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--cases", default="ball1m,wing")
-    ap.add_argument("--run-case", type=int, default=1)
-    args = ap.parse_args()
-    from open_ludwig_amd import _lib
-    if _lib.device_count() < 1:
-        raise SystemExit("slice_cost.py needs a GPU")
+    args = parse_args("slice_cost.py", ("--reps", dict(type=int, default=7)), ("--cases", dict(default="ball1m,wing")),
+                      ("--run-case", dict(type=int, default=1)))
     rows = []
     for key in args.cases.split(","):
-        rows.append(measure(key, args.reps))
-        print(json.dumps(rows[-1]), flush=True)
+        add_row(rows, measure(key, args.reps))
     if args.run_case:
         t = run_case_cost(3)
-        rows.append({"case": "ball1m run_case, 8 coarse steps", "wall_s": t,
-                     "flow_output_step_s": round(t["flow"] - t["none"], 3), "slice_output_step_s": round(t["slice"] - t["none"], 3)})
-        print(json.dumps(rows[-1]), flush=True)
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(rows, fh, indent=1)
+        add_row(rows, {"case": "ball1m run_case, 8 coarse steps", "wall_s": t,
+                       "flow_output_step_s": round(t["flow"] - t["none"], 3), "slice_output_step_s": round(t["slice"] - t["none"], 3)})
+    write_rows(rows, args.out)
 
 
 if __name__ == "__main__":

@@ -8,29 +8,13 @@ Per case:
   step_and_sample  a coarse step plus a sample of every level, per coarse step, sampling every `interval` steps
 GB/s = 176 B x owned cells / sample_ms. Host clock around work that ends in a device synchronise; the medians of a few repetitions.
 usage: stats_cost.py [--out FILE]  (default: print only)"""
-import argparse
-import json
-import os
-import sys
 import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 import numpy as np
 
+from _cost_common import add_row, box_case, golden_case, parse_args, timed, write_rows
+
 BYTES_PER_CELL = 4 + 12 + 2 * 80
-
-
-def _timed(fn, sync, reps):
-    out = []
-    for _ in range(reps):
-        sync()
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(out))
 
 
 def measure(name, grids, params, u, n_steps=20, n_samples=20, reps=5, interval=10):
@@ -52,8 +36,8 @@ def measure(name, grids, params, u, n_steps=20, n_samples=20, reps=5, interval=1
 
     steps(4)                                                       # warm-up: code objects, level streams
     sample_all(t[0] - 1)
-    step_ms = _timed(lambda: steps(n_steps), sync, reps) / n_steps
-    sample_ms = _timed(lambda: [sample_all(t[0] - 1) for _ in range(n_samples)], sync, reps) / n_samples
+    step_ms = timed(lambda: steps(n_steps), sync, reps) / n_steps
+    sample_ms = timed(lambda: [sample_all(t[0] - 1) for _ in range(n_samples)], sync, reps) / n_samples
     replay = []
     for _ in range(reps):
         for d in dev:
@@ -69,7 +53,7 @@ def measure(name, grids, params, u, n_steps=20, n_samples=20, reps=5, interval=1
         for _ in range(n_steps // interval):
             steps(interval)
             sample_all(t[0] - 1)
-    both_ms = _timed(run_sampled, sync, reps) / (n_steps // interval * interval)
+    both_ms = timed(run_sampled, sync, reps) / (n_steps // interval * interval)
     cells = sum(512 * g.n_blocks for g in grids)
     res = {"case": name, "levels": len(grids), "blocks": [g.n_blocks for g in grids], "cells": cells,
            "step_ms": round(step_ms, 4), "sample_ms": round(sample_ms, 4),
@@ -83,25 +67,12 @@ def measure(name, grids, params, u, n_steps=20, n_samples=20, reps=5, interval=1
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    from open_ludwig_amd import _lib, cases
-    if _lib.device_count() < 1:
-        raise SystemExit("stats_cost.py needs a GPU")
+    args = parse_args("stats_cost.py")
     rows = []
-    grids, params = cases.periodic_box((32, 32, 32), init=False)
-    rows.append(measure("periodic 256^3", grids, params, 0.0))
-    from open_ludwig_amd import preprocess as pp
-    g = os.path.join(ROOT, "tests", "golden")
-    cfg = pp.load_case_configuration(os.path.join(g, "ball1m_config.yaml"), {"basic": {"surface_resolution": 25, "flow": {"velocity": 4.0}}})
-    grids, _, phys, _ = pp.setup_multilevel_domain(cfg, os.path.join(g, "ball1m.stl"))
-    rows.append(measure("ball1m sphere, 3 levels (Re 266k setup)", grids, pp.solver_params(cfg, phys), cfg.u_lattice))
-    for r in rows:
-        print(json.dumps(r))
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(rows, fh, indent=1)
+    add_row(rows, measure(*box_case()))
+    name, cfg, grids, _, _, params = golden_case()
+    add_row(rows, measure(name, grids, params, cfg.u_lattice))
+    write_rows(rows, args.out)
 
 
 if __name__ == "__main__":

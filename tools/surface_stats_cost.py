@@ -10,24 +10,11 @@ Every measurement is BATCHES batches of 8 coarse steps (run_case's async_depth),
 bracketed by two HIP events on the levels' stream (the null stream; the events see the host time between the synchronised batches
 too, as a run does). The medians of `--reps` alternating rounds, in ms per coarse step, and the overhead of each against `off`.
 usage: surface_stats_cost.py [--out FILE] [--reps N] [--cases ball1m,wing]"""
-import argparse
-import json
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
 import numpy as np
 
-from probe_cost import _HipEvent
+from _cost_common import HipEvent, add_row, golden_case, parse_args, write_rows
 
 BATCH, BATCHES = 8, 8
-CASES = {"ball1m": ("ball1m sphere, 3 levels (Re 266k setup)", "ball1m", "ball1m.stl",
-                    {"basic": {"surface_resolution": 25, "flow": {"velocity": 4.0}}}),
-         "wing": ("wing5deg, surface resolution 200, 3 levels", "wing5deg", "wing5deg_model.stl",
-                  {"basic": {"surface_resolution": 200, "num_levels": 3}})}
 
 
 def measure(name, grids, mesh, phys, params, u, reps):
@@ -42,7 +29,7 @@ def measure(name, grids, mesh, phys, params, u, reps):
             "surface_1": [ss.DeviceSurfaceStats(plan, dev[fin], fin, grids[fin].tau, phys, 1, 1), True],
             "surface_10": [ss.DeviceSurfaceStats(plan, dev[fin], fin, grids[fin].tau, phys, 1, 10), True]}
     t_next = [1]
-    ev0, ev1 = _HipEvent(), _HipEvent()
+    ev0, ev1 = HipEvent(), HipEvent()
 
     def run(key):
         S, store = sets[key]
@@ -79,25 +66,12 @@ def measure(name, grids, mesh, phys, params, u, reps):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=9)
-    ap.add_argument("--cases", default="ball1m,wing")
-    args = ap.parse_args()
-    from open_ludwig_amd import _lib, preprocess as pp
-    if _lib.device_count() < 1:
-        raise SystemExit("surface_stats_cost.py needs a GPU")
-    g = os.path.join(ROOT, "tests", "golden")
+    args = parse_args("surface_stats_cost.py", ("--reps", dict(type=int, default=9)), ("--cases", dict(default="ball1m,wing")))
     rows = []
     for key in args.cases.split(","):
-        name, cfg_name, stl, over = CASES[key]
-        cfg = pp.load_case_configuration(os.path.join(g, cfg_name + "_config.yaml"), over)
-        grids, mesh, phys, _ = pp.setup_multilevel_domain(cfg, os.path.join(g, stl))
-        rows.append(measure(name, grids, mesh, phys, pp.solver_params(cfg, phys), cfg.u_lattice, args.reps))
-        print(json.dumps(rows[-1]), flush=True)
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(rows, fh, indent=1)
+        name, cfg, grids, mesh, phys, params = golden_case(key)
+        add_row(rows, measure(name, grids, mesh, phys, params, cfg.u_lattice, args.reps))
+    write_rows(rows, args.out)
 
 
 if __name__ == "__main__":
