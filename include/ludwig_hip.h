@@ -288,6 +288,59 @@ int  ludwig_level_stats_download(const LudwigLevel *level, int stat, double *hos
  * Runs on the level's stream: one small download, one synchronisation. A level created with n_owned < 0 returns the empty record. */
 int  ludwig_level_monitor(LudwigLevel *level, int64_t t_sub, int64_t *counts, int64_t *cells, float *extremes, double *sums);
 
+/* ---- wall diagnostics: what the wall model does in its own range (no reference counterpart: the reference reads y_plus_target and
+ * never computes a y+) ----
+ * The wall-model state of a cell is what perform_timestep_v2!'s kernel passes through on its way to the wall force
+ * (src/physics_kernels.jl:206-236), restated operation by operation in float32 from (wall_dist, the level's tau, rho, |u| =
+ * sqrt(ux ux + uy uy + uz uz)): u_tau, y_plus = u_tau wall_dist / nu - the FINAL u_tau, not the provisional one that picks the branch -
+ * and a code: 0 not near the wall (!(0 < wall_dist < 10)) or an obstacle cell, 1 near the wall but the model is skipped (|u| <= 1e-6 or
+ * nu <= 1e-10), 2 the power law's u_tau is kept (y_p <= 11.81 or u_plus_law <= 0.1), 3 the log law replaced it; 4 is or-ed in where the
+ * step applies a force (tau_wall > tau_res). Codes 0 and 1 give u_tau = y_plus = 0. The step stores rho and u after the sponge and before
+ * the force, so the state sub-step t_sub wrote is exactly what that sub-step's wall model saw.
+ *
+ * ludwig_level_wall_census: one all-integer record from one pass over the blocks this device owns (blocks without a near-wall cell are
+ * skipped): rho as ludwig_level_download(LUDWIG_RHO) would return it now (an elided store is replayed first), the velocity buffer sub-step
+ * t_sub wrote (vel_temp if t_sub is even, vel if odd), the level's wall_dist, obstacle and tau.
+ *   near_cells   non-obstacle cells with 0 < wall_dist < 10
+ *   evaluated    of those, the cells with code >= 2 whose y_plus and wall shear rho u_tau u_tau are both finite
+ *   log_law, forced   of the evaluated cells, those with code 3 / with the force bit
+ *   non_finite   cells with code >= 2 whose y_plus or wall shear is not finite; they count here and in near_cells only
+ *   min_bits, max_bits   the float32 bits of the least / greatest y_plus over the evaluated cells (positive floats order as unsigned
+ *                integers); 0xFFFFFFFF / 0 when there is none
+ *   hist         the evaluated cells by y_plus, eight bins per octave from the bits alone: with e8 = bits >> 20 (the exponent and the top
+ *                three mantissa bits) bin 0 if e8 < 936 (y_plus < 2^-10), bin 1 + (e8 - 936) for 936 <= e8 < 1128, bin 193 if e8 >= 1128
+ *                (2^14 and above); the lower edge of bin j in 1..193 is the float with bits (935 + j) << 20
+ * Integer sums commute, so the record depends on neither the block order nor on how the level is cut over ranks: the records of the
+ * ranks add up (min / max of the bits) to one device's. The 1.6-KB device record is made by the first call; a level never asked
+ * allocates and launches nothing. Runs on the level's stream: one small download, one synchronisation. A level created with
+ * n_owned < 0 returns the empty record. */
+#define LUDWIG_WALL_BINS 194
+typedef struct LudwigWallCensus {
+    uint64_t near_cells, evaluated, log_law, forced, non_finite;
+    uint32_t min_bits, max_bits;
+    uint64_t hist[LUDWIG_WALL_BINS];
+} LudwigWallCensus;
+int  ludwig_level_wall_census(LudwigLevel *level, int64_t t_sub, LudwigWallCensus *out);
+
+/* A wall-surface set lives on one level (the finest). Triangle i reads its nearest fluid cell (reference block index blocks[i], 0-based,
+ * -1 = none found; cell cells[i] = x + 8 y + 64 z) and has the normal normals[3i + 0..2]. A compute evaluates seven float32 values per
+ * triangle, [7][n_tri]: p exactly as ludwig_map_surface_stresses does for that cell; tau_model_x, y, z = (rho u_tau u_tau) stress_scale
+ * along the tangential velocity u - (u.n) n (that call's direction), zero where |u_t| <= 1e-10 or code < 2; u_tau; y_plus; the code as
+ * a float. The wall distance of the model is the LEVEL's wall_dist at the cell - the one the step used - and tau the level's own; of sp
+ * only pressure_scale and stress_scale are read. A triangle without a cell gives the p of rho = 1 and zeros. n_tri = 0 is allowed (a rank
+ * that owns none of the triangles). The level may hold at most 2^31 / 512 blocks. */
+typedef struct LudwigWallSurface LudwigWallSurface;   /* opaque */
+int  ludwig_wall_surface_create(LudwigLevel *level, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *normals,
+                                const LudwigSurfaceParams *sp, LudwigWallSurface **out);
+/* frees the set, not the level; it does not touch the level, so it may come before or after its destruction */
+void ludwig_wall_surface_destroy(LudwigWallSurface *set);
+/* evaluate the state sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd; rho as a download would return it), queued on the
+ * level's stream, no host synchronisation */
+int  ludwig_wall_surface_compute(LudwigWallSurface *set, int64_t t_sub);
+/* the last computed values [7][n_tri] in the caller's triangle order (bytes must be 7 * n_tri * 4); synchronizes the level's stream.
+ * LUDWIG_ERR_STATE before the first compute. */
+int  ludwig_wall_surface_download(LudwigWallSurface *set, float *values, size_t bytes);
+
 /* ---- velocity-gradient fields (no reference counterpart for the output; the gradient is compute_velocity_gradients,
  * src/physics_utils.jl:44-82, the one WALE uses) ----
  * Per cell of the blocks this device owns, from one velocity buffer u: g_ij = (0.5f (u_i(+e_j) - u_i(-e_j))) * scale with the

@@ -225,6 +225,41 @@ function surface_stats_download!(sums::Matrix{Float64}, s::Ptr{Cvoid})
     return Int(n[])
 end
 
+# wall diagnostics (no reference counterpart: Y_PLUS_TARGET is read and never used): the wall model's y+, u_tau and modelled shear
+"""LudwigWallCensus of include/ludwig_hip.h: counts, the Float32 bits of the least / greatest y+, 194 bins (eight per octave)"""
+struct WallCensus
+    near_cells::UInt64
+    evaluated::UInt64
+    log_law::UInt64
+    forced::UInt64
+    non_finite::UInt64
+    min_bits::UInt32
+    max_bits::UInt32
+    hist::NTuple{194,UInt64}
+end
+"""the census of the level's owned blocks from the state sub-step `timestep` wrote (vel_temp if even, vel if odd; rho as stored)"""
+function wall_census(d::DeviceLevel, timestep::Integer)
+    out = Ref{WallCensus}()
+    check(ccall((:ludwig_level_wall_census, LIB), Cint, (Ptr{Cvoid}, Int64, Ref{WallCensus}), d.handle, Int64(timestep), out))
+    return out[]
+end
+"""a wall-surface set on `grid`: per triangle its nearest fluid cell (0-based reference block index, -1 = none; cell x + 8y + 64z)
+and normal (3 x n); the two scales from `sp`. Free it with `wall_surface_destroy`."""
+function wall_surface_create(grid::DeviceLevel, blocks::Vector{Int32}, cells::Vector{Int32}, normals::Matrix{Float32}, sp::SurfaceParams)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve blocks cells normals check(ccall((:ludwig_wall_surface_create, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ref{SurfaceParams}, Ref{Ptr{Cvoid}}),
+        grid.handle, Int32(length(blocks)), blocks, cells, normals, sp, out))
+    return out[]
+end
+wall_surface_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_wall_surface_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""evaluate the state the level's sub-step `timestep` wrote (queued on the level's stream)"""
+wall_surface_compute!(s::Ptr{Cvoid}, timestep::Integer) =
+    check(ccall((:ludwig_wall_surface_compute, LIB), Cint, (Ptr{Cvoid}, Int64), s, Int64(timestep)))
+"""the last values into `values` (n_tri x 7: p, tau_model_x, y, z, u_tau, y_plus, code)"""
+wall_surface_download!(values::Matrix{Float32}, s::Ptr{Cvoid}) =
+    GC.@preserve values check(ccall((:ludwig_wall_surface_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), s, values, sizeof(values)))
+
 """
 Multi-GPU hosts only: a HIP stream for the stepping kernels that leaves `reserved_cus` compute units to the halo exchange
 (`ludwig_stream_create`, include/ludwig_hip.h); hand it to `ludwig_level_set_stream`. No counterpart in the reference.

@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = [
     "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
     "ludwig_slices_create", "ludwig_slices_destroy", "ludwig_slices_sample", "ludwig_slices_download",
     "ludwig_level_monitor",
+    "ludwig_level_wall_census", "ludwig_wall_surface_create", "ludwig_wall_surface_destroy", "ludwig_wall_surface_compute",
+    "ludwig_wall_surface_download",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -96,6 +98,16 @@ class BatchSamplers(C.Structure):
     _fields_ = [
         ("probes", C.c_void_p), ("probes_start_step", C.c_int64), ("probes_interval", C.c_int32),
         ("surface", C.c_void_p), ("surface_start_step", C.c_int64), ("surface_interval", C.c_int32),
+    ]
+
+
+WALL_BINS = 194
+
+
+class WallCensus(C.Structure):
+    _fields_ = [
+        ("near_cells", C.c_uint64), ("evaluated", C.c_uint64), ("log_law", C.c_uint64), ("forced", C.c_uint64),
+        ("non_finite", C.c_uint64), ("min_bits", C.c_uint32), ("max_bits", C.c_uint32), ("hist", C.c_uint64 * WALL_BINS),
     ]
 
 
@@ -194,6 +206,11 @@ def load() -> C.CDLL:
         "ludwig_slices_destroy": (None, [vp]),
         "ludwig_slices_sample": (C.c_int, [vp, i64]),
         "ludwig_slices_download": (C.c_int, [vp, vp, C.c_size_t]),
+        "ludwig_level_wall_census": (C.c_int, [vp, i64, C.POINTER(WallCensus)]),
+        "ludwig_wall_surface_create": (C.c_int, [vp, i32, vp, vp, vp, C.POINTER(SurfaceParams), C.POINTER(vp)]),
+        "ludwig_wall_surface_destroy": (None, [vp]),
+        "ludwig_wall_surface_compute": (C.c_int, [vp, i64]),
+        "ludwig_wall_surface_download": (C.c_int, [vp, vp, C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

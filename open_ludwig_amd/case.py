@@ -22,6 +22,7 @@ from . import probes as probes_mod
 from . import slices as slices_mod
 from . import statistics as stats_mod
 from . import surface_stats as surface_mod
+from . import wall_diagnostics as wall_mod
 from .blocks import adapt
 from .preprocess import CaseConfig, DomainParameters, setup_multilevel_domain, solver_params
 from .solver_control import execute_timestep_batch, ramp_velocity
@@ -39,8 +40,8 @@ class DiagRow:
 
 
 def _close_observers(st) -> None:
-    """close a stepper's probe, surface and slice sets (each may be None)"""
-    for name in ("probes", "surface", "slices"):
+    """close a stepper's probe, surface, slice and wall-surface sets (each may be None)"""
+    for name in ("probes", "surface", "slices", "wall_surface"):
         obs = getattr(st, name)
         if obs is not None:
             obs.close()
@@ -59,6 +60,7 @@ class HipStepper:
         self._series = None
         self.surface = None                    # surface_stats_setup
         self.slices = None                     # slices_setup
+        self.wall_surface = None               # wall_diagnostics_setup
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.probes is None:
@@ -118,6 +120,27 @@ class HipStepper:
         slices_mod.check_sample_step(t_coarse, *self._slice_steps)
         self.slices.sample(t_coarse)
         return self.slices.download()
+
+    # -- wall diagnostics (no reference counterpart) --
+    def wall_diagnostics_setup(self, mesh, params, plan=None):
+        """a wall-surface set for `mesh` on the finest level; plan: the surface statistics' SurfacePlan when that observer is on too
+        (one plan, not two). Returns the plan. The census needs no setup."""
+        fin = len(self.host) - 1
+        if plan is None:
+            plan = surface_mod.plan_surface(mesh, self.host[fin], params)
+        if self.wall_surface is not None:
+            self.wall_surface.close()
+        self.wall_surface = wall_mod.DeviceWallSurface(plan, self.dev[fin], params)
+        return plan
+
+    def wall_census(self, level: int, t_coarse: int):
+        """the wall_diagnostics.Census of a level's newest state after coarse step t_coarse (the last batch must have ended there)"""
+        return wall_mod.census(self.dev[level], stats_mod.t_sub_after(level, t_coarse))
+
+    def wall_surface_values(self, t_coarse: int) -> np.ndarray:
+        """[7, n_tri] float32 (wall_diagnostics.ROWS) of the finest level's newest state after coarse step t_coarse"""
+        self.wall_surface.compute(stats_mod.t_sub_after(len(self.host) - 1, t_coarse))
+        return self.wall_surface.download()
 
     def field(self, level: int, name: str) -> np.ndarray:
         return self.dev[level].download(name)
@@ -208,6 +231,8 @@ class DistributedStepper:
         self.surface = None                    # this rank's surface set (None: it holds no copy of the finest level)
         self._slice_plans = None               # slices_setup: the global plans
         self.slices = None                     # this rank's slice set (None: it owns no base block of a valid point)
+        self._wall_cfg = None                  # wall_diagnostics_setup: (plan, params)
+        self.wall_surface = None               # this rank's wall-surface set (None: it holds no copy of the finest level)
 
     def _level_owner(self, level: int) -> np.ndarray:
         g = self.host[level]
@@ -283,6 +308,8 @@ class DistributedStepper:
             self._surface_create()
         if self._slice_plans is not None:
             self._slices_create()
+        if self._wall_cfg is not None:
+            self._wall_surface_create()
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.runner is None:
@@ -446,6 +473,59 @@ class DistributedStepper:
                 sel, sums, n = part
                 out[:, sel] = sums
         return out, n
+
+    # -- wall diagnostics: every rank takes the census of its owned blocks (integer records: their sum is one device's) and evaluates the
+    # triangles whose cell it owns (the rule of _triangle_map; the model's stencil is the cell itself: no ghost is read) --
+    def wall_diagnostics_setup(self, mesh, params, plan=None):
+        """returns the global surface_stats.SurfacePlan; the rank's set is made with the first batch (or now, after it)"""
+        fin = len(self.host) - 1
+        if plan is None:
+            plan = surface_mod.plan_surface(mesh, self.host[fin], params)
+        if self.wall_surface is not None:
+            self.wall_surface.close()
+            self.wall_surface = None
+        self._wall_cfg = (plan, params)
+        if self.runner is not None:
+            self._wall_surface_create()
+        return plan
+
+    def _wall_surface_create(self) -> None:
+        plan, params = self._wall_cfg
+        fin = len(self.host) - 1
+        owner = self._level_owner(fin)
+        self._wall_sel = np.flatnonzero(plan.found & (owner[np.maximum(plan.blocks, 0)] == self.rank))
+        lv = self.runner.levels[fin]
+        if lv is None:
+            assert self._wall_sel.size == 0
+            return
+        local = plan.subset(self._wall_sel)
+        local.blocks = self._owned_g2l(fin)[local.blocks].astype(np.int32)
+        assert (local.blocks >= 0).all()
+        self.wall_surface = wall_mod.DeviceWallSurface(local, lv, params)
+
+    def wall_census(self, level: int, t_coarse: int):
+        """the wall_diagnostics.Census of the GLOBAL level after coarse step t_coarse on rank 0 (None elsewhere): the ranks' records
+        gathered and merged (wall_diagnostics.merge), exactly one device's; collective"""
+        held = self._owning(level)
+        parts = self._gather(wall_mod.census(held[0], stats_mod.t_sub_after(level, t_coarse)) if held else None)
+        return None if parts is None else wall_mod.merge(parts)
+
+    def wall_surface_values(self, t_coarse: int):
+        """[7, n_tri] float32 in triangle order on rank 0 (None elsewhere); a triangle without a cell holds the documented zeros;
+        collective"""
+        plan = self._wall_cfg[0]
+        mine = None
+        if self.wall_surface is not None:
+            self.wall_surface.compute(stats_mod.t_sub_after(len(self.host) - 1, t_coarse))
+            mine = (self._wall_sel, self.wall_surface.download())
+        parts = self._gather(mine)
+        if parts is None:
+            return None
+        out = np.zeros((len(wall_mod.ROWS), plan.n), dtype=np.float32)
+        for part in parts:
+            if part is not None:
+                out[:, part[0]] = part[1]
+        return out
 
     # -- collectives of a few scalars --
     def _comm_device(self):
@@ -627,7 +707,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     state at batch end (where rho_min is taken; no batch is cut) - on the device where the stepper offers monitor, else from downloaded
     fields (monitor.host_monitor); flow_monitor.csv gains one row per level and the warnings go to `log`. With
     cfg.flow_monitor_stop_on_divergence the run ends once a level holds non-finite fluid cells: that step's rows and files are
-    written, then monitor.FlowDiverged is raised (on every rank of a distributed run)."""
+    written, then monitor.FlowDiverged is raised (on every rank of a distributed run).
+    With cfg.wall_diagnostics_enabled, at every diagnostics step and after the last step, from the state at batch end (no batch is cut):
+    a wall_diagnostics.Census of every level (when the wall model is on) into wall_model.csv and the forces of pressure plus modelled
+    wall shear into wall_forces.csv; on flow output steps surface_%06d.vtu gains wall_diagnostics.finalize's arrays. Device only: a
+    stepper without wall_diagnostics_setup raises."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
@@ -640,6 +724,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     # a plane outside the domain is refused before anything is allocated on a device
     splans = [slices_mod.plan_slice(spec, grids, params.mesh_offset) for spec in cfg.slices_planes] if slices_on else []
     st = stepper_factory(grids)
+    wall_on = bool(cfg.wall_diagnostics_enabled)
+    if wall_on and not hasattr(st, "wall_diagnostics_setup"):
+        if hasattr(st, "close"):
+            st.close()
+        raise RuntimeError(f"advanced.wall_diagnostics is enabled, but {type(st).__name__} offers no wall_diagnostics_setup: the wall "
+                           "diagnostics are evaluated on the device only")
     total_steps = steps if steps is not None else cfg.steps
     rows: List[DiagRow] = []
     batch = cfg.async_depth
@@ -660,6 +750,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         else:
             splan = surface_mod.plan_surface(mesh, grids[fin], params)
             surf_host = surface_mod.HostSurfaceStats(splan, grids[fin].tau, params, surf_start, surf_interval)
+    if wall_on:
+        st.wall_diagnostics_setup(mesh, params, splan if surf_on else None)      # one plan for both surface observers
+    wall_band = cfg.wall_diagnostics_band
+    wall_taken = [None, None]            # the coarse step of the last wall-surface values, and the values
     if writing:
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "convergence.csv"), "w") as io:
@@ -678,6 +772,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         if cfg.flow_monitor_enabled:
             with open(os.path.join(out_dir, "flow_monitor.csv"), "w") as io:
                 io.write(monitor_mod.CSV_HEADER + "\n")
+        if wall_on:
+            with open(os.path.join(out_dir, "wall_model.csv"), "w") as io:
+                io.write(wall_mod.wall_model_csv_header(cfg.y_plus_target, wall_band) + "\n")
+            with open(os.path.join(out_dir, "wall_forces.csv"), "w") as io:
+                io.write(wall_mod.WALL_FORCES_CSV_HEADER + "\n")
     probes_written = [0]
 
     def take_monitor(step, state_step):
@@ -703,6 +802,27 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                 diverged = monitor_mod.FlowDiverged(step, g.level_id, rec.first_bad,
                                                     monitor_mod.cell_coordinates(rec.first_bad, g.dx, params.mesh_offset), rec.n_bad)
         return diverged
+
+    def wall_values(state_step):
+        """the wall-surface values of the state after coarse step state_step, evaluated once per step (collective in a distributed run)"""
+        if wall_taken[0] != state_step:
+            wall_taken[:] = [state_step, st.wall_surface_values(state_step)]
+        return wall_taken[1]
+
+    def take_wall(step, state_step):
+        """a census of every level (with the wall model on) and the modelled surface loads from the state after coarse step state_step;
+        rows out (collective in a distributed run)"""
+        if sp.wall_model_active:
+            for lvl, g in enumerate(grids):
+                rec = st.wall_census(lvl, state_step)
+                if writing and rec is not None:
+                    with open(os.path.join(out_dir, "wall_model.csv"), "a") as io:
+                        io.write(wall_mod.wall_model_csv_row(step, g.level_id, rec, wall_band) + "\n")
+        vals = wall_values(state_step)
+        if writing and vals is not None:
+            fr_model = wall_mod.model_forces(mesh, vals, params, cfg.symmetric_analysis)
+            with open(os.path.join(out_dir, "wall_forces.csv"), "a") as io:
+                io.write(wall_mod.wall_forces_csv_row(step, mesh, vals, fr_model) + "\n")
 
     def flush_probes():
         """append the samples not yet in probes.csv (collective in a distributed run)"""
@@ -758,7 +878,7 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)
             else:
                 st.batch(t, actual, u_curr, sp)
-            monitored = False
+            monitored = wall_done = False
             if batch_end % cfg.diag_freq < actual or batch_end == total_steps:
                 diag_step = (batch_end // cfg.diag_freq) * cfg.diag_freq
                 if t <= diag_step <= batch_end:
@@ -790,8 +910,13 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     if monitor_on:
                         diverged = take_monitor(diag_step, batch_end)
                         monitored = True
+                    if wall_on:
+                        take_wall(diag_step, batch_end)
+                        wall_done = True
             if monitor_on and batch_end == total_steps and not monitored:
                 diverged = take_monitor(batch_end, batch_end)          # the last step is no diagnostics step: a record of the end state
+            if wall_on and batch_end == total_steps and not wall_done:
+                take_wall(batch_end, batch_end)
             if out_dir is not None and batch_end % cfg.output_freq < actual:                      # src/main.jl:213-231
                 out_step = (batch_end // cfg.output_freq) * cfg.output_freq
                 if t <= out_step <= batch_end:
@@ -816,10 +941,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         derived = [(name, (lambda lvl, k=k: grad[lvl][k]), ncomp) for name, k, ncomp in grad_names]
                     if cfg.forces_enabled and (fr is None or fr.maps is None or out_step != (out_step // cfg.diag_freq) * cfg.diag_freq):
                         fr = _aerodynamics(st, grids, mesh, params, cfg.symmetric_analysis, want_maps=True)
+                    wall_vals = wall_values(batch_end) if wall_on and cfg.forces_enabled else None          # collective
                     if writing:
                         out_mod.export_merged_mesh(out_step, grids, fields, out_dir, cfg.output_fields, derived=derived)
                         if cfg.forces_enabled:
-                            out_mod.save_surface_vtk(os.path.join(out_dir, "surface_%06d" % out_step), mesh, *fr.maps)
+                            extra = list(wall_mod.finalize(wall_vals, params).items()) if wall_vals is not None else None
+                            out_mod.save_surface_vtk(os.path.join(out_dir, "surface_%06d" % out_step), mesh, *fr.maps, extra=extra)
                     if stats_on and stats_window[0] > 0:
                         finals = {lvl: st.statistics(lvl) for lvl in sorted({l for l, _ in mesh_arrays_needed})}   # collective
                         if writing:

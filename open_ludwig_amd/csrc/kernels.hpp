@@ -1616,4 +1616,160 @@ __global__ __launch_bounds__(256) void k_monitor_combine(MonitorRecord *__restri
     out[blockIdx.x] = o;
 }
 
+// ---- wall diagnostics (ludwig_level_wall_census, ludwig_wall_surface_*; no reference counterpart: the reference reads y_plus_target
+// and never computes a y+) ----
+// The state wall_model_force_mag passes through on its way to the force, restated operation by operation (same operand order, jl_pow /
+// jl_log, -ffp-contract=off) beside it; that function is left alone. code: WALL_FAR not near the wall (!(0 < d < 10)), WALL_SKIPPED near
+// the wall but the model is skipped (u_mag <= 1e-6 or nu_visc <= 1e-10), WALL_POWER the power law's u_tau is kept (y_p <= 11.81 or
+// u_plus_law <= 0.1), WALL_LOG the log law replaced it; WALL_FORCED is or-ed in where the step applies a force (tau_wall > tau_res).
+// y_plus is the FINAL u_tau * dist_wall / nu_visc, not the provisional y_p that picks the branch. Codes below WALL_POWER give zeros.
+constexpr int WALL_FAR = 0, WALL_SKIPPED = 1, WALL_POWER = 2, WALL_LOG = 3, WALL_FORCED = 4;
+struct WallState {
+    float u_tau, y_plus;
+    int code;
+};
+__device__ __forceinline__ WallState wall_model_state(float dist_wall, float tau_molecular, float rho, float u_mag)
+{
+    WallState s;
+    s.u_tau = 0.0f; s.y_plus = 0.0f; s.code = WALL_FAR;
+    if (dist_wall > 0.0f && dist_wall < 10.0f) {
+        s.code = WALL_SKIPPED;
+        const float nu_visc = (tau_molecular - 0.5f) / 3.0f;
+        if (u_mag > 1.0e-6f && nu_visc > 1.0e-10f) {
+            float u_tau = u_mag * jl_pow(nu_visc / (dist_wall * u_mag + 1.0e-10f), 1.0f / 7.0f) *
+                          jl_pow(2.0f * 8.3f, -1.0f / 7.0f);
+            u_tau = jl_max(u_tau, 1.0e-6f);
+            const float y_p = u_tau * dist_wall / nu_visc;
+            s.code = WALL_POWER;
+            if (y_p > 11.81f) {
+                const float u_plus_law = (1.0f / KAPPA) * jl_log(y_p) + 5.2f;
+                if (u_plus_law > 0.1f) {
+                    u_tau = u_tau * ((u_mag / u_tau) / u_plus_law);
+                    u_tau = jl_max(u_tau, 1.0e-6f);
+                    s.code = WALL_LOG;
+                }
+            }
+            const float tau_wall = rho * u_tau * u_tau;
+            const float tau_res = rho * nu_visc * (u_mag / dist_wall);
+            if (tau_wall > tau_res) s.code |= WALL_FORCED;
+            s.u_tau = u_tau;
+            s.y_plus = u_tau * dist_wall / nu_visc;
+        }
+    }
+    return s;
+}
+
+// The census of one level: LudwigWallCensus of include/ludwig_hip.h, all integers. A cell is NEAR when it is no obstacle cell and
+// 0 < wall_dist < 10; EVALUATED when the model ran (code >= WALL_POWER) and both its y+ and its wall shear rho u_tau u_tau are finite,
+// NON_FINITE when the model ran and one of them is not (such a cell counts there and, NEAR apart, nowhere else). min / max are the float32
+// bits of y+ over the evaluated cells - y+ is positive there, and positive floats order as unsigned integers. The histogram's bin is a
+// shift of those bits: e8 = bits >> 20 is the exponent with the top three mantissa bits, eight bins per octave; bin 0 below 2^-10,
+// bin 193 from 2^14 on. Integer sums commute: the record depends on neither block order, workgroup scheduling nor a rank's cut.
+constexpr int WALL_BINS = 194, WALL_E8_FIRST = 936, WALL_E8_END = 1128;
+struct WallCensusRecord {
+    unsigned long long near_cells, evaluated, log_law, forced, non_finite;
+    uint32_t min_bits, max_bits;
+    unsigned long long hist[WALL_BINS];
+};
+__device__ __forceinline__ int wall_bin_of_bits(uint32_t bits)
+{
+    const int e8 = (int)(bits >> 20);
+    return e8 < WALL_E8_FIRST ? 0 : (e8 >= WALL_E8_END ? WALL_BINS - 1 : 1 + (e8 - WALL_E8_FIRST));
+}
+
+// One workgroup per owned block (internal order: the owned blocks come first), two x-consecutive cells per lane; a block without
+// FLAG_HAS_NEAR_WALL leaves at once (the whole workgroup: no barrier is skipped by a part of it). Counts in LDS, then the non-zero
+// entries go to the global record with integer atomics. 21 B per cell of a flagged block.
+__global__ __launch_bounds__(256) void k_wall_census(WallCensusRecord *__restrict__ rec, const float *__restrict__ rho,
+                                                     const float *__restrict__ vel, const uint8_t *__restrict__ obstacle,
+                                                     const float *__restrict__ wall_dist, const int32_t *__restrict__ meta, float tau)
+{
+    constexpr int N_NEAR = WALL_BINS, N_EVAL = WALL_BINS + 1, N_LOG = WALL_BINS + 2, N_FORCED = WALL_BINS + 3, N_BAD = WALL_BINS + 4,
+                  N_COUNTS = WALL_BINS + 5;
+    __shared__ uint32_t count[N_COUNTS];
+    __shared__ uint32_t ext[2];
+    const int64_t b = (int64_t)blockIdx.x;
+    if (!(meta[b * NBR_STRIDE + NBR_FLAGS] & FLAG_HAS_NEAR_WALL)) return;
+    const int t = (int)threadIdx.x, c = 2 * t;
+    if (t < N_COUNTS) count[t] = 0u;
+    if (t == 0) { ext[0] = 0xFFFFFFFFu; ext[1] = 0u; }
+    __syncthreads();
+    const float2 wd = *(const float2 *)(wall_dist + b * CELLS + c);
+    const uchar2 ob = *(const uchar2 *)(obstacle + b * CELLS + c);
+    const float2 rh = *(const float2 *)(rho + b * CELLS + c);
+    const float *v = vel + b * 3 * CELLS + c;
+    const float2 vx = *(const float2 *)v, vy = *(const float2 *)(v + CELLS), vz = *(const float2 *)(v + 2 * CELLS);
+#pragma unroll 1
+    for (int j = 0; j < 2; ++j) {                                     // one copy of the double-precision pow / log for both cells
+        const float d = j ? wd.y : wd.x;
+        if ((j ? ob.y : ob.x) != 0 || !(d > 0.0f && d < 10.0f)) continue;
+        atomicAdd(&count[N_NEAR], 1u);
+        const float ux = j ? vx.y : vx.x, uy = j ? vy.y : vy.x, uz = j ? vz.y : vz.x, r = j ? rh.y : rh.x;
+        const WallState s = wall_model_state(d, tau, r, sqrtf(ux * ux + uy * uy + uz * uz));
+        if ((s.code & 3) < WALL_POWER) continue;
+        if (!monitor_finite(s.y_plus) || !monitor_finite(r * s.u_tau * s.u_tau)) {
+            atomicAdd(&count[N_BAD], 1u);
+            continue;
+        }
+        const uint32_t bits = __float_as_uint(s.y_plus);
+        atomicAdd(&count[N_EVAL], 1u);
+        if ((s.code & 3) == WALL_LOG) atomicAdd(&count[N_LOG], 1u);
+        if (s.code & WALL_FORCED) atomicAdd(&count[N_FORCED], 1u);
+        atomicAdd(&count[wall_bin_of_bits(bits)], 1u);
+        atomicMin(&ext[0], bits);
+        atomicMax(&ext[1], bits);
+    }
+    __syncthreads();
+    if (t < N_COUNTS) {
+        const uint32_t n = count[t];
+        if (n) {
+            // the record as 200 eight-byte words: five counters, the min / max pair, the histogram
+            unsigned long long *words = reinterpret_cast<unsigned long long *>(rec);
+            atomicAdd(words + (t < WALL_BINS ? 6 + t : t - WALL_BINS), (unsigned long long)n);
+        }
+    }
+    if (t == 0 && count[N_EVAL]) {
+        atomicMin(&rec->min_bits, ext[0]);
+        atomicMax(&rec->max_bits, ext[1]);
+    }
+}
+
+// One lane per triangle of a wall-surface set: out = [WALL_SURFACE_ROWS][n] floats p, tau_model_x, tau_model_y, tau_model_z, u_tau,
+// y_plus, code. cell[i] = internal block * 512 + cell of the triangle's nearest fluid cell (-1: none), nrm = [3][n]. p and the
+// tangential direction are wall_stress's expressions; the wall distance is the LEVEL's wall_dist at the cell (what the step used), not
+// the triangle's own; the shear is (rho u_tau u_tau) stress_scale along the tangential velocity, zero where umag <= 1e-10 or the model
+// did not run. A triangle without a cell gives the p of rho = 1 and zeros.
+constexpr int WALL_SURFACE_ROWS = 7;
+__global__ __launch_bounds__(256) void k_wall_surface(float *__restrict__ out, const int32_t *__restrict__ cell, const float *__restrict__ nrm,
+                                                      int n, const float *__restrict__ rho, const float *__restrict__ vel,
+                                                      const uint8_t *__restrict__ obstacle, const float *__restrict__ wall_dist, float tau,
+                                                      float pressure_scale, float stress_scale)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
+    const int32_t c = cell[i];
+    float r = 1.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    WallState s;
+    s.u_tau = 0.0f; s.y_plus = 0.0f; s.code = WALL_FAR;
+    if (c >= 0) {
+        const int64_t b = c >> 9, cc = c & 511;
+        const float *v = vel + b * (3 * CELLS) + cc;
+        const float ux = v[0], uy = v[CELLS], uz = v[2 * CELLS], nx = nrm[i], ny = nrm[n + i], nz = nrm[2 * n + i];
+        r = rho[c];
+        if (obstacle[c] == 0) s = wall_model_state(wall_dist[c], tau, r, sqrtf(ux * ux + uy * uy + uz * uz));
+        const float udn = ux * nx + uy * ny + uz * nz;
+        const float utx = ux - udn * nx, uty = uy - udn * ny, utz = uz - udn * nz;
+        const float umag = sqrtf(utx * utx + uty * uty + utz * utz);
+        if (umag > 1.0e-10f && (s.code & 3) >= WALL_POWER) {
+            const float tmag = (r * s.u_tau * s.u_tau) * stress_scale;
+            sx = (utx / umag) * tmag; sy = (uty / umag) * tmag; sz = (utz / umag) * tmag;
+        }
+    }
+    const int64_t N = n;
+    float *o = out + i;
+    o[0] = ((r - 1.0f) / 3.0f) * pressure_scale;
+    o[N] = sx; o[2 * N] = sy; o[3 * N] = sz;
+    o[4 * N] = s.u_tau; o[5 * N] = s.y_plus; o[6 * N] = (float)s.code;
+}
+
 }  // namespace lw

@@ -193,6 +193,8 @@ struct LudwigLevel {
     // flow monitor (ludwig_level_monitor): one MonitorRecord per owned block in the reference block order, then the records of every
     // combine stage (512 -> 1) behind them; allocated by the first call
     MonitorRecord *monitor_slab = nullptr;
+    // wall diagnostics (ludwig_level_wall_census): the one device record, allocated by the first call
+    WallCensusRecord *wall_census = nullptr;
 };
 
 namespace {
@@ -1094,6 +1096,7 @@ void ludwig_level_destroy(LudwigLevel *L)
     if (L->stats) (void)hipFree(L->stats);
     if (L->grad) (void)hipFree(L->grad);
     if (L->monitor_slab) (void)hipFree(L->monitor_slab);
+    if (L->wall_census) (void)hipFree(L->wall_census);
     if (L->d_ref2int) (void)hipFree(L->d_ref2int);
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->own_stream) (void)hipStreamDestroy(L->own_stream);
@@ -2200,6 +2203,125 @@ int ludwig_level_monitor(LudwigLevel *L, int64_t t_sub, int64_t *counts, int64_t
         cells[4 * i + 2] = (int64_t)((keys[i] >> 9) & mask);
         cells[4 * i + 3] = (int64_t)(keys[i] & 511);
     }
+    return LUDWIG_OK;
+}
+
+// ---- wall diagnostics (ludwig_level_wall_census, ludwig_wall_surface_*; no reference counterpart) ----
+static_assert(sizeof(LudwigWallCensus) == sizeof(WallCensusRecord) && LUDWIG_WALL_BINS == WALL_BINS, "the census record is the ABI's");
+
+int ludwig_level_wall_census(LudwigLevel *L, int64_t t_sub, LudwigWallCensus *out)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    if (!out) return fail(LUDWIG_ERR_INVALID, "wall census: null output");
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "wall census: t_sub %lld < 0", (long long)t_sub);
+    memset(out, 0, sizeof *out);
+    out->min_bits = 0xFFFFFFFFu;
+    if (L->n_owned == 0) return LUDWIG_OK;            // no owned blocks: the empty record, nothing allocated
+    LW_HIP(hipSetDevice(L->device));
+    if (!L->wall_census) {
+        const int r = dev_alloc(L, &L->wall_census, 1);
+        if (r) return r;
+    }
+    LW_ENSURE_RHO(L);
+    LW_HIP(hipMemcpyAsync(L->wall_census, out, sizeof *out, hipMemcpyHostToDevice, L->stream));      // the empty record
+    hipLaunchKernelGGL(k_wall_census, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->wall_census, (const float *)L->rho,
+                       vel_out(L, t_sub), (const uint8_t *)L->obstacle, (const float *)L->wall_dist, (const int32_t *)L->meta, L->tau);
+    LW_HIP(hipGetLastError());
+    LW_HIP(hipMemcpyAsync(out, L->wall_census, sizeof *out, hipMemcpyDeviceToHost, L->stream));
+    LW_HIP(hipStreamSynchronize(L->stream));
+    return LUDWIG_OK;
+}
+
+// Per triangle, in the caller's order: the nearest fluid cell in the internal block order (-1: none) and [3][n] floats of normal;
+// [WALL_SURFACE_ROWS][n] float32 results. The set does not own its level.
+struct LudwigWallSurface {
+    LudwigLevel *level = nullptr;
+    int device = 0, n_tri = 0;
+    float pressure_scale = 0.0f, stress_scale = 0.0f;
+    int32_t *cell = nullptr;
+    float *nrm = nullptr, *out = nullptr;
+    bool computed = false;
+};
+
+void ludwig_wall_surface_destroy(LudwigWallSurface *S)
+{
+    if (!S) return;
+    (void)hipSetDevice(S->device);
+    if (S->cell) (void)hipFree(S->cell);
+    if (S->nrm) (void)hipFree(S->nrm);
+    if (S->out) (void)hipFree(S->out);
+    delete S;
+}
+
+int ludwig_wall_surface_create(LudwigLevel *L, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *normals,
+                               const LudwigSurfaceParams *sp, LudwigWallSurface **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!L || !sp || n_tri < 0 || (n_tri > 0 && (!blocks || !cells || !normals))) return fail(LUDWIG_ERR_INVALID, "null argument");
+    // the kernel indexes cells as internal block * 512 + cell in 32 bits
+    if (n_tri > 0 && (int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "wall surface: level has %d blocks, more than 32-bit cell indices reach", L->n_blocks);
+    // everything is checked before anything is allocated
+    std::vector<int32_t> hc((size_t)n_tri);
+    std::vector<float> hn((size_t)n_tri * 3);
+    for (int32_t i = 0; i < n_tri; ++i) {
+        const int32_t b = blocks[i], x = cells[i];
+        if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "wall surface: triangle %d: block %d not in -1..%d", i, b, L->n_blocks - 1);
+        if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "wall surface: triangle %d: cell %d not in 0..511", i, x);
+        hc[i] = b < 0 ? -1 : internal_cell(L, b, x);
+        for (int a = 0; a < 3; ++a) hn[(size_t)a * n_tri + i] = normals[3 * i + a];
+    }
+    LudwigWallSurface *S = new (std::nothrow) LudwigWallSurface;
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "wall surface: out of host memory");
+    S->level = L;
+    S->device = L->device;
+    S->n_tri = n_tri;
+    S->pressure_scale = sp->pressure_scale;
+    S->stress_scale = sp->stress_scale;
+    int r = set_device(S->device);
+    if (r == LUDWIG_OK && n_tri > 0) {
+        hipError_t e = hipSuccess;
+        upload_table(e, hc, S->cell);
+        upload_table(e, hn, S->nrm);
+        if (e == hipSuccess) e = hipMalloc((void **)&S->out, (size_t)n_tri * WALL_SURFACE_ROWS * sizeof(float));
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "wall surface: %d triangles: %s", n_tri, hipGetErrorString(e));
+    }
+    if (r != LUDWIG_OK) {
+        ludwig_wall_surface_destroy(S);
+        return r;
+    }
+    *out = S;
+    return LUDWIG_OK;
+}
+
+int ludwig_wall_surface_compute(LudwigWallSurface *S, int64_t t_sub)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null wall surface set");
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "wall surface: t_sub %lld < 0", (long long)t_sub);
+    LudwigLevel *L = S->level;
+    if (S->n_tri > 0) {
+        LW_HIP(hipSetDevice(S->device));
+        LW_ENSURE_RHO(L);
+        hipLaunchKernelGGL(k_wall_surface, dim3((unsigned)((S->n_tri + 255) / 256)), dim3(256), 0, L->stream, S->out, (const int32_t *)S->cell,
+                           (const float *)S->nrm, S->n_tri, (const float *)L->rho, vel_out(L, t_sub), (const uint8_t *)L->obstacle,
+                           (const float *)L->wall_dist, L->tau, S->pressure_scale, S->stress_scale);
+        LW_HIP(hipGetLastError());
+    }
+    S->computed = true;
+    return LUDWIG_OK;
+}
+
+int ludwig_wall_surface_download(LudwigWallSurface *S, float *values, size_t bytes)
+{
+    if (!S || (!values && bytes > 0)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    const size_t want = (size_t)S->n_tri * WALL_SURFACE_ROWS * sizeof(float);
+    if (bytes != want) return fail(LUDWIG_ERR_INVALID, "wall surface: got %zu bytes, expected %zu", bytes, want);
+    if (!S->computed) return fail(LUDWIG_ERR_STATE, "wall surface: download before ludwig_wall_surface_compute");
+    if (want == 0) return LUDWIG_OK;
+    LW_HIP(hipSetDevice(S->device));
+    LW_HIP(hipStreamSynchronize(S->level->stream));
+    LW_HIP(hipMemcpy(values, S->out, want, hipMemcpyDeviceToHost));
     return LUDWIG_OK;
 }
 

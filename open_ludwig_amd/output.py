@@ -238,8 +238,9 @@ def export_mean_mesh(t_step: int, grids, stats_of_level, window: Tuple[int, int,
 # ----------------------------------------------------------------------------------------------------------------
 # surface export + CSV (src/forces/io.jl)
 # ----------------------------------------------------------------------------------------------------------------
-def save_surface_vtk(filename: str, mesh, p, sx, sy, sz) -> str:
-    """save_surface_vtk (src/forces/io.jl:26-82): 3 Float64 points per triangle, 8 cell arrays, uncompressed."""
+def save_surface_vtk(filename: str, mesh, p, sx, sy, sz, extra=None) -> str:
+    """save_surface_vtk (src/forces/io.jl:26-82): 3 Float64 points per triangle, 8 cell arrays, uncompressed. extra: (name, float32
+    [n_tri]) cell arrays written after those (the wall diagnostics); without them the file is the reference's."""
     n = mesh.triangles.shape[0]
     p, sx, sy, sz = (np.asarray(a, dtype=np.float32) for a in (p, sx, sy, sz))
     pts = np.asarray(mesh.triangles, dtype=np.float64).reshape(n * 3, 3)
@@ -248,6 +249,7 @@ def save_surface_vtk(filename: str, mesh, p, sx, sy, sz) -> str:
           ("ShearMagnitude_Pa", np.sqrt(sx ** 2 + sy ** 2 + sz ** 2)),
           ("Normal", np.asarray(mesh.normals, dtype=np.float32)), ("Area_m2", np.asarray(mesh.areas, dtype=np.float32)),
           ("MappingQuality", quality)]
+    cd += [(name, np.ascontiguousarray(a, dtype=np.float32)) for name, a in (extra or ())]
     return write_vtu(filename, pts, np.arange(3 * n, dtype=np.int64), np.arange(1, n + 1, dtype=np.int64) * 3,
                      np.full(n, VTK_TRIANGLE, dtype=np.uint8), cd, compress=False)
 

@@ -120,6 +120,12 @@ class CaseConfig:
     # here): a health record of every level at every diagnostics step, written to flow_monitor.csv (monitor.py)
     flow_monitor_enabled: bool = False
     flow_monitor_stop_on_divergence: bool = False       # end the run with monitor.FlowDiverged once a level holds non-finite fluid cells
+    # wall diagnostics, advanced.wall_diagnostics (no reference counterpart; the reference reads y_plus_target and uses it nowhere): the y+,
+    # friction velocity and modelled wall shear of the wall model at every diagnostics step, written to wall_model.csv, wall_forces.csv
+    # and the surface file (wall_diagnostics.py)
+    wall_diagnostics_enabled: bool = False
+    wall_diagnostics_band: Tuple[float, float] = (30.0, 300.0)      # the y+ range ShareInBand counts, 0 < lo < hi
+    y_plus_target: float = 100.0                        # advanced.high_re.wall_model.y_plus_target, echoed in wall_model.csv
 
     @property
     def reference_area_config(self) -> float:
@@ -155,6 +161,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     probes = _probes_config(g("advanced", "probes", default=None))
     slices = _slices_config(g("advanced", "slices", default=None))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
+    wall_diag = _wall_diagnostics_config(g("advanced", "wall_diagnostics", default=None))
     return CaseConfig(
         stl_file=g("basic", "stl_file", required=True), stl_scale=float(g("basic", "stl_scale", required=True)),
         surface_resolution=int(g("basic", "surface_resolution", required=True)), num_levels=int(g("basic", "num_levels", required=True)),
@@ -206,6 +213,8 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **probes,
         **slices,
         **flow_monitor,
+        **wall_diag,
+        y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
     )
 
 
@@ -260,6 +269,19 @@ def _flow_monitor_config(mc) -> dict:
             raise ValueError(f"advanced.flow_monitor.{key} must be true or false, got {v!r}")
         vals[key] = v
     return dict(flow_monitor_enabled=vals["enabled"], flow_monitor_stop_on_divergence=vals["stop_on_divergence"])
+
+
+def _wall_diagnostics_config(wc) -> dict:
+    """advanced.wall_diagnostics: {enabled: false, band: [30.0, 300.0]} -> CaseConfig fields. Absent: the defaults."""
+    from .wall_diagnostics import check_band
+    if wc is None:
+        return {}
+    if not isinstance(wc, dict):
+        raise ValueError("advanced.wall_diagnostics must be a mapping")
+    enabled = wc.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError(f"advanced.wall_diagnostics.enabled must be true or false, got {enabled!r}")
+    return dict(wall_diagnostics_enabled=enabled, wall_diagnostics_band=check_band(wc.get("band", (30.0, 300.0))))
 
 
 SLICE_FIELDS = ("density", "velocity", "velocity_magnitude", "vorticity", "q_criterion")   # basic.simulation.output_fields keys
