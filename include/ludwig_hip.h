@@ -448,6 +448,37 @@ int  ludwig_slices_sample(LudwigSlices *slices, int64_t t_coarse);
 /* the last sample: bytes = n_rows * n_points * 4 (n_rows 5, or 9 with LUDWIG_SLICE_GRADIENT). Synchronizes the levels' streams. */
 int  ludwig_slices_download(LudwigSlices *slices, float *values, size_t bytes);
 
+/* ---- subgrid model: the WALE eddy viscosity the step collides with, and its time-averaged measures (no reference counterpart for the
+ * output; the model is perform_timestep_v2!'s, src/physics_kernels.jl:251-300) ----
+ * Per cell of the blocks this device owns, from one velocity buffer u: the gradient in lattice units g_ij = 0.5f (u_i(+e_j) - u_i(-e_j))
+ * with the neighbour value of get_velocity_neighbor (no block across a face: the cell's own value), then the step's WALE block restated
+ * operation by operation in float32 up to nu_t = max(nu_model, nu_sgs_background), and |S|^2 = 2 OP2. Evaluated on the buffer sub-step
+ * t_sub wrote, nu_t is bit for bit the value sub-step t_sub + 1 collides with. The code says which branch gave it: 0 OP1 <= 1e-12,
+ * 1 denom <= 1e-12 (both: nu_t = nu_sgs_background), 2 the model is evaluated and the background floor wins, 3 the model is above the
+ * floor. Obstacle cells give 0 and code 0 and add +0.0 to the sums.
+ * c_wale and nu_sgs_background are not arguments: a level records the two values every step call gives it (LudwigStepFlags), and these
+ * calls evaluate with them. LUDWIG_ERR_STATE on a level with owned blocks that has never been stepped.
+ * The field buffer (8 B per cell) is allocated by the first compute, the sums (24 B per cell) by the first reset; a level that calls
+ * neither allocates and launches nothing. A level created with n_owned < 0 accepts every call and does nothing. */
+enum LudwigSubgridField { LUDWIG_SUBGRID_NU = 0, LUDWIG_SUBGRID_CODE = 1 };   /* nu_t; the code as a float */
+/* vel_field: LUDWIG_VEL or LUDWIG_VEL_TEMP. Reads vel, obstacle and the neighbour table only; queued on the level's stream, no host
+ * synchronisation. */
+int  ludwig_level_subgrid_fields_compute(LudwigLevel *level, int vel_field);
+/* the last computed field in the reference layout [8,8,8,n_blocks] Float32, reference block order, ghost blocks zero; bytes =
+ * 2048 n_blocks. Synchronizes the stream. LUDWIG_ERR_STATE before the first compute. */
+int  ludwig_level_subgrid_fields_download(const LudwigLevel *level, int which, float *host, size_t bytes);
+/* Sums in double precision: S_nu += nu_t, S_nunu += nu_t nu_t, S_eps += nu_t |S|^2, the float32 values widened first (a product of two
+ * floats is exact in double); each a plain sequential addition per cell in sample order, so a float64 replay reproduces every bit. */
+enum LudwigSubgridSum { LUDWIG_SUBGRID_SUM_NU = 0, LUDWIG_SUBGRID_SUM_NUNU = 1, LUDWIG_SUBGRID_SUM_EPS = 2 };
+/* allocate on the first call, zero the sums, n = 0 (queued on the level's stream) */
+int  ludwig_level_subgrid_stats_reset(LudwigLevel *level);
+/* add one sample from the velocity buffer sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd). Queued on the level's stream, no
+ * host synchronisation. LUDWIG_ERR_STATE before the first reset. */
+int  ludwig_level_subgrid_stats_accumulate(LudwigLevel *level, int64_t t_sub);
+/* one sum in the reference layout [8,8,8,n_blocks] Float64, reference block order, ghost blocks zero; bytes = 4096 n_blocks; *n_samples
+ * (may be NULL) = samples since the last reset. Synchronizes the stream. LUDWIG_ERR_STATE before the first reset. */
+int  ludwig_level_subgrid_stats_download(const LudwigLevel *level, int which, double *host, size_t bytes, int64_t *n_samples);
+
 /* ---- halo exchange helpers (no reference counterpart: the reference is single-device) ---- */
 /* dst[i] = field[index[i]] / field[index[i]] = src[i]; index, dst, src are DEVICE pointers, index holds element
  * offsets into the field in the reference layout. hip_stream: the stream to queue on (hipStream_t), NULL = the

@@ -260,6 +260,29 @@ wall_surface_compute!(s::Ptr{Cvoid}, timestep::Integer) =
 wall_surface_download!(values::Matrix{Float32}, s::Ptr{Cvoid}) =
     GC.@preserve values check(ccall((:ludwig_wall_surface_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), s, values, sizeof(values)))
 
+# subgrid model: the WALE eddy viscosity the step collides with, its branch code, and the time-averaged sums (no reference counterpart
+# for the output; the model is perform_timestep_v2!'s). c_wale and nu_sgs_background are those of the level's last step.
+const SUBGRID_NU, SUBGRID_CODE = Int32(0), Int32(1)
+const SUBGRID_SUM_NU, SUBGRID_SUM_NUNU, SUBGRID_SUM_EPS = Int32(0), Int32(1), Int32(2)
+"""nu_t (after the background floor) and the branch code of the owned cells from `vel_field` (VEL or VEL_TEMP)"""
+subgrid_fields_compute!(d::DeviceLevel, vel_field::Integer) =
+    check(ccall((:ludwig_level_subgrid_fields_compute, LIB), Cint, (Ptr{Cvoid}, Cint), d.handle, Cint(vel_field)))
+"""the last computed field (SUBGRID_NU or SUBGRID_CODE) into a preallocated Array{Float32}(8,8,8,n_blocks)"""
+subgrid_fields_download!(a::Array{Float32}, d::DeviceLevel, which::Int32) =
+    GC.@preserve a check(ccall((:ludwig_level_subgrid_fields_download, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Csize_t),
+                               d.handle, which, pointer(a), sizeof(a)))
+subgrid_stats_reset!(d::DeviceLevel) = check(ccall((:ludwig_level_subgrid_stats_reset, LIB), Cint, (Ptr{Cvoid},), d.handle))
+"""add one sample from the velocity buffer sub-step `timestep` wrote"""
+subgrid_stats_accumulate!(d::DeviceLevel, timestep::Integer) =
+    check(ccall((:ludwig_level_subgrid_stats_accumulate, LIB), Cint, (Ptr{Cvoid}, Int64), d.handle, Int64(timestep)))
+"""one sum (SUBGRID_SUM_NU, _NUNU, _EPS) into a preallocated Array{Float64}(8,8,8,n_blocks); returns the number of samples"""
+function subgrid_stats_download!(a::Array{Float64}, d::DeviceLevel, which::Int32)
+    n = Ref{Int64}(0)
+    GC.@preserve a check(ccall((:ludwig_level_subgrid_stats_download, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Csize_t, Ref{Int64}),
+                               d.handle, which, pointer(a), sizeof(a), n))
+    return n[]
+end
+
 """
 Multi-GPU hosts only: a HIP stream for the stepping kernels that leaves `reserved_cus` compute units to the halo exchange
 (`ludwig_stream_create`, include/ludwig_hip.h); hand it to `ludwig_level_set_stream`. No counterpart in the reference.

@@ -26,6 +26,9 @@ GRAD_VORTICITY, GRAD_Q = range(2)
 GRAD_NAMES = {"vorticity": (GRAD_VORTICITY, 3), "q": (GRAD_Q, 1)}
 # ludwig_slices_create flags
 SLICE_GRADIENT = 1
+# enum LudwigSubgridField / LudwigSubgridSum: one component each
+SUBGRID_FIELD_NAMES = {"nu": 0, "code": 1}
+SUBGRID_SUM_NAMES = {"nu": 0, "nunu": 1, "eps": 2}
 # enum LudwigPart
 PART_ALL, PART_BOUNDARY, PART_INTERIOR = 0, 1, 2
 
@@ -44,6 +47,8 @@ EXPORTED_SYMBOLS = [
     "ludwig_halo_plan_exchange_ms", "ludwig_step_distributed",
     "ludwig_level_stats_reset", "ludwig_level_stats_accumulate", "ludwig_level_stats_download",
     "ludwig_level_gradient_fields_compute", "ludwig_level_gradient_fields_download",
+    "ludwig_level_subgrid_fields_compute", "ludwig_level_subgrid_fields_download", "ludwig_level_subgrid_stats_reset",
+    "ludwig_level_subgrid_stats_accumulate", "ludwig_level_subgrid_stats_download",
     "ludwig_probes_create", "ludwig_probes_destroy", "ludwig_probes_sample", "ludwig_probes_download",
     "ludwig_execute_timestep_batch_probes",
     "ludwig_surface_stats_create", "ludwig_surface_stats_destroy", "ludwig_surface_stats_reset", "ludwig_surface_stats_accumulate",
@@ -191,6 +196,11 @@ def load() -> C.CDLL:
         "ludwig_level_stats_download": (C.c_int, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int64)]),
         "ludwig_level_gradient_fields_compute": (C.c_int, [vp, i32, f32]),
         "ludwig_level_gradient_fields_download": (C.c_int, [vp, i32, vp, C.c_size_t]),
+        "ludwig_level_subgrid_fields_compute": (C.c_int, [vp, i32]),
+        "ludwig_level_subgrid_fields_download": (C.c_int, [vp, i32, vp, C.c_size_t]),
+        "ludwig_level_subgrid_stats_reset": (C.c_int, [vp]),
+        "ludwig_level_subgrid_stats_accumulate": (C.c_int, [vp, i64]),
+        "ludwig_level_subgrid_stats_download": (C.c_int, [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int64)]),
         "ludwig_probes_create": (C.c_int, [C.POINTER(vp), i32, i32, vp, vp, vp, vp, i32, C.POINTER(vp)]),
         "ludwig_probes_destroy": (None, [vp]),
         "ludwig_probes_sample": (C.c_int, [vp, i32, i64]),

@@ -367,6 +367,38 @@ class DeviceLevel(_lib.Handle):
             out.append(a)
         return out[0], out[1]
 
+    # -- subgrid model (subgrid.py; no reference counterpart for the output) --
+    def subgrid_fields(self, vel_name: str) -> Tuple[np.ndarray, np.ndarray]:
+        """nu_t (after the background floor) and the branch code as a float, both Float32 [8,8,8,n_blocks] (reference layout, ghost
+        blocks 0), of the owned cells from the velocity buffer `vel_name` ('vel' | 'vel_temp'), with the c_wale and nu_sgs_background
+        of the level's last step"""
+        if vel_name not in ("vel", "vel_temp"):
+            raise ValueError(f"subgrid fields: vel_name must be 'vel' or 'vel_temp', got {vel_name!r}")
+        _lib.check(self._lib.ludwig_level_subgrid_fields_compute(self.handle, _lib.FIELD_NAMES[vel_name]))
+        out = []
+        for name in ("nu", "code"):
+            a = np.empty((BLOCK_SIZE,) * 3 + (self.n_blocks,), dtype=np.float32, order="F")
+            _lib.check(self._lib.ludwig_level_subgrid_fields_download(self.handle, _lib.SUBGRID_FIELD_NAMES[name],
+                                                                      a.ctypes.data if a.size else None, a.nbytes))
+            out.append(a)
+        return out[0], out[1]
+
+    def subgrid_stats_reset(self) -> None:
+        """zero the device sums of nu_t, nu_t^2, nu_t |S|^2 (allocated by the first call) and the sample count"""
+        _lib.check(self._lib.ludwig_level_subgrid_stats_reset(self.handle))
+
+    def subgrid_stats_accumulate(self, t_sub: int) -> None:
+        """add the model's state on the velocity sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd), queued on the level's stream"""
+        _lib.check(self._lib.ludwig_level_subgrid_stats_accumulate(self.handle, int(t_sub)))
+
+    def subgrid_stats_download(self, which: str) -> Tuple[np.ndarray, int]:
+        """('nu' | 'nunu' | 'eps') -> (Float64 sums [8,8,8,n_blocks] in the reference layout, samples); ghost blocks are 0"""
+        a = np.empty((BLOCK_SIZE,) * 3 + (self.n_blocks,), dtype=np.float64, order="F")
+        n = C.c_int64(0)
+        _lib.check(self._lib.ludwig_level_subgrid_stats_download(self.handle, _lib.SUBGRID_SUM_NAMES[which], a.ctypes.data if a.size else None,
+                                                                 a.nbytes, C.byref(n)))
+        return a, int(n.value)
+
     def init_equilibrium(self) -> None:
         """init_eq! (src/main.jl:109-134)"""
         _lib.check(self._lib.ludwig_init_equilibrium(self.handle))

@@ -21,6 +21,7 @@ from . import monitor as monitor_mod
 from . import probes as probes_mod
 from . import slices as slices_mod
 from . import statistics as stats_mod
+from . import subgrid as subgrid_mod
 from . import surface_stats as surface_mod
 from . import wall_diagnostics as wall_mod
 from .blocks import adapt
@@ -183,6 +184,26 @@ class HipStepper:
     def gradient_fields(self, level: int, vel_name: str, scale):
         """(vorticity [8,8,8,nb,3], Q [8,8,8,nb]) of a level from its `vel_name` buffer, derivatives times `scale` (Float32)"""
         return self.dev[level].gradient_fields(vel_name, scale)
+
+    # -- subgrid model (subgrid.py; no reference counterpart for the output) --
+    def subgrid_fields(self, level: int, vel_name: str):
+        """(nu_t [8,8,8,nb], branch code as a float [8,8,8,nb]) of a level from its `vel_name` buffer (Float32)"""
+        return self.dev[level].subgrid_fields(vel_name)
+
+    def subgrid_stats_reset(self) -> None:
+        for d in self.dev:
+            d.subgrid_stats_reset()
+
+    def subgrid_stats_sample(self, t_coarse: int) -> None:
+        """add the model's state on every level's newest velocity after coarse step t_coarse to its device sums (queued)"""
+        for lvl, d in enumerate(self.dev):
+            d.subgrid_stats_accumulate(stats_mod.t_sub_after(lvl, t_coarse))
+
+    def subgrid_stats_sums(self, level: int):
+        """(S_nu, S_nunu, S_eps, n) of a level, Float64 in the reference layout"""
+        d = self.dev[level]
+        (a, n), (b, _), (c, _) = (d.subgrid_stats_download(k) for k in ("nu", "nunu", "eps"))
+        return a, b, c, n
 
     def close(self):
         _close_observers(self)
@@ -658,6 +679,40 @@ class DistributedStepper:
         self._scatter_blocks(parts, [w_all, q_all])
         return w_all, q_all
 
+    # -- subgrid model: every rank works on its owned blocks after batch(); the face stencil is the gradient fields', so their argument
+    # holds unchanged (the 'vel' halo ghosts are current for both buffers) --
+    def subgrid_fields(self, level: int, vel_name: str):
+        """(nu_t, code) of the GLOBAL level, assembled on rank 0 (None elsewhere); collective"""
+        held = self._owning(level)
+        parts = self._gather(self._owned_blocks(held[1], held[0].subgrid_fields(vel_name)) if held else None)
+        if parts is None:
+            return None
+        out = [np.zeros((8, 8, 8, self.host[level].n_blocks), dtype=np.float32, order="F") for _ in range(2)]
+        self._scatter_blocks(parts, out)
+        return out[0], out[1]
+
+    def subgrid_stats_reset(self) -> None:
+        for _, lv in self._held():
+            lv.subgrid_stats_reset()
+
+    def subgrid_stats_sample(self, t_coarse: int) -> None:
+        for lvl, lv in self._held():
+            lv.subgrid_stats_accumulate(stats_mod.t_sub_after(lvl, t_coarse))
+
+    def subgrid_stats_sums(self, level: int):
+        """(S_nu, S_nunu, S_eps, n) of the GLOBAL level, assembled on rank 0 (None elsewhere); collective"""
+        held, mine = self._owning(level), None
+        if held:
+            got = [held[0].subgrid_stats_download(k) for k in ("nu", "nunu", "eps")]
+            mine = self._owned_blocks(held[1], [a for a, _ in got]) + (got[0][1],)
+        parts = self._gather(mine)
+        if parts is None:
+            return None
+        out = [np.zeros((8, 8, 8, self.host[level].n_blocks), dtype=np.float64, order="F") for _ in range(3)]
+        self._scatter_blocks(parts, out)
+        n = ([0] + [part[2] for part in parts if part is not None])[-1]
+        return out[0], out[1], out[2], n
+
     def close(self):
         _close_observers(self)
         if self.runner is not None:
@@ -711,7 +766,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     With cfg.wall_diagnostics_enabled, at every diagnostics step and after the last step, from the state at batch end (no batch is cut):
     a wall_diagnostics.Census of every level (when the wall model is on) into wall_model.csv and the forces of pressure plus modelled
     wall shear into wall_forces.csv; on flow output steps surface_%06d.vtu gains wall_diagnostics.finalize's arrays. Device only: a
-    stepper without wall_diagnostics_setup raises."""
+    stepper without wall_diagnostics_setup raises.
+    "EddyViscosityRatio" in cfg.output_fields adds nu_t / nu of the step's own WALE model (subgrid.py) to the flow file, Float32, from the
+    file's velocity buffer. With cfg.statistics_subgrid the model's sums are sampled at exactly the flow statistics' sampled steps (same
+    reset) and flow_mean_%06d.vtu gains subgrid.MEAN_ARRAYS after its own arrays. Device only: a stepper without subgrid_fields raises."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
@@ -730,6 +788,14 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             st.close()
         raise RuntimeError(f"advanced.wall_diagnostics is enabled, but {type(st).__name__} offers no wall_diagnostics_setup: the wall "
                            "diagnostics are evaluated on the device only")
+    eddy_on = "EddyViscosityRatio" in cfg.output_fields
+    subgrid_on = bool(cfg.statistics_subgrid)
+    if (eddy_on or subgrid_on) and not hasattr(st, "subgrid_fields"):
+        if hasattr(st, "close"):
+            st.close()
+        key = "basic.simulation.output_fields.eddy_viscosity" if eddy_on else "advanced.statistics.subgrid"
+        raise RuntimeError(f"{key} is set, but {type(st).__name__} offers no subgrid_fields: the subgrid model's eddy viscosity is "
+                           "evaluated on the device only")
     total_steps = steps if steps is not None else cfg.steps
     rows: List[DiagRow] = []
     batch = cfg.async_depth
@@ -862,8 +928,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     if stats_on and stats_mod.is_sample_step(s_step, cfg.statistics_start_step, cfg.statistics_interval):
                         if s_step == cfg.statistics_start_step:
                             st.stats_reset()
+                            if subgrid_on:
+                                st.subgrid_stats_reset()
                             stats_window = [0, s_step, s_step]
                         st.stats_sample(s_step)
+                        if subgrid_on:
+                            st.subgrid_stats_sample(s_step)
                         stats_window[0] += 1
                         stats_window[2] = s_step
                     if surf_host is not None and stats_mod.is_sample_step(s_step, surf_start, surf_interval):
@@ -939,6 +1009,13 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         grad = {lvl: st.gradient_fields(lvl, vel_name, np.float32(1.0 / grids[lvl].dx))      # collective
                                 for lvl in sorted({l for l, _ in mesh_arrays_needed})}
                         derived = [(name, (lambda lvl, k=k: grad[lvl][k]), ncomp) for name, k, ncomp in grad_names]
+                    if eddy_on:
+                        # nu_t of the buffer the file's Velocity comes from over the level's nu, both Float32
+                        eddy = {}
+                        for lvl in sorted({l for l, _ in mesh_arrays_needed}):
+                            got = st.subgrid_fields(lvl, vel_name)                                               # collective
+                            eddy[lvl] = subgrid_mod.ratio_field(got[0], grids[lvl].tau) if got is not None else None
+                        derived = (derived or []) + [("EddyViscosityRatio", eddy.__getitem__, 1)]
                     if cfg.forces_enabled and (fr is None or fr.maps is None or out_step != (out_step // cfg.diag_freq) * cfg.diag_freq):
                         fr = _aerodynamics(st, grids, mesh, params, cfg.symmetric_analysis, want_maps=True)
                     wall_vals = wall_values(batch_end) if wall_on and cfg.forces_enabled else None          # collective
@@ -949,8 +1026,16 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                             out_mod.save_surface_vtk(os.path.join(out_dir, "surface_%06d" % out_step), mesh, *fr.maps, extra=extra)
                     if stats_on and stats_window[0] > 0:
                         finals = {lvl: st.statistics(lvl) for lvl in sorted({l for l, _ in mesh_arrays_needed})}   # collective
+                        sgs, sgs_extra = {}, None
+                        if subgrid_on:
+                            for lvl in sorted(finals):
+                                sums = st.subgrid_stats_sums(lvl)                                                # collective
+                                if sums is not None:
+                                    sgs[lvl] = subgrid_mod.finalize(*sums, subgrid_mod.level_viscosity(grids[lvl].tau),
+                                                                    cfg.statistics_subgrid_ck, finals[lvl]["tke"])
+                            sgs_extra = [(name, (lambda lvl, k=k: sgs[lvl][k])) for name, k in subgrid_mod.MEAN_ARRAYS]
                         if writing:
-                            out_mod.export_mean_mesh(out_step, grids, finals.__getitem__, tuple(stats_window), out_dir)
+                            out_mod.export_mean_mesh(out_step, grids, finals.__getitem__, tuple(stats_window), out_dir, extra=sgs_extra)
                     if surf_on:
                         got = surf_host.download() if surf_host is not None else st.surface_stats_sums()        # collective
                         if writing and got is not None and got[1] > 0:

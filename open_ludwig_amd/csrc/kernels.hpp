@@ -284,6 +284,58 @@ __device__ __forceinline__ int source_block(const NeighbourIds &n, const LanePos
     else if constexpr (cy != 0) sel = yo ? cY : c00;
     return sel;
 }
+// ---- the WALE model as a function (k_subgrid; no reference counterpart as a function) ----
+// finish_cell's "WALE eddy viscosity" block below, restated operation by operation from gsq11 to the background floor: the same operand
+// order, the same 1.0e-12f guards, the same sqrtf(sqrtf(jl_max(OP1, 1.0e-12f))), under the same -ffp-contract=off, so on the gradient
+// the step forms it gives the step's nu_eddy bit for bit. The step keeps its own block; this one serves the observers.
+// nu_eddy: the effective value after the floor, what the step turns into tau_turb. s2 = 2 OP2 = |S|^2 = 2 S_ij S_ij (the doubling is
+// exact). code: SUBGRID_NO_OP1 - OP1 <= 1e-12 (or NaN), SUBGRID_NO_DENOM - denom <= 1e-12 (or NaN), SUBGRID_FLOOR - the model is
+// evaluated and is not above nu_bg, so the floor wins (a NaN model value, which jl_max propagates, is here too), SUBGRID_MODEL - the
+// model is above the floor.
+constexpr int SUBGRID_NO_OP1 = 0, SUBGRID_NO_DENOM = 1, SUBGRID_FLOOR = 2, SUBGRID_MODEL = 3;
+struct WaleState {
+    float nu_eddy, s2;
+    int code;
+};
+__device__ __forceinline__ WaleState wale_state(float g11, float g12, float g13, float g21, float g22, float g23, float g31, float g32,
+                                                float g33, float c_wale, float nu_bg)
+{
+    const float gsq11 = g11 * g11 + g12 * g21 + g13 * g31;
+    const float gsq12 = g11 * g12 + g12 * g22 + g13 * g32;
+    const float gsq13 = g11 * g13 + g12 * g23 + g13 * g33;
+    const float gsq21 = g21 * g11 + g22 * g21 + g23 * g31;
+    const float gsq22 = g21 * g12 + g22 * g22 + g23 * g32;
+    const float gsq23 = g21 * g13 + g22 * g23 + g23 * g33;
+    const float gsq31 = g31 * g11 + g32 * g21 + g33 * g31;
+    const float gsq32 = g31 * g12 + g32 * g22 + g33 * g32;
+    const float gsq33 = g31 * g13 + g32 * g23 + g33 * g33;
+
+    const float tr_gsq = gsq11 + gsq22 + gsq33;
+    const float tr_term = tr_gsq / 3.0f;
+    const float Sd11 = gsq11 - tr_term, Sd22 = gsq22 - tr_term, Sd33 = gsq33 - tr_term;
+    const float Sd12 = 0.5f * (gsq12 + gsq21), Sd13 = 0.5f * (gsq13 + gsq31), Sd23 = 0.5f * (gsq23 + gsq32);
+    const float S12 = 0.5f * (g12 + g21), S13 = 0.5f * (g13 + g31), S23 = 0.5f * (g23 + g32);
+    const float OP1 = Sd11 * Sd11 + Sd22 * Sd22 + Sd33 * Sd33 + 2.0f * (Sd12 * Sd12 + Sd13 * Sd13 + Sd23 * Sd23);
+    const float OP2 = g11 * g11 + g22 * g22 + g33 * g33 + 2.0f * (S12 * S12 + S13 * S13 + S23 * S23);
+
+    WaleState w;
+    w.code = SUBGRID_NO_OP1;
+    float nu_eddy = 0.0f;
+    if (OP1 > 1.0e-12f) {
+        const float OP1_32 = OP1 * sqrtf(OP1);
+        const float OP2_52 = OP2 * OP2 * sqrtf(jl_max(OP2, 1.0e-12f));
+        const float denom = OP2_52 + OP1 * sqrtf(sqrtf(jl_max(OP1, 1.0e-12f)));
+        w.code = SUBGRID_NO_DENOM;
+        if (denom > 1.0e-12f) {
+            nu_eddy = (c_wale * c_wale) * OP1_32 / denom;
+            w.code = nu_eddy > nu_bg ? SUBGRID_MODEL : SUBGRID_FLOOR;
+        }
+    }
+    w.nu_eddy = jl_max(nu_eddy, nu_bg);
+    w.s2 = 2.0f * OP2;
+    return w;
+}
+
 // Everything after the loads: moments, obstacle bounce, sponge, wall model, WALE, regularized collision, stores.
 // reference src/physics_kernels.jl:144-354. fs = the 27 pulled populations, u?_? = previous-step velocity of the six
 // face neighbours. Shared by the per-wave kernel and the x-run kernel.
@@ -1144,16 +1196,12 @@ __global__ __launch_bounds__(256) void k_accumulate_stats(double *__restrict__ s
 constexpr int GRAD_COMPONENTS = 4;
 constexpr int GRAD_TILE = 10;                                   // 8 cells + one halo layer on each side
 constexpr int GRAD_HALO = 6 * 3 * 64;                           // faces x components x cells of a face layer
-__global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restrict__ out, const float *__restrict__ vel,
-                                                                  const uint8_t *__restrict__ obstacle,
-                                                                  const int32_t *__restrict__ meta, float scale)
+// The staging both stencil kernels share (k_velocity_gradient_fields, k_subgrid): block b of `vel` and its face halo into u, lane t's two
+// cells at `at` and `at + 1`. The caller synchronizes the workgroup before it reads u.
+__device__ __forceinline__ void stage_velocity_tile(float *u, const float *__restrict__ vel, const int32_t *__restrict__ meta,
+                                                    const int64_t b, const int t, const int c, const int at)
 {
     constexpr int T = GRAD_TILE, T2 = GRAD_TILE * GRAD_TILE, T3 = T2 * GRAD_TILE;
-    __shared__ float u[3 * T3];
-    const int64_t b = blockIdx.x;
-    const int t = (int)threadIdx.x;
-    const int c = 2 * t, x = c & 7, y = (c >> 3) & 7, z = c >> 6;
-    const int at = (x + 1) + T * (y + 1) + T2 * (z + 1);
     const float *vb = vel + b * 3 * CELLS;
     float2 own[3];
 #pragma unroll
@@ -1192,6 +1240,19 @@ __global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restr
 #pragma unroll
     for (int r = 0; r < 5; ++r)
         if (hat[r] >= 0) u[hat[r]] = h[r];
+}
+
+__global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restrict__ out, const float *__restrict__ vel,
+                                                                  const uint8_t *__restrict__ obstacle,
+                                                                  const int32_t *__restrict__ meta, float scale)
+{
+    constexpr int T = GRAD_TILE, T2 = GRAD_TILE * GRAD_TILE, T3 = T2 * GRAD_TILE;
+    __shared__ float u[3 * T3];
+    const int64_t b = blockIdx.x;
+    const int t = (int)threadIdx.x;
+    const int c = 2 * t, x = c & 7, y = (c >> 3) & 7, z = c >> 6;
+    const int at = (x + 1) + T * (y + 1) + T2 * (z + 1);
+    stage_velocity_tile(u, vel, meta, b, t, c, at);
     const uint8_t ob0 = obstacle[b * CELLS + c], ob1 = obstacle[b * CELLS + c + 1];
     __syncthreads();
     float res[GRAD_COMPONENTS][2];
@@ -1214,6 +1275,61 @@ __global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restr
     float *o = out + b * GRAD_COMPONENTS * CELLS + c;
 #pragma unroll
     for (int m = 0; m < GRAD_COMPONENTS; ++m) *(float2 *)(o + m * CELLS) = make_float2(res[m][0], res[m][1]);
+}
+
+// ---- subgrid model (ludwig_level_subgrid_*; no reference counterpart for the output; the model is the step's, wale_state above) ----
+// One workgroup per owned block, staged like k_velocity_gradient_fields (stage_velocity_tile), two x-consecutive cells per lane. The
+// gradient is the step's, in lattice units with no scale: g_ij = 0.5f (u_i(+e_j) - u_i(-e_j)), a missing face neighbour block giving
+// the cell's own value. Evaluated on the velocity sub-step t wrote, nu_eddy is therefore exactly the value sub-step t + 1 collides
+// with (that step reads this buffer as vel_in). Obstacle cells take no part: 0 and code 0, +0.0 into the sums.
+//   <SUBGRID_FIELDS> out: [internal block][2][512] floats - nu_eddy (after the floor) and the code as a float.
+//   <SUBGRID_SUMS>   out: [internal block][3][512] doubles - S_nu += nu, S_nunu += nu nu, S_eps += nu s2 with nu, s2 widened first: a
+//                    product of two floats is exact in double, every sum a plain sequential += per cell in sample order, no atomics.
+constexpr int SUBGRID_FIELDS = 0, SUBGRID_SUMS = 1;
+constexpr int SUBGRID_FIELD_COMPONENTS = 2, SUBGRID_SUM_COMPONENTS = 3;
+template <int MODE>
+__global__ __launch_bounds__(256) void k_subgrid(std::conditional_t<MODE == SUBGRID_SUMS, double, float> *__restrict__ out,
+                                                 const float *__restrict__ vel, const uint8_t *__restrict__ obstacle,
+                                                 const int32_t *__restrict__ meta, float c_wale, float nu_bg)
+{
+    constexpr int T = GRAD_TILE, T2 = GRAD_TILE * GRAD_TILE, T3 = T2 * GRAD_TILE;
+    __shared__ float u[3 * T3];
+    const int64_t b = blockIdx.x;
+    const int t = (int)threadIdx.x;
+    const int c = 2 * t, x = c & 7, y = (c >> 3) & 7, z = c >> 6;
+    const int at = (x + 1) + T * (y + 1) + T2 * (z + 1);
+    stage_velocity_tile(u, vel, meta, b, t, c, at);
+    const uint8_t ob0 = obstacle[b * CELLS + c], ob1 = obstacle[b * CELLS + c + 1];
+    __syncthreads();
+    WaleState w[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int a = at + s;
+        const float *ux = u, *uy = u + T3, *uz = u + 2 * T3;
+        w[s] = wale_state(0.5f * (ux[a + 1] - ux[a - 1]), 0.5f * (ux[a + T] - ux[a - T]), 0.5f * (ux[a + T2] - ux[a - T2]),
+                          0.5f * (uy[a + 1] - uy[a - 1]), 0.5f * (uy[a + T] - uy[a - T]), 0.5f * (uy[a + T2] - uy[a - T2]),
+                          0.5f * (uz[a + 1] - uz[a - 1]), 0.5f * (uz[a + T] - uz[a - T]), 0.5f * (uz[a + T2] - uz[a - T2]), c_wale, nu_bg);
+    }
+    const bool solid0 = ob0 != 0, solid1 = ob1 != 0;
+    if constexpr (MODE == SUBGRID_FIELDS) {
+        float *o = out + b * SUBGRID_FIELD_COMPONENTS * CELLS + c;
+        *(float2 *)o = make_float2(solid0 ? 0.0f : w[0].nu_eddy, solid1 ? 0.0f : w[1].nu_eddy);
+        *(float2 *)(o + CELLS) = make_float2(solid0 ? 0.0f : (float)w[0].code, solid1 ? 0.0f : (float)w[1].code);
+    } else {
+        const double n0 = w[0].nu_eddy, n1 = w[1].nu_eddy, e0 = w[0].s2, e1 = w[1].s2;
+        const double add[SUBGRID_SUM_COMPONENTS][2] = {{solid0 ? 0.0 : n0, solid1 ? 0.0 : n1},
+                                                       {solid0 ? 0.0 : n0 * n0, solid1 ? 0.0 : n1 * n1},
+                                                       {solid0 ? 0.0 : n0 * e0, solid1 ? 0.0 : n1 * e1}};
+        double *sm = out + b * SUBGRID_SUM_COMPONENTS * CELLS + c;
+#pragma unroll
+        for (int m = 0; m < SUBGRID_SUM_COMPONENTS; ++m) {
+            double2 *p = (double2 *)(sm + m * CELLS);
+            double2 v = *p;
+            v.x += add[m][0];
+            v.y += add[m][1];
+            *p = v;
+        }
+    }
 }
 
 // ---- probes (ludwig_probes_*; no reference counterpart) ----

@@ -190,6 +190,17 @@ struct LudwigLevel {
     // allocated (and zeroed) by the first compute; only the owned blocks are ever written, the ghost blocks stay zero
     float *grad = nullptr;
     bool grad_ready = false;            // compute has been called
+    // subgrid model (ludwig_level_subgrid_*). The model constants are the step's own: every stream-collide launch of this level records
+    // the c_wale and nu_sgs_background it was given, and the observers evaluate with those, so they cannot disagree with the step.
+    // fields: [n_blocks][SUBGRID_FIELD_COMPONENTS][512] floats, allocated (and zeroed) by the first compute; sums: [n_blocks]
+    // [SUBGRID_SUM_COMPONENTS][512] doubles, allocated by the first reset. Internal block order; the ghost blocks stay zero.
+    bool wale_known = false;            // a step has run
+    float c_wale = 0.0f, nu_bg = 0.0f;
+    float *subgrid_fields = nullptr;
+    bool subgrid_fields_ready = false;  // compute has been called
+    double *subgrid_sums = nullptr;
+    bool subgrid_stats_ready = false;   // reset has been called
+    int64_t subgrid_n = 0;              // samples accumulated since
     // flow monitor (ludwig_level_monitor): one MonitorRecord per owned block in the reference block order, then the records of every
     // combine stage (512 -> 1) behind them; allocated by the first call
     MonitorRecord *monitor_slab = nullptr;
@@ -797,6 +808,9 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
     if (!L || !fl) return fail(LUDWIG_ERR_INVALID, "null level or flags");
     if (part < 0 || part >= N_PARTS) return fail(LUDWIG_ERR_INVALID, "bad part %d", part);
     if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "t_sub must be >= 0");
+    L->wale_known = true;                     // what ludwig_level_subgrid_* evaluates with
+    L->c_wale = fl->c_wale;
+    L->nu_bg = fl->nu_sgs_background;
     if (L->n_blocks == 0) return LUDWIG_OK;   // reference src/physics_v2.jl:41
     if (parent && parent->device != L->device) return fail(LUDWIG_ERR_INVALID, "parent level lives on another device");
     LW_HIP(hipSetDevice(L->device));
@@ -1095,6 +1109,8 @@ void ludwig_level_destroy(LudwigLevel *L)
     if (L->f_iface) (void)hipFree(L->f_iface);
     if (L->stats) (void)hipFree(L->stats);
     if (L->grad) (void)hipFree(L->grad);
+    if (L->subgrid_fields) (void)hipFree(L->subgrid_fields);
+    if (L->subgrid_sums) (void)hipFree(L->subgrid_sums);
     if (L->monitor_slab) (void)hipFree(L->monitor_slab);
     if (L->wall_census) (void)hipFree(L->wall_census);
     if (L->d_ref2int) (void)hipFree(L->d_ref2int);
@@ -2379,6 +2395,99 @@ int ludwig_level_gradient_fields_download(const LudwigLevel *L, int which, float
         return LUDWIG_OK;
     }
     return download_components(L, (const float *)L->grad, GRAD_COMPONENTS, first, K, host, "gradient fields download");
+}
+
+// ---- subgrid model (ludwig_level_subgrid_*; no reference counterpart) ----
+static int subgrid_model_known(const LudwigLevel *L, const char *what)
+{
+    if (L->wale_known) return LUDWIG_OK;
+    return fail(LUDWIG_ERR_STATE, "subgrid %s: the level has not been stepped yet, so it holds no c_wale / nu_sgs_background", what);
+}
+
+int ludwig_level_subgrid_fields_compute(LudwigLevel *L, int vel_field)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    if (vel_field != LUDWIG_VEL && vel_field != LUDWIG_VEL_TEMP) return fail(LUDWIG_ERR_INVALID, "vel_field must be LUDWIG_VEL or LUDWIG_VEL_TEMP");
+    if (L->n_owned == 0) {                            // no owned blocks: nothing to compute, nothing allocated
+        L->subgrid_fields_ready = true;
+        return LUDWIG_OK;
+    }
+    if (const int r = subgrid_model_known(L, "fields")) return r;
+    LW_HIP(hipSetDevice(L->device));
+    if (!L->subgrid_fields) {
+        const size_t n = (size_t)L->n_blocks * SUBGRID_FIELD_COMPONENTS * CELLS;
+        const int r = dev_alloc(L, &L->subgrid_fields, n);
+        if (r) return r;
+        LW_HIP(hipMemsetAsync(L->subgrid_fields, 0, n * sizeof(float), L->stream));   // the ghost blocks are never written
+    }
+    hipLaunchKernelGGL(k_subgrid<SUBGRID_FIELDS>, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->subgrid_fields,
+                       (const float *)L->vel[vel_field == LUDWIG_VEL ? 0 : 1], (const uint8_t *)L->obstacle, (const int32_t *)L->meta,
+                       L->c_wale, L->nu_bg);
+    LW_HIP(hipGetLastError());
+    L->subgrid_fields_ready = true;
+    return LUDWIG_OK;
+}
+
+int ludwig_level_subgrid_fields_download(const LudwigLevel *L, int which, float *host, size_t bytes)
+{
+    if (!L || (!host && bytes > 0)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (which != LUDWIG_SUBGRID_NU && which != LUDWIG_SUBGRID_CODE) return fail(LUDWIG_ERR_INVALID, "bad subgrid field %d", which);
+    if (!L->subgrid_fields_ready) return fail(LUDWIG_ERR_STATE, "subgrid fields: download before ludwig_level_subgrid_fields_compute");
+    const size_t plane = (size_t)L->sk * sizeof(float);
+    if (bytes != plane) return fail(LUDWIG_ERR_INVALID, "subgrid field %d: got %zu bytes, expected %zu", which, bytes, plane);
+    if (plane == 0) return LUDWIG_OK;
+    if (!L->subgrid_fields) {                         // no owned blocks: every block is a ghost
+        memset(host, 0, bytes);
+        return LUDWIG_OK;
+    }
+    return download_components(L, (const float *)L->subgrid_fields, SUBGRID_FIELD_COMPONENTS, which, 1, host, "subgrid fields download");
+}
+
+int ludwig_level_subgrid_stats_reset(LudwigLevel *L)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    L->subgrid_stats_ready = true;
+    L->subgrid_n = 0;
+    if (L->n_owned == 0) return LUDWIG_OK;           // no owned blocks: nothing to accumulate, nothing allocated
+    LW_HIP(hipSetDevice(L->device));
+    const size_t n = (size_t)L->n_blocks * SUBGRID_SUM_COMPONENTS * CELLS;
+    if (!L->subgrid_sums) {
+        const int r = dev_alloc(L, &L->subgrid_sums, n);
+        if (r) { L->subgrid_stats_ready = false; return r; }
+    }
+    LW_HIP(hipMemsetAsync(L->subgrid_sums, 0, n * sizeof(double), L->stream));
+    return LUDWIG_OK;
+}
+
+int ludwig_level_subgrid_stats_accumulate(LudwigLevel *L, int64_t t_sub)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    if (!L->subgrid_stats_ready) return fail(LUDWIG_ERR_STATE, "subgrid statistics: accumulate before ludwig_level_subgrid_stats_reset");
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "subgrid statistics: t_sub %lld < 0", (long long)t_sub);
+    if (L->n_owned == 0) return LUDWIG_OK;
+    if (const int r = subgrid_model_known(L, "statistics")) return r;
+    LW_HIP(hipSetDevice(L->device));
+    hipLaunchKernelGGL(k_subgrid<SUBGRID_SUMS>, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->subgrid_sums,
+                       (const float *)vel_out(L, t_sub), (const uint8_t *)L->obstacle, (const int32_t *)L->meta, L->c_wale, L->nu_bg);
+    LW_HIP(hipGetLastError());
+    ++L->subgrid_n;
+    return LUDWIG_OK;
+}
+
+int ludwig_level_subgrid_stats_download(const LudwigLevel *L, int which, double *host, size_t bytes, int64_t *n_samples)
+{
+    if (!L || (!host && bytes > 0)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (which < LUDWIG_SUBGRID_SUM_NU || which > LUDWIG_SUBGRID_SUM_EPS) return fail(LUDWIG_ERR_INVALID, "bad subgrid statistic %d", which);
+    if (!L->subgrid_stats_ready) return fail(LUDWIG_ERR_STATE, "subgrid statistics: download before ludwig_level_subgrid_stats_reset");
+    const size_t plane = (size_t)L->sk * sizeof(double);
+    if (bytes != plane) return fail(LUDWIG_ERR_INVALID, "subgrid statistic %d: got %zu bytes, expected %zu", which, bytes, plane);
+    if (n_samples) *n_samples = L->subgrid_n;
+    if (plane == 0) return LUDWIG_OK;
+    if (!L->subgrid_sums) {                           // no owned blocks: every block is a ghost
+        memset(host, 0, bytes);
+        return LUDWIG_OK;
+    }
+    return download_components(L, (const double *)L->subgrid_sums, SUBGRID_SUM_COMPONENTS, which, 1, host, "subgrid statistics download");
 }
 
 void ludwig_probes_destroy(LudwigProbes *P)

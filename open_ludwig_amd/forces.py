@@ -104,6 +104,11 @@ def nearest_fluid_cells(mesh, obstacle, block_pointer, dx, params, search_radius
     return NearestCells(found, best_b, best_l[:, 0], best_l[:, 1], best_l[:, 2], best_wd)
 
 
+def lattice_viscosity(tau):
+    """nu = (tau - 1/2) / 3 of a level in lattice units, Float32 as the kernels form it (wall_model_force_mag, wall_stress)"""
+    return (f32(tau) - f32(0.5)) / f32(3.0)
+
+
 def stress_from_cells(best_rho, best_u, best_wd, found, normals, tau, params):
     """compute_stress_from_cell (src/forces/surface.jl:32-96) for arrays of winning cells: rho [n], u [n,3], wall distance
     [n] (lattice units), found [n], triangle normals [n,3]. Returns (p, tau_x, tau_y, tau_z) Float32 [Pa]."""
@@ -116,7 +121,7 @@ def stress_from_cells(best_rho, best_u, best_wd, found, normals, tau, params):
     udn = ux * nrm[:, 0] + uy * nrm[:, 1] + uz * nrm[:, 2]
     utx, uty, utz = ux - udn * nrm[:, 0], uy - udn * nrm[:, 1], uz - udn * nrm[:, 2]
     umag = np.sqrt(utx * utx + uty * uty + utz * utz)
-    nu_lat = (f32(tau) - f32(0.5)) / f32(3.0)
+    nu_lat = lattice_viscosity(tau)
     use = (umag > f32(1e-10)) & (wall_dist > f32(0.01))
     safe = np.where(use, umag, f32(1.0))
     tmag = (best_rho * nu_lat * umag / wall_dist) * stress_scale

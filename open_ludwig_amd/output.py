@@ -213,11 +213,14 @@ def export_merged_mesh(t_step: int, grids, fields, out_dir: str, output_fields: 
     return write_vtu(os.path.join(out_dir, "flow_%06d" % t_step), m["points"], m["connectivity"], m["offsets"], m["types"], cd, compress)
 
 
-def export_mean_mesh(t_step: int, grids, stats_of_level, window: Tuple[int, int, int], out_dir: str, compress: bool = True) -> Optional[str]:
+def export_mean_mesh(t_step: int, grids, stats_of_level, window: Tuple[int, int, int], out_dir: str, compress: bool = True,
+                     extra: Optional[Sequence[Tuple[str, Callable]]] = None) -> Optional[str]:
     """<out_dir>/flow_mean_%06d.vtu: the time-averaged flow (no reference counterpart) on the mesh of flow_%06d.vtu - same blocks
     (select_export_blocks), points and cell order. stats_of_level(lvl) -> the finalised statistics of that level
     (statistics.finalize: mean_rho, mean_u, reynolds_stress, tke; Float64 in the reference layout); window = (samples, first
-    step, last step), written as Int64 FieldData. Cell arrays Float32 except Obstacle (UInt8) and Level (Int32)."""
+    step, last step), written as Int64 FieldData. Cell arrays Float32 except Obstacle (UInt8) and Level (Int32).
+    extra: optional scalar cell arrays, (name, array_of_level) with array_of_level(lvl) -> [8,8,8,nb] (the subgrid measures, subgrid.py),
+    written as Float32 after the arrays above in the order given; without it the file is those arrays alone."""
     valid = select_export_blocks([g.active_block_coords for g in grids])
     if not valid:
         return None
@@ -230,6 +233,8 @@ def export_mean_mesh(t_step: int, grids, stats_of_level, window: Tuple[int, int,
     rho, u, rs, k, obst = _gather_cells(geo, arrays, (np.float32,) * 4 + (np.uint8,), (1, 3, 6, 1, 1))
     cd = [("MeanDensity", rho), ("MeanVelocity", u), ("ReynoldsStress", rs), ("TurbulentKineticEnergy", k),
           ("Obstacle", obst), ("Level", geo["Level"])]
+    for name, array_of_level in extra or ():
+        cd.append((name, _gather_cells(geo, lambda lvl: (np.asarray(array_of_level(lvl)).astype(np.float32),), (np.float32,), (1,))[0]))
     fd = [(name, np.array([v], dtype=np.int64)) for name, v in zip(("StatisticsSamples", "StatisticsFirstStep", "StatisticsLastStep"), window)]
     return write_vtu(os.path.join(out_dir, "flow_mean_%06d" % t_step), geo["points"], geo["connectivity"], geo["offsets"], geo["types"],
                      cd, compress, field_data=fd)

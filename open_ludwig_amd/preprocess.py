@@ -98,6 +98,10 @@ class CaseConfig:
     statistics_enabled: bool = False
     statistics_start_step: int = 1      # first sampled coarse step (the sums are reset there); YAML default: ramp_steps
     statistics_interval: int = 10       # coarse steps between samples
+    # advanced.statistics.subgrid (subgrid.py): the subgrid model's sums at the flow statistics' sampled steps, five more arrays in
+    # flow_mean_%06d.vtu; subgrid_ck: the constant of k_sgs = (nu_t / (c_k Delta))^2
+    statistics_subgrid: bool = False
+    statistics_subgrid_ck: float = 0.094
     # surface statistics, advanced.surface_statistics (no reference counterpart): per-triangle mean / rms wall loads of the finest level,
     # written to surface_mean_%06d.vtu and forces_mean.csv on output steps (surface_stats.py)
     surface_statistics_enabled: bool = False
@@ -154,6 +158,13 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     stats_interval = int(g("advanced", "statistics", "interval", default=10))
     if stats_interval < 1:
         raise ValueError(f"advanced.statistics.interval must be >= 1, got {stats_interval}")
+    stats_subgrid = bool(g("advanced", "statistics", "subgrid", default=False))
+    stats_subgrid_ck = float(g("advanced", "statistics", "subgrid_ck", default=0.094))
+    if stats_subgrid and not bool(g("advanced", "statistics", "enabled", default=False)):
+        raise ValueError("advanced.statistics.subgrid is true, but advanced.statistics.enabled is not: the subgrid measures are "
+                         "sampled with the flow statistics")
+    if stats_subgrid and not stats_subgrid_ck > 0.0:
+        raise ValueError(f"advanced.statistics.subgrid_ck must be > 0, got {stats_subgrid_ck}")
     surf_start = int(g("advanced", "surface_statistics", "start_step", default=ramp_steps))
     surf_interval = int(g("advanced", "surface_statistics", "interval", default=1))
     if surf_interval < 1:
@@ -201,13 +212,16 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         # bouzidi is read by the reference's loader (config_loader.jl:148) but never written by io_vtk.jl. vorticity (the reference's
         # loader defaults it to true, config_loader.jl:145, and never writes it) and q_criterion (not a reference key) add device-computed
         # arrays to the flow file; both default to FALSE here, because the reference writes neither and every shipped config says false.
+        # eddy_viscosity (not a reference key, default false) adds EddyViscosityRatio, nu_t / nu of the step's own WALE model (subgrid.py).
         output_fields=tuple(name for key, name in (("density", "Density"), ("velocity", "Velocity"), ("velocity_magnitude", "VelocityMagnitude"),
                                                    ("obstacle", "Obstacle"), ("level", "Level"))
                             if bool(g("basic", "simulation", "output_fields", key, default=True)))
-                      + tuple(name for key, name in (("vorticity", "Vorticity"), ("q_criterion", "QCriterion"))
+                      + tuple(name for key, name in (("vorticity", "Vorticity"), ("q_criterion", "QCriterion"),
+                                                     ("eddy_viscosity", "EddyViscosityRatio"))
                               if bool(g("basic", "simulation", "output_fields", key, default=False))),
         statistics_enabled=bool(g("advanced", "statistics", "enabled", default=False)),
         statistics_start_step=max(stats_start, 1), statistics_interval=stats_interval,
+        statistics_subgrid=stats_subgrid, statistics_subgrid_ck=stats_subgrid_ck,
         surface_statistics_enabled=bool(g("advanced", "surface_statistics", "enabled", default=False)),
         surface_statistics_start_step=max(surf_start, 1), surface_statistics_interval=surf_interval,
         **probes,
