@@ -189,21 +189,7 @@ __device__ __forceinline__ const float *cell_ptr(const float *base, int blk, uin
 template <bool WIDE>
 __device__ __forceinline__ float ld_f32(const float *base, int blk, uint32_t block_bytes, uint32_t inner)
 {
-#ifdef LW_NT_LOADS
-    return __builtin_nontemporal_load(cell_ptr<WIDE>(base, blk, block_bytes, inner));
-#else
     return *cell_ptr<WIDE>(base, blk, block_bytes, inner);
-#endif
-}
-// load of a line that has exactly ONE reader in the launch (non-temporal: do not keep it in L2 / Infinity Cache)
-template <bool WIDE>
-__device__ __forceinline__ float ld_f32_once(const float *base, int blk, uint32_t block_bytes, uint32_t inner)
-{
-#ifdef LW_NT_SINGLE_READER
-    return __builtin_nontemporal_load(cell_ptr<WIDE>(base, blk, block_bytes, inner));
-#else
-    return ld_f32<WIDE>(base, blk, block_bytes, inner);
-#endif
 }
 // the wave's own block (wave-uniform id): uniform 64-bit base, 32-bit per-lane offset, at any level size
 __device__ __forceinline__ float ld_own(const float *base, int blk, uint32_t block_bytes, uint32_t inner)
@@ -236,20 +222,8 @@ struct NeighbourIds {
 __device__ __forceinline__ NeighbourIds load_neighbour_ids(const int32_t *__restrict__ meta, int z)
 {
     int nb[27];
-#ifdef LW_DIAG_ARITH_NBR   // timing-only: neighbour ids of the 32^3 periodic box computed, not loaded (no dependent scalar load)
-    {
-        const int b0 = (int)(meta - (const int32_t *)nullptr) / NBR_STRIDE;   // caller passes meta = nullptr + b * stride
-        const int bz = b0 & 31, by = (b0 >> 5) & 31, bx = b0 >> 10;
-#pragma unroll
-        for (int d = 0; d < 27; ++d) {
-            const int ox = d % 3 - 1, oy = (d / 3) % 3 - 1, oz = d / 9 - 1;
-            nb[d] = ((((bx + ox) & 31) << 5) | ((by + oy) & 31)) << 5 | ((bz + oz) & 31);
-        }
-    }
-#else
 #pragma unroll
     for (int d = 0; d < 27; ++d) nb[d] = meta[d];            // wave-uniform -> scalar loads, one burst
-#endif
     NeighbourIds n;
     const bool z_lo = z == 0, z_hi = z == 7;                 // wave-uniform
 #pragma unroll
@@ -345,20 +319,6 @@ __device__ __forceinline__ void finish_cell(const SCParams &p, const int flags, 
                                             const float ux_N, const float uy_N, const float uz_N, const float ux_S, const float uy_S, const float uz_S,
                                             const float ux_T, const float uy_T, const float uz_T, const float ux_B, const float uy_B, const float uz_B)
 {
-#ifdef LW_DIAG_NO_MATH   // timing-only diagnostic build: same loads and stores, no collision arithmetic; results are wrong
-    {
-        float acc = ux_E + uy_E + uz_E + ux_W + uy_W + uz_W + ux_N + uy_N + uz_N + ux_S + uy_S + uz_S + ux_T + uy_T + uz_T + ux_B + uy_B + uz_B;
-        st_f32(p.vel_out, own.b, V_BLOCK_BYTES, own.cell4, acc);
-        st_f32(p.vel_out, own.b, V_BLOCK_BYTES, COMP_BYTES + own.cell4, fs[1]);
-        st_f32(p.vel_out, own.b, V_BLOCK_BYTES, 2 * COMP_BYTES + own.cell4, fs[2]);
-        st_f32(p.rho, own.b, S_BLOCK_BYTES, own.cell4, fs[0]);
-        static_for<0, Q>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            st_f32(p.f_out, own.b, F_BLOCK_BYTES, k * COMP_BYTES + own.cell4, fs[k]);
-        });
-        return;
-    }
-#endif
     // moments in the reference's order: rho += f_k; j += f_k * c_k for k = 1..27
     float rho = 0.0f, jx = 0.0f, jy = 0.0f, jz = 0.0f;
     static_for<0, Q>([&](auto kc) {
@@ -645,13 +605,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE &
     LanePos l;
     l.x = lane & 7; l.y = lane >> 3;
     l.x0 = l.x == 0; l.x7 = l.x == 7; l.y0 = l.y == 0; l.y7 = l.y == 7;
-#ifdef LW_DIAG_ARITH_NBR
-    const int32_t *__restrict__ meta = (const int32_t *)nullptr + (size_t)b * NBR_STRIDE;
-    const int flags = FLAG_ALL_NEIGHBOURS;
-#else
     const int32_t *__restrict__ meta = p.meta + (size_t)b * NBR_STRIDE;
     const int flags = meta[NBR_FLAGS];
-#endif
     const NeighbourIds nbr = load_neighbour_ids(meta, z);
     const Own own{b, (uint32_t)((l.x + 8 * l.y + 64 * z) * 4)};
     // wave-uniform: a run may be shorter than the workgroup (several short runs, or single blocks, share one)
@@ -663,27 +618,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE &
     // ---- aligned loads: value of population k at (x, y - cy, z - cz) ----
     static_for<0, Q>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
-#ifdef LW_DIAG_NO_YSHIFT   // timing-only
-        constexpr int cx = CX(k), cy = 0, g = 1 - CZ(k);
-#else
         constexpr int cx = CX(k), cy = CY(k), g = 1 - CZ(k);
-#endif
         const bool yo = cy == 1 ? l.y0 : (cy == -1 ? l.y7 : false);
         const int c00 = nbr.id[g][4], cY = nbr.id[g][4 - 3 * cy];
         int sel = cy != 0 ? (yo ? cY : c00) : c00;
         if constexpr (GENERAL) sel = sel >= 0 ? sel : b;      // missing block: in-bounds dummy, patched after the exchange
         const uint32_t rowz = (uint32_t)(k * COMP_BYTES) + (uint32_t)((8 * ((l.y - cy) & 7)) * 4) + (uint32_t)(nbr.zs[g] * 256);
         // populations with cy = 0: the block is wave-uniform (SGPR base) and the two lines of this plane are read by this wave
-        // only (the x neighbours get their column through LDS, nobody shifts rows) -> single reader
-        if constexpr (cy == 0) fs[k] = ld_f32_once<true>(p.f_in, sel, F_BLOCK_BYTES, rowz + (uint32_t)(l.x * 4));
+        // only (the x neighbours get their column through LDS, nobody shifts rows)
+        if constexpr (cy == 0) fs[k] = ld_f32<true>(p.f_in, sel, F_BLOCK_BYTES, rowz + (uint32_t)(l.x * 4));
         else fs[k] = ld_f32<WIDE>(p.f_in, sel, F_BLOCK_BYTES, rowz + (uint32_t)(l.x * 4));
         halo[k] = 0.0f;
         if constexpr (cx != 0) {
-#ifdef LW_DIAG_NO_OUTER   // timing-only
-            if (false) {
-#else
             if (cx == 1 ? first : last) {                     // the run's outer face: strided column of the x / xy neighbour
-#endif
                 const int cX = nbr.id[g][4 - cx], cXY = nbr.id[g][4 - cx - 3 * cy];
                 int selx = cy != 0 ? (yo ? cXY : cX) : cX;
                 if constexpr (GENERAL) selx = selx >= 0 ? selx : b;
@@ -712,16 +659,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE &
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const uint32_t cb = (uint32_t)c * COMP_BYTES;
-#if defined(LW_DIAG_NO_VEL)   // timing-only
-            uc[c] = __int_as_float(own.cell4 + c); uT[c] = uc[c]; uB[c] = uc[c]; uy_edge[c] = 0.0f; ux_edge_lo[c] = 0.0f; ux_edge_hi[c] = 0.0f;
-            (void)cb; (void)inT; (void)inB; (void)inY; (void)inXlo; (void)inXhi;
-#elif defined(LW_DIAG_NO_VEL_TB)
-            uc[c] = ld_own(p.vel_in, b, V_BLOCK_BYTES, cb + own.cell4); uT[c] = uc[c]; uB[c] = uc[c];
-            uy_edge[c] = 0.0f; ux_edge_lo[c] = 0.0f; ux_edge_hi[c] = 0.0f;
-            if (l.y0 || l.y7) uy_edge[c] = ld_f32<WIDE>(p.vel_in, by_, V_BLOCK_BYTES, cb + inY);
-            if (first) { if (l.x0) ux_edge_lo[c] = ld_own(p.vel_in, bXlo, V_BLOCK_BYTES, cb + inXlo); }
-            if (last) { if (l.x7) ux_edge_hi[c] = ld_own(p.vel_in, bXhi, V_BLOCK_BYTES, cb + inXhi); }
-#else
             uc[c] = ld_own(p.vel_in, b, V_BLOCK_BYTES, cb + own.cell4);
             uT[c] = ld_own(p.vel_in, bT, V_BLOCK_BYTES, cb + inT);
             uB[c] = ld_own(p.vel_in, bB, V_BLOCK_BYTES, cb + inB);
@@ -729,12 +666,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE &
             if (l.y0 || l.y7) uy_edge[c] = ld_f32<WIDE>(p.vel_in, by_, V_BLOCK_BYTES, cb + inY);
             if (first) { if (l.x0) ux_edge_lo[c] = ld_own(p.vel_in, bXlo, V_BLOCK_BYTES, cb + inXlo); }
             if (last) { if (l.x7) ux_edge_hi[c] = ld_own(p.vel_in, bXhi, V_BLOCK_BYTES, cb + inXhi); }
-#endif
         }
     }
 
     // ---- publish the face columns the neighbouring waves need ----
-#ifndef LW_DIAG_NO_XCH
     static_for<0, Q>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         constexpr int cx = CX(k);
@@ -748,29 +683,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE &
             if (l.x0) xch[wave][21 + c][l.y] = uc[c];
         }
     }
-#endif
     }   // if (active)
-#ifndef LW_DIAG_NO_XCH
     __syncthreads();
-#endif
     if (!active) return;
-#ifdef LW_DIAG_NO_XCH   // timing-only: no LDS traffic at all
-#define LW_XCH(w, s, y) 0.0f
-#else
-#define LW_XCH(w, s, y) xch[w][s][y]
-#endif
     const int wlo = first ? 0 : wave - 1, whi = last ? NW - 1 : wave + 1;
     static_for<0, Q>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         constexpr int cx = CX(k);
         if constexpr (cx == 1) {
             const float inner = dpp_from_lower_lane(fs[k]);
-            const float edge = first ? halo[k] : LW_XCH(wlo, XSLOT(k), l.y);
+            const float edge = first ? halo[k] : xch[wlo][XSLOT(k)][l.y];
             fs[k] = l.x0 ? edge : inner;
         }
         if constexpr (cx == -1) {
             const float inner = dpp_from_upper_lane(fs[k]);
-            const float edge = last ? halo[k] : LW_XCH(whi, XSLOT(k), l.y);
+            const float edge = last ? halo[k] : xch[whi][XSLOT(k)][l.y];
             fs[k] = l.x7 ? edge : inner;
         }
     });
@@ -784,8 +711,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE &
     float uE[3], uW[3], uN[3], uS[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float e_edge = last ? ux_edge_hi[c] : LW_XCH(whi, 21 + c, l.y);
-        const float w_edge = first ? ux_edge_lo[c] : LW_XCH(wlo, 18 + c, l.y);
+        const float e_edge = last ? ux_edge_hi[c] : xch[whi][21 + c][l.y];
+        const float w_edge = first ? ux_edge_lo[c] : xch[wlo][18 + c][l.y];
         // cross-lane reads must execute with ALL lanes active: never inside an arm of ?: (that arm runs under a
         // reduced EXEC mask and a DPP read of an inactive lane silently keeps the old value)
         const float e_in = dpp_from_upper_lane(uc[c]), w_in = dpp_from_lower_lane(uc[c]);

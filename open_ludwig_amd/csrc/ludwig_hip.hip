@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/ludwig_hip.h"
+#include "all_or_nothing.hpp"
 #include "kernels.hpp"
 
 using namespace lw;
@@ -41,6 +42,45 @@ int fail(int code, const char *fmt, ...)
 
 constexpr int N_PARTS = 3, N_CLASSES = 3;   // class 1 = blocks with a missing neighbour (GENERAL instantiation), 2 = all-neighbour blocks; 0 unused
 constexpr int XRUN = 4, XRUN_MAX = 4;       // waves per workgroup = blocks of an x-run (8 and 16 were tried in rounds 1-2: slower)
+
+// ---- switches: every getenv of this file. INTEGRATION.md ("Environment switches") lists exactly these names with the same read times ----------
+namespace env {
+
+bool is_set(const char *name) { return getenv(name) != nullptr; }
+int flag(const char *name) { const char *e = getenv(name); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }      // 0 / 1, -1 = unset
+
+// LUDWIG_MERGE_CLASSES=0/1: never / always one launch for both block classes (-1: by size). Per level creation and per set_order.
+int merge_classes() { return flag("LUDWIG_MERGE_CLASSES"); }
+// LUDWIG_REFERENCE_BLOCK_ORDER: device arrays keep the caller's block order. Per level creation.
+bool reference_block_order() { return is_set("LUDWIG_REFERENCE_BLOCK_ORDER"); }
+// LUDWIG_WIDE_ADDR: 64-bit per-lane addresses at any level size. Per level creation.
+bool wide_addr() { return is_set("LUDWIG_WIDE_ADDR"); }
+// LUDWIG_FULL_POST_COLLISION: f_post_collision stored in every block, as the reference. Per level creation.
+bool full_post_collision() { return is_set("LUDWIG_FULL_POST_COLLISION"); }
+// LUDWIG_POST_ROWS=0: f_post_collision stored in whole blocks with a reader, not by x-rows. Per level creation.
+bool post_rows_off() { const char *e = getenv("LUDWIG_POST_ROWS"); return e && e[0] == '0'; }
+// LUDWIG_EAGER_RHO: every step stores rho. Per process (first step).
+bool eager_rho() { static const bool v = is_set("LUDWIG_EAGER_RHO"); return v; }
+// LUDWIG_NO_IFACE_AHEAD: the child-side interface pass produces one sub-step's values at a time. Per call (every such pass).
+bool no_iface_ahead() { return is_set("LUDWIG_NO_IFACE_AHEAD"); }
+// LUDWIG_RHO_OLD_COPY: copy_to_old!'s rho copy stays a copy inside a batch (not fused into the step). Per call (every save in a batch).
+bool rho_old_copy() { return is_set("LUDWIG_RHO_OLD_COPY"); }
+// LUDWIG_BATCH_SERIAL: a batch keeps every level on the caller's stream. Per process (first batch of more than one level).
+bool batch_serial() { static const bool v = is_set("LUDWIG_BATCH_SERIAL"); return v; }
+// LUDWIG_CHILD_SIDE_IFACE: level streams run the interface pass on the child's stream, not the parent's. Per process (first batch).
+bool child_side_iface() { static const bool v = is_set("LUDWIG_CHILD_SIDE_IFACE"); return v; }
+// LUDWIG_IFACE_HOIST=0/1: a middle level's child-side pass never / always ahead of its wait (-1: by size). Per process (first hoist).
+int iface_hoist() { static const int v = flag("LUDWIG_IFACE_HOIST"); return v; }
+// LUDWIG_LEVEL_STREAM_PRIORITY=0/2: level streams all at one priority / graded (1, unset: the finest level highest). Per call (every batch).
+int level_stream_priority() { const char *e = getenv("LUDWIG_LEVEL_STREAM_PRIORITY"); return e ? atoi(e) : 1; }
+// LUDWIG_RCCL_LIB: path of the RCCL library, tried after one already mapped in the process. Per process (first communicator).
+const char *rccl_lib() { return getenv("LUDWIG_RCCL_LIB"); }
+// LUDWIG_HALO_SELF_VIA_RCCL: a rank's messages to itself go through RCCL too. Per halo plan created.
+bool halo_self_via_rccl() { return is_set("LUDWIG_HALO_SELF_VIA_RCCL"); }
+// LUDWIG_HALO_TRACE: host microseconds of every exchange call on stderr. Per process (first exchange).
+bool halo_trace() { static const bool v = is_set("LUDWIG_HALO_TRACE"); return v; }
+
+}  // namespace env
 
 }  // namespace
 
@@ -118,19 +158,34 @@ struct LudwigLevel {
     float4 *source_mac[N_PARTS] = {};   // per source cell, rewritten every pass: interpolated rho, ux, uy, uz
     float4 *source_mac2[N_PARTS] = {};  // the same for the speculated weight of the next sub-step
     float *f_iface2 = nullptr;
-    // Interface values computed ahead for the second sub-step of a pair (reference src/solver_control.jl:63-83: the child
-    // steps 2t with weight 0.0 and 2t+1 with 0.5 against the same parent buffers): valid while the parent was not written.
-    struct IfaceAhead {
+    // What a set of interface values was computed from and for; every placement of the pass keeps its record in this one form, so a
+    // key cannot be known to one and forgotten by another. The values hold while the parent was not written (parent_version) and
+    // the question is asked for the same sub-step (or pair), weight, parent tau and blending mode.
+    struct IfaceKey {
         bool valid = false;
         const LudwigLevel *parent = nullptr;
         uint64_t parent_version = 0;
-        int64_t t_sub = 0;            // the sub-step the speculated values are for
+        int64_t step = 0;             // the sub-step the values are for; pair_ready: the pair, t_sub >> 1
         float tw = 0.0f, tau_parent = 0.0f;
         int use_temporal = 0;
-    } ahead[N_PARTS];
+        int set = 0;                  // pair_ready only: which pair of side buffers holds the values
+        void fill(const LudwigLevel *parent_, int64_t step_, float tw_, float tau_parent_, int use_temporal_)
+        {
+            valid = true; parent = parent_; parent_version = parent_->version; step = step_;
+            tw = tw_; tau_parent = tau_parent_; use_temporal = use_temporal_;
+        }
+        bool matches(const LudwigLevel *parent_, int64_t step_, float tw_, float tau_parent_, int use_temporal_) const
+        {
+            return valid && parent == parent_ && parent_version == parent_->version && step == step_ && tw == tw_ &&
+                   tau_parent == tau_parent_ && use_temporal == use_temporal_;
+        }
+    };
+    // Interface values computed ahead for the second sub-step of a pair (reference src/solver_control.jl:63-83: the child
+    // steps 2t with weight 0.0 and 2t+1 with 0.5 against the same parent buffers), in f_iface2.
+    IfaceKey ahead[N_PARTS];
     // Interface values produced BEFORE the step that uses them (interface_prepass: level streams run a parent level's interface
-    // pass ahead of its wait for the children, see recursive_step): same keys as IfaceAhead, values in f_iface.
-    IfaceAhead prepared[N_PARTS];
+    // pass ahead of its wait for the children, see recursive_step), in f_iface.
+    IfaceKey prepared[N_PARTS];
     // Lazy rho. The step writes `rho` (4 of 244 B per cell update) for readers that mostly are not there: the next step
     // overwrites it unread unless a child level interpolates from it (every step), or a diagnostic / download / save asks
     // for it (now and then). A level nobody has read `rho` of in between therefore skips the store and remembers the
@@ -159,14 +214,7 @@ struct LudwigLevel {
     // level is still stepping pair t - 1 out of the other set. This level's own stream then carries no interface kernels at all.
     float *f_iface_b = nullptr, *f_iface2_b = nullptr;             // set 1 (set 0 = f_iface, f_iface2)
     float4 *mac_b = nullptr, *mac2_b = nullptr;                    // scratch of set 1's pass (LUDWIG_PART_ALL)
-    struct PairReady {
-        bool valid = false;
-        const LudwigLevel *parent = nullptr;
-        uint64_t parent_version = 0;
-        int64_t pair = -1;                                         // t_sub >> 1 of the sub-steps the values are for
-        float tau_parent = 0.0f;
-        int use_temporal = 0, set = 0;
-    } pair_ready;
+    IfaceKey pair_ready;                                           // step = the pair; tw = the first sub-step's weight, the second's is 0.5
     hipEvent_t ev_pair_done[2] = {nullptr, nullptr};               // recorded on THIS level's stream after the second sub-step of a pair
     bool pair_done_set[2] = {false, false};
     hipEvent_t ev_stepped = nullptr;    // recorded on this level's stream after each of its steps (collision + Bouzidi)
@@ -338,9 +386,8 @@ constexpr int MERGE_BELOW_BLOCKS = 8192;      // 4.2 M cells: above that a pass 
 bool merge_classes(const LudwigLevel *L, const std::vector<int32_t> &general, const std::vector<int32_t> &fast)
 {
     if (general.empty() || fast.empty()) return false;
-    const char *e = getenv("LUDWIG_MERGE_CLASSES");
-    if (e) return atoi(e) != 0;
-    return L->n_owned < MERGE_BELOW_BLOCKS;
+    const int e = env::merge_classes();
+    return e >= 0 ? e != 0 : L->n_owned < MERGE_BELOW_BLOCKS;
 }
 
 int set_items(LudwigLevel *L, int part, const int32_t *items, int64_t n)
@@ -616,8 +663,10 @@ int build_interface_links(LudwigLevel *L, const LudwigLevel *parent, int nx_g, i
     return LUDWIG_OK;
 }
 
-// the parent-side pointers of a step / an interface pass for sub-step t_sub
-static void fill_parent_params(SCParams &p, const LudwigLevel *parent, int64_t t_sub)
+// Everything of SCParams an interface pass reads, for the pass or the step of `L` at sub-step t_sub: the parent-side pointers, the
+// two relaxation times, the temporal weight and blending mode, the global box. A step adds its own fields (launch_stream_collide).
+static void fill_pass_params(SCParams &p, const LudwigLevel *L, const LudwigLevel *parent, int64_t t_sub, float parent_tau,
+                             float temporal_weight, const LudwigStepFlags *fl)
 {
     if (parent) {
         const int pout = ((t_sub >> 1) % 2 == 0) ? 1 : 0;   // output buffer of the parent's step t_sub >> 1
@@ -629,16 +678,59 @@ static void fill_parent_params(SCParams &p, const LudwigLevel *parent, int64_t t
         p.pf_old = parent->has_temporal ? (parent->old_alias >= 0 ? parent->f[parent->old_alias] : parent->f_old) : parent->f[pout];
         p.prho_old = parent->has_temporal ? parent->rho_old : parent->rho;
         p.pvel_old = parent->has_temporal ? (parent->old_alias >= 0 ? parent->vel[parent->old_alias] : parent->vel_old) : parent->vel[pout];
-        p.is_level_1 = 0;
-    } else {
-        p.is_level_1 = 1;
     }
+    p.is_level_1 = parent ? 0 : 1;
+    p.tau = L->tau;
+    p.tau_parent = parent_tau;
+    p.temporal_weight = temporal_weight;
+    const int scale = 1 << (L->level_id - 1);   // reference src/physics_v2.jl:55-56
+    p.nx_g = fl->domain_nx * scale; p.ny_g = fl->domain_ny * scale; p.nz_g = fl->domain_nz * scale;
+    // a parent without temporal storage cannot be blended with (reference would index a dummy array)
+    p.use_temporal = (fl->use_temporal_interp && (!parent || parent->has_temporal)) ? 1 : 0;
+}
+
+// One pair of side buffers of a level's interface pass: the values for the pass's own weight, those for the second sub-step of the
+// pair (TWO), and the per-source scratch of each. Set 0 is the level's own; set 1 exists on levels whose parent runs the pass.
+struct IfaceBuffers {
+    float *f_iface, *f_iface2;
+    float4 *mac, *mac2;
+};
+
+static IfaceBuffers iface_buffers(const LudwigLevel *L, int part, int set)
+{
+    if (set) return {L->f_iface_b, L->f_iface2_b, L->mac_b, L->mac2_b};
+    return {L->f_iface, L->f_iface2, L->source_mac[part], L->source_mac2[part]};
+}
+
+// The two kernels of an interface pass of L's `part` on `st`: into b.f_iface for p's weight and, with `two`, into b.f_iface2 for 0.5.
+static int launch_interface_kernels(const LudwigLevel *L, int part, SCParams p, const IfaceBuffers &b, bool two, hipStream_t st)
+{
+    p.f_iface = b.f_iface;
+    p.n_iface_blocks = L->n_iface_blocks;
+    InterfaceArgs a{};
+    a.corners = L->sources[part]; a.weights = L->source_w[part];
+    a.mac = b.mac; a.mac2 = b.mac2;
+    a.links = L->links[part];
+    a.f_iface2 = b.f_iface2;
+    a.tw2 = 0.5f;
+    a.n_sources = L->n_sources[part]; a.n_links = L->n_links[part];
+    const dim3 gs((unsigned)((a.n_sources + 255) / 256)), gl((unsigned)((a.n_links + 255) / 256));
+    if (two) {
+        hipLaunchKernelGGL(k_interface_sources<true>, gs, dim3(256), 0, st, p, a);
+        hipLaunchKernelGGL(k_interface_links<true>, gl, dim3(256), 0, st, p, a);
+    } else {
+        hipLaunchKernelGGL(k_interface_sources<false>, gs, dim3(256), 0, st, p, a);
+        hipLaunchKernelGGL(k_interface_links<false>, gl, dim3(256), 0, st, p, a);
+    }
+    LW_HIP(hipGetLastError());
+    return LUDWIG_OK;
 }
 
 // Coarse -> fine interface pass for the general blocks of `part` (reference src/physics_kernels.jl:122-137), in two halves.
 // interface_decide: leaves p.f_iface pointing at the values sub-step t_sub loads and says whether kernels have to run for them
-// (IFACE_LAUNCH) or they exist already - produced ahead by interface_prepass (READY) or together with the previous sub-step's (HIT).
-// interface_launch: the two kernels on `st`. ahead_of_step: called by interface_prepass, before the step's own launch.
+// (IFACE_LAUNCH) or they exist already - produced ahead by the parent's stream or by interface_prepass (READY), or together with the
+// previous sub-step's (HIT). interface_launch: the two kernels on `st`. ahead_of_step: called by interface_prepass, before the step's
+// own launch.
 enum IfaceState { IFACE_NONE, IFACE_READY, IFACE_HIT, IFACE_LAUNCH };
 
 static int interface_decide(LudwigLevel *L, const LudwigLevel *parent, int part, SCParams &p, int64_t t_sub, float parent_tau,
@@ -651,31 +743,30 @@ static int interface_decide(LudwigLevel *L, const LudwigLevel *parent, int part,
     p.f_iface = L->f_iface;
     p.n_iface_blocks = L->n_iface_blocks;
     if (L->n_links[part] == 0) return LUDWIG_OK;
-    {   // values the parent's stream has produced for this pair of sub-steps (recursive_step: parent-side interface pass)
-        const LudwigLevel::PairReady &pr = L->pair_ready;
-        if (!ahead_of_step && part == LUDWIG_PART_ALL && pr.valid && pr.parent == parent && pr.parent_version == parent->version &&
-            pr.pair == (t_sub >> 1) && pr.tau_parent == parent_tau && pr.use_temporal == p.use_temporal &&
-            temporal_weight == ((t_sub & 1) ? 0.5f : 0.0f)) {
-            float *const first = pr.set ? L->f_iface_b : L->f_iface, *const second = pr.set ? L->f_iface2_b : L->f_iface2;
-            p.f_iface = (t_sub & 1) ? second : first;
-            *state = IFACE_READY;
-            return LUDWIG_OK;
-        }
+    // 1. produced by the parent's stream for this pair of sub-steps (interface_pass_for_child)? One record serves both sub-steps:
+    //    the first half of its set was made with weight 0.0, the second with 0.5
+    const LudwigLevel::IfaceKey &pr = L->pair_ready;
+    if (!ahead_of_step && part == LUDWIG_PART_ALL && temporal_weight == ((t_sub & 1) ? 0.5f : 0.0f) &&
+        pr.matches(parent, t_sub >> 1, 0.0f, parent_tau, p.use_temporal)) {
+        const IfaceBuffers b = iface_buffers(L, part, pr.set);
+        p.f_iface = (t_sub & 1) ? b.f_iface2 : b.f_iface;
+        *state = IFACE_READY;
+        return LUDWIG_OK;
     }
-    LudwigLevel::IfaceAhead &pre = L->prepared[part];
-    const bool ready = pre.valid && pre.parent == parent && pre.parent_version == parent->version && pre.t_sub == t_sub &&
-                       pre.tw == temporal_weight && pre.tau_parent == parent_tau && pre.use_temporal == p.use_temporal;
+    // 2. prepared ahead of this step (interface_prepass)? The look-ahead record for t_sub + 1 stays as it is
+    LudwigLevel::IfaceKey &pre = L->prepared[part];
+    const bool ready = pre.matches(parent, t_sub, temporal_weight, parent_tau, p.use_temporal);
     pre.valid = ready && ahead_of_step;
     *state = IFACE_READY;
-    if (ready) return LUDWIG_OK;                 // produced by interface_prepass; the look-ahead record for t_sub + 1 stays as it is
-    LudwigLevel::IfaceAhead &ah = L->ahead[part];
-    const bool hit = ah.valid && ah.parent == parent && ah.parent_version == parent->version && ah.t_sub == t_sub &&
-                     ah.tw == temporal_weight && ah.tau_parent == parent_tau && ah.use_temporal == p.use_temporal;
+    if (ready) return LUDWIG_OK;
+    // 3. speculated together with the previous sub-step's values?
+    LudwigLevel::IfaceKey &ah = L->ahead[part];
+    const bool hit = ah.matches(parent, t_sub, temporal_weight, parent_tau, p.use_temporal);
     if (hit && ahead_of_step) return LUDWIG_OK;  // nothing to do ahead: the step will find the values in f_iface2
     ah.valid = false;
     *state = IFACE_HIT;
     if (hit) {
-        p.f_iface = L->f_iface2;                 // computed together with the previous sub-step's values
+        p.f_iface = L->f_iface2;
         return LUDWIG_OK;
     }
     *state = IFACE_LAUNCH;
@@ -685,32 +776,12 @@ static int interface_decide(LudwigLevel *L, const LudwigLevel *parent, int part,
 static int interface_launch(LudwigLevel *L, const LudwigLevel *parent, int part, const SCParams &p, int64_t t_sub, float parent_tau,
                             float temporal_weight, bool ahead_of_step, hipStream_t st)
 {
-    LudwigLevel::IfaceAhead &pre = L->prepared[part];
-    LudwigLevel::IfaceAhead &ah = L->ahead[part];
     // first sub-step of a pair (even t_sub): also produce the values for t_sub + 1 at weight 0.5
-    const bool two = (t_sub % 2 == 0) && !parent->external_writer && getenv("LUDWIG_NO_IFACE_AHEAD") == nullptr;
-    InterfaceArgs a{};
-    a.corners = L->sources[part]; a.weights = L->source_w[part];
-    a.mac = L->source_mac[part]; a.mac2 = L->source_mac2[part];
-    a.links = L->links[part];
-    a.f_iface2 = L->f_iface2;
-    a.tw2 = 0.5f;
-    a.n_sources = L->n_sources[part]; a.n_links = L->n_links[part];
-    const dim3 gs((unsigned)((a.n_sources + 255) / 256)), gl((unsigned)((a.n_links + 255) / 256));
-    if (two) {
-        hipLaunchKernelGGL(k_interface_sources<true>, gs, dim3(256), 0, st, p, a);
-        hipLaunchKernelGGL(k_interface_links<true>, gl, dim3(256), 0, st, p, a);
-        ah.valid = true; ah.parent = parent; ah.parent_version = parent->version; ah.t_sub = t_sub + 1;
-        ah.tw = a.tw2; ah.tau_parent = parent_tau; ah.use_temporal = p.use_temporal;
-    } else {
-        hipLaunchKernelGGL(k_interface_sources<false>, gs, dim3(256), 0, st, p, a);
-        hipLaunchKernelGGL(k_interface_links<false>, gl, dim3(256), 0, st, p, a);
-    }
-    LW_HIP(hipGetLastError());
-    if (ahead_of_step) {
-        pre.valid = true; pre.parent = parent; pre.parent_version = parent->version; pre.t_sub = t_sub;
-        pre.tw = temporal_weight; pre.tau_parent = parent_tau; pre.use_temporal = p.use_temporal;
-    }
+    const bool two = (t_sub % 2 == 0) && !parent->external_writer && !env::no_iface_ahead();
+    if (two) L->ahead[part].fill(parent, t_sub + 1, 0.5f, parent_tau, p.use_temporal);
+    const int r = launch_interface_kernels(L, part, p, iface_buffers(L, part, 0), two, st);
+    if (r) return r;
+    if (ahead_of_step) L->prepared[part].fill(parent, t_sub, temporal_weight, parent_tau, p.use_temporal);
     // level streams (ludwig_execute_timestep_batch): the parent's buffers have been read - the last time for this
     // pair of sub-steps when the values for the second one were produced alongside
     if (parent->ev_consumed && L->own_stream && L->stream == L->own_stream) {
@@ -720,13 +791,22 @@ static int interface_launch(LudwigLevel *L, const LudwigLevel *parent, int part,
     return LUDWIG_OK;
 }
 
-static int interface_pass(LudwigLevel *L, const LudwigLevel *parent, int part, SCParams &p, int64_t t_sub, float parent_tau,
-                          float temporal_weight, bool ahead_of_step)
+// The second pair of side buffers of C and the two events that guard its sets - all of it, or nothing: after a failure every slot
+// is null again and nothing is counted, so a later batch tries again instead of finding half a set.
+static int make_second_iface_set(LudwigLevel *C, size_t n_side, size_t n_src)
 {
-    IfaceState state;
-    const int r = interface_decide(L, parent, part, p, t_sub, parent_tau, temporal_weight, ahead_of_step, &state);
-    if (r || state != IFACE_LAUNCH) return r;
-    return interface_launch(L, parent, part, p, t_sub, parent_tau, temporal_weight, ahead_of_step, L->stream);
+    if (C->f_iface_b) return LUDWIG_OK;
+    void **const bufs[4] = {(void **)&C->f_iface_b, (void **)&C->f_iface2_b, (void **)&C->mac_b, (void **)&C->mac2_b};
+    const size_t bytes[4] = {n_side * sizeof(float), n_side * sizeof(float), n_src * sizeof(float4), n_src * sizeof(float4)};
+    hipEvent_t *const evs[2] = {&C->ev_pair_done[0], &C->ev_pair_done[1]};
+    hipError_t e = hipSuccess;
+    const bool made = lw::make_all_or_nothing(
+        bufs, bytes, evs, [&](void **q, size_t n) { return (e = hipMalloc(q, n)) == hipSuccess; }, [](void *q) { (void)hipFree(q); },
+        [&](hipEvent_t *ev) { return (e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) == hipSuccess; },
+        [](hipEvent_t ev) { (void)hipEventDestroy(ev); });
+    if (!made) return fail(LUDWIG_ERR_HIP, "second set of interface side buffers: %s", hipGetErrorString(e));
+    C->device_bytes += (int64_t)(bytes[0] + bytes[1] + bytes[2] + bytes[3]);
+    return LUDWIG_OK;
 }
 
 // Parent-side interface pass: `parent` has just stepped t_pair on ITS stream; the interface values its child C needs for sub-steps
@@ -738,47 +818,19 @@ static int interface_pass(LudwigLevel *L, const LudwigLevel *parent, int part, S
 // two pairs ago - waited for through C's ev_pair_done. Same kernels, same arguments as the child-side pass: same bits.
 static int interface_pass_for_child(LudwigLevel *parent, LudwigLevel *C, int64_t t_pair, const LudwigStepFlags *fl)
 {
-    if (C->n_blocks == 0 || C->n_items[LUDWIG_PART_ALL][1] == 0 || parent->external_writer) return LUDWIG_OK;
+    const int part = LUDWIG_PART_ALL;
+    if (C->n_blocks == 0 || C->n_items[part][1] == 0 || parent->external_writer) return LUDWIG_OK;
     SCParams p{};
-    const int64_t t_sub = 2 * t_pair;
-    fill_parent_params(p, parent, t_sub);
-    p.tau = C->tau;
-    p.tau_parent = parent->tau;
-    p.temporal_weight = 0.0f;
-    const int scale = 1 << (C->level_id - 1);
-    p.nx_g = fl->domain_nx * scale; p.ny_g = fl->domain_ny * scale; p.nz_g = fl->domain_nz * scale;
-    p.use_temporal = (fl->use_temporal_interp && parent->has_temporal) ? 1 : 0;
+    fill_pass_params(p, C, parent, 2 * t_pair, parent->tau, 0.0f, fl);
     int rc = build_interface_links(C, parent, p.nx_g, p.ny_g, p.nz_g);
     if (rc) return rc;
-    const int part = LUDWIG_PART_ALL;
     if (C->n_links[part] == 0) return LUDWIG_OK;
+    if ((rc = make_second_iface_set(C, (size_t)C->n_iface_blocks * CELLS * Q, (size_t)C->n_sources[part]))) return rc;
     const int set = (int)(t_pair & 1);
-    const size_t n_side = (size_t)C->n_iface_blocks * CELLS * Q, n_src = (size_t)C->n_sources[part];
-    if (!C->f_iface_b) {
-        LW_HIP(hipMalloc((void **)&C->f_iface_b, n_side * sizeof(float)));
-        LW_HIP(hipMalloc((void **)&C->f_iface2_b, n_side * sizeof(float)));
-        LW_HIP(hipMalloc((void **)&C->mac_b, n_src * sizeof(float4)));
-        LW_HIP(hipMalloc((void **)&C->mac2_b, n_src * sizeof(float4)));
-        C->device_bytes += (int64_t)(2 * n_side * sizeof(float) + 2 * n_src * sizeof(float4));
-        for (hipEvent_t &ev : C->ev_pair_done) LW_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
     if (C->pair_done_set[set]) LW_HIP(hipStreamWaitEvent(parent->stream, C->ev_pair_done[set], 0));      // C has finished with this set
-    p.f_iface = set ? C->f_iface_b : C->f_iface;
-    p.n_iface_blocks = C->n_iface_blocks;
-    InterfaceArgs a{};
-    a.corners = C->sources[part]; a.weights = C->source_w[part];
-    a.mac = set ? C->mac_b : C->source_mac[part]; a.mac2 = set ? C->mac2_b : C->source_mac2[part];
-    a.links = C->links[part];
-    a.f_iface2 = set ? C->f_iface2_b : C->f_iface2;
-    a.tw2 = 0.5f;
-    a.n_sources = C->n_sources[part]; a.n_links = C->n_links[part];
-    const dim3 gs((unsigned)((a.n_sources + 255) / 256)), gl((unsigned)((a.n_links + 255) / 256));
-    hipLaunchKernelGGL(k_interface_sources<true>, gs, dim3(256), 0, parent->stream, p, a);
-    hipLaunchKernelGGL(k_interface_links<true>, gl, dim3(256), 0, parent->stream, p, a);
-    LW_HIP(hipGetLastError());
-    LudwigLevel::PairReady &pr = C->pair_ready;
-    pr.valid = true; pr.parent = parent; pr.parent_version = parent->version; pr.pair = t_pair;
-    pr.tau_parent = parent->tau; pr.use_temporal = p.use_temporal; pr.set = set;
+    if ((rc = launch_interface_kernels(C, part, p, iface_buffers(C, part, set), true, parent->stream))) return rc;
+    C->pair_ready.fill(parent, t_pair, 0.0f, parent->tau, p.use_temporal);
+    C->pair_ready.set = set;
     C->ahead[part].valid = false;          // the child-side look-ahead buffers (set 0's second half) are about to be / have been reused
     C->prepared[part].valid = false;
     return LUDWIG_OK;
@@ -789,17 +841,15 @@ static int interface_pass_for_child(LudwigLevel *parent, LudwigLevel *C, int64_t
 static int interface_prepass(LudwigLevel *L, const LudwigLevel *parent, int64_t t_sub, float parent_tau, float temporal_weight,
                              const LudwigStepFlags *fl)
 {
-    if (!parent || L->n_blocks == 0 || L->n_items[LUDWIG_PART_ALL][1] == 0) return LUDWIG_OK;
+    const int part = LUDWIG_PART_ALL;
+    if (!parent || L->n_blocks == 0 || L->n_items[part][1] == 0) return LUDWIG_OK;
     LW_HIP(hipSetDevice(L->device));
     SCParams p{};
-    fill_parent_params(p, parent, t_sub);
-    p.tau = L->tau;
-    p.tau_parent = parent_tau;
-    p.temporal_weight = temporal_weight;
-    const int scale = 1 << (L->level_id - 1);
-    p.nx_g = fl->domain_nx * scale; p.ny_g = fl->domain_ny * scale; p.nz_g = fl->domain_nz * scale;
-    p.use_temporal = (fl->use_temporal_interp && parent->has_temporal) ? 1 : 0;
-    return interface_pass(L, parent, LUDWIG_PART_ALL, p, t_sub, parent_tau, temporal_weight, true);
+    fill_pass_params(p, L, parent, t_sub, parent_tau, temporal_weight, fl);
+    IfaceState state;
+    const int r = interface_decide(L, parent, part, p, t_sub, parent_tau, temporal_weight, true, &state);
+    if (r || state != IFACE_LAUNCH) return r;
+    return interface_launch(L, parent, part, p, t_sub, parent_tau, temporal_weight, true, L->stream);
 }
 
 int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_sub, float u_curr, float parent_tau,
@@ -837,21 +887,14 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
     p.sponge = L->sponge;
     p.wall_dist = L->wall_dist;
     p.meta = L->meta;
-    fill_parent_params(p, parent, t_sub);
-    p.tau = L->tau;
-    p.tau_parent = parent_tau;
+    fill_pass_params(p, L, parent, t_sub, parent_tau, temporal_weight, fl);
     p.c_wale = fl->c_wale;
     p.nu_bg = fl->nu_sgs_background;
     p.u_inlet = u_curr;
     p.inlet_turbulence = fl->inlet_turbulence;
-    p.temporal_weight = temporal_weight;
     p.is_symmetric = fl->is_symmetric ? 1 : 0;
-    const int scale = 1 << (L->level_id - 1);   // reference src/physics_v2.jl:55-56
-    p.nx_g = fl->domain_nx * scale; p.ny_g = fl->domain_ny * scale; p.nz_g = fl->domain_nz * scale;
     p.wall_model = fl->wall_model_active ? 1 : 0;
     p.seed = (int32_t)(t_sub % 1000000);        // reference src/physics_v2.jl:76
-    // a parent without temporal storage cannot be blended with (reference would index a dummy array)
-    p.use_temporal = (fl->use_temporal_interp && (!parent || parent->has_temporal)) ? 1 : 0;
     p.sponge_blend = fl->sponge_blend_distributions ? 1 : 0;
 
     // lazy rho: who reads rho before this level's next step?
@@ -862,9 +905,8 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
         if (r) return r;
     }
     {
-        static const bool eager_env = getenv("LUDWIG_EAGER_RHO") != nullptr;
         if (t_sub != L->last_step_t) { ++L->step_count; L->last_step_t = t_sub; }
-        const bool store = L->rho_eager || eager_env || part != LUDWIG_PART_ALL;
+        const bool store = env::eager_rho() || L->rho_eager || part != LUDWIG_PART_ALL;
         // This launch reuses the previous step's INPUT buffer as its output. A whole-level launch supersedes the elided rho of
         // the previous one (the reference would be overwriting it right now, unread); a part launch covers only some of the
         // cells, so the rest is produced first, while its inputs still exist.
@@ -913,9 +955,6 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
         const int r = interface_decide(L, parent, part, p, t_sub, parent_tau, temporal_weight, false, &istate);
         if (r) return r;
     }
-    // (Round 3 tried to take the interface pass - the one piece of a sub-step that reads the PARENT, and whose result only the general
-    // blocks read - off the chain: all-neighbour blocks first, before the wait for the parent's step; and the pass on a side stream
-    // under them. Both measured slower than this merged launch, at any stream priority: profiles/r03_split_substep_ab.txt. Removed.)
     {
         if (parent_wait) LW_HIP(hipStreamWaitEvent(cs, parent_wait, 0));
         int r;
@@ -1138,7 +1177,7 @@ int ludwig_level_create(const LudwigLevelHost *h, int device, LudwigLevel **out)
     if (out) *out = nullptr;
     if (!h || !out) return fail(LUDWIG_ERR_INVALID, "null argument");
     const int32_t nb = h->n_blocks;
-    if (nb <= 1 || getenv("LUDWIG_REFERENCE_BLOCK_ORDER") || !h->neighbor_table || !h->map_x || !h->map_y || !h->map_z)
+    if (nb <= 1 || env::reference_block_order() || !h->neighbor_table || !h->map_x || !h->map_y || !h->map_z)
         return level_create_impl(h, device, out, false);
     const int n_owned = h->n_owned > 0 ? h->n_owned : (h->n_owned < 0 ? 0 : nb);
     if (n_owned > nb) return fail(LUDWIG_ERR_INVALID, "n_owned > n_blocks");
@@ -1239,7 +1278,7 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
     L->tau = h->tau;
     L->gdx = h->grid_dim_x; L->gdy = h->grid_dim_y; L->gdz = h->grid_dim_z;
     L->sk = (int64_t)h->n_blocks * CELLS;
-    L->wide = (int64_t)h->n_blocks * (int64_t)F_BLOCK_BYTES >= ((int64_t)1 << 32) || getenv("LUDWIG_WIDE_ADDR") != nullptr;
+    L->wide = (int64_t)h->n_blocks * (int64_t)F_BLOCK_BYTES >= ((int64_t)1 << 32) || env::wide_addr();
     const size_t c = (size_t)L->sk, nb = (size_t)h->n_blocks;
     L->has_temporal = h->enable_temporal_interpolation && nb > 0;            // reference src/blocks.jl:123
     L->bouzidi_enabled = h->n_boundary_cells > 0 && h->bouzidi_q_map;        // reference src/blocks.jl:152
@@ -1374,7 +1413,7 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
             // where f_post_collision has a reader: blocks that hold a Bouzidi cell or a cell next to one (a link q < 1/2 reads
             // the cell one step behind, possibly across a block face). No cell list on this rank (forced store, multi-GPU:
             // the readers are a peer's cells), store_post_collision_everywhere or LUDWIG_FULL_POST_COLLISION set: every block, as the reference.
-            const bool fixed = h->store_post_collision_everywhere != 0 || getenv("LUDWIG_FULL_POST_COLLISION") != nullptr;
+            const bool fixed = h->store_post_collision_everywhere != 0 || env::full_post_collision();
             const bool everywhere = L->n_bc == 0 || fixed;
             L->post_mode = fixed ? 1 : (L->n_bc == 0 ? 2 : 0);
             for (int b = 0; b < L->n_blocks && everywhere; ++b) L->h_meta[(size_t)b * NBR_STRIDE + NBR_FLAGS] |= FLAG_STORE_POST;
@@ -1391,8 +1430,7 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
             }
             // inside those blocks: the x-rows a link with q > 0 reads - its own cell and the cell one step behind
             // (LUDWIG_POST_ROWS=0: whole blocks, round 2's granularity)
-            const char *pr = getenv("LUDWIG_POST_ROWS");
-            if (!fixed && !(pr && pr[0] == '0')) {
+            if (!fixed && !env::post_rows_off()) {
                 L->h_post_rows.assign((size_t)L->n_blocks * 2, 0u);
                 auto mark = [&](int cell) { const int row = (cell & (CELLS - 1)) >> 3; L->h_post_rows[(size_t)(cell / CELLS) * 2 + (row >> 5)] |= 1u << (row & 31); };
                 for (const int4 &l : bl) { mark(l.x); if (l.w >= 0) mark(l.w); }
@@ -1690,7 +1728,7 @@ static int save_old_impl(LudwigLevel *L, int64_t t_sub, bool defer_rho)
         const int r = ensure_rho(L);
         if (r) return r;
     }
-    if (defer_rho && L->n_owned == L->n_blocks && !L->external_writer && getenv("LUDWIG_RHO_OLD_COPY") == nullptr) {
+    if (defer_rho && L->n_owned == L->n_blocks && !L->external_writer && !env::rho_old_copy()) {
         L->rho_old_pending = true;                   // the step that follows saves it cell by cell (launch_stream_collide)
         return LUDWIG_OK;
     }
@@ -1698,22 +1736,6 @@ static int save_old_impl(LudwigLevel *L, int64_t t_sub, bool defer_rho)
     LW_HIP(hipMemcpyAsync(L->rho_old, L->rho, c * 4, hipMemcpyDeviceToDevice, L->stream));
     return LUDWIG_OK;
 }
-
-// Level streams. The reference steps its levels strictly one after the other (src/solver_control.jl:21-143), and every launch
-// of a small level leaves most of the 256 CUs idle. The data dependencies are weaker than the call order: coupling is one-way,
-// coarse -> fine, and a child reads its parent's buffers only in its interface pass (k_interface_sources / _links, once per
-// pair of sub-steps). So each level gets a HIP stream of its own and two events:
-//   * a child's sub-step waits for its parent's step (parent->ev_stepped) before it interpolates from it;
-//   * a parent's NEXT step - which overwrites the buffer holding its old state, rho and rho_old - waits until the child's
-//     interface pass has read them (ev_consumed, recorded on the child's stream right after that pass).
-// Launches are still issued in the reference's order; the GPU then runs level 1's step t + 1 under the finer levels' sub-steps
-// of step t, and a middle level's second sub-step under its children's first pair. Same kernels, same inputs: same bits.
-// The finest level is the critical chain (2^(n-1) sub-steps per coarse step): its stream gets the highest priority, the others the
-// lowest, so the coarser levels only fill what it leaves free. Measured on one box, alternating (profiles/
-// r02_level_streams_with_priorities_ab_one_box.txt): 3-level sphere 0.419 -> 0.393 ms per coarse step, real wing 1.011 -> 0.949,
-// 4-level sphere 1.72 -> 1.52; without the priorities 0.402 / 0.982 / 1.58 (and on another box the 4-level case got slower).
-// LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
-static bool level_streams() { static const bool v = getenv("LUDWIG_BATCH_SERIAL") == nullptr; return v; }
 
 // ---- what the observers share (statistics, gradient fields, monitor, probes, surface statistics, slices) ----
 namespace {
@@ -1891,26 +1913,22 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         // the only reader of the parent is this level's interface pass: the wait for the parent's step goes where that pass goes
         // (launch_stream_collide) - unless the pass is hoisted below
         const bool need_parent = parent && (L->waited_parent != parent || L->waited_gen != parent->stepped_gen);
-        bool hoisting = false;
-        if (has_children && L->ev_consumed_set) {
-            static const char *he0 = getenv("LUDWIG_IFACE_HOIST");
-            hoisting = he0 ? atoi(he0) != 0 : 20 * (int64_t)L->n_blocks >= 9 * (int64_t)levels[lvl]->n_blocks;
-        }
+        // This level's own interface pass reads the parent and writes side buffers: it need not wait for the children to have
+        // read THIS level's buffers, only the step behind it must. Running it ahead (hoisted) shortens what is left to do after the
+        // wait. That pays when this level is not much smaller than its child - its step then comes in late for the child's next
+        // pair of sub-steps (3-level sphere, 1000 blocks under 1728: 25 us late per coarse step, 0.370 -> 0.337 ms) - and costs
+        // when the child dwarfs it and nothing was late (wing, 1728 under 5256: 0.848 -> 0.883 ms of added contention).
+        // LUDWIG_IFACE_HOIST=0 / 1 overrides the size rule.
+        const bool wait_children = has_children && L->ev_consumed_set;
+        const bool hoist = wait_children && (env::iface_hoist() >= 0 ? env::iface_hoist() != 0
+                                                                     : 20 * (int64_t)L->n_blocks >= 9 * (int64_t)levels[lvl]->n_blocks);
         if (need_parent) {
-            // handed to launch_stream_collide, which waits right before the interface pass
-            if (hoisting) LW_HIP(hipStreamWaitEvent(L->stream, parent->ev_stepped, 0));
+            // a hoisted pass needs the parent now; otherwise the wait is handed to launch_stream_collide, which waits right before the pass
+            if (hoist) LW_HIP(hipStreamWaitEvent(L->stream, parent->ev_stepped, 0));
             else L->parent_wait = parent->ev_stepped;
             L->waited_parent = parent; L->waited_gen = parent->stepped_gen;
         }
-        if (has_children && L->ev_consumed_set) {
-            // This level's own interface pass reads the parent and writes side buffers: it need not wait for the children to have
-            // read THIS level's buffers, only the step behind it must. Running it ahead shortens what is left to do after the wait.
-            // That pays when this level is not much smaller than its child - its step then comes in late for the child's next
-            // pair of sub-steps (3-level sphere, 1000 blocks under 1728: 25 us late per coarse step, 0.370 -> 0.337 ms) - and costs
-            // when the child dwarfs it and nothing was late (wing, 1728 under 5256: 0.848 -> 0.883 ms of added contention).
-            // LUDWIG_IFACE_HOIST=0 / 1 overrides the size rule.
-            static const char *he = getenv("LUDWIG_IFACE_HOIST");
-            const bool hoist = he ? atoi(he) != 0 : 20 * (int64_t)L->n_blocks >= 9 * (int64_t)levels[lvl]->n_blocks;
+        if (wait_children) {
             if (hoist && (rc = interface_prepass(L, parent, t_sub, parent_tau, temporal_weight, fl))) return rc;
             LW_HIP(hipStreamWaitEvent(L->stream, L->ev_consumed, 0));
         }
@@ -1918,7 +1936,7 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
     if (has_children && fl->use_temporal_interp && L->has_temporal)
         if ((rc = save_old_impl(L, t_sub, true))) return rc;      // rho's part rides in the step's launch where it can
     if ((rc = ludwig_step(L, parent, t_sub, u_vel, parent_tau, temporal_weight, fl))) return rc;
-    static const bool parent_side = getenv("LUDWIG_CHILD_SIDE_IFACE") == nullptr;      // LUDWIG_CHILD_SIDE_IFACE=1: round 2's placement
+    const bool parent_side = !env::child_side_iface();
     if (concurrent && parent && parent_side && (t_sub & 1) && L->ev_pair_done[0]) {
         // this level has read the last of set (t_sub >> 1) & 1 of its interface values: the parent's stream may overwrite it
         const int set = (int)((t_sub >> 1) & 1);
@@ -1968,12 +1986,26 @@ int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, 
     return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr);
 }
 
+// Level streams. The reference steps its levels strictly one after the other (src/solver_control.jl:21-143), and every launch
+// of a small level leaves most of the 256 CUs idle. The data dependencies are weaker than the call order: coupling is one-way,
+// coarse -> fine, and a child reads its parent's buffers only in its interface pass (k_interface_sources / _links, once per
+// pair of sub-steps). So each level gets a HIP stream of its own and two events:
+//   * a child's sub-step waits for its parent's step (parent->ev_stepped) before it interpolates from it;
+//   * a parent's NEXT step - which overwrites the buffer holding its old state, rho and rho_old - waits until the child's
+//     interface pass has read them (ev_consumed, recorded on the child's stream right after that pass).
+// Launches are still issued in the reference's order; the GPU then runs level 1's step t + 1 under the finer levels' sub-steps
+// of step t, and a middle level's second sub-step under its children's first pair. Same kernels, same inputs: same bits.
+// The finest level is the critical chain (2^(n-1) sub-steps per coarse step): its stream gets the highest priority, the others the
+// lowest, so the coarser levels only fill what it leaves free. Measured on one box, alternating (profiles/
+// r02_level_streams_with_priorities_ab_one_box.txt): 3-level sphere 0.419 -> 0.393 ms per coarse step, real wing 1.011 -> 0.949,
+// 4-level sphere 1.72 -> 1.52; without the priorities 0.402 / 0.982 / 1.58 (and on another box the 4-level case got slower).
+// LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
 static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                       const LudwigStepFlags *flags, const LudwigBatchSamplers *s)
 {
     LudwigProbes *probes = s ? s->probes : nullptr;
     LudwigSurfaceStats *surface = s ? s->surface : nullptr;
-    const bool concurrent = n_levels > 1 && level_streams();
+    const bool concurrent = n_levels > 1 && !env::batch_serial();
     hipStream_t user_stream = levels[0]->stream;
     if (concurrent) {
         LW_HIP(hipSetDevice(levels[0]->device));
@@ -1982,8 +2014,7 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         //    batch never finds a level with a stream but no events. The levels keep the caller's stream until all of it exists.
         int pr_least = 0, pr_greatest = 0;
         LW_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-        const char *pe = getenv("LUDWIG_LEVEL_STREAM_PRIORITY");
-        const bool use_pr = !pe || atoi(pe) != 0;
+        const int pr_mode = env::level_stream_priority();
         hipError_t e = hipSuccess;
         for (int i = 0; i < n_levels && e == hipSuccess; ++i) {
             LudwigLevel *L = levels[i];
@@ -1992,8 +2023,8 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
             // coarser levels fill what it leaves free (graded priorities: no better)
             // LUDWIG_LEVEL_STREAM_PRIORITY=2: graded - the finest level highest, its parent (whose stream carries the finest level's interface
             // pass since round 3) one below, the rest lowest
-            int pr = !use_pr ? pr_least : (i == n_levels - 1 ? pr_greatest : pr_least);
-            if (pe && atoi(pe) == 2) pr = std::min(pr_least, pr_greatest + (n_levels - 1 - i));
+            int pr = pr_mode == 0 ? pr_least : (i == n_levels - 1 ? pr_greatest : pr_least);
+            if (pr_mode == 2) pr = std::min(pr_least, pr_greatest + (n_levels - 1 - i));
             if (!L->own_stream) e = hipStreamCreateWithPriority(&L->own_stream, hipStreamNonBlocking, pr);
             if (e == hipSuccess && !L->ev_stepped) e = hipEventCreateWithFlags(&L->ev_stepped, hipEventDisableTiming);
             if (e == hipSuccess && !L->ev_consumed) e = hipEventCreateWithFlags(&L->ev_consumed, hipEventDisableTiming);
@@ -3011,10 +3042,10 @@ RcclApi *rccl()
     tried = true;
     std::string loaded;
     dl_iterate_phdr(find_loaded_rccl, &loaded);
-    const char *env = getenv("LUDWIG_RCCL_LIB");
+    const char *env_path = env::rccl_lib();
     std::vector<std::string> names;
     if (!loaded.empty()) names.push_back(loaded);
-    if (env) names.push_back(env);
+    if (env_path) names.push_back(env_path);
     names.push_back("librccl.so.1");
     names.push_back("librccl.so");
     for (const std::string &n : names) {
@@ -3257,7 +3288,7 @@ int ludwig_halo_plan_create(LudwigLevel *L, LudwigComm *comm, const LudwigHaloPl
     if (!P) return fail(LUDWIG_ERR_ALLOC, "host allocation failed");
     P->L = L; P->comm = comm;
     P->peers.assign(desc->peer_ranks, desc->peer_ranks + desc->n_peers);
-    P->self_via_rccl = comm && getenv("LUDWIG_HALO_SELF_VIA_RCCL") != nullptr;
+    P->self_via_rccl = comm && env::halo_self_via_rccl();
     int rc = LUDWIG_OK;
     auto upload = [&](const auto &v, auto **dst) -> int {
         *dst = nullptr;
@@ -3381,7 +3412,7 @@ int ludwig_halo_exchange(LudwigHaloPlan *P, int32_t n, const int32_t *groups, co
 {
     if (!P || n < 0 || n > LUDWIG_HALO_GROUPS || (n > 0 && (!groups || !fields))) return fail(LUDWIG_ERR_INVALID, "bad argument");
     // LUDWIG_HALO_TRACE=1: host microseconds of the three parts of this call on stderr (what an exchange costs the host)
-    static const bool trace = getenv("LUDWIG_HALO_TRACE") != nullptr;
+    const bool trace = env::halo_trace();
     const double h0 = trace ? host_now_us() : 0.0;
     double h1 = 0.0, h2 = 0.0;
     LudwigLevel *L = P->L;

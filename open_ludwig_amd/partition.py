@@ -746,7 +746,8 @@ class DistributedLevelRunner:
         self.ex.join()
 
     def flush(self) -> None:
-        """kept for callers of the round-2 schedule (the exchange used to be enqueued one launch late): nothing to do"""
+        """nothing to do since step() enqueues its own exchange (it used to be enqueued one launch late); bench.py still calls this
+        before its barrier, so the name stays"""
 
     def synchronize(self) -> None:
         self.torch.cuda.synchronize(self.dev)

@@ -199,6 +199,30 @@ def test_native_batch_driver_equals_python_recursion(gpu):
         d.close()
 
 
+def test_interface_values_do_not_outlive_a_change_of_placement(gpu):
+    """The same device levels stepped under one placement of the coarse->fine interface pass after the other: a native batch of 2
+    coarse steps (level streams: the pass on the parent's stream, the pair records valid at its end), 1 coarse step call by call from
+    Python in the reference's recursion order (one stream: the pass on the child's side, with the look-ahead), a native batch of 2
+    more. Every placement keys its values by the one record type (IfaceKey); a record that survives the change when it should not, or
+    is dropped when it should hold, shows as a mismatch on level 2 or 3. Bit for bit the oracle after the second and the third phase."""
+    grids, params = cases.tunnel_with_sphere((6, 4, 4), levels=3, wall_model=True, tau=0.5003)
+    dev = [adapt(g, 0) for g in grids]
+    u = np.float32(0.05)
+    for t_start, n, native in ((1, 2, True), (3, 1, False), (4, 2, True)):
+        execute_timestep_batch(dev, t_start, n, u, params, native=native)
+        oracle.execute_timestep_batch(grids, t_start, n, u, params)
+        if t_start == 1:
+            continue
+        done = t_start + n - 1
+        for i, (g, d) in enumerate(zip(grids, dev)):
+            fn, vn = oracle.newest_buffers(i, done)
+            for name in (fn, vn, "rho"):
+                assert np.isfinite(getattr(g, name)).all(), f"oracle produced non-finite {name}"
+                assert np.array_equal(d.download(name), getattr(g, name)), f"after coarse step {done}: level {i + 1} {name} differs"
+    for d in dev:
+        d.close()
+
+
 def test_tunnel_batches_match_single_batch(gpu):
     """execute_timestep_batch! called in batches of 2 (async_depth) must give what one long batch gives."""
     grids, params = cases.tunnel_with_sphere((5, 3, 3), levels=2)

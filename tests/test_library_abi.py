@@ -179,3 +179,30 @@ def test_multi_gpu_entry_points_reject_bad_arguments_without_a_device():
     assert lib.ludwig_level_field_layout(None, 0, None, None, None) == -1
     lib.ludwig_comm_destroy(None)
     lib.ludwig_halo_plan_destroy(None)                                                               # destroying nothing is a no-op
+
+
+def test_side_buffer_set_is_made_completely_or_not_at_all(tmp_path):
+    """The second set of a level's interface side buffers (four buffers, two events) goes through csrc/all_or_nothing.hpp; the
+    stand-alone program fails the allocator at each of the six positions in turn and finds every slot null and nothing live after each.
+    Built with the address and undefined-behaviour sanitizers (runtime linked statically, so the program needs nothing around it): a
+    double free or a use of a released pointer ends the program with an error too."""
+    exe = str(tmp_path / "all_or_nothing_check")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-static-libasan", "-static-libubsan", "-I" + build.CSRC, os.path.join(ROOT, "tests", "all_or_nothing_check.cpp"),
+                    "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "all-or-nothing OK" in out.stdout, out.stdout + out.stderr
+
+
+def test_switch_table_lists_the_switches_the_library_reads():
+    """Every getenv of ludwig_hip.hip sits in its `namespace env` block, and INTEGRATION.md's table of the library's switches names
+    exactly the variables that block reads."""
+    src = open(os.path.join(build.CSRC, "ludwig_hip.hip")).read()
+    block = src[src.index("namespace env {"):src.index("}  // namespace env")]
+    assert "getenv(" not in src.replace(block, ""), "a getenv outside the switches block"
+    in_code = set(re.findall(r'"(LUDWIG_[A-Z_]+)"', block))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("| switch of `libludwig_hip.so` |"):]
+    table = table[:table.index("\n\n")]
+    in_doc = set(re.findall(r"`(LUDWIG_[A-Z_]+)", "\n".join(row.split("|")[1] for row in table.splitlines()[2:])))
+    assert in_code and in_code == in_doc, (sorted(in_code - in_doc), sorted(in_doc - in_code))
