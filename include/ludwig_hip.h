@@ -426,6 +426,39 @@ typedef struct LudwigBatchSamplers {
 int  ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                            float u_curr, const LudwigStepFlags *flags, const LudwigBatchSamplers *s);
 
+/* ---- force series: the integrated surface loads per sampled coarse step (no reference counterpart) ----
+ * A force-series set lives on one level (the finest). Triangle i has the cell, wall distance and normal of a surface set (above), an
+ * area area[i] and a moment arm arm[a * n_tri + i] (a = 0..2: centre + offset - moment centre, formed by the caller in float32).
+ * A sample evaluates per triangle, in float32 without contraction: p, tau as ludwig_map_surface_stresses does for the cell (zeros
+ * without one; sp->tau, pressure_scale, stress_scale, the other fields of sp are ignored), dFp_j = ((-p) n_j) A, dFv_j = tau_j A,
+ * dF = dFp + dFv, dM = (ry dF_z - rz dF_y, rz dF_x - rx dF_z, rx dF_y - ry dF_x), covered = |p| > 1e-10f. The nine values Fp(3), Fv(3),
+ * M(3) are widened to float64 and added in one fixed balanced tree over the triangles in the caller's order: adjacent pairs halved,
+ * +0.0 appended wherever a length is odd, until one value is left (the tree over the triangles zero-padded to the next power of two).
+ * The count of covered triangles is an integer sum. No atomics: a record depends on nothing but the state and the triangle order.
+ * One record = 9 float64 + 1 int64, kept in a device ring of `capacity` records until it is downloaded.
+ * Creating the set makes the level store rho after every step (see ludwig_level_set_rho_store). n_tri = 0 is allowed (a rank that
+ * owns none of the triangles): its records are zeros and nothing is launched. The level may hold at most 2^31 / 512 blocks. */
+typedef struct LudwigForceSeries LudwigForceSeries;   /* opaque */
+int  ludwig_force_series_create(LudwigLevel *level, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *wall_dist,
+                                const float *normals, const float *area, const float *arm, const LudwigSurfaceParams *sp,
+                                int32_t capacity, LudwigForceSeries **out);
+/* frees the set, not the level; it does not touch the level, so it may come before or after its destruction */
+void ludwig_force_series_destroy(LudwigForceSeries *set);
+/* one record of the state sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd; rho as a download would return it), filed
+ * under coarse step t_coarse; queued on the level's stream, no host synchronisation. LUDWIG_ERR_STATE when the ring is full. */
+int  ludwig_force_series_sample(LudwigForceSeries *set, int64_t t_sub, int64_t t_coarse);
+/* the n records taken since the last download, oldest first: sums[9 i + 0..8], covered[i], steps[i]. Synchronizes the level's stream,
+ * then empties the ring. LUDWIG_ERR_INVALID when n > max_samples. */
+int  ludwig_force_series_download(LudwigForceSeries *set, double *sums, int64_t *covered, int64_t *steps, int32_t max_samples,
+                                  int32_t *n_samples);
+/* ludwig_execute_timestep_batch_sampled (s may be NULL) with the force series fs sampled inside the batch: at coarse steps
+ * start_step + k interval (k >= 0), on its level's own stream, right after that level's last sub-step of the coarse step. fs = NULL is
+ * ludwig_execute_timestep_batch_sampled itself. Fails before stepping anything with LUDWIG_ERR_STATE if the batch's records would
+ * overflow the free ring, with LUDWIG_ERR_INVALID if the set's level is not in `levels` or interval < 1. */
+int  ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
+                                         float u_curr, const LudwigStepFlags *flags, const LudwigBatchSamplers *s,
+                                         LudwigForceSeries *fs, int64_t start_step, int32_t interval);
+
 /* ---- slices: planar grids of points sampled after a coarse step (no reference counterpart) ----
  * A slice set is made over a level array. Point p with valid[p] != 0 lives on level level_index[p] (0-based) and has the probes'
  * stencil: 8 corners c = dx + 2 dy + 4 dz (reference block index blocks[8p + c], cell cells[8p + c] = x + 8 y + 64 z), corner 0 the

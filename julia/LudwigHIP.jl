@@ -225,6 +225,31 @@ function surface_stats_download!(sums::Matrix{Float64}, s::Ptr{Cvoid})
     return Int(n[])
 end
 
+# force series (no reference counterpart): the nine integrated load sums Fp(3), Fv(3), M(3) and the coverage count per sampled coarse step
+"""a force-series set on `grid`: per triangle its nearest fluid cell (0-based reference block index, -1 = none; cell x + 8y + 64z), wall
+distance in lattice units, normal (3 x n), area and moment arm (n x 3: centre + offset - moment centre in Float32); tau and the two
+scales from `sp`; a ring of `capacity` records. Free it with `force_series_destroy`."""
+function force_series_create(grid::DeviceLevel, blocks::Vector{Int32}, cells::Vector{Int32}, wall_dist::Vector{Float32},
+                             normals::Matrix{Float32}, area::Vector{Float32}, arm::Matrix{Float32}, sp::SurfaceParams, capacity::Integer)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve blocks cells wall_dist normals area arm check(ccall((:ludwig_force_series_create, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ref{SurfaceParams}, Int32,
+         Ref{Ptr{Cvoid}}),
+        grid.handle, Int32(length(blocks)), blocks, cells, wall_dist, normals, area, arm, sp, Int32(capacity), out))
+    return out[]
+end
+force_series_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_force_series_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""one record of the state the level's sub-step `timestep` wrote, filed under coarse step `t_coarse` (queued on the level's stream)"""
+force_series_sample!(s::Ptr{Cvoid}, timestep::Integer, t_coarse::Integer) =
+    check(ccall((:ludwig_force_series_sample, LIB), Cint, (Ptr{Cvoid}, Int64, Int64), s, Int64(timestep), Int64(t_coarse)))
+"""the records taken since the last download into sums (9 x capacity), covered and steps (capacity); returns how many; empties the ring"""
+function force_series_download!(sums::Matrix{Float64}, covered::Vector{Int64}, steps::Vector{Int64}, s::Ptr{Cvoid})
+    n = Ref{Int32}(0)
+    GC.@preserve sums covered steps check(ccall((:ludwig_force_series_download, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int32, Ref{Int32}), s, sums, covered, steps, Int32(length(steps)), n))
+    return Int(n[])
+end
+
 # wall diagnostics (no reference counterpart: Y_PLUS_TARGET is read and never used): the wall model's y+, u_tau and modelled shear
 """LudwigWallCensus of include/ludwig_hip.h: counts, the Float32 bits of the least / greatest y+, 194 bins (eight per octave)"""
 struct WallCensus
@@ -410,6 +435,18 @@ function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch
     GC.@preserve handles check(ccall((:ludwig_execute_timestep_batch_sampled, LIB), Cint,
                                      (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ref{BatchSamplers}),
                                      handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, s))
+end
+
+"""execute_timestep_batch! with the sets of `s` and the force series `forces` (at coarse steps start_step + k interval) sampled inside
+the batch; `s = nothing` is the C call's `s = NULL`: the force series alone"""
+function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                                 s::Union{BatchSamplers,Nothing}, forces::Ptr{Cvoid}, start_step::Integer, interval::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    sp = s === nothing ? C_NULL : Ref(s)
+    GC.@preserve handles sp check(ccall((:ludwig_execute_timestep_batch_loads, LIB), Cint,
+                                        (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{BatchSamplers}, Ptr{Cvoid}, Int64, Int32),
+                                        handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, sp, forces,
+                                        Int64(start_step), Int32(interval)))
 end
 
 end # module

@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = [
     "ludwig_level_monitor",
     "ludwig_level_wall_census", "ludwig_wall_surface_create", "ludwig_wall_surface_destroy", "ludwig_wall_surface_compute",
     "ludwig_wall_surface_download",
+    "ludwig_force_series_create", "ludwig_force_series_destroy", "ludwig_force_series_sample", "ludwig_force_series_download",
+    "ludwig_execute_timestep_batch_loads",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -221,6 +223,12 @@ def load() -> C.CDLL:
         "ludwig_wall_surface_destroy": (None, [vp]),
         "ludwig_wall_surface_compute": (C.c_int, [vp, i64]),
         "ludwig_wall_surface_download": (C.c_int, [vp, vp, C.c_size_t]),
+        "ludwig_force_series_create": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(SurfaceParams), i32, C.POINTER(vp)]),
+        "ludwig_force_series_destroy": (None, [vp]),
+        "ludwig_force_series_sample": (C.c_int, [vp, i64, i64]),
+        "ludwig_force_series_download": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(C.c_int32)]),
+        "ludwig_execute_timestep_batch_loads": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers),
+                                                          vp, i64, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

@@ -16,6 +16,7 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
+from . import force_series as fseries_mod
 from . import forces as forces_mod
 from . import monitor as monitor_mod
 from . import probes as probes_mod
@@ -41,8 +42,8 @@ class DiagRow:
 
 
 def _close_observers(st) -> None:
-    """close a stepper's probe, surface, slice and wall-surface sets (each may be None)"""
-    for name in ("probes", "surface", "slices", "wall_surface"):
+    """close a stepper's probe, surface, slice, wall-surface and force-series sets (each may be None)"""
+    for name in ("probes", "surface", "slices", "wall_surface", "forces"):
         obs = getattr(st, name)
         if obs is not None:
             obs.close()
@@ -52,31 +53,40 @@ def _close_observers(st) -> None:
 class HipStepper:
     """grids on one MI355X behind libludwig_hip.so"""
 
-    def __init__(self, host_grids, device: int = 0):
+    def __init__(self, host_grids, device: int = 0, upload_state: bool = False):
+        """upload_state: start from the host grids' own state arrays instead of the rest state run_case starts from"""
         self.host = host_grids
-        self.dev = [adapt(g, device, upload_state=False) for g in host_grids]
-        for d in self.dev:
-            d.init_equilibrium()               # src/main.jl:126-135 (every state array: nothing of the host's to upload first)
+        self.dev = [adapt(g, device, upload_state=upload_state) for g in host_grids]
+        if not upload_state:
+            for d in self.dev:
+                d.init_equilibrium()           # src/main.jl:126-135 (every state array: nothing of the host's to upload first)
         self.probes = None                     # probes_setup
         self._series = None
         self.surface = None                    # surface_stats_setup
         self.slices = None                     # slices_setup
         self.wall_surface = None               # wall_diagnostics_setup
+        self.forces = None                     # force_series_setup
+        self._fseries = None
+        self._surface_plan = None              # (mesh, params, plan) of the surface statistics, shared with the force series
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
-        if self.probes is None:
+        if self.probes is None and self.forces is None:
             execute_timestep_batch(self.dev, t_start, n, u_curr, params, surface=self.surface)
             return
-        # sampled inside the C batch, the ring drained after it; a batch with more samples than the ring holds is cut where it fills
-        # (the same inlet speed: the same steps, the same bits)
-        P, t, end = self.probes, t_start, t_start + n - 1
+        # sampled inside the C batch, the rings drained after it; a batch with more samples than a ring holds is cut where the first one
+        # fills (the same inlet speed: the same steps, the same bits)
+        P, F, t, end = self.probes, self.forces, t_start, t_start + n - 1
         while t <= end:
             seg_end = end
-            if probes_mod.samples_in(t, end, P.start_step, P.interval) > P.capacity:
-                first = P.start_step + max(0, -(-(t - P.start_step) // P.interval)) * P.interval
-                seg_end = first + (P.capacity - 1) * P.interval
-            execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P, surface=self.surface)
-            self._series.append(*P.download())
+            if P is not None:
+                seg_end = min(seg_end, fseries_mod.segment_end(t, end, P.start_step, P.interval, P.capacity))
+            if F is not None:
+                seg_end = min(seg_end, fseries_mod.segment_end(t, end, F.start_step, F.interval, F.capacity))
+            execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P, surface=self.surface, forces=F)
+            if P is not None:
+                self._series.append(*P.download())
+            if F is not None:
+                self._fseries.append(*F.download())
             t = seg_end + 1
 
     # -- probes (no reference counterpart) --
@@ -100,11 +110,38 @@ class HipStepper:
         if self.surface is not None:
             self.surface.close()
         self.surface = surface_mod.DeviceSurfaceStats(plan, self.dev[fin], fin, self.host[fin].tau, params, max(int(start_step), 1), interval)
+        self._surface_plan = (mesh, params, plan)
         return plan
 
     def surface_stats_sums(self):
         """(sums [7, n_tri] Float64, samples) of the surface set"""
         return self.surface.download()
+
+    # -- force series (no reference counterpart) --
+    def force_series_setup(self, mesh, params, start_step: int = 1, interval: int = 1, capacity: int = 64):
+        """record the integrated loads of `mesh` on the finest level at coarse steps start_step + k interval, inside every batch; reuses
+        the surface statistics' plan when that observer was set up with this very mesh and params object (else it plans anew); returns
+        the surface_stats.SurfacePlan"""
+        fin = len(self.host) - 1
+        cached = self._surface_plan
+        if cached is not None and cached[0] is mesh and cached[1] is params:
+            plan = cached[2]
+        else:
+            plan = surface_mod.plan_surface(mesh, self.host[fin], params)
+        if self.forces is not None:
+            self.forces.close()
+        self.forces = fseries_mod.from_mesh(mesh, plan, self.dev[fin], fin, self.host[fin].tau, params, max(int(start_step), 1), interval,
+                                            capacity)
+        self._fseries = fseries_mod.Series()
+        return plan
+
+    def force_series(self):
+        """(coarse steps [n] int64, sums [n, 9] Float64: Fp(3), Fv(3), M(3), covered [n] int64) of every record so far"""
+        return self._fseries.arrays()
+
+    def force_series_new(self):
+        """the same, of the records drained since the last force_series_new() only (what run_case writes after a batch)"""
+        return self._fseries.take_new()
 
     # -- slices (no reference counterpart) --
     def slices_setup(self, plans, start_step: int = 1, interval: int = 1) -> None:
@@ -254,6 +291,8 @@ class DistributedStepper:
         self.slices = None                     # this rank's slice set (None: it owns no base block of a valid point)
         self._wall_cfg = None                  # wall_diagnostics_setup: (plan, params)
         self.wall_surface = None               # this rank's wall-surface set (None: it holds no copy of the finest level)
+        self._forces_cfg = None                # force_series_setup: (mesh, plan, params, start_step, interval, capacity)
+        self.forces = None                     # this rank's force-series set (None: it holds no copy of the finest level)
 
     def _level_owner(self, level: int) -> np.ndarray:
         g = self.host[level]
@@ -331,12 +370,14 @@ class DistributedStepper:
             self._slices_create()
         if self._wall_cfg is not None:
             self._wall_surface_create()
+        if self._forces_cfg is not None:
+            self._forces_create()
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.runner is None:
             self._start(params)
         self.runner.params = params
-        P, S = self.probes, self.surface
+        P, S, F = self.probes, self.surface, self.forces
         fin = len(self.host) - 1
         for t in range(t_start, t_start + n):
             self.runner.step(t, u_curr)
@@ -351,10 +392,20 @@ class DistributedStepper:
                     self.runner._join(lvl)     # the level's ghosts (peer corners) are in place
                     P.sample(lvl, stats_mod.t_sub_after(lvl, t))
                 self._probe_pending += 1
+            if F is not None and F.is_sample_step(t):
+                if self._force_pending == F.capacity:
+                    self._fseries.append(*F.download())
+                    self._force_pending = 0
+                self.runner._join(fin)
+                F.sample(stats_mod.t_sub_after(fin, t), t)
+                self._force_pending += 1
         self.runner.synchronize()
         if P is not None:
             self._series.append(*P.download())
             self._probe_pending = 0
+        if F is not None:
+            self._fseries.append(*F.download())
+            self._force_pending = 0
 
     # -- probes: each rank samples the probes whose base cell it owns; the series is gathered to rank 0 in probe order --
     def probes_setup(self, plan, start_step: int = 1, interval: int = 1, capacity: int = 64) -> None:
@@ -494,6 +545,65 @@ class DistributedStepper:
                 sel, sums, n = part
                 out[:, sel] = sums
         return out, n
+
+    # -- force series: each rank reduces the triangles whose cell it owns (the rule of _triangle_map) in global triangle order; a
+    # triangle without a cell adds signed zeros only and belongs to nobody. The ranks' records are added in rank order in Float64 on
+    # rank 0: other trees than one device's, so the sums agree to Float64 rounding, not bit for bit; the coverage count is exact --
+    def force_series_setup(self, mesh, params, start_step: int = 1, interval: int = 1, capacity: int = 64):
+        """returns the global surface_stats.SurfacePlan (the surface statistics' when that observer was set up first); the rank's set
+        is made with the first batch (or now, after it)"""
+        if int(interval) < 1:
+            raise ValueError(f"force series: interval {interval} < 1")
+        fin = len(self.host) - 1
+        plan = self._surface_cfg[0] if self._surface_cfg is not None else surface_mod.plan_surface(mesh, self.host[fin], params)
+        if self.forces is not None:
+            self.forces.close()
+            self.forces = None
+        self._forces_cfg = (mesh, plan, params, max(int(start_step), 1), int(interval), int(capacity))
+        self._fseries_total = fseries_mod.Series()                   # rank 0: the gathered history
+        if self.runner is not None:
+            self._forces_create()
+        return plan
+
+    def _forces_create(self) -> None:
+        mesh, plan, params, start, interval, capacity = self._forces_cfg
+        fin = len(self.host) - 1
+        owner = self._level_owner(fin)
+        self._forces_sel = np.flatnonzero(plan.found & (owner[np.maximum(plan.blocks, 0)] == self.rank))
+        lv = self.runner.levels[fin]
+        if lv is None:
+            assert self._forces_sel.size == 0
+            return
+        local = plan.subset(self._forces_sel)
+        local.blocks = self._owned_g2l(fin)[local.blocks].astype(np.int32)
+        assert (local.blocks >= 0).all()
+        self.forces = fseries_mod.from_mesh(mesh, local, lv, fin, self.host[fin].tau, params, start, interval, capacity,
+                                            select=self._forces_sel)
+        self._fseries = fseries_mod.Series()
+        self._force_pending = 0
+
+    def force_series_new(self):
+        """(coarse steps [n] int64, sums [n, 9] Float64, covered [n] int64) of the records drained since the last force_series_new(),
+        on rank 0 (None elsewhere); collective. Only these records cross the ranks; rank 0 keeps the history."""
+        parts = self._gather(self._fseries.take_new() if self.forces is not None else None)
+        if parts is None:
+            return None
+        got = [p for p in parts if p is not None]
+        if not got:
+            return np.zeros(0, np.int64), np.zeros((0, 9), np.float64), np.zeros(0, np.int64)
+        steps = got[0][0]
+        sums = np.zeros((steps.size, 9), dtype=np.float64)
+        cov = np.zeros(steps.size, dtype=np.int64)
+        for st, s9, c in got:                  # rank order
+            assert np.array_equal(st, steps), "ranks sampled different steps"
+            sums = sums + s9
+            cov = cov + c
+        self._fseries_total.append(steps, sums, cov)
+        return steps, sums, cov
+
+    def force_series(self):
+        """the same of every record so far, on rank 0 (None elsewhere); collective (it gathers what is new first)"""
+        return None if self.force_series_new() is None else self._fseries_total.arrays()
 
     # -- wall diagnostics: every rank takes the census of its owned blocks (integer records: their sum is one device's) and evaluates the
     # triangles whose cell it owns (the rule of _triangle_map; the model's stencil is the cell itself: no ghost is read) --
@@ -768,7 +878,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     wall shear into wall_forces.csv; on flow output steps surface_%06d.vtu gains wall_diagnostics.finalize's arrays. Device only: a
     stepper without wall_diagnostics_setup raises.
     "EddyViscosityRatio" in cfg.output_fields adds nu_t / nu of the step's own WALE model (subgrid.py) to the flow file, Float32, from the
-    file's velocity buffer. With cfg.statistics_subgrid the model's sums are sampled at exactly the flow statistics' sampled steps (same
+    file's velocity buffer.
+    With cfg.forces_series_enabled (advanced.forces.series), the finest level's integrated loads are reduced on the device inside the
+    batches at the coarse steps start_step + k interval (force_series.py) and forces_series.csv gains one row per sampled step after
+    every batch, with that batch's inlet speed; `log` gets the mean and rms of Cd, Cl, Cmy over the rows after ramp_steps at the end. No
+    batch is cut for it beyond the ring's capacity. Device only: a stepper without force_series_setup raises.
+    With cfg.statistics_subgrid the model's sums are sampled at exactly the flow statistics' sampled steps (same
     reset) and flow_mean_%06d.vtu gains subgrid.MEAN_ARRAYS after its own arrays. Device only: a stepper without subgrid_fields raises."""
     import time as _time
     from . import output as out_mod
@@ -796,6 +911,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         key = "basic.simulation.output_fields.eddy_viscosity" if eddy_on else "advanced.statistics.subgrid"
         raise RuntimeError(f"{key} is set, but {type(st).__name__} offers no subgrid_fields: the subgrid model's eddy viscosity is "
                            "evaluated on the device only")
+    fseries_on = bool(cfg.forces_series_enabled)
+    if fseries_on and not hasattr(st, "force_series_setup"):
+        if hasattr(st, "close"):
+            st.close()
+        raise RuntimeError(f"advanced.forces.series is enabled, but {type(st).__name__} offers no force_series_setup: the force series "
+                           "is reduced on the device only")
     total_steps = steps if steps is not None else cfg.steps
     rows: List[DiagRow] = []
     batch = cfg.async_depth
@@ -818,6 +939,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             surf_host = surface_mod.HostSurfaceStats(splan, grids[fin].tau, params, surf_start, surf_interval)
     if wall_on:
         st.wall_diagnostics_setup(mesh, params, splan if surf_on else None)      # one plan for both surface observers
+    if fseries_on:                       # after the surface statistics: one plan for both
+        st.force_series_setup(mesh, params, cfg.forces_series_start_step, cfg.forces_series_interval, max(batch, 1))
     wall_band = cfg.wall_diagnostics_band
     wall_taken = [None, None]            # the coarse step of the last wall-surface values, and the values
     if writing:
@@ -829,6 +952,9 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         if surf_on:
             with open(os.path.join(out_dir, "forces_mean.csv"), "w") as io:
                 io.write(surface_mod.FORCES_MEAN_CSV_HEADER + "\n")
+        if fseries_on:
+            with open(os.path.join(out_dir, "forces_series.csv"), "w") as io:
+                io.write(fseries_mod.csv_header() + "\n")
         if slices_on:
             slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
         if probes_on:
@@ -899,6 +1025,24 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             with open(os.path.join(out_dir, "probes.csv"), "a") as io:
                 io.writelines(r + "\n" for r in new_rows)
             probes_written[0] = p_steps.size
+    fseries_coeffs = []                  # (Cd, Cl, Cmy) of the rows after the ramp
+
+    def flush_force_series(u_batch):
+        """append the records the batch that has just ended drained - only those leave the stepper - to forces_series.csv (collective in a
+        distributed run)"""
+        series = st.force_series_new()
+        if series is None:
+            return
+        f_steps, f_sums, f_cov = series
+        lines = []
+        for i in range(f_steps.size):
+            fr_i = forces_mod.finish_forces(f_sums[i], int(f_cov[i]), params, cfg.symmetric_analysis)
+            lines.append(fseries_mod.csv_row(int(f_steps[i]), float(f_steps[i]) * params.time_scale, fr_i, u_batch))
+            if f_steps[i] > cfg.ramp_steps:
+                fseries_coeffs.append((fr_i.Cd, fr_i.Cl, fr_i.Cmy))
+        if writing and lines:
+            with open(os.path.join(out_dir, "forces_series.csv"), "a") as io:
+                io.writelines(l + "\n" for l in lines)
     t0 = last_diag = _time.time()
     total_cells = sum(g.n_blocks * 512 for g in grids)
     fr = None
@@ -948,6 +1092,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)
             else:
                 st.batch(t, actual, u_curr, sp)
+            if fseries_on:
+                flush_force_series(u_curr)
             monitored = wall_done = False
             if batch_end % cfg.diag_freq < actual or batch_end == total_steps:
                 diag_step = (batch_end // cfg.diag_freq) * cfg.diag_freq
@@ -1053,6 +1199,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             t = batch_end + 1
         if probes_on:
             flush_probes()
+        if fseries_on and log:
+            for name, k in (("Cd", 0), ("Cl", 1), ("Cmy", 2)):
+                m, r = fseries_mod.mean_rms(c[k] for c in fseries_coeffs)
+                log(f"force series {name}: mean {m:.6f} rms {r:.6f} over {len(fseries_coeffs)} rows after step {cfg.ramp_steps}")
     finally:
         if hasattr(st, "close"):
             st.close()

@@ -1659,6 +1659,123 @@ __global__ __launch_bounds__(256) void k_monitor_combine(MonitorRecord *__restri
     out[blockIdx.x] = o;
 }
 
+// ---- force series (ludwig_force_series_*; the nine sums of integrate_forces_kernel!, reference src/forces/surface.jl:282-366, per
+// sampled coarse step) ----
+// Triangle i reads cell[i] (internal block * 512 + cell, -1: none) and rec = [8][n] floats: wall distance, normal x, y, z, area, arm x,
+// y, z. Per triangle, float32 with -ffp-contract=off: p, tau from wall_stress (zeros without a cell), dFp_j = ((-p) n_j) A,
+// dFv_j = tau_j A, dF = dFp + dFv, dM = arm x dF in the operand order of forces.partial_force_sums; covered = |p| > 1e-10f. The nine
+// values are widened to double and summed in ONE balanced tree over the triangles in the caller's order: adjacent pairs halved, +0.0
+// where a length is odd, and no addition once one value is left - the tree over the triangles padded with +0.0 to the next power of
+// two (forces.tree_sum_f64). A level of the tree that joins nodes of `half` elements adds iff count > half: below that the right-hand
+// node is padding and the halving has already ended, so a total of -0.0 keeps its sign.
+// k_force_chunks: one workgroup per 512 consecutive triangles, two per lane (tree level 1), an xor-butterfly over the wave, the four
+// waves through LDS; one ForceRecord per chunk with plain stores. k_force_combine: 512 records -> 1 per workgroup and launch, until
+// one is left; missing records are +0.0. No atomics.
+struct ForceRecord {
+    double s[9];                   // Fp(3), Fv(3), M(3)
+    long long covered;
+};
+constexpr int FORCE_REC_ROWS = 8;
+// the butterfly over a wave whose lanes each hold the sum of 2 elements of `count` (whole tree): lane 0 of each aligned group of 2^k
+// lanes ends with the group's node; every lane takes part in every shuffle
+__device__ __forceinline__ double force_wave_sum(double x, int64_t count)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double q = __shfl_xor(x, o, 64);
+        if (count > 2 * o) x += q;
+    }
+    return x;
+}
+// the four wave nodes (128 elements each) of a workgroup -> its node
+__device__ __forceinline__ double force_join_waves(double p0, double p1, double p2, double p3, int64_t count)
+{
+    const double a = count > 128 ? p0 + p1 : p0, b = p2 + p3;
+    return count > 256 ? a + b : a;
+}
+__device__ __forceinline__ bool force_contributions(float c[9], int64_t i, int64_t n, const int32_t *__restrict__ cell,
+                                                    const float *__restrict__ rec, const float *__restrict__ rho,
+                                                    const float *__restrict__ vel, float tau, float pressure_scale, float stress_scale)
+{
+    const int32_t cc = cell[i];
+    const float nx = rec[n + i], ny = rec[2 * n + i], nz = rec[3 * n + i], A = rec[4 * n + i];
+    const float rx = rec[5 * n + i], ry = rec[6 * n + i], rz = rec[7 * n + i];
+    float p = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f;
+    if (cc >= 0) {
+        const int64_t b = cc >> 9, x = cc & 511;
+        const float *v = vel + b * (3 * CELLS) + x;
+        wall_stress(rho[cc], v[0], v[CELLS], v[2 * CELLS], nx, ny, nz, rec[i], tau, pressure_scale, stress_scale, p, sx, sy, sz);
+    }
+    c[0] = ((-p) * nx) * A; c[1] = ((-p) * ny) * A; c[2] = ((-p) * nz) * A;
+    c[3] = sx * A; c[4] = sy * A; c[5] = sz * A;
+    const float fx = c[0] + c[3], fy = c[1] + c[4], fz = c[2] + c[5];
+    c[6] = ry * fz - rz * fy; c[7] = rz * fx - rx * fz; c[8] = rx * fy - ry * fx;
+    return fabsf(p) > 1.0e-10f;
+}
+
+__global__ __launch_bounds__(256) void k_force_chunks(ForceRecord *__restrict__ slab, const int32_t *__restrict__ cell,
+                                                      const float *__restrict__ rec, int n, const float *__restrict__ rho,
+                                                      const float *__restrict__ vel, float tau, float pressure_scale, float stress_scale)
+{
+    __shared__ double part[4][9];
+    __shared__ int cov[4];
+    const int t = (int)threadIdx.x;
+    const int64_t N = n, i = (int64_t)blockIdx.x * CELLS + 2 * t;
+    float c0[9], c1[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c0[k] = c1[k] = 0.0f;
+    bool k0 = false, k1 = false;
+    if (i < N) k0 = force_contributions(c0, i, N, cell, rec, rho, vel, tau, pressure_scale, stress_scale);
+    if (i + 1 < N) k1 = force_contributions(c1, i + 1, N, cell, rec, rho, vel, tau, pressure_scale, stress_scale);
+    const int n_cov = __popcll(__ballot(k0)) + __popcll(__ballot(k1));
+    double s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = force_wave_sum(N > 1 ? (double)c0[k] + (double)c1[k] : (double)c0[k], N);
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) part[t >> 6][k] = s[k];
+        cov[t >> 6] = n_cov;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    ForceRecord o;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], N);
+    o.covered = (long long)((cov[0] + cov[1]) + (cov[2] + cov[3]));
+    slab[blockIdx.x] = o;
+}
+
+__global__ __launch_bounds__(256) void k_force_combine(ForceRecord *__restrict__ out, const ForceRecord *__restrict__ in, int64_t n)
+{
+    __shared__ double part[4][9];
+    __shared__ long long cov[4];
+    const int t = (int)threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * CELLS + 2 * t;
+    ForceRecord a, b;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a.s[k] = b.s[k] = 0.0;
+    a.covered = b.covered = 0;
+    if (i < n) a = in[i];
+    if (i + 1 < n) b = in[i + 1];
+    a.covered += b.covered;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a.covered += __shfl_xor(a.covered, o, 64);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) a.s[k] = force_wave_sum(n > 1 ? a.s[k] + b.s[k] : a.s[k], n);
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) part[t >> 6][k] = a.s[k];
+        cov[t >> 6] = a.covered;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    ForceRecord o;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], n);
+    o.covered = (cov[0] + cov[1]) + (cov[2] + cov[3]);
+    out[blockIdx.x] = o;
+}
+
 // ---- wall diagnostics (ludwig_level_wall_census, ludwig_wall_surface_*; no reference counterpart: the reference reads y_plus_target
 // and never computes a y+) ----
 // The state wall_model_force_mag passes through on its way to the force, restated operation by operation (same operand order, jl_pow /

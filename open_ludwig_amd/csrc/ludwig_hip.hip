@@ -1887,14 +1887,54 @@ static int surface_stats_launch(LudwigSurfaceStats *S, int64_t t_sub)
     return LUDWIG_OK;
 }
 
+// ---- force series (ludwig_force_series_*; no reference counterpart) ----
+// Per triangle, in the caller's order: the nearest fluid cell in the internal block order (-1: none) and [FORCE_REC_ROWS][n] floats of
+// wall distance, normal, area and moment arm; a slab of per-chunk records for the stages of the tree and one device ring [capacity] of
+// finished records. The host keeps the coarse step of every used slot; _download empties it. The set does not own its level.
+struct LudwigForceSeries {
+    LudwigLevel *level = nullptr;
+    int device = 0, n_tri = 0, capacity = 0;
+    float tau = 0.0f, pressure_scale = 0.0f, stress_scale = 0.0f;
+    int32_t *cell = nullptr;
+    float *rec = nullptr;
+    ForceRecord *slab = nullptr;                // n_chunks records, then ceil(n / 512) until two or more are left (none for one chunk)
+    ForceRecord *ring = nullptr;
+    std::vector<int64_t> slot_step;             // coarse step of each used slot, oldest first
+};
+
+// one record of the state sub-step t_sub wrote into the next free slot (the caller has checked that there is one)
+static int force_series_launch(LudwigForceSeries *F, int64_t t_sub, int64_t t_coarse)
+{
+    LudwigLevel *L = F->level;
+    ForceRecord *dst = F->ring + F->slot_step.size();
+    if (F->n_tri > 0) {                                   // (no triangle: the record of zeros is made by _download, nothing is launched)
+        LW_ENSURE_RHO(L);                                 // a no-op on the level, which stores it every step since the set was made
+        int64_t n = ((int64_t)F->n_tri + CELLS - 1) / CELLS;
+        ForceRecord *in = F->slab;
+        hipLaunchKernelGGL(k_force_chunks, dim3((unsigned)n), dim3(CELLS / 2), 0, L->stream, n == 1 ? dst : in, F->cell, F->rec, F->n_tri,
+                           L->rho, vel_out(L, t_sub), F->tau, F->pressure_scale, F->stress_scale);
+        LW_HIP(hipGetLastError());
+        while (n > 1) {
+            const int64_t m = (n + CELLS - 1) / CELLS;
+            hipLaunchKernelGGL(k_force_combine, dim3((unsigned)m), dim3(CELLS / 2), 0, L->stream, m == 1 ? dst : in + n, in, n);
+            LW_HIP(hipGetLastError());
+            in += n;
+            n = m;
+        }
+    }
+    F->slot_step.push_back(t_coarse);
+    return LUDWIG_OK;
+}
+
 // Sampling inside a batch (ludwig_execute_timestep_batch_sampled): the coarse step being run, the probes' ring slot (-1 = not sampled)
 // and whether the surface set samples this step.
 struct BatchHook {
     LudwigProbes *P = nullptr;
     LudwigSurfaceStats *S = nullptr;
+    LudwigForceSeries *F = nullptr;
     int64_t t = 0;
     int slot = -1;
-    bool surface = false;
+    bool surface = false, forces = false;
 };
 static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub);
 
@@ -1948,13 +1988,14 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         LW_HIP(hipEventRecord(L->ev_stepped, L->stream));
         ++L->stepped_gen;
     }
-    if (ph && (ph->slot >= 0 || ph->surface)) {
-        // the level's last sub-step of a sampled coarse step: the probes and the surface set of this level read its newest rho / vel
+    if (ph && (ph->slot >= 0 || ph->surface || ph->forces)) {
+        // the level's last sub-step of a sampled coarse step: the probes and the surface sets of this level read its newest rho / vel
         // on its own stream, behind the step (and behind the event its children wait for) and ahead of the next write to either
         const int64_t m = (int64_t)1 << (lvl - 1);
         if (t_sub == m * ph->t + m - 1) {
             if (ph->slot >= 0 && (rc = probes_launch(ph->P, lvl - 1, ph->slot, t_sub))) return rc;
             if (ph->surface && ph->S->level == L && (rc = surface_stats_launch(ph->S, t_sub))) return rc;
+            if (ph->forces && ph->F->level == L && (rc = force_series_launch(ph->F, t_sub, ph->t))) return rc;
         }
     }
     if (has_children) {
@@ -1975,8 +2016,14 @@ static int check_batch_levels(LudwigLevel *const *levels, int32_t n_levels, int3
     return LUDWIG_OK;
 }
 
+// the force series a batch samples (ludwig_execute_timestep_batch_loads): at coarse steps start_step + k interval
+struct ForceSampler {
+    LudwigForceSeries *set = nullptr;
+    int64_t start_step = 0;
+    int32_t interval = 1;
+};
 static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s);
+                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs = nullptr);
 
 int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                                   const LudwigStepFlags *flags)
@@ -2001,10 +2048,11 @@ int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, 
 // 4-level sphere 1.72 -> 1.52; without the priorities 0.402 / 0.982 / 1.58 (and on another box the 4-level case got slower).
 // LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
 static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s)
+                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs)
 {
     LudwigProbes *probes = s ? s->probes : nullptr;
     LudwigSurfaceStats *surface = s ? s->surface : nullptr;
+    LudwigForceSeries *forces = fs ? fs->set : nullptr;
     const bool concurrent = n_levels > 1 && !env::batch_serial();
     hipStream_t user_stream = levels[0]->stream;
     if (concurrent) {
@@ -2064,7 +2112,7 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
     int rc = LUDWIG_OK;
     for (int32_t o = 0; o < batch_size && rc == LUDWIG_OK; ++o) {
         const int64_t t = t_start + o;
-        if (!probes && !surface) {
+        if (!probes && !surface && !forces) {
             rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent);
             continue;
         }
@@ -2074,6 +2122,8 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         ph.t = t;
         if (probes && step_sampled(t, s->probes_start_step, s->probes_interval)) ph.slot = probes_open_slot(probes, t);
         ph.surface = surface && step_sampled(t, s->surface_start_step, s->surface_interval);
+        ph.F = forces;
+        ph.forces = forces && step_sampled(t, fs->start_step, fs->interval);
         rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
     }
     if (concurrent) {
@@ -2652,12 +2702,21 @@ int ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_l
     return ludwig_execute_timestep_batch_sampled(levels, n_levels, t_start, batch_size, u_curr, flags, &s);
 }
 
+static int check_batch_samplers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, const LudwigBatchSamplers *s);
+
 int ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                                           const LudwigStepFlags *flags, const LudwigBatchSamplers *s)
 {
     int r = check_batch_levels(levels, n_levels, batch_size, flags);
     if (r) return r;
     if (!s || (!s->probes && !s->surface)) return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr);
+    if ((r = check_batch_samplers(levels, n_levels, t_start, batch_size, s))) return r;
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s);
+}
+
+// what ludwig_execute_timestep_batch_sampled refuses before it steps anything (s with at least one set)
+static int check_batch_samplers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, const LudwigBatchSamplers *s)
+{
     if (LudwigProbes *probes = s->probes) {
         const int32_t interval = s->probes_interval;
         const int64_t start_step = s->probes_start_step;
@@ -2677,7 +2736,7 @@ int ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_
         for (int i = 0; i < n_levels; ++i) in_batch = in_batch || levels[i] == S->level;
         if (!in_batch) return fail(LUDWIG_ERR_INVALID, "surface statistics: the set's level is not in the batch");
     }
-    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s);
+    return LUDWIG_OK;
 }
 
 void ludwig_surface_stats_destroy(LudwigSurfaceStats *S)
@@ -2769,6 +2828,131 @@ int ludwig_surface_stats_download(LudwigSurfaceStats *S, double *sums, size_t by
     LW_HIP(hipStreamSynchronize(S->level->stream));
     LW_HIP(hipMemcpy(sums, S->sums, want, hipMemcpyDeviceToHost));
     return LUDWIG_OK;
+}
+
+// ---- force series (ludwig_force_series_*) ----
+void ludwig_force_series_destroy(LudwigForceSeries *F)
+{
+    if (!F) return;
+    (void)hipSetDevice(F->device);
+    if (F->cell) (void)hipFree(F->cell);
+    if (F->rec) (void)hipFree(F->rec);
+    if (F->slab) (void)hipFree(F->slab);
+    if (F->ring) (void)hipFree(F->ring);
+    delete F;
+}
+
+int ludwig_force_series_create(LudwigLevel *L, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *wall_dist,
+                               const float *normals, const float *area, const float *arm, const LudwigSurfaceParams *sp, int32_t capacity,
+                               LudwigForceSeries **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!L || !sp || n_tri < 0 || (n_tri > 0 && (!blocks || !cells || !wall_dist || !normals || !area || !arm)))
+        return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (capacity < 1) return fail(LUDWIG_ERR_INVALID, "force series: capacity %d < 1", capacity);
+    // the kernel indexes cells as internal block * 512 + cell in 32 bits
+    if (n_tri > 0 && (int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "force series: level has %d blocks, more than 32-bit cell indices reach", L->n_blocks);
+    // everything is checked before anything is allocated
+    const size_t n = (size_t)n_tri;
+    std::vector<int32_t> hc(n);
+    std::vector<float> hr(n * FORCE_REC_ROWS);
+    for (int32_t i = 0; i < n_tri; ++i) {
+        const int32_t b = blocks[i], x = cells[i];
+        if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "force series: triangle %d: block %d not in -1..%d", i, b, L->n_blocks - 1);
+        if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "force series: triangle %d: cell %d not in 0..511", i, x);
+        hc[i] = b < 0 ? -1 : internal_cell(L, b, x);
+        hr[i] = wall_dist[i];
+        for (int a = 0; a < 3; ++a) hr[(size_t)(a + 1) * n + i] = normals[3 * (size_t)i + a];
+        hr[4 * n + i] = area[i];
+        for (int a = 0; a < 3; ++a) hr[(size_t)(a + 5) * n + i] = arm[(size_t)a * n + i];
+    }
+    LudwigForceSeries *F = new (std::nothrow) LudwigForceSeries;
+    if (!F) return fail(LUDWIG_ERR_ALLOC, "force series: out of host memory");
+    F->level = L;
+    F->device = L->device;
+    F->n_tri = n_tri;
+    F->capacity = capacity;
+    F->tau = sp->tau;
+    F->pressure_scale = sp->pressure_scale;
+    F->stress_scale = sp->stress_scale;
+    int r = set_device(F->device);
+    if (r == LUDWIG_OK && n_tri > 0) {
+        size_t slab = 0;                                   // records of every stage but the last, which goes into the ring
+        for (size_t m = (n + CELLS - 1) / CELLS; m > 1; m = (m + CELLS - 1) / CELLS) slab += m;
+        hipError_t e = hipSuccess;
+        upload_table(e, hc, F->cell);
+        upload_table(e, hr, F->rec);
+        if (e == hipSuccess && slab > 0) e = hipMalloc((void **)&F->slab, slab * sizeof(ForceRecord));
+        if (e == hipSuccess) e = hipMalloc((void **)&F->ring, (size_t)capacity * sizeof(ForceRecord));
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "force series: %d triangles, %d records: %s", n_tri, capacity, hipGetErrorString(e));
+    }
+    // a sample reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now on
+    if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(L, 1);
+    if (r != LUDWIG_OK) {
+        ludwig_force_series_destroy(F);
+        return r;
+    }
+    *out = F;
+    return LUDWIG_OK;
+}
+
+int ludwig_force_series_sample(LudwigForceSeries *F, int64_t t_sub, int64_t t_coarse)
+{
+    if (!F) return fail(LUDWIG_ERR_INVALID, "null force series");
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "force series: t_sub %lld < 0", (long long)t_sub);
+    if ((int)F->slot_step.size() >= F->capacity)
+        return fail(LUDWIG_ERR_STATE, "force series: ring full (%d records): download first", F->capacity);
+    LW_HIP(hipSetDevice(F->device));
+    return force_series_launch(F, t_sub, t_coarse);
+}
+
+int ludwig_force_series_download(LudwigForceSeries *F, double *sums, int64_t *covered, int64_t *steps, int32_t max_samples, int32_t *n_samples)
+{
+    if (!F || !n_samples || max_samples < 0 || (max_samples > 0 && (!sums || !covered || !steps))) return fail(LUDWIG_ERR_INVALID, "null argument");
+    const int n = (int)F->slot_step.size();
+    if (n > max_samples) return fail(LUDWIG_ERR_INVALID, "force series: %d records waiting, room for %d", n, max_samples);
+    *n_samples = n;
+    if (n == 0) return LUDWIG_OK;
+    std::vector<ForceRecord> rec((size_t)n);               // value-initialised: the records of a set without triangles
+    if (F->n_tri > 0) {
+        LW_HIP(hipSetDevice(F->device));
+        LW_HIP(hipStreamSynchronize(F->level->stream));
+        LW_HIP(hipMemcpy(rec.data(), F->ring, (size_t)n * sizeof(ForceRecord), hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 9; ++k) sums[9 * (size_t)i + k] = rec[i].s[k];
+        covered[i] = rec[i].covered;
+        steps[i] = F->slot_step[i];
+    }
+    F->slot_step.clear();
+    return LUDWIG_OK;
+}
+
+int ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                        const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
+                                        int32_t interval)
+{
+    if (!fs) return ludwig_execute_timestep_batch_sampled(levels, n_levels, t_start, batch_size, u_curr, flags, s);
+    int r = check_batch_levels(levels, n_levels, batch_size, flags);
+    if (r) return r;
+    if (s && !s->probes && !s->surface) s = nullptr;
+    if (s && (r = check_batch_samplers(levels, n_levels, t_start, batch_size, s))) return r;
+    if (interval < 1) return fail(LUDWIG_ERR_INVALID, "force series: interval %d < 1", interval);
+    bool in_batch = false;
+    for (int i = 0; i < n_levels; ++i) in_batch = in_batch || levels[i] == fs->level;
+    if (!in_batch) return fail(LUDWIG_ERR_INVALID, "force series: the set's level is not in the batch");
+    // nothing is stepped when the batch's records would not fit
+    const int64_t k = batch_size > 0 ? samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
+    if ((int64_t)fs->slot_step.size() + k > fs->capacity)
+        return fail(LUDWIG_ERR_STATE, "force series: %lld records of this batch overflow the ring (%d of %d used): download first", (long long)k,
+                    (int)fs->slot_step.size(), fs->capacity);
+    ForceSampler f;
+    f.set = fs;
+    f.start_step = start_step;
+    f.interval = interval;
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s, &f);
 }
 
 // ---- slices (ludwig_slices_*; no reference counterpart) ----

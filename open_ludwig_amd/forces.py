@@ -19,6 +19,7 @@ from typing import Tuple
 import numpy as np
 
 from .blocks import BLOCK_SIZE
+from .monitor import tree_sum as tree_sum_f64    # noqa: F401  (one halving tree for the monitor's sums and the force series' records)
 
 f32 = np.float32
 
@@ -187,6 +188,40 @@ def partial_force_sums(mesh, p, tau_x, tau_y, tau_z, params, select=None) -> np.
         out[3 + i] = np.sum(dFv[:, i], dtype=np.float32)
         out[6 + i] = np.sum(dM[:, i], dtype=np.float32)
     return out
+
+
+def moment_arms(mesh, params, select=None) -> np.ndarray:
+    """Float32 [3, n]: rx, ry, rz exactly as partial_force_sums forms them, (float32(c) + float32(off)) - float32(mc)"""
+    off = params.mesh_offset.astype(np.float32)
+    c = mesh.centers.astype(np.float32)
+    if select is not None:
+        c = c[select]
+    mc = np.asarray(params.moment_center, dtype=np.float32)
+    return np.ascontiguousarray(np.stack([(c[:, k] + off[k]) - mc[k] for k in range(3)]), dtype=np.float32)
+
+
+def force_series_contributions(mesh, p, tau_x, tau_y, tau_z, params, select=None) -> Tuple[np.ndarray, int]:
+    """What every triangle adds to the nine sums of partial_force_sums, with its expressions and operand order: Float32 [n, 9] =
+    dFp(3), dFv(3), dM(3), and the coverage count |p| > 1e-10 of integrate_surface_forces. One record of the device force series
+    (k_force_chunks / k_force_combine) is tree_sum_f64 of every column widened to Float64, bit for bit."""
+    nrm = mesh.normals.astype(np.float32)
+    A = mesh.areas.astype(np.float32)
+    if select is not None:
+        nrm, A = nrm[select], A[select]
+    p, tau_x, tau_y, tau_z = (np.asarray(a, dtype=np.float32) for a in (p, tau_x, tau_y, tau_z))
+    rx, ry, rz = moment_arms(mesh, params, select)
+    dFp = np.stack([-p * nrm[:, 0] * A, -p * nrm[:, 1] * A, -p * nrm[:, 2] * A], axis=1)
+    dFv = np.stack([tau_x * A, tau_y * A, tau_z * A], axis=1)
+    dF = dFp + dFv
+    dM = np.stack([ry * dF[:, 2] - rz * dF[:, 1], rz * dF[:, 0] - rx * dF[:, 2], rx * dF[:, 1] - ry * dF[:, 0]], axis=1)
+    out = np.concatenate([dFp, dFv, dM], axis=1).astype(np.float32)
+    return out, int(np.count_nonzero(np.abs(p) > f32(1e-10)))
+
+
+def record_of(contributions: np.ndarray) -> np.ndarray:
+    """Float64 [9]: the force series' record of Float32 contributions [n, 9] (the empty set gives +0.0)"""
+    c = np.asarray(contributions, dtype=np.float32).astype(np.float64)
+    return np.array([tree_sum_f64(c[:, k]) for k in range(9)], dtype=np.float64)
 
 
 def finish_forces(sums, coverage: int, params, symmetric: bool = False) -> ForceResult:

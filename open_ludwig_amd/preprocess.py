@@ -90,6 +90,11 @@ class CaseConfig:
     q_min_threshold: np.float32 = np.float32(0.001)
     forces_enabled: bool = True
     moment_center: Tuple[float, float, float] = (0.25, 0.0, 0.0)
+    # force series, advanced.forces.series (no reference counterpart): the integrated loads of the finest level reduced on the device
+    # at every `interval`-th coarse step from `start_step`, written to forces_series.csv (force_series.py)
+    forces_series_enabled: bool = False
+    forces_series_start_step: int = 1
+    forces_series_interval: int = 1
     diag_freq: int = 500
     async_depth: int = 8
     case_dir: str = ""
@@ -169,6 +174,8 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     surf_interval = int(g("advanced", "surface_statistics", "interval", default=1))
     if surf_interval < 1:
         raise ValueError(f"advanced.surface_statistics.interval must be >= 1, got {surf_interval}")
+    forces_series = _forces_series_config(g("advanced", "forces", "series", default=None),
+                                          bool(g("advanced", "forces", "enabled", default=True)))
     probes = _probes_config(g("advanced", "probes", default=None))
     slices = _slices_config(g("advanced", "slices", default=None))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
@@ -224,12 +231,31 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         statistics_subgrid=stats_subgrid, statistics_subgrid_ck=stats_subgrid_ck,
         surface_statistics_enabled=bool(g("advanced", "surface_statistics", "enabled", default=False)),
         surface_statistics_start_step=max(surf_start, 1), surface_statistics_interval=surf_interval,
+        **forces_series,
         **probes,
         **slices,
         **flow_monitor,
         **wall_diag,
         y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
     )
+
+
+def _forces_series_config(fc, forces_enabled: bool) -> dict:
+    """advanced.forces.series: {enabled: false, start_step: 1, interval: 1} -> CaseConfig fields. Absent or disabled: the defaults
+    (nothing is allocated, launched or written)."""
+    if fc is None:
+        return {}
+    if not isinstance(fc, dict):
+        raise ValueError("advanced.forces.series must be a mapping")
+    if not bool(fc.get("enabled", False)):
+        return {}
+    if not forces_enabled:
+        raise ValueError("advanced.forces.series.enabled is true, but advanced.forces.enabled is not: the series is the force "
+                         "integration, sampled every step")
+    start, interval = int(fc.get("start_step", 1)), int(fc.get("interval", 1))
+    if interval < 1:
+        raise ValueError(f"advanced.forces.series.interval must be >= 1, got {interval}")
+    return {"forces_series_enabled": True, "forces_series_start_step": max(start, 1), "forces_series_interval": interval}
 
 
 def _probes_config(pc) -> dict:

@@ -37,7 +37,7 @@ def recursive_step(grids: Sequence[DeviceLevel], current_lvl: int, t_sub: int, p
 
 
 def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_size: int, u_curr,
-                           params: SolverParams, native: bool = True, probes=None, surface=None) -> None:
+                           params: SolverParams, native: bool = True, probes=None, surface=None, forces=None) -> None:
     """execute_timestep_batch! (src/solver_control.jl:145-165); t_start is 1-based like the reference's loop.
 
     native=True (default): the whole batch is one C call (ludwig_execute_timestep_batch runs the same recursion inside
@@ -46,15 +46,23 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
     probes: a probes.DeviceProbes made over `grids`, sampled after every coarse step start_step + k interval (native: inside the C
     batch, ludwig_execute_timestep_batch_probes; else through its sample() after the coarse step) - the same bits either way.
     surface: a surface_stats.DeviceSurfaceStats on one of `grids`, sampled after every coarse step start_step + k interval (native:
-    inside the C batch, ludwig_execute_timestep_batch_sampled; else through its accumulate() after the coarse step)."""
+    inside the C batch, ludwig_execute_timestep_batch_sampled; else through its accumulate() after the coarse step).
+    forces: a force_series.DeviceForceSeries on one of `grids`, sampled after every coarse step start_step + k interval (native: inside
+    the C batch, ludwig_execute_timestep_batch_loads; else through its sample() after the coarse step)."""
     if native:
         import ctypes as C
         from . import _lib
         arr = (C.c_void_p * len(grids))(*[g.handle for g in grids])
         fl = params.to_c()
-        if surface is not None:
+        if surface is not None or forces is not None:
             smp = _lib.BatchSamplers(probes.handle.value if probes is not None else None, probes.start_step if probes is not None else 0,
-                                     probes.interval if probes is not None else 1, surface.handle.value, surface.start_step, surface.interval)
+                                     probes.interval if probes is not None else 1, surface.handle.value if surface is not None else None,
+                                     surface.start_step if surface is not None else 0, surface.interval if surface is not None else 1)
+        if forces is not None:
+            _lib.check(_lib.load().ludwig_execute_timestep_batch_loads(arr, len(grids), int(t_start), int(batch_size),
+                                                                       float(np.float32(u_curr)), C.byref(fl), C.byref(smp), forces.handle,
+                                                                       forces.start_step, forces.interval))
+        elif surface is not None:
             _lib.check(_lib.load().ludwig_execute_timestep_batch_sampled(arr, len(grids), int(t_start), int(batch_size),
                                                                          float(np.float32(u_curr)), C.byref(fl), C.byref(smp)))
         elif probes is None:
@@ -74,6 +82,8 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
                 probes.sample(lvl, t_sub_after(lvl, t))
         if surface is not None and surface.is_sample_step(t):
             surface.accumulate(t_sub_after(surface.level_index, t))
+        if forces is not None and forces.is_sample_step(t):
+            forces.sample(t_sub_after(forces.level_index, t), t)
     grids[0].synchronize()                             # KernelAbstractions.synchronize(backend)
 
 
