@@ -12,7 +12,8 @@
  *     column-major A[x,y,z,b,k] -> linear (x-1) + 8(y-1) + 64(z-1) + 512(b-1) + 512*n_blocks*(k-1);
  *     index tables keep the reference's 1-based values with 0 = absent.
  *   - every function returns LUDWIG_OK (0) or a negative LUDWIG_ERR_* code and never throws;
- *     the message is available from ludwig_last_error() (thread-local).
+ *     the message is available from ludwig_last_error() (thread-local). One positive status exists,
+ *     LUDWIG_ISO_REFUSED of ludwig_level_isosurface_extract: no error, a surface over the caller's cap.
  *   - a LudwigLevel is not re-entrant; calls are asynchronous on the level's HIP stream and
  *     ordered by it; ludwig_sync() is the reference's KernelAbstractions.synchronize.
  *   - lattice tables (c, w, opp, mirror_y, mirror_z of src/physics_v2.jl:99-117) are compile-time
@@ -355,6 +356,38 @@ int  ludwig_level_gradient_fields_compute(LudwigLevel *level, int vel_field, flo
 /* the last computed field in the reference layout [8,8,8,n_blocks,K] Float32, reference block order, ghost blocks zero; bytes =
  * 2048 n_blocks K. Synchronizes the stream. LUDWIG_ERR_STATE before the first compute. */
 int  ludwig_level_gradient_fields_download(const LudwigLevel *level, int which, float *host, size_t bytes);
+
+/* ---- iso-surfaces: the triangles of s = value on one level, extracted on the device (no reference counterpart) ----
+ * s per cell: LUDWIG_ISO_DENSITY rho as a download would return it; LUDWIG_ISO_VELOCITY_MAGNITUDE sqrtf((ux ux + uy uy) + uz uz) of
+ * vel_field; LUDWIG_ISO_Q_CRITERION / LUDWIG_ISO_VORTICITY_MAGNITUDE Q / sqrtf((wx wx + wy wy) + wz wz) of
+ * ludwig_level_gradient_fields_compute(level, vel_field, scale), which the call performs (the gradient fields then hold that result).
+ * Surfaces live on the dual grid: a cube is anchored at a cell (x, y, z) of a block, its corner c = dx + 2 dy + 4 dz is the cell
+ * (x + dx, y + dy, z + dz), through the anchor block's neighbour row where it lies beyond the block (a periodic entry continues the
+ * surface unwrapped). A cube is live iff its anchor block is owned and skip[block] == 0, its anchor's global cell coordinates
+ * (8 (map - 1) + x, ...) lie in [cell_lo, cell_hi) per axis, all eight corner blocks exist, no corner is an obstacle cell and all
+ * eight s are finite. Each live cube is split into the tetrahedra (0,1,3,7) (0,3,2,7) (0,2,6,7) (0,6,4,7) (0,4,5,7) (0,5,1,7); a corner is
+ * inside iff s >= value; 1 or 3 inside corners of a tetrahedron give one triangle, 2 give two, wound (by an integer table) so that the
+ * normal points from the inside corners to the outside ones. A vertex on the edge (a, b), a < b as cube corner numbers:
+ * t = fminf(fmaxf((value - s_a) / (s_b - s_a), 0), 1); position g_a + t (b - a) in cell units of the level, g_a the anchor's global cell
+ * coordinates plus a's offset; attributes rho, ux, uy, uz = q_a + t (q_b - q_a) (rho and vel_field); key = 512 block + cell of a and of
+ * b, reference block order (the level must hold fewer than 2^31 / 512 blocks). Float32, no contraction: every cube that shares an edge
+ * gives its vertex the same bits. Triangles are ordered by anchor block (reference order), anchor cell x + 8 y + 64 z, tetrahedron,
+ * first / second triangle - whatever the internal block order or the scheduling.
+ * The buffers belong to the level, are allocated by the first extraction and grow when needed; a level that never extracts allocates
+ * and launches nothing. A level created with n_owned < 0 accepts every call and does nothing (0 triangles). */
+enum LudwigIsoScalar { LUDWIG_ISO_DENSITY = 0, LUDWIG_ISO_VELOCITY_MAGNITUDE = 1, LUDWIG_ISO_Q_CRITERION = 2,
+                       LUDWIG_ISO_VORTICITY_MAGNITUDE = 3 };
+#define LUDWIG_ISO_REFUSED     1   /* not an error: more than max_triangles, nothing was emitted */
+/* vel_field: LUDWIG_VEL or LUDWIG_VEL_TEMP; scale, value: finite (scale non-zero where the gradient is used); skip: n_blocks bytes in
+ * the reference block order, or NULL for none; cell_lo, cell_hi: 3 ints each, cell_lo <= cell_hi; max_triangles >= 0. Counts on the
+ * level's stream, brings the per-block counts to the host (one synchronisation), then queues the emission. *n_triangles = the count;
+ * when it exceeds max_triangles nothing is emitted, the call returns LUDWIG_ISO_REFUSED and a download gives 0 triangles. */
+int  ludwig_level_isosurface_extract(LudwigLevel *level, int which, int vel_field, float scale, float value, const uint8_t *skip,
+                                     const int32_t *cell_lo, const int32_t *cell_hi, int64_t max_triangles, int64_t *n_triangles);
+/* the last extraction of n triangles: positions [n][3][3] and attributes [n][3][4] floats, keys [n][3][2] int32; the byte counts must
+ * be 36 n, 48 n, 24 n. Synchronizes the stream. LUDWIG_ERR_STATE before the first extraction. */
+int  ludwig_level_isosurface_download(LudwigLevel *level, float *positions, size_t position_bytes, float *attributes,
+                                      size_t attribute_bytes, int32_t *keys, size_t key_bytes);
 
 /* ---- probes: time series of rho and u at points (no reference counterpart) ----
  * A probe set is made over a level array (the batch's). Probe p lives on level level_index[p] (0-based) and has 8 stencil corners

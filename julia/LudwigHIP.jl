@@ -155,6 +155,32 @@ gradient_fields_download!(a::Array{Float32}, d::DeviceLevel, which::Int32) =
     GC.@preserve a check(ccall((:ludwig_level_gradient_fields_download, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Csize_t),
                                d.handle, which, pointer(a), sizeof(a)))
 
+# iso-surfaces (no reference counterpart): the triangles of s = value on one level, extracted on the device
+const ISO_DENSITY = Int32(0)
+const ISO_VELOCITY_MAGNITUDE = Int32(1)
+const ISO_Q_CRITERION = Int32(2)
+const ISO_VORTICITY_MAGNITUDE = Int32(3)
+const ISO_REFUSED = Cint(1)
+"""count the triangles of `which` = value on the level and, unless there are more than `max_triangles`, emit them into the level's
+buffers: (n_triangles, emitted). vel_field: VEL or VEL_TEMP; scale: the gradient's (1/dx); skip: per block (reference order) non-zero
+where no cube is anchored, or `nothing`; cell_lo / cell_hi: the box of anchor cells, 3 Int32 each."""
+function isosurface_extract!(d::DeviceLevel, which::Integer, vel_field::Integer, scale::Real, value::Real,
+                             skip::Union{Nothing,Vector{UInt8}}, cell_lo::Vector{Int32}, cell_hi::Vector{Int32}, max_triangles::Integer)
+    n = Ref{Int64}(0)
+    sk = skip === nothing ? UInt8[] : skip
+    rc = GC.@preserve sk cell_lo cell_hi ccall((:ludwig_level_isosurface_extract, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Cfloat, Cfloat, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Int64, Ref{Int64}),
+        d.handle, Cint(which), Cint(vel_field), Float32(scale), Float32(value), skip === nothing ? Ptr{UInt8}(C_NULL) : pointer(sk),
+        cell_lo, cell_hi, Int64(max_triangles), n)
+    rc == ISO_REFUSED || check(rc)
+    return Int(n[]), rc != ISO_REFUSED
+end
+"""the last extraction into positions (3 x 3 x n Float32), attributes (4 x 3 x n Float32: rho, ux, uy, uz) and keys (2 x 3 x n Int32)"""
+isosurface_download!(positions::Array{Float32,3}, attributes::Array{Float32,3}, keys::Array{Int32,3}, d::DeviceLevel) =
+    GC.@preserve positions attributes keys check(ccall((:ludwig_level_isosurface_download, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Ptr{Float32}, Csize_t, Ptr{Int32}, Csize_t),
+        d.handle, positions, sizeof(positions), attributes, sizeof(attributes), keys, sizeof(keys)))
+
 # probes (no reference counterpart): rho, u at points, trilinear in float32 (x, then y, then z), sampled into a device ring
 """a probe set over `grids`: per probe its 0-based level, 8 stencil corners (reference block index, cell x + 8y + 64z; corners that
 are no fluid cell of that level already replaced by the base cell) as 8 x n Int32 matrices, weights 3 x n Float32, ring capacity in

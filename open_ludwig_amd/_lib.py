@@ -26,6 +26,9 @@ GRAD_VORTICITY, GRAD_Q = range(2)
 GRAD_NAMES = {"vorticity": (GRAD_VORTICITY, 3), "q": (GRAD_Q, 1)}
 # ludwig_slices_create flags
 SLICE_GRADIENT = 1
+# enum LudwigIsoScalar (isosurface.FIELDS, in this order) and the status of an extraction refused by its cap (no error)
+ISO_NAMES = {"density": 0, "velocity_magnitude": 1, "q_criterion": 2, "vorticity_magnitude": 3}
+ISO_REFUSED = 1
 # enum LudwigSubgridField / LudwigSubgridSum: one component each
 SUBGRID_FIELD_NAMES = {"nu": 0, "code": 1}
 SUBGRID_SUM_NAMES = {"nu": 0, "nunu": 1, "eps": 2}
@@ -55,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
     "ludwig_slices_create", "ludwig_slices_destroy", "ludwig_slices_sample", "ludwig_slices_download",
     "ludwig_level_monitor",
+    "ludwig_level_isosurface_extract", "ludwig_level_isosurface_download",
     "ludwig_level_wall_census", "ludwig_wall_surface_create", "ludwig_wall_surface_destroy", "ludwig_wall_surface_compute",
     "ludwig_wall_surface_download",
     "ludwig_force_series_create", "ludwig_force_series_destroy", "ludwig_force_series_sample", "ludwig_force_series_download",
@@ -218,6 +222,8 @@ def load() -> C.CDLL:
         "ludwig_slices_destroy": (None, [vp]),
         "ludwig_slices_sample": (C.c_int, [vp, i64]),
         "ludwig_slices_download": (C.c_int, [vp, vp, C.c_size_t]),
+        "ludwig_level_isosurface_extract": (C.c_int, [vp, i32, i32, f32, f32, vp, vp, vp, i64, C.POINTER(C.c_int64)]),
+        "ludwig_level_isosurface_download": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]),
         "ludwig_level_wall_census": (C.c_int, [vp, i64, C.POINTER(WallCensus)]),
         "ludwig_wall_surface_create": (C.c_int, [vp, i32, vp, vp, vp, C.POINTER(SurfaceParams), C.POINTER(vp)]),
         "ludwig_wall_surface_destroy": (None, [vp]),

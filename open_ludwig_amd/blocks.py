@@ -367,6 +367,41 @@ class DeviceLevel(_lib.Handle):
             out.append(a)
         return out[0], out[1]
 
+    # -- iso-surfaces (isosurface.py; no reference counterpart) --
+    def isosurface(self, field: str, value, vel_name: str = "vel", scale=1.0, skip=None, cell_lo=(0, 0, 0), cell_hi=None,
+                   max_triangles: int = 50_000_000, download: bool = True):
+        """the triangles of the surface `field` = value ('density' | 'velocity_magnitude' | 'q_criterion' | 'vorticity_magnitude';
+        isosurface.py states the definition), extracted on the device from rho and the velocity buffer `vel_name`, with the gradient's
+        derivatives times `scale` (float32, e.g. 1/dx). skip: per block (reference order) non-zero where no cube is anchored, or None;
+        cell_lo / cell_hi: the box of anchor cells in global cell coordinates (None: no upper bound).
+        -> (n_triangles, positions [n, 3, 3] in cell units, attributes [n, 3, 4] = rho, ux, uy, uz, keys [n, 3, 2] Int32); when the
+        count exceeds max_triangles nothing is emitted and the arrays are None; download=False: the count alone, arrays None."""
+        from .isosurface import CELL_MAX, check_field
+        if vel_name not in ("vel", "vel_temp"):
+            raise ValueError(f"isosurface: vel_name must be 'vel' or 'vel_temp', got {vel_name!r}")
+        which = check_field(field)
+        lo = np.ascontiguousarray(cell_lo, dtype=np.int32).reshape(3)
+        hi = np.full(3, CELL_MAX, np.int32) if cell_hi is None else np.ascontiguousarray(cell_hi, dtype=np.int32).reshape(3)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+            if sk.size != self.n_blocks:
+                raise ValueError(f"isosurface: skip has {sk.size} entries for {self.n_blocks} blocks")
+        n = C.c_int64(0)
+        rc = self._lib.ludwig_level_isosurface_extract(self.handle, which, _lib.FIELD_NAMES[vel_name], float(np.float32(scale)),
+                                                       float(np.float32(value)), sk.ctypes.data if sk is not None and sk.size else None,
+                                                       lo.ctypes.data, hi.ctypes.data, int(max_triangles), C.byref(n))
+        if rc != _lib.ISO_REFUSED:
+            _lib.check(rc)
+        nt = int(n.value)
+        if rc == _lib.ISO_REFUSED or not download:
+            return nt, None, None, None
+        pos, att, keys = np.empty((nt, 3, 3), np.float32), np.empty((nt, 3, 4), np.float32), np.empty((nt, 3, 2), np.int32)
+        _lib.check(self._lib.ludwig_level_isosurface_download(self.handle, pos.ctypes.data if nt else None, pos.nbytes,
+                                                              att.ctypes.data if nt else None, att.nbytes,
+                                                              keys.ctypes.data if nt else None, keys.nbytes))
+        return nt, pos, att, keys
+
     # -- subgrid model (subgrid.py; no reference counterpart for the output) --
     def subgrid_fields(self, vel_name: str) -> Tuple[np.ndarray, np.ndarray]:
         """nu_t (after the background floor) and the branch code as a float, both Float32 [8,8,8,n_blocks] (reference layout, ghost

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import force_series as fseries_mod
 from . import forces as forces_mod
+from . import isosurface as iso_mod
 from . import monitor as monitor_mod
 from . import probes as probes_mod
 from . import slices as slices_mod
@@ -221,6 +222,20 @@ class HipStepper:
     def gradient_fields(self, level: int, vel_name: str, scale):
         """(vorticity [8,8,8,nb,3], Q [8,8,8,nb]) of a level from its `vel_name` buffer, derivatives times `scale` (Float32)"""
         return self.dev[level].gradient_fields(vel_name, scale)
+
+    # -- iso-surfaces (isosurface.py; no reference counterpart) --
+    def isosurfaces_setup(self, start_step: int = 1, interval: int = 1) -> None:
+        """the caller extracts after the coarse steps start_step + k interval (run_case cuts its batches there); nothing is allocated
+        before the first extraction"""
+        self._iso_steps = iso_mod.check_schedule(start_step, interval)
+
+    def isosurface(self, level: int, field: str, value, t_coarse: int, skip=None, cell_lo=(0, 0, 0), cell_hi=None,
+                   max_triangles: int = 50_000_000, download: bool = True):
+        """DeviceLevel.isosurface of a level's newest state after coarse step t_coarse (the last batch must have ended there), with
+        derivatives per unit length (scale 1/dx): (n_triangles, positions, attributes, keys), the arrays None when refused"""
+        vel_name = "vel_temp" if stats_mod.t_sub_after(level, t_coarse) % 2 == 0 else "vel"
+        return self.dev[level].isosurface(field, value, vel_name, np.float32(1.0 / self.host[level].dx), skip, cell_lo, cell_hi,
+                                          max_triangles, download)
 
     # -- subgrid model (subgrid.py; no reference counterpart for the output) --
     def subgrid_fields(self, level: int, vel_name: str):
@@ -789,6 +804,12 @@ class DistributedStepper:
         self._scatter_blocks(parts, [w_all, q_all])
         return w_all, q_all
 
+    # -- iso-surfaces: not over ranks. A cube reads the first layer of seven neighbour blocks; on a rank's ghost blocks the gradient
+    # fields do not exist and rho / vel are current only where a halo asks for them --
+    def isosurfaces_setup(self, start_step: int = 1, interval: int = 1) -> None:
+        raise RuntimeError("advanced.isosurfaces is enabled, but a distributed run cannot extract iso-surfaces yet: ghost blocks hold no "
+                           "gradient fields and only part of rho / vel (DESIGN section 8, Next)")
+
     # -- subgrid model: every rank works on its owned blocks after batch(); the face stencil is the gradient fields', so their argument
     # holds unchanged (the 'vel' halo ghosts are current for both buffers) --
     def subgrid_fields(self, level: int, vel_name: str):
@@ -868,6 +889,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     With cfg.slices_enabled, every plane is sampled after the coarse steps start_step + k interval - batches are cut there with the
     batch's own inlet speed - on the device where the stepper offers slices_setup, else from downloaded fields (slices.host_sample);
     each sample is written to slice_<name>_%06d.vti and listed in slice_<name>.pvd (slices.py).
+    With cfg.isosurfaces_enabled, every surface is extracted after the coarse steps start_step + k interval - batches are cut there as for
+    slices - from the newest state of every level that exports blocks, with the blocks the flow file drops skipped: on the device where
+    the stepper offers isosurface, else from downloaded fields (isosurface.extract_host). The levels are merged in ascending order into
+    iso_<name>_%06d.vtp, listed in iso_<name>.pvd; a sample of more than max_triangles triangles writes no file and logs one line
+    (isosurface.py). A stepper whose isosurfaces_setup raises (the distributed one) ends the run before the first step.
     With cfg.flow_monitor_enabled, a monitor.Record of every level is taken at every diagnostics step and after the last step, from the
     state at batch end (where rho_min is taken; no batch is cut) - on the device where the stepper offers monitor, else from downloaded
     fields (monitor.host_monitor); flow_monitor.csv gains one row per level and the warnings go to `log`. With
@@ -897,6 +923,15 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     # a plane outside the domain is refused before anything is allocated on a device
     splans = [slices_mod.plan_slice(spec, grids, params.mesh_offset) for spec in cfg.slices_planes] if slices_on else []
     st = stepper_factory(grids)
+    iso_on = bool(cfg.isosurfaces_enabled)
+    iso_start, iso_interval = cfg.isosurfaces_start_step, cfg.isosurfaces_interval
+    if iso_on and hasattr(st, "isosurfaces_setup"):
+        try:
+            st.isosurfaces_setup(iso_start, iso_interval)
+        except Exception:
+            if hasattr(st, "close"):
+                st.close()
+            raise
     wall_on = bool(cfg.wall_diagnostics_enabled)
     if wall_on and not hasattr(st, "wall_diagnostics_setup"):
         if hasattr(st, "close"):
@@ -957,6 +992,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                 io.write(fseries_mod.csv_header() + "\n")
         if slices_on:
             slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
+        if iso_on:
+            iso_writer = iso_mod.IsoWriter(out_dir, [s.name for s in cfg.isosurfaces_surfaces], params.time_scale)
         if probes_on:
             probes_mod.write_points_csv(os.path.join(out_dir, "probes_points.csv"), pplan, grids)
             with open(os.path.join(out_dir, "probes.csv"), "w") as io:
@@ -994,6 +1031,39 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                 diverged = monitor_mod.FlowDiverged(step, g.level_id, rec.first_bad,
                                                     monitor_mod.cell_coordinates(rec.first_bad, g.dx, params.mesh_offset), rec.n_bad)
         return diverged
+
+    if iso_on:
+        iso_skips = iso_mod.skip_flags(grids)
+        iso_boxes = {s.name: [iso_mod.cell_box(s.bounds, g.dx, params.mesh_offset) for g in grids] for s in cfg.isosurfaces_surfaces}
+
+    def take_isosurfaces(step):
+        """every surface from the state after coarse step `step`, levels merged in ascending order; files out"""
+        cap = int(cfg.isosurfaces_max_triangles)
+        for spec in cfg.isosurfaces_surfaces:
+            boxes = iso_boxes[spec.name]
+            if hasattr(st, "isosurface"):
+                parts, total, refused = [], 0, False
+                for li, g in enumerate(grids):
+                    if iso_skips[li].all():
+                        continue
+                    # once the cap is passed the remaining levels are only counted
+                    n, pos, att, keys = st.isosurface(li, spec.field, spec.value, step, iso_skips[li], boxes[li][0], boxes[li][1],
+                                                      0 if refused else cap - total)
+                    total += n
+                    if pos is None:
+                        refused = True
+                    else:
+                        parts.append((li, g.dx, pos, att, keys))
+            else:
+                parts = iso_mod.host_extract_levels(st, grids, spec.field, spec.value, step, boxes, iso_skips)
+                total = sum(p[2].shape[0] for p in parts)
+                refused = total > cap
+            if refused:
+                if log:
+                    log(f"isosurface {spec.name!r}: step {step}: {total} triangles, more than advanced.isosurfaces.max_triangles = {cap}; "
+                        "no file written")
+            elif writing:
+                iso_writer.write(step, spec.name, iso_mod.merge_levels(parts))
 
     def wall_values(state_step):
         """the wall-surface values of the state after coarse step state_step, evaluated once per step (collective in a distributed run)"""
@@ -1057,7 +1127,7 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if stats_on or surf_host is not None or slices_on:
+            if stats_on or surf_host is not None or slices_on or iso_on:
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
@@ -1066,6 +1136,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     cuts.update(stats_mod.sample_steps(t, batch_end, surf_start, surf_interval))
                 if slices_on:
                     cuts.update(stats_mod.sample_steps(t, batch_end, sl_start, sl_interval))
+                if iso_on:
+                    cuts.update(stats_mod.sample_steps(t, batch_end, iso_start, iso_interval))
                 seg = t
                 for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
@@ -1087,6 +1159,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         got = st.slices_sample(s_step) if dev_slices else slices_mod.host_sample(st, splans, grids, s_step)
                         if writing:
                             slice_writer.write(s_step, got)
+                    if iso_on and stats_mod.is_sample_step(s_step, iso_start, iso_interval):
+                        take_isosurfaces(s_step)
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)

@@ -1384,6 +1384,249 @@ __global__ __launch_bounds__(64) void k_slice_sample(float *__restrict__ out, in
     }
 }
 
+// ---- iso-surfaces (ludwig_level_isosurface_*; no reference counterpart; open_ludwig_amd/isosurface.py states the definition and
+// restates it in numpy bit for bit) ----
+// Workgroup r = reference block r of the owned ones (the output order), 256 lanes, two x-consecutive anchor cells per lane. The block's
+// 9 x 9 x 9 tile of the scalar - the block and the first layer of its +x, +y, +z face, edge and corner neighbours - is staged in LDS
+// (2.9 KB); a corner that cannot take part (no block there, an obstacle cell, a non-finite value) is staged as NaN, so "all eight
+// corners finite" is the whole liveness test of a cube once its anchor passes (block not skipped, global cell in [lo, hi)).
+// k_iso_count writes the block's triangle count; the host scans the counts (int64) into block offsets; k_iso_emit recomputes the per-cell
+// counts, scans them in cell order (wave scan with shuffles, the four wave totals through LDS) and writes every triangle at its place with
+// plain stores: no atomics, so the order depends on neither the internal block order nor scheduling.
+// The eight corner values stay in registers: the tetrahedra are unrolled with compile-time corner numbers, and what depends on the case
+// (which tetrahedron edge a vertex sits on) selects among four registers, never indexes an array.
+constexpr int ISO_TILE = 9, ISO_TILE2 = 81, ISO_TILE3 = 729;
+enum { ISO_DENSITY = 0, ISO_VELOCITY_MAGNITUDE = 1, ISO_Q_CRITERION = 2, ISO_VORTICITY_MAGNITUDE = 3 };
+constexpr int ISO_POS_FLOATS = 9, ISO_ATT_FLOATS = 12, ISO_KEY_INTS = 6;      // per triangle: 3 x (3 | 4 | 2)
+
+struct IsoArgs {
+    const float *s;            // the scalar of cell c of internal block b: s[b * s_stride + c]
+    int64_t s_stride;
+    const uint8_t *obstacle;
+    const int32_t *meta;
+    const int32_t *ref2int;    // nullptr: the reference order is kept
+    const uint8_t *skip;       // [n_owned], reference order: non-zero = no cube is anchored in the block
+    int32_t lo[3], hi[3];
+    float value;
+};
+
+// the corners of tetrahedron k: 0, then two consecutive corners of the cycle 1 3 2 6 4 5 around the diagonal, then 7
+__host__ __device__ constexpr int iso_tet_corner(int k, int j)
+{
+    constexpr int cyc[6] = {1, 3, 2, 6, 4, 5};
+    return j == 0 ? 0 : j == 3 ? 7 : cyc[(k + j - 1) % 6];
+}
+__device__ __forceinline__ int iso_case_triangles(int m)
+{
+    const int n = __popc((unsigned)m);
+    return (n == 1 || n == 3) ? 1 : (n == 2 ? 2 : 0);
+}
+__device__ __forceinline__ bool iso_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+template <class T>
+__device__ __forceinline__ T iso_sel4(T a, T b, T c, T d, int i) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
+
+// value[c] = sqrtf((a^2 + b^2) + c^2) of the first three components of src [block][K][512]: the velocity (K = 3), or the vorticity
+// of the gradient fields (K = 4). Every block of the level, ghosts included (their gradient fields are 0).
+template <int WHICH>
+__global__ __launch_bounds__(256) void k_iso_scalar(float *__restrict__ out, const float *__restrict__ src)
+{
+    static_assert(WHICH == ISO_VELOCITY_MAGNITUDE || WHICH == ISO_VORTICITY_MAGNITUDE, "the other scalars are read in place");
+    constexpr int K = WHICH == ISO_VELOCITY_MAGNITUDE ? 3 : GRAD_COMPONENTS;
+    const int64_t b = blockIdx.x;
+    const int c = 2 * (int)threadIdx.x;
+    const float *p = src + b * K * CELLS + c;
+    const float2 x = *(const float2 *)p, y = *(const float2 *)(p + CELLS), z = *(const float2 *)(p + 2 * CELLS);
+    *(float2 *)(out + b * CELLS + c) = make_float2(sqrtf((x.x * x.x + y.x * y.x) + z.x * z.x), sqrtf((x.y * x.y + y.y * y.y) + z.y * z.y));
+}
+
+// stage the tile of internal block b; returns bit 0: some staged value is inside (>= value), bit 1: some is outside
+__device__ __forceinline__ int iso_stage_tile(float *tile, const IsoArgs &a, const int64_t b, const int t)
+{
+    int seen = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const int i = t + 256 * r;
+        if (i < ISO_TILE3) {
+            const int tz = i / ISO_TILE2, ty = (i - tz * ISO_TILE2) / ISO_TILE, tx = i - tz * ISO_TILE2 - ty * ISO_TILE;
+            const int ox = tx >> 3, oy = ty >> 3, oz = tz >> 3;
+            int64_t nb = b;
+            if (ox | oy | oz) nb = a.meta[b * NBR_STRIDE + DIR(ox, oy, oz)];
+            float v = __int_as_float(0x7fc00000);
+            if (nb >= 0) {
+                const int cell = (tx & 7) + 8 * (ty & 7) + 64 * (tz & 7);
+                const float q = a.s[nb * a.s_stride + cell];
+                if (a.obstacle[nb * CELLS + cell] == 0 && iso_finite(q)) v = q;
+            }
+            tile[i] = v;
+            seen |= (v >= a.value ? 1 : 0) | (v < a.value ? 2 : 0);
+        }
+    }
+    return seen;
+}
+
+// the eight corners of the cube anchored at (x, y, z) and its triangle count (0 when the cube is not live)
+__device__ __forceinline__ int iso_cube(float (&v)[8], const float *tile, const IsoArgs &a, const int32_t *row, int x, int y, int z)
+{
+    const int at = x + ISO_TILE * y + ISO_TILE2 * z;
+    bool live = true;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        v[c] = tile[at + (c & 1) + ISO_TILE * ((c >> 1) & 1) + ISO_TILE2 * (c >> 2)];
+        live = live && iso_finite(v[c]);
+    }
+    const int gx = (row[NBR_BX] - 1) * BS + x, gy = (row[NBR_BY] - 1) * BS + y, gz = (row[NBR_BZ] - 1) * BS + z;
+    live = live && gx >= a.lo[0] && gx < a.hi[0] && gy >= a.lo[1] && gy < a.hi[1] && gz >= a.lo[2] && gz < a.hi[2];
+    if (!live) return 0;
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        int m = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m |= (v[iso_tet_corner(k, j)] >= a.value ? 1 : 0) << j;
+        n += iso_case_triangles(m);
+    }
+    return n;
+}
+
+__global__ __launch_bounds__(256) void k_iso_count(int32_t *__restrict__ counts, const IsoArgs a)
+{
+    __shared__ float tile[ISO_TILE3];
+    __shared__ int wseen[4], wsum[4];
+    const int r = (int)blockIdx.x, t = (int)threadIdx.x;
+    if (a.skip[r]) {
+        if (t == 0) counts[r] = 0;
+        return;
+    }
+    const int64_t b = a.ref2int ? a.ref2int[r] : r;
+    const int seen = iso_stage_tile(tile, a, b, t);
+    const int s_in = __ballot(seen & 1) != 0, s_out = __ballot(seen & 2) != 0;
+    if ((t & 63) == 0) wseen[t >> 6] = s_in | (s_out << 1);
+    __syncthreads();
+    if (((wseen[0] | wseen[1]) | (wseen[2] | wseen[3])) != 3) {      // the tile does not straddle the value
+        if (t == 0) counts[r] = 0;
+        return;
+    }
+    const int c = 2 * t, x = c & 7, y = (c >> 3) & 7, z = c >> 6;
+    const int32_t *row = a.meta + b * NBR_STRIDE;
+    float v[8];
+    int n = iso_cube(v, tile, a, row, x, y, z);
+    n += iso_cube(v, tile, a, row, x + 1, y, z);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) n += __shfl_xor(n, o, 64);
+    if ((t & 63) == 0) wsum[t >> 6] = n;
+    __syncthreads();
+    if (t == 0) counts[r] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+struct IsoEmitArgs {
+    const int32_t *counts;     // [n_owned] what k_iso_count wrote
+    const int64_t *offsets;    // [n_owned] their exclusive scan
+    int64_t n_triangles;       // the total: nothing is written at or beyond it
+    const int32_t *int2ref;    // nullptr: the reference order is kept
+    const float *rho, *vel;
+    float *pos, *att;          // [n_triangles][3][3], [n_triangles][3][4]
+    int32_t *keys;             // [n_triangles][3][2]
+};
+
+// vertex `slot` (3 * triangle + corner of the triangle) on edge e of tetrahedron K of the cube anchored at (x, y, z) of internal block b
+template <int K>
+__device__ __forceinline__ void iso_vertex(const IsoArgs &a, const IsoEmitArgs &o, const float (&v)[8], const int64_t b,
+                                           const int32_t *row, int x, int y, int z, int e, int64_t slot)
+{
+    constexpr int c0 = iso_tet_corner(K, 0), c1 = iso_tet_corner(K, 1), c2 = iso_tet_corner(K, 2), c3 = iso_tet_corner(K, 3);
+    // tetrahedron edges 0..5 = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), two bits per end
+    const int i = (0x940 >> (2 * e)) & 3, j = (0xFB9 >> (2 * e)) & 3;
+    const int ci = iso_sel4(c0, c1, c2, c3, i), cj = iso_sel4(c0, c1, c2, c3, j);
+    const float si = iso_sel4(v[c0], v[c1], v[c2], v[c3], i), sj = iso_sel4(v[c0], v[c1], v[c2], v[c3], j);
+    const bool fwd = ci < cj;
+    const int ca = fwd ? ci : cj, cb = fwd ? cj : ci;
+    const float sa = fwd ? si : sj, sb = fwd ? sj : si;
+    float tt = (a.value - sa) / (sb - sa);
+    tt = fminf(fmaxf(tt, 0.0f), 1.0f);
+    const int ax = x + (ca & 1), ay = y + ((ca >> 1) & 1), az = z + (ca >> 2);
+    const int bx = x + (cb & 1), by = y + ((cb >> 1) & 1), bz = z + (cb >> 2);
+    const int gx = (row[NBR_BX] - 1) * BS, gy = (row[NBR_BY] - 1) * BS, gz = (row[NBR_BZ] - 1) * BS;
+    float *p = o.pos + 3 * slot;
+    p[0] = (float)(gx + ax) + tt * (float)(bx - ax);
+    p[1] = (float)(gy + ay) + tt * (float)(by - ay);
+    p[2] = (float)(gz + az) + tt * (float)(bz - az);
+    // the cells of a and b: every corner block of a live cube exists
+    int64_t na = b, nb = b;
+    if ((ax | ay | az) >> 3) na = row[DIR(ax >> 3, ay >> 3, az >> 3)];
+    if ((bx | by | bz) >> 3) nb = row[DIR(bx >> 3, by >> 3, bz >> 3)];
+    const int xa = (ax & 7) + 8 * (ay & 7) + 64 * (az & 7), xb = (bx & 7) + 8 * (by & 7) + 64 * (bz & 7);
+    const float ra = o.rho[na * CELLS + xa], rb = o.rho[nb * CELLS + xb];
+    float4 q;
+    q.x = ra + tt * (rb - ra);
+    const float *va = o.vel + na * 3 * CELLS + xa, *vb = o.vel + nb * 3 * CELLS + xb;
+    q.y = va[0] + tt * (vb[0] - va[0]);
+    q.z = va[CELLS] + tt * (vb[CELLS] - va[CELLS]);
+    q.w = va[2 * CELLS] + tt * (vb[2 * CELLS] - va[2 * CELLS]);
+    *(float4 *)(o.att + 4 * slot) = q;
+    const int32_t ka = (int32_t)(o.int2ref ? o.int2ref[na] : na) * CELLS + xa, kb = (int32_t)(o.int2ref ? o.int2ref[nb] : nb) * CELLS + xb;
+    *(int2 *)(o.keys + 2 * slot) = make_int2(ka, kb);
+}
+
+// the triangles of one live cube, from triangle `tri` on
+__device__ __forceinline__ void iso_emit_cube(const IsoArgs &a, const IsoEmitArgs &o, const float (&v)[8], const int64_t b,
+                                              const int32_t *row, int x, int y, int z, int64_t tri)
+{
+    // case = sum of 2^j over the inside corners j of the tetrahedron -> its triangles: bits 18..19 how many, then 3 bits per vertex, the
+    // tetrahedron edge it sits on; wound so that the normal points from the inside corners to the outside ones (every tetrahedron of
+    // the split has positive orientation); case 15 - m is case m reversed (isosurface.CASE_TRIANGLES)
+    const uint32_t cases[16] = {0x0, 0x40088, 0x400e0, 0x9c311, 0x40159, 0x95158, 0x8d160, 0x40162,
+                                0x4012a, 0xa5148, 0x9d150, 0x400e9, 0x94319, 0x40118, 0x40050, 0x0};
+#define LW_ISO_TET(K)                                                                                          \
+    {                                                                                                          \
+        int m = 0;                                                                                             \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) m |= (v[iso_tet_corner(K, j)] >= a.value ? 1 : 0) << j;  \
+        const uint32_t w = cases[m];                                                                           \
+        const int nv = 3 * (int)(w >> 18);                                                                     \
+        if (tri + (nv / 3) <= o.n_triangles)                                                                   \
+            for (int q = 0; q < nv; ++q) iso_vertex<K>(a, o, v, b, row, x, y, z, (int)((w >> (3 * q)) & 7u), 3 * tri + q); \
+        tri += nv / 3;                                                                                         \
+    }
+    LW_ISO_TET(0) LW_ISO_TET(1) LW_ISO_TET(2) LW_ISO_TET(3) LW_ISO_TET(4) LW_ISO_TET(5)
+#undef LW_ISO_TET
+}
+
+__global__ __launch_bounds__(256) void k_iso_emit(const IsoArgs a, const IsoEmitArgs o)
+{
+    __shared__ float tile[ISO_TILE3];
+    __shared__ int wsum[4];
+    const int r = (int)blockIdx.x, t = (int)threadIdx.x;
+    if (o.counts[r] == 0) return;
+    const int64_t b = a.ref2int ? a.ref2int[r] : r;
+    (void)iso_stage_tile(tile, a, b, t);
+    __syncthreads();
+    const int c = 2 * t, x = c & 7, y = (c >> 3) & 7, z = c >> 6;
+    const int32_t *row = a.meta + b * NBR_STRIDE;
+    float v[8];
+    const int n0 = iso_cube(v, tile, a, row, x, y, z), n1 = iso_cube(v, tile, a, row, x + 1, y, z);
+    // exclusive scan over the block's 512 cells in cell order: lanes hold consecutive pairs, waves consecutive lanes
+    int inc = n0 + n1;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(inc, d, 64);
+        if ((t & 63) >= d) inc += up;
+    }
+    if ((t & 63) == 63) wsum[t >> 6] = inc;
+    __syncthreads();
+    int before = inc - (n0 + n1);
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+        if (w < (t >> 6)) before += wsum[w];
+    const int64_t first = o.offsets[r] + before;
+    if (n0 > 0) {
+        (void)iso_cube(v, tile, a, row, x, y, z);
+        iso_emit_cube(a, o, v, b, row, x, y, z, first);
+    }
+    if (n1 > 0) {
+        (void)iso_cube(v, tile, a, row, x + 1, y, z);
+        iso_emit_cube(a, o, v, b, row, x + 1, y, z, first + n0);
+    }
+}
+
 // ---- internal storage (ludwig_hip.hip "block order", "block-major"): the caller's arrays keep the reference's layout,
 // [8,8,8,n_blocks,K] with the reference's block order; the device arrays hold the blocks in the library's own order, block-major.
 // ref2int[b_reference] = b_internal (nullptr = same order) ----

@@ -254,6 +254,18 @@ struct LudwigLevel {
     MonitorRecord *monitor_slab = nullptr;
     // wall diagnostics (ludwig_level_wall_census): the one device record, allocated by the first call
     WallCensusRecord *wall_census = nullptr;
+    // iso-surfaces (ludwig_level_isosurface_*): everything is allocated by the first extraction. iso_scalar: [n_blocks][512], the
+    // magnitudes that are stored nowhere; counts / offsets / skip: one entry per owned block in the reference block order; the triangle
+    // buffers hold iso_capacity triangles and grow when an extraction needs more.
+    float *iso_scalar = nullptr;
+    int32_t *iso_counts = nullptr;
+    int64_t *iso_offsets = nullptr;
+    uint8_t *iso_skip = nullptr;
+    int32_t *d_int2ref = nullptr;       // the internal -> reference block order on the device (a vertex key names reference blocks)
+    float *iso_pos = nullptr, *iso_att = nullptr;
+    int32_t *iso_keys = nullptr;
+    int64_t iso_capacity = 0;
+    int64_t iso_n = -1;                 // triangles of the last extraction (0 after a refusal); -1: none yet
 };
 
 namespace {
@@ -1152,6 +1164,11 @@ void ludwig_level_destroy(LudwigLevel *L)
     if (L->subgrid_sums) (void)hipFree(L->subgrid_sums);
     if (L->monitor_slab) (void)hipFree(L->monitor_slab);
     if (L->wall_census) (void)hipFree(L->wall_census);
+    {
+        void *iso[] = {L->iso_scalar, L->iso_counts, L->iso_offsets, L->iso_skip, L->d_int2ref, L->iso_pos, L->iso_att, L->iso_keys};
+        for (void *q : iso)
+            if (q) (void)hipFree(q);
+    }
     if (L->d_ref2int) (void)hipFree(L->d_ref2int);
     if (L->scratch) (void)hipFree(L->scratch);
     if (L->own_stream) (void)hipStreamDestroy(L->own_stream);
@@ -2477,6 +2494,131 @@ int ludwig_level_gradient_fields_download(const LudwigLevel *L, int which, float
     }
     return download_components(L, (const float *)L->grad, GRAD_COMPONENTS, first, K, host, "gradient fields download");
 }
+
+// ---- iso-surfaces (ludwig_level_isosurface_*; no reference counterpart) ----
+#define LW_ISO_TRY(expr) do { const int r_ = (expr); if (r_) return r_; } while (0)
+int ludwig_level_isosurface_extract(LudwigLevel *L, int which, int vel_field, float scale, float value, const uint8_t *skip,
+                                    const int32_t *cell_lo, const int32_t *cell_hi, int64_t max_triangles, int64_t *n_triangles)
+{
+    if (!L || !cell_lo || !cell_hi || !n_triangles) return fail(LUDWIG_ERR_INVALID, "isosurface: null argument");
+    *n_triangles = 0;
+    if (which < LUDWIG_ISO_DENSITY || which > LUDWIG_ISO_VORTICITY_MAGNITUDE) return fail(LUDWIG_ERR_INVALID, "isosurface: unknown scalar %d", which);
+    if (vel_field != LUDWIG_VEL && vel_field != LUDWIG_VEL_TEMP) return fail(LUDWIG_ERR_INVALID, "isosurface: vel_field must be LUDWIG_VEL or LUDWIG_VEL_TEMP");
+    if (!std::isfinite(value)) return fail(LUDWIG_ERR_INVALID, "isosurface: value %g must be finite", (double)value);
+    if (!std::isfinite(scale)) return fail(LUDWIG_ERR_INVALID, "isosurface: scale %g must be finite", (double)scale);
+    const bool gradient = which == LUDWIG_ISO_Q_CRITERION || which == LUDWIG_ISO_VORTICITY_MAGNITUDE;
+    if (gradient && scale == 0.0f) return fail(LUDWIG_ERR_INVALID, "isosurface: scale must be non-zero for a scalar of the velocity gradient");
+    for (int a = 0; a < 3; ++a)
+        if (cell_lo[a] > cell_hi[a]) return fail(LUDWIG_ERR_INVALID, "isosurface: cell_lo[%d] = %d > cell_hi[%d] = %d", a, cell_lo[a], a, cell_hi[a]);
+    if (max_triangles < 0) return fail(LUDWIG_ERR_INVALID, "isosurface: max_triangles %lld < 0", (long long)max_triangles);
+    if ((int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "isosurface: level has %d blocks, more than 32-bit vertex keys reach", L->n_blocks);
+    if (L->n_owned == 0) {                            // no owned blocks: the empty surface, nothing allocated
+        L->iso_n = 0;
+        return LUDWIG_OK;
+    }
+    LW_HIP(hipSetDevice(L->device));
+    LW_ENSURE_RHO(L);                                 // the attributes, and the scalar of LUDWIG_ISO_DENSITY
+    if (gradient) {
+        const int r = ludwig_level_gradient_fields_compute(L, vel_field, scale);
+        if (r) return r;
+    }
+    const float *vel = L->vel[vel_field == LUDWIG_VEL ? 0 : 1];
+    const size_t no = (size_t)L->n_owned;
+    if (!L->iso_counts) LW_ISO_TRY(dev_alloc(L, &L->iso_counts, no));
+    if (!L->iso_offsets) LW_ISO_TRY(dev_alloc(L, &L->iso_offsets, no));
+    if (!L->iso_skip) LW_ISO_TRY(dev_alloc(L, &L->iso_skip, no));
+    if (!L->ref2int.empty() && !L->d_int2ref) {
+        LW_ISO_TRY(dev_alloc(L, &L->d_int2ref, (size_t)L->n_blocks));
+        LW_HIP(hipMemcpyAsync(L->d_int2ref, L->int2ref.data(), (size_t)L->n_blocks * sizeof(int32_t), hipMemcpyHostToDevice, L->stream));
+    }
+    IsoArgs a;
+    if (which == LUDWIG_ISO_DENSITY) { a.s = L->rho; a.s_stride = CELLS; }
+    else if (which == LUDWIG_ISO_Q_CRITERION) { a.s = L->grad + 3 * CELLS; a.s_stride = GRAD_COMPONENTS * CELLS; }
+    else {
+        if (!L->iso_scalar) LW_ISO_TRY(dev_alloc(L, &L->iso_scalar, (size_t)L->sk));
+        if (which == LUDWIG_ISO_VELOCITY_MAGNITUDE)
+            hipLaunchKernelGGL(k_iso_scalar<ISO_VELOCITY_MAGNITUDE>, dim3((unsigned)L->n_blocks), dim3(CELLS / 2), 0, L->stream, L->iso_scalar, vel);
+        else
+            hipLaunchKernelGGL(k_iso_scalar<ISO_VORTICITY_MAGNITUDE>, dim3((unsigned)L->n_blocks), dim3(CELLS / 2), 0, L->stream, L->iso_scalar,
+                               (const float *)L->grad);
+        LW_HIP(hipGetLastError());
+        a.s = L->iso_scalar; a.s_stride = CELLS;
+    }
+    a.obstacle = L->obstacle;
+    a.meta = L->meta;
+    a.ref2int = L->d_ref2int;
+    a.skip = L->iso_skip;
+    for (int i = 0; i < 3; ++i) { a.lo[i] = cell_lo[i]; a.hi[i] = cell_hi[i]; }
+    a.value = value;
+    // the owned blocks are the first n_owned of the reference order; the caller's array is read before this call returns (the count
+    // below synchronizes)
+    if (skip) LW_HIP(hipMemcpyAsync(L->iso_skip, skip, no, hipMemcpyHostToDevice, L->stream));
+    else LW_HIP(hipMemsetAsync(L->iso_skip, 0, no, L->stream));
+    hipLaunchKernelGGL(k_iso_count, dim3((unsigned)no), dim3(CELLS / 2), 0, L->stream, L->iso_counts, a);
+    LW_HIP(hipGetLastError());
+    std::vector<int32_t> counts(no);
+    LW_HIP(hipMemcpyAsync(counts.data(), L->iso_counts, no * sizeof(int32_t), hipMemcpyDeviceToHost, L->stream));
+    LW_HIP(hipStreamSynchronize(L->stream));
+    std::vector<int64_t> offsets(no);
+    int64_t total = 0;
+    for (size_t r = 0; r < no; ++r) {
+        offsets[r] = total;
+        total += counts[r];
+    }
+    *n_triangles = total;
+    L->iso_n = 0;
+    if (total > max_triangles) return LUDWIG_ISO_REFUSED;     // the caller reports it; nothing is allocated for a surface nobody can hold
+    if (total == 0) return LUDWIG_OK;
+    if (total > L->iso_capacity) {
+        float **fb[] = {&L->iso_pos, &L->iso_att};
+        for (float **q : fb)
+            if (*q) { (void)hipFree(*q); *q = nullptr; }
+        if (L->iso_keys) { (void)hipFree(L->iso_keys); L->iso_keys = nullptr; }
+        L->iso_capacity = 0;
+        LW_ISO_TRY(dev_alloc(L, &L->iso_pos, (size_t)total * ISO_POS_FLOATS));
+        LW_ISO_TRY(dev_alloc(L, &L->iso_att, (size_t)total * ISO_ATT_FLOATS));
+        LW_ISO_TRY(dev_alloc(L, &L->iso_keys, (size_t)total * ISO_KEY_INTS));
+        L->iso_capacity = total;
+    }
+    LW_HIP(hipMemcpyAsync(L->iso_offsets, offsets.data(), no * sizeof(int64_t), hipMemcpyHostToDevice, L->stream));
+    IsoEmitArgs o;
+    o.counts = L->iso_counts;
+    o.offsets = L->iso_offsets;
+    o.n_triangles = total;
+    o.int2ref = L->d_int2ref;
+    o.rho = L->rho;
+    o.vel = vel;
+    o.pos = L->iso_pos;
+    o.att = L->iso_att;
+    o.keys = L->iso_keys;
+    hipLaunchKernelGGL(k_iso_emit, dim3((unsigned)no), dim3(CELLS / 2), 0, L->stream, a, o);
+    LW_HIP(hipGetLastError());
+    LW_HIP(hipStreamSynchronize(L->stream));                  // `offsets` leaves scope
+    L->iso_n = total;
+    return LUDWIG_OK;
+}
+
+int ludwig_level_isosurface_download(LudwigLevel *L, float *positions, size_t position_bytes, float *attributes, size_t attribute_bytes,
+                                     int32_t *keys, size_t key_bytes)
+{
+    if (!L) return fail(LUDWIG_ERR_INVALID, "null level");
+    if (L->iso_n < 0) return fail(LUDWIG_ERR_STATE, "isosurface: download before ludwig_level_isosurface_extract");
+    const size_t n = (size_t)L->iso_n;
+    const size_t want[3] = {n * ISO_POS_FLOATS * sizeof(float), n * ISO_ATT_FLOATS * sizeof(float), n * ISO_KEY_INTS * sizeof(int32_t)};
+    if (position_bytes != want[0] || attribute_bytes != want[1] || key_bytes != want[2])
+        return fail(LUDWIG_ERR_INVALID, "isosurface: got %zu, %zu, %zu bytes, expected %zu, %zu, %zu", position_bytes, attribute_bytes, key_bytes,
+                    want[0], want[1], want[2]);
+    if (n == 0) return LUDWIG_OK;
+    if (!positions || !attributes || !keys) return fail(LUDWIG_ERR_INVALID, "isosurface: null output");
+    LW_HIP(hipSetDevice(L->device));
+    LW_HIP(hipStreamSynchronize(L->stream));
+    LW_HIP(hipMemcpy(positions, L->iso_pos, want[0], hipMemcpyDeviceToHost));
+    LW_HIP(hipMemcpy(attributes, L->iso_att, want[1], hipMemcpyDeviceToHost));
+    LW_HIP(hipMemcpy(keys, L->iso_keys, want[2], hipMemcpyDeviceToHost));
+    return LUDWIG_OK;
+}
+#undef LW_ISO_TRY
 
 // ---- subgrid model (ludwig_level_subgrid_*; no reference counterpart) ----
 static int subgrid_model_known(const LudwigLevel *L, const char *what)

@@ -92,6 +92,41 @@ def write_vtu(filename: str, points: np.ndarray, connectivity: np.ndarray, offse
     return path
 
 
+def write_vtp(filename: str, points: np.ndarray, triangles: np.ndarray, density: np.ndarray, velocity: np.ndarray, level: np.ndarray,
+              compress: bool = True) -> str:
+    """VTK XML PolyData of an iso-surface (no reference counterpart; isosurface.py): welded points [n, 3] Float32 in the flow file's
+    frame, triangles [m, 3] of point indices, point arrays Density, Velocity, VelocityMagnitude = sqrt((ux^2 + uy^2) + uz^2) of the
+    interpolated components, cell array Level (Int32). Written whole, then renamed. Returns the path."""
+    path = filename if filename.endswith(".vtp") else filename + ".vtp"
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    tri = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    rho = np.ascontiguousarray(density, dtype=np.float32).reshape(-1)
+    vel = np.ascontiguousarray(velocity, dtype=np.float32).reshape(-1, 3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mag = np.sqrt((vel[:, 0] * vel[:, 0] + vel[:, 1] * vel[:, 1]) + vel[:, 2] * vel[:, 2]).astype(np.float32)
+    comp_attr = ' compressor="vtkZLibDataCompressor"' if compress else ""
+    tmp = path + ".part"
+    with open(tmp, "w") as io:
+        io.write('<?xml version="1.0" encoding="utf-8"?>\n')
+        io.write(f'<VTKFile type="PolyData" version="1.0" byte_order="LittleEndian" header_type="UInt64"{comp_attr}>\n')
+        io.write("<PolyData>\n")
+        io.write(f'<Piece NumberOfPoints="{pts.shape[0]}" NumberOfVerts="0" NumberOfLines="0" NumberOfStrips="0" '
+                 f'NumberOfPolys="{tri.shape[0]}">\n')
+        io.write("<Points>\n" + _data_array("Points", pts, compress, 3) + "</Points>\n")
+        io.write("<Polys>\n")
+        io.write(_data_array("connectivity", tri.reshape(-1), compress))
+        io.write(_data_array("offsets", np.arange(1, tri.shape[0] + 1, dtype=np.int64) * 3, compress))
+        io.write("</Polys>\n<PointData>\n")
+        io.write(_data_array("Density", rho, compress))
+        io.write(_data_array("Velocity", vel, compress, 3))
+        io.write(_data_array("VelocityMagnitude", mag, compress))
+        io.write("</PointData>\n<CellData>\n")
+        io.write(_data_array("Level", np.ascontiguousarray(level, dtype=np.int32).reshape(-1), compress))
+        io.write("</CellData>\n</Piece>\n</PolyData>\n</VTKFile>\n")
+    os.replace(tmp, path)
+    return path
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # flow export (src/io_vtk.jl)
 # ----------------------------------------------------------------------------------------------------------------

@@ -125,6 +125,13 @@ class CaseConfig:
     slices_start_step: int = 1
     slices_interval: int = 1
     slices_planes: Tuple["SlicePlane", ...] = ()
+    # iso-surfaces, advanced.isosurfaces (no reference counterpart): surfaces extracted on the device every `interval` coarse steps
+    # from `start_step`, written to iso_<name>_%06d.vtp and iso_<name>.pvd (isosurface.py)
+    isosurfaces_enabled: bool = False
+    isosurfaces_start_step: int = 1
+    isosurfaces_interval: int = 1
+    isosurfaces_max_triangles: int = 50_000_000
+    isosurfaces_surfaces: Tuple["IsoSurfaceSpec", ...] = ()
     # flow monitor, advanced.flow_monitor (no reference counterpart; its advanced.diagnostics.stability_check is read by nobody, there or
     # here): a health record of every level at every diagnostics step, written to flow_monitor.csv (monitor.py)
     flow_monitor_enabled: bool = False
@@ -178,6 +185,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
                                           bool(g("advanced", "forces", "enabled", default=True)))
     probes = _probes_config(g("advanced", "probes", default=None))
     slices = _slices_config(g("advanced", "slices", default=None))
+    isosurfaces = _isosurfaces_config(g("advanced", "isosurfaces", default=None))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
     wall_diag = _wall_diagnostics_config(g("advanced", "wall_diagnostics", default=None))
     return CaseConfig(
@@ -234,6 +242,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **forces_series,
         **probes,
         **slices,
+        **isosurfaces,
         **flow_monitor,
         **wall_diag,
         y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
@@ -409,6 +418,73 @@ def _slices_config(sc) -> dict:
                 raise ValueError(f"{where}: {n} points, more than {SLICE_MAX_POINTS} per plane")
         planes.append(SlicePlane(name, "xyz".index(normal), position, bounds, spacing, tuple(f for f in SLICE_FIELDS if f in fields)))
     return dict(slices_enabled=True, slices_start_step=start, slices_interval=interval, slices_planes=tuple(planes))
+
+
+ISOSURFACE_FIELDS = ("density", "velocity_magnitude", "q_criterion", "vorticity_magnitude")      # isosurface.FIELDS
+
+
+@dataclass(frozen=True)
+class IsoSurfaceSpec:
+    """one surface of advanced.isosurfaces.surfaces (semantics: isosurface.py)"""
+    name: str
+    field: str                                              # one of ISOSURFACE_FIELDS
+    value: float
+    bounds: Optional[Tuple[Tuple[float, float], Tuple[float, float], Tuple[float, float]]] = None   # x, y, z; STL frame; None: everything
+
+
+def _isosurfaces_config(ic) -> dict:
+    """advanced.isosurfaces: {enabled: false, start_step: 1, interval: 1, max_triangles: 50000000, surfaces: [{name, field, value,
+    bounds?}]} -> CaseConfig fields. Absent or disabled: the defaults."""
+    if ic is None:
+        return {}
+    if not isinstance(ic, dict):
+        raise ValueError("advanced.isosurfaces must be a mapping")
+    if not bool(ic.get("enabled", False)):
+        return {}
+    start, interval, cap = int(ic.get("start_step", 1)), int(ic.get("interval", 1)), int(ic.get("max_triangles", 50_000_000))
+    if interval < 1:
+        raise ValueError(f"advanced.isosurfaces.interval must be >= 1, got {interval}")
+    if start < 1:
+        raise ValueError(f"advanced.isosurfaces.start_step must be >= 1, got {start}")
+    if cap < 1:
+        raise ValueError(f"advanced.isosurfaces.max_triangles must be >= 1, got {cap}")
+    raw = ic.get("surfaces") or []
+    if not isinstance(raw, (list, tuple)) or not raw:
+        raise ValueError("advanced.isosurfaces.enabled needs at least one entry in advanced.isosurfaces.surfaces")
+    surfaces, seen = [], set()
+    for i, sc in enumerate(raw):
+        where = f"advanced.isosurfaces.surfaces[{i}]"
+        if not isinstance(sc, dict):
+            raise ValueError(f"{where} must be a mapping")
+        name = str(sc.get("name", ""))
+        if not name or not all(ch.isalnum() or ch in "_-." for ch in name) or name.startswith("."):
+            raise ValueError(f"{where}.name {name!r} is not a plain file-name stem")
+        if name in seen:
+            raise ValueError(f"{where}.name {name!r} is not unique")
+        seen.add(name)
+        field = str(sc.get("field", ""))
+        if field not in ISOSURFACE_FIELDS:
+            raise ValueError(f"{where}.field {sc.get('field')!r} is unknown (one of {', '.join(ISOSURFACE_FIELDS)})")
+        if "value" not in sc:
+            raise ValueError(f"{where}.value is required")
+        try:
+            value = float(sc["value"])
+        except (TypeError, ValueError):
+            raise ValueError(f"{where}.value {sc['value']!r} is not a number") from None
+        if not math.isfinite(value):
+            raise ValueError(f"{where}.value {value} is not finite")
+        bounds = sc.get("bounds")
+        if bounds is not None:
+            ok = isinstance(bounds, (list, tuple)) and len(bounds) == 3 and all(isinstance(b, (list, tuple)) and len(b) == 2 for b in bounds)
+            if not ok:
+                raise ValueError(f"{where}.bounds must be [[x0, x1], [y0, y1], [z0, z1]], got {bounds!r}")
+            bounds = tuple((float(b[0]), float(b[1])) for b in bounds)
+            for lo, hi in bounds:
+                if not (math.isfinite(lo) and math.isfinite(hi)) or not lo < hi:
+                    raise ValueError(f"{where}.bounds {list(map(list, bounds))} must be finite with lower < upper")
+        surfaces.append(IsoSurfaceSpec(name, field, value, bounds))
+    return dict(isosurfaces_enabled=True, isosurfaces_start_step=start, isosurfaces_interval=interval, isosurfaces_max_triangles=cap,
+                isosurfaces_surfaces=tuple(surfaces))
 
 
 # ----------------------------------------------------------------------------------------------------------------
