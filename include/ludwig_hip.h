@@ -514,6 +514,40 @@ int  ludwig_slices_sample(LudwigSlices *slices, int64_t t_coarse);
 /* the last sample: bytes = n_rows * n_points * 4 (n_rows 5, or 9 with LUDWIG_SLICE_GRADIENT). Synchronizes the levels' streams. */
 int  ludwig_slices_download(LudwigSlices *slices, float *values, size_t bytes);
 
+/* ---- streamlines: lines traced through the level hierarchy on the device (no reference counterpart) ----
+ * A streamline set is made over a level array, all of it: every level must have been created with block_pointer, hold no ghost blocks
+ * and lie on one device. The kernel locates a moving point on the hierarchy itself, through each level's dense block_pointer. Float32,
+ * no contraction; open_ludwig_amd/streamlines.py (trace_host) restates every bit.
+ * A position P is three floats in cell units of level index 0, domain frame (a point of the flow file divided by that level's dx). On
+ * level index li the cell coordinate is g = P 2^li - 0.5f. sample(P): from the finest level down, the level holds P iff every g_a is
+ * finite, 0 <= g_a and floorf(g_a) <= 8 grid_dim_a - 1 (tested in float), and block_pointer[floorf(g) / 8] > 0; the finest such level
+ * is chosen, none: code 1 (a periodic neighbour is not followed). Base cell i0 = floorf(g); an obstacle cell: code 2. Weights
+ * g - floorf(g); corners i0 + {0,1}^3, c = dx + 2 dy + 4 dz, each found through block_pointer; a corner outside the grid, in an absent
+ * block or in an obstacle cell is replaced by the base cell; rho, ux, uy, uz trilinear as ludwig_probes_* (x, then y, then z).
+ * A line from seed P with sign s: k = 0; loop: (rho, u, li) = sample(P), on failure the line ends with that code and P is no vertex;
+ * vertex k = (P, rho, u, li); k == max_steps: code 0; m = sqrtf((ux ux + uy uy) + uz uz), !(m >= min_speed): code 3;
+ * h = step 2^-li; Pm = P + (0.5f h) (s u / m) per component (divide, times s, times 0.5f h, add); um = sample(Pm) (its code ends the
+ * line), mm likewise, !(mm >= min_speed): code 3; P = P + h (s um / mm); k += 1. A line has 0 .. max_steps + 1 vertices. */
+typedef struct LudwigStreamlines LudwigStreamlines;   /* opaque */
+enum { LUDWIG_STREAM_END_STEPS = 0, LUDWIG_STREAM_END_OUTSIDE = 1, LUDWIG_STREAM_END_OBSTACLE = 2, LUDWIG_STREAM_END_SLOW = 3 };
+/* seeds: 3 n_lines floats; sign: n_lines floats, each 1 or -1; step > 0 in cells of the level a step starts on; max_steps >= 0.
+ * Uploads every level's block_pointer (in the library's block order) and allocates [n_lines][max_steps + 1] records of 8 floats
+ * (x, y, z, rho, ux, uy, uz, level index as a float), counts and codes. n_lines = 0 is allowed (seeds, sign may be NULL) and never
+ * launches. LUDWIG_ERR_STATE: a level without block_pointer or with ghost blocks, or levels on different devices; LUDWIG_ERR_INVALID:
+ * step <= 0 or not finite, max_steps < 0, more than 2^31 - 1 records, a sign that is not +-1, n_levels not in 1..30. */
+int  ludwig_streamlines_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_lines, const float *seeds, const float *sign,
+                               float step, float min_speed, int32_t max_steps, LudwigStreamlines **out);
+/* frees the set, not the levels */
+void ludwig_streamlines_destroy(LudwigStreamlines *set);
+/* trace every line through every level's newest state after coarse step t_coarse (level index li: sub-step 2^li (t_coarse + 1) - 1,
+ * vel_temp if that is even, vel if odd; rho as a download would return it). One launch on the first level's stream, ordered after
+ * everything queued on the other levels' streams, which in turn wait for it. Writes only the set's own buffers. */
+int  ludwig_streamlines_trace(LudwigStreamlines *set, int64_t t_coarse);
+/* the last trace: counts and codes [n_lines] int32, vertices [n_lines][max_steps + 1][8] floats of which the first max(count)
+ * records of each line are brought down (the rest of the caller's array is left alone); bytes = the size of the whole vertex array.
+ * Synchronizes. LUDWIG_ERR_STATE before the first trace. */
+int  ludwig_streamlines_download(LudwigStreamlines *set, int32_t *counts, int32_t *codes, float *vertices, size_t bytes);
+
 /* ---- subgrid model: the WALE eddy viscosity the step collides with, and its time-averaged measures (no reference counterpart for the
  * output; the model is perform_timestep_v2!'s, src/physics_kernels.jl:251-300) ----
  * Per cell of the blocks this device owns, from one velocity buffer u: the gradient in lattice units g_ij = 0.5f (u_i(+e_j) - u_i(-e_j))

@@ -227,6 +227,33 @@ slices_sample!(s::Ptr{Cvoid}, t_coarse::Integer) = check(ccall((:ludwig_slices_s
 slices_download!(values::Matrix{Float32}, s::Ptr{Cvoid}) =
     GC.@preserve values check(ccall((:ludwig_slices_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), s, values, sizeof(values)))
 
+# streamlines (no reference counterpart): lines traced through ALL levels on the device; the kernel locates every point itself
+const STREAM_END_STEPS = Int32(0)
+const STREAM_END_OUTSIDE = Int32(1)
+const STREAM_END_OBSTACLE = Int32(2)
+const STREAM_END_SLOW = Int32(3)
+"""a streamline set over every level of `grids` (each created with block_pointer, without ghost blocks): seeds 3 x n Float32 in cell
+units of the first level (domain frame), sign n Float32 (1 or -1), step in cells of the level a step starts on, min_speed, max_steps.
+Free it with `streamlines_destroy`."""
+function streamlines_create(grids::Vector{DeviceLevel}, seeds::Matrix{Float32}, sign::Vector{Float32}, step::Real, min_speed::Real,
+                            max_steps::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles seeds sign check(ccall((:ludwig_streamlines_create, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Cfloat, Cfloat, Int32, Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int32(length(sign)), seeds, sign, Float32(step), Float32(min_speed), Int32(max_steps), out))
+    return out[]
+end
+streamlines_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_streamlines_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""trace every line through the newest state of all levels after coarse step `t_coarse` (one launch, queued)"""
+streamlines_trace!(s::Ptr{Cvoid}, t_coarse::Integer) =
+    check(ccall((:ludwig_streamlines_trace, LIB), Cint, (Ptr{Cvoid}, Int64), s, Int64(t_coarse)))
+"""the last trace into counts and codes (n Int32) and vertices (8 x (max_steps + 1) x n Float32: x, y, z, rho, ux, uy, uz, level
+index; only the first maximum(counts) records of each line are written)"""
+streamlines_download!(counts::Vector{Int32}, codes::Vector{Int32}, vertices::Array{Float32,3}, s::Ptr{Cvoid}) =
+    GC.@preserve counts codes vertices check(ccall((:ludwig_streamlines_download, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Csize_t), s, counts, codes, vertices, sizeof(vertices)))
+
 # surface statistics (no reference counterpart): 7 float64 sums per triangle of p, p^2, tau, |tau|, |tau|^2 at its nearest fluid cell
 """a surface set on `grid`: per triangle its nearest fluid cell (0-based reference block index, -1 = none; cell x + 8y + 64z), wall
 distance in lattice units and normal (3 x n); tau and the two scales from `sp`. Free it with `surface_stats_destroy`."""

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_surface_stats_create", "ludwig_surface_stats_destroy", "ludwig_surface_stats_reset", "ludwig_surface_stats_accumulate",
     "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
     "ludwig_slices_create", "ludwig_slices_destroy", "ludwig_slices_sample", "ludwig_slices_download",
+    "ludwig_streamlines_create", "ludwig_streamlines_destroy", "ludwig_streamlines_trace", "ludwig_streamlines_download",
     "ludwig_level_monitor",
     "ludwig_level_isosurface_extract", "ludwig_level_isosurface_download",
     "ludwig_level_wall_census", "ludwig_wall_surface_create", "ludwig_wall_surface_destroy", "ludwig_wall_surface_compute",
@@ -222,6 +223,10 @@ def load() -> C.CDLL:
         "ludwig_slices_destroy": (None, [vp]),
         "ludwig_slices_sample": (C.c_int, [vp, i64]),
         "ludwig_slices_download": (C.c_int, [vp, vp, C.c_size_t]),
+        "ludwig_streamlines_create": (C.c_int, [vp, i32, i32, vp, vp, f32, f32, i32, C.POINTER(vp)]),
+        "ludwig_streamlines_destroy": (None, [vp]),
+        "ludwig_streamlines_trace": (C.c_int, [vp, i64]),
+        "ludwig_streamlines_download": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),
         "ludwig_level_isosurface_extract": (C.c_int, [vp, i32, i32, f32, f32, vp, vp, vp, i64, C.POINTER(C.c_int64)]),
         "ludwig_level_isosurface_download": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]),
         "ludwig_level_wall_census": (C.c_int, [vp, i64, C.POINTER(WallCensus)]),

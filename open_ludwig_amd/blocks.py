@@ -402,6 +402,30 @@ class DeviceLevel(_lib.Handle):
                                                               keys.ctypes.data if nt else None, keys.nbytes))
         return nt, pos, att, keys
 
+    # -- streamlines (streamlines.py; no reference counterpart) --
+    def streamlines_setup(self, seeds, sign, step=0.5, min_speed=1.0e-6, max_steps: int = 2000):
+        """a streamline set over this level alone (a hierarchy: streamlines.DeviceStreamlines over all its levels): seeds [n, 3]
+        float32 in cell units of the level, sign [n] +-1. Replaces the level's earlier set; close() frees it."""
+        from .streamlines import DeviceStreamlines
+        old = getattr(self, "_streamlines", None)
+        if old is not None:
+            old.close()
+        self._streamlines = DeviceStreamlines([self], seeds, sign, step, min_speed, max_steps)
+        return self._streamlines
+
+    def close(self) -> None:
+        old = getattr(self, "_streamlines", None)
+        if old is not None:
+            old.close()
+            self._streamlines = None
+        super().close()
+
+    def streamlines(self, t_coarse: int):
+        """trace the set of streamlines_setup through the state after coarse step t_coarse (vel_temp if t_coarse is even, vel if odd)
+        -> (counts, codes, records [n, max_steps + 1, 8])"""
+        self._streamlines.trace(t_coarse)
+        return self._streamlines.download()
+
     # -- subgrid model (subgrid.py; no reference counterpart for the output) --
     def subgrid_fields(self, vel_name: str) -> Tuple[np.ndarray, np.ndarray]:
         """nu_t (after the background floor) and the branch code as a float, both Float32 [8,8,8,n_blocks] (reference layout, ghost

@@ -22,6 +22,7 @@ from . import isosurface as iso_mod
 from . import monitor as monitor_mod
 from . import probes as probes_mod
 from . import slices as slices_mod
+from . import streamlines as stream_mod
 from . import statistics as stats_mod
 from . import subgrid as subgrid_mod
 from . import surface_stats as surface_mod
@@ -69,6 +70,7 @@ class HipStepper:
         self.forces = None                     # force_series_setup
         self._fseries = None
         self._surface_plan = None              # (mesh, params, plan) of the surface statistics, shared with the force series
+        self.stream_set = None                 # streamlines_setup
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.probes is None and self.forces is None:
@@ -237,6 +239,22 @@ class HipStepper:
         return self.dev[level].isosurface(field, value, vel_name, np.float32(1.0 / self.host[level].dx), skip, cell_lo, cell_hi,
                                           max_triangles, download)
 
+    # -- streamlines (streamlines.py; no reference counterpart) --
+    def streamlines_setup(self, seeds, sign, step=0.5, min_speed=1.0e-6, max_steps: int = 2000, start_step: int = 1,
+                          interval: int = 1) -> None:
+        """one device set over every level: seeds [n, 3] float32 in cell units of level 1 (streamlines.seed_positions), sign [n] +-1;
+        the caller traces after the coarse steps start_step + k interval (run_case cuts its batches there)"""
+        self._stream_steps = stream_mod.check_schedule(start_step, interval)
+        if self.stream_set is not None:
+            self.stream_set.close()
+        self.stream_set = stream_mod.DeviceStreamlines(self.dev, seeds, sign, step, min_speed, max_steps)
+
+    def streamlines(self, t_coarse: int):
+        """trace every line through the newest state of all levels after coarse step t_coarse (the last batch must have ended there):
+        (counts [n], codes [n], records [n, max_steps + 1, 8])"""
+        self.stream_set.trace(t_coarse)
+        return self.stream_set.download()
+
     # -- subgrid model (subgrid.py; no reference counterpart for the output) --
     def subgrid_fields(self, level: int, vel_name: str):
         """(nu_t [8,8,8,nb], branch code as a float [8,8,8,nb]) of a level from its `vel_name` buffer (Float32)"""
@@ -259,6 +277,9 @@ class HipStepper:
 
     def close(self):
         _close_observers(self)
+        if self.stream_set is not None:
+            self.stream_set.close()
+            self.stream_set = None
         for d in self.dev:
             d.close()
 
@@ -810,6 +831,11 @@ class DistributedStepper:
         raise RuntimeError("advanced.isosurfaces is enabled, but a distributed run cannot extract iso-surfaces yet: ghost blocks hold no "
                            "gradient fields and only part of rho / vel (DESIGN section 8, Next)")
 
+    # -- streamlines: not over ranks. A line wanders through every level and every block, and a rank holds only its own --
+    def streamlines_setup(self, *args, **kwargs) -> None:
+        raise RuntimeError("advanced.streamlines is enabled, but a distributed run cannot trace streamlines yet: a line crosses the "
+                           "ranks' blocks, and each rank holds only its own (DESIGN section 8, Next)")
+
     # -- subgrid model: every rank works on its owned blocks after batch(); the face stencil is the gradient fields', so their argument
     # holds unchanged (the 'vel' halo ghosts are current for both buffers) --
     def subgrid_fields(self, level: int, vel_name: str):
@@ -894,6 +920,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     the stepper offers isosurface, else from downloaded fields (isosurface.extract_host). The levels are merged in ascending order into
     iso_<name>_%06d.vtp, listed in iso_<name>.pvd; a sample of more than max_triangles triangles writes no file and logs one line
     (isosurface.py). A stepper whose isosurfaces_setup raises (the distributed one) ends the run before the first step.
+    With cfg.streamlines_enabled, every seed group's lines are traced after the coarse steps start_step + k interval - batches are cut
+    there as for slices - through the newest state of all levels: on the device where the stepper offers streamlines, else from
+    downloaded fields (streamlines.trace_host). Each group is written to stream_<name>_%06d.vtp, listed in stream_<name>.pvd; lines of
+    fewer than two vertices are left out of the file and counted in the log (streamlines.py). A stepper whose streamlines_setup raises
+    (the distributed one) ends the run before the first step.
     With cfg.flow_monitor_enabled, a monitor.Record of every level is taken at every diagnostics step and after the last step, from the
     state at batch end (where rho_min is taken; no batch is cut) - on the device where the stepper offers monitor, else from downloaded
     fields (monitor.host_monitor); flow_monitor.csv gains one row per level and the warnings go to `log`. With
@@ -932,6 +963,19 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             if hasattr(st, "close"):
                 st.close()
             raise
+    stream_on = bool(cfg.streamlines_enabled)
+    stream_start, stream_interval = cfg.streamlines_start_step, cfg.streamlines_interval
+    if stream_on:
+        stream_plan = stream_mod.SeedPlan([(s.name, np.asarray(s.points, dtype=np.float64)) for s in cfg.streamlines_seeds],
+                                          cfg.streamlines_direction, params.mesh_offset, grids[0].dx)
+        if hasattr(st, "streamlines_setup"):
+            try:
+                st.streamlines_setup(stream_plan.seeds, stream_plan.sign, cfg.streamlines_step, cfg.streamlines_min_speed,
+                                     cfg.streamlines_max_steps, stream_start, stream_interval)
+            except Exception:
+                if hasattr(st, "close"):
+                    st.close()
+                raise
     wall_on = bool(cfg.wall_diagnostics_enabled)
     if wall_on and not hasattr(st, "wall_diagnostics_setup"):
         if hasattr(st, "close"):
@@ -992,6 +1036,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                 io.write(fseries_mod.csv_header() + "\n")
         if slices_on:
             slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
+        if stream_on:
+            stream_writer = stream_mod.StreamlineWriter(out_dir, stream_plan, params.time_scale)
         if iso_on:
             iso_writer = iso_mod.IsoWriter(out_dir, [s.name for s in cfg.isosurfaces_surfaces], params.time_scale)
         if probes_on:
@@ -1065,6 +1111,19 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             elif writing:
                 iso_writer.write(step, spec.name, iso_mod.merge_levels(parts))
 
+    def take_streamlines(step):
+        """every group's lines through the state after coarse step `step`; files out, one log line per group"""
+        if hasattr(st, "streamlines"):
+            counts, codes, records = st.streamlines(step)
+        else:
+            counts, codes, records = stream_mod.trace_host(stream_mod.stepper_levels(st, grids, step), stream_plan.seeds, stream_plan.sign,
+                                                           cfg.streamlines_step, cfg.streamlines_min_speed, cfg.streamlines_max_steps)
+        if writing:
+            stream_writer.write(step, counts, codes, records)
+        if log:
+            for gi, name in enumerate(stream_plan.names):
+                log(f"streamlines {name!r}: step {step}: {stream_mod.summary(stream_plan, gi, counts, codes)}")
+
     def wall_values(state_step):
         """the wall-surface values of the state after coarse step state_step, evaluated once per step (collective in a distributed run)"""
         if wall_taken[0] != state_step:
@@ -1127,7 +1186,7 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if stats_on or surf_host is not None or slices_on or iso_on:
+            if stats_on or surf_host is not None or slices_on or iso_on or stream_on:
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
@@ -1138,6 +1197,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     cuts.update(stats_mod.sample_steps(t, batch_end, sl_start, sl_interval))
                 if iso_on:
                     cuts.update(stats_mod.sample_steps(t, batch_end, iso_start, iso_interval))
+                if stream_on:
+                    cuts.update(stats_mod.sample_steps(t, batch_end, stream_start, stream_interval))
                 seg = t
                 for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
@@ -1161,6 +1222,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                             slice_writer.write(s_step, got)
                     if iso_on and stats_mod.is_sample_step(s_step, iso_start, iso_interval):
                         take_isosurfaces(s_step)
+                    if stream_on and stats_mod.is_sample_step(s_step, stream_start, stream_interval):
+                        take_streamlines(s_step)
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)

@@ -1384,6 +1384,174 @@ __global__ __launch_bounds__(64) void k_slice_sample(float *__restrict__ out, in
     }
 }
 
+// ---- streamlines (ludwig_streamlines_*; no reference counterpart; include/ludwig_hip.h states the definition and
+// open_ludwig_amd/streamlines.py restates it in numpy bit for bit) ----
+// The one observer whose points move: nothing is planned on the host, the kernel locates every point on the level hierarchy itself
+// (stream_sample). Eight lanes per line, one wave = eight lines. A pass is a chain of dependent loads - block_pointer of every level,
+// block_pointer of the corner, obstacle, then rho and u - 2 max_steps samples long, so the lanes of a group split what is independent:
+//   locate: lane c tests level n_levels - 1 - c (8 levels per round; all lookups in flight together), the finest hit wins through a
+//           shuffle maximum;
+//   gather: lane c finds stencil corner c = dx + 2 dy + 4 dz on the chosen level and loads its obstacle flag and its four values; a
+//           corner that is no fluid cell of the level takes the base cell's values from lane 0 (the probes' rule);
+//   lerp:   three rounds of __shfl_xor (1: x, 2: y, 4: z), every lane evaluating probe_lerp on its pair, so that after the third all
+//           eight hold the probes' result; the position update is then computed by all eight alike.
+// The lanes of a group run the same control flow on the same bits, so a shuffle always meets its seven partners. No index depends on
+// unchecked data: a coordinate is converted to an integer only after the float range test, a block index is used only when the
+// block_pointer entry is positive (the set's creation has checked every entry against the level's block count). Lanes 0 and 1 write a
+// vertex's 32-byte record as one float4 each. Nothing but the set's own buffers is written.
+struct StreamLevel {
+    const int32_t *bp;           // [gx][gy][gz], x fastest: internal block + 1, 0 = absent
+    const uint8_t *obstacle;     // [block][512]
+    const float *rho;            // [block][512]
+    const float *vel[2];         // vel, vel_temp: [block][3][512]
+    int32_t gx, gy, gz;          // blocks per axis
+    int32_t n_blocks;
+};
+
+struct StreamArgs {
+    const StreamLevel *lv;       // [n_levels] in device memory: a lane indexes it with its own level
+    int32_t n_levels;
+    uint32_t temp_mask;          // bit li: level li's newest velocity is vel_temp
+    const float *seeds;          // [n_lines][3]
+    const float *sign;           // [n_lines] +-1
+    int32_t n_lines, max_steps;
+    float step, min_speed;
+    float *rec;                  // [n_lines][max_steps + 1][8]
+    int32_t *counts, *codes;     // [n_lines]
+};
+
+constexpr int STREAM_END_STEPS = 0, STREAM_END_OUTSIDE = 1, STREAM_END_OBSTACLE = 2, STREAM_END_SLOW = 3;
+constexpr int STREAM_REC_FLOATS = 8;
+
+__device__ __forceinline__ float stream_group_lerp(float v, int c, int bit, float w)
+{
+    const float o = __shfl_xor(v, bit, 8);
+    return (c & bit) ? probe_lerp(o, v, w) : probe_lerp(v, o, w);
+}
+
+// cell coordinate of P on level li and whether the level's grid holds it: g, then base cell i0 (valid only if true is returned)
+__device__ __forceinline__ bool stream_cell(const StreamLevel &L, int li, float px, float py, float pz, float g[3], int i0[3])
+{
+    const float sc = ldexpf(1.0f, li);                               // exact
+    g[0] = px * sc - 0.5f;
+    g[1] = py * sc - 0.5f;
+    g[2] = pz * sc - 0.5f;
+    const float fx = floorf(g[0]), fy = floorf(g[1]), fz = floorf(g[2]);
+    // NaN fails every comparison, an infinity the upper one
+    const bool in = g[0] >= 0.0f && g[1] >= 0.0f && g[2] >= 0.0f && fx <= (float)(8 * L.gx - 1) && fy <= (float)(8 * L.gy - 1) &&
+                    fz <= (float)(8 * L.gz - 1);
+    i0[0] = in ? (int)fx : 0;
+    i0[1] = in ? (int)fy : 0;
+    i0[2] = in ? (int)fz : 0;
+    return in;
+}
+
+// internal block of the cell (x, y, z) of level L, -1: outside the grid or no block there
+__device__ __forceinline__ int stream_block(const StreamLevel &L, int x, int y, int z)
+{
+    if (x < 0 || y < 0 || z < 0 || x >= 8 * L.gx || y >= 8 * L.gy || z >= 8 * L.gz) return -1;
+    return L.bp[(x >> 3) + (int64_t)L.gx * ((y >> 3) + (int64_t)L.gy * (z >> 3))] - 1;
+}
+
+// sample(P) by the group of eight; c = the lane's corner. Returns the end code (0: found) - the same in all eight lanes - and
+// rho, ux, uy, uz in q, the level index in li.
+// `mine` = the table entry of level n_levels - 1 - c (the lane's level in the first round of the locate), kept in registers.
+__device__ __forceinline__ int stream_sample(const StreamArgs &a, const StreamLevel &mine, int c, float px, float py, float pz, float q[4],
+                                             int &li)
+{
+    // locate: the finest level whose active blocks hold the base cell
+    int found = -1;
+    for (int top = a.n_levels - 1; top >= 0 && found < 0; top -= 8) {
+        const int l = top - c;
+        int hit = -1;
+        if (l >= 0) {
+            float g[3];
+            int i0[3];
+            if (top == a.n_levels - 1) {
+                if (stream_cell(mine, l, px, py, pz, g, i0) && stream_block(mine, i0[0], i0[1], i0[2]) >= 0) hit = l;
+            } else {
+                const StreamLevel &L = a.lv[l];
+                if (stream_cell(L, l, px, py, pz, g, i0) && stream_block(L, i0[0], i0[1], i0[2]) >= 0) hit = l;
+            }
+        }
+        hit = max(hit, __shfl_xor(hit, 1, 8));
+        hit = max(hit, __shfl_xor(hit, 2, 8));
+        hit = max(hit, __shfl_xor(hit, 4, 8));
+        found = hit;
+    }
+    if (found < 0) return STREAM_END_OUTSIDE;
+    li = found;
+    // gather: this lane's corner on the chosen level
+    const StreamLevel &L = a.lv[found];
+    float g[3];
+    int i0[3];
+    (void)stream_cell(L, found, px, py, pz, g, i0);
+    const int x = i0[0] + (c & 1), y = i0[1] + ((c >> 1) & 1), z = i0[2] + (c >> 2);
+    const int b = stream_block(L, x, y, z);
+    bool fluid = false;
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (b >= 0) {
+        const int cell = (x & 7) + 8 * (y & 7) + 64 * (z & 7);
+        fluid = L.obstacle[(int64_t)b * CELLS + cell] == 0;
+        if (fluid) {
+            const float *vel = L.vel[(a.temp_mask >> found) & 1u];
+            v[0] = L.rho[(int64_t)b * CELLS + cell];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[1 + k] = vel[((int64_t)b * 3 + k) * CELLS + cell];
+        }
+    }
+    const int base_fluid = __shfl((int)fluid, 0, 8);
+    if (!base_fluid) return STREAM_END_OBSTACLE;
+    const float wx = g[0] - floorf(g[0]), wy = g[1] - floorf(g[1]), wz = g[2] - floorf(g[2]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float v0 = __shfl(v[k], 0, 8);
+        float t = fluid ? v[k] : v0;
+        t = stream_group_lerp(t, c, 1, wx);
+        t = stream_group_lerp(t, c, 2, wy);
+        q[k] = stream_group_lerp(t, c, 4, wz);
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(64) void k_streamlines(const StreamArgs a)
+{
+    const int lane = (int)(blockIdx.x * 64 + threadIdx.x);
+    const int line = lane >> 3, c = lane & 7;
+    if (line >= a.n_lines) return;                                   // a whole group leaves together
+    float px = a.seeds[3 * line], py = a.seeds[3 * line + 1], pz = a.seeds[3 * line + 2];
+    const float s = a.sign[line];
+    float4 *rec = (float4 *)(a.rec + (int64_t)line * (a.max_steps + 1) * STREAM_REC_FLOATS);
+    const StreamLevel mine = a.lv[max(a.n_levels - 1 - c, 0)];
+    int k = 0, code = -1;
+    while (code < 0) {
+        float q[4], qm[4];
+        int li = 0, lm = 0;
+        const int r = stream_sample(a, mine, c, px, py, pz, q, li);
+        if (r) { code = r; break; }
+        if (c == 0) rec[2 * k] = make_float4(px, py, pz, q[0]);
+        if (c == 1) rec[2 * k + 1] = make_float4(q[1], q[2], q[3], (float)li);
+        ++k;
+        if (k > a.max_steps) { code = STREAM_END_STEPS; break; }
+        const float m = sqrtf((q[1] * q[1] + q[2] * q[2]) + q[3] * q[3]);
+        if (!(m >= a.min_speed)) { code = STREAM_END_SLOW; break; }
+        const float h = ldexpf(a.step, -li);                         // exact
+        const float hh = 0.5f * h;
+        const float mx = px + hh * ((q[1] / m) * s), my = py + hh * ((q[2] / m) * s), mz = pz + hh * ((q[3] / m) * s);
+        const int rm = stream_sample(a, mine, c, mx, my, mz, qm, lm);
+        if (rm) { code = rm; break; }
+        const float mm = sqrtf((qm[1] * qm[1] + qm[2] * qm[2]) + qm[3] * qm[3]);
+        if (!(mm >= a.min_speed)) { code = STREAM_END_SLOW; break; }
+        px = px + h * ((qm[1] / mm) * s);
+        py = py + h * ((qm[2] / mm) * s);
+        pz = pz + h * ((qm[3] / mm) * s);
+    }
+    if (c == 0) {
+        a.counts[line] = k;
+        a.codes[line] = code;
+    }
+}
+
 // ---- iso-surfaces (ludwig_level_isosurface_*; no reference counterpart; open_ludwig_amd/isosurface.py states the definition and
 // restates it in numpy bit for bit) ----
 // Workgroup r = reference block r of the owned ones (the output order), 256 lanes, two x-consecutive anchor cells per lane. The block's

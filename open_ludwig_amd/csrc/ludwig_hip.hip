@@ -3270,6 +3270,174 @@ int ludwig_slices_download(LudwigSlices *S, float *values, size_t bytes)
     return LUDWIG_OK;
 }
 
+// ---- streamlines (ludwig_streamlines_*; no reference counterpart) ----
+// Per level its block_pointer on the device (internal block order, as the level keeps it) inside one table of StreamLevel entries; the
+// records [n_lines][max_steps + 1][8], counts and codes. One event orders the trace after the other levels' streams and them after it.
+struct LudwigStreamlines {
+    int device = 0;
+    int n_levels = 0, n_lines = 0, max_steps = 0;
+    float step = 0.0f, min_speed = 0.0f;
+    std::vector<LudwigLevel *> levels;
+    std::vector<int32_t *> bp;                  // per level, device
+    StreamLevel *table = nullptr;               // [n_levels], device
+    float *seeds = nullptr, *sign = nullptr;
+    float *rec = nullptr;
+    int32_t *counts = nullptr, *codes = nullptr;
+    hipEvent_t ev = nullptr;
+    bool traced = false;
+};
+
+void ludwig_streamlines_destroy(LudwigStreamlines *S)
+{
+    if (!S) return;
+    (void)hipSetDevice(S->device);
+    for (int32_t *q : S->bp)
+        if (q) (void)hipFree(q);
+    void *bufs[] = {S->table, S->seeds, S->sign, S->rec, S->counts, S->codes};
+    for (void *q : bufs)
+        if (q) (void)hipFree(q);
+    if (S->ev) (void)hipEventDestroy(S->ev);
+    delete S;
+}
+
+int ludwig_streamlines_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_lines, const float *seeds, const float *sign,
+                              float step, float min_speed, int32_t max_steps, LudwigStreamlines **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels || (n_lines > 0 && (!seeds || !sign))) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > 30) return fail(LUDWIG_ERR_INVALID, "streamlines: n_levels %d not in 1..30", n_levels);
+    if (n_lines < 0) return fail(LUDWIG_ERR_INVALID, "streamlines: n_lines %d < 0", n_lines);
+    if (!(step > 0.0f) || !std::isfinite(step)) return fail(LUDWIG_ERR_INVALID, "streamlines: step %g must be positive and finite", (double)step);
+    if (max_steps < 0) return fail(LUDWIG_ERR_INVALID, "streamlines: max_steps %d < 0", max_steps);
+    if ((int64_t)n_lines * ((int64_t)max_steps + 1) > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "streamlines: %d lines of %d steps are more than 2^31 - 1 records", n_lines, max_steps);
+    for (int32_t i = 0; i < n_lines; ++i)
+        if (sign[i] != 1.0f && sign[i] != -1.0f) return fail(LUDWIG_ERR_INVALID, "streamlines: sign[%d] = %g is neither 1 nor -1", i, (double)sign[i]);
+    for (int li = 0; li < n_levels; ++li) {
+        const LudwigLevel *L = levels[li];
+        if (!L) return fail(LUDWIG_ERR_INVALID, "streamlines: level %d is null", li);
+        if (L->device != levels[0]->device) return fail(LUDWIG_ERR_STATE, "streamlines: levels on different devices");
+        if (L->n_owned != L->n_blocks)
+            return fail(LUDWIG_ERR_STATE, "streamlines: level %d holds ghost blocks (%d of %d owned): a line cannot cross ranks", li, L->n_owned,
+                        L->n_blocks);
+        if (L->h_block_pointer.size() != (size_t)L->gdx * L->gdy * L->gdz || (L->n_blocks > 0 && L->h_block_pointer.empty()))
+            return fail(LUDWIG_ERR_STATE, "streamlines: level %d was created without block_pointer", li);
+        if ((int64_t)L->gdx * 8 > (1 << 24) || (int64_t)L->gdy * 8 > (1 << 24) || (int64_t)L->gdz * 8 > (1 << 24))
+            return fail(LUDWIG_ERR_INVALID, "streamlines: level %d has more cells per axis than float32 counts exactly", li);
+        // the kernel trusts a positive entry as a block index
+        for (const int32_t v : L->h_block_pointer)
+            if (v < 0 || v > L->n_blocks) return fail(LUDWIG_ERR_STATE, "streamlines: level %d: block_pointer entry %d out of range", li, v);
+    }
+    LudwigStreamlines *S = new (std::nothrow) LudwigStreamlines;
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "streamlines: out of host memory");
+    S->device = levels[0]->device;
+    S->n_levels = n_levels;
+    S->n_lines = n_lines;
+    S->max_steps = max_steps;
+    S->step = step;
+    S->min_speed = min_speed;
+    S->levels.assign(levels, levels + n_levels);
+    S->bp.assign(n_levels, nullptr);
+    int r = set_device(S->device);
+    hipError_t e = hipSuccess;
+    std::vector<StreamLevel> table(n_levels);
+    for (int li = 0; li < n_levels && r == LUDWIG_OK && e == hipSuccess; ++li) {
+        const LudwigLevel *L = levels[li];
+        if (!L->h_block_pointer.empty()) upload_table(e, L->h_block_pointer, S->bp[li]);
+        StreamLevel &t = table[li];
+        t.bp = S->bp[li];
+        t.obstacle = L->obstacle;
+        t.rho = L->rho;
+        t.vel[0] = L->vel[0];
+        t.vel[1] = L->vel[1];
+        t.gx = L->gdx; t.gy = L->gdy; t.gz = L->gdz;
+        t.n_blocks = L->n_blocks;
+    }
+    if (r == LUDWIG_OK) {
+        upload_table(e, table, S->table);
+        if (n_lines > 0) {
+            const size_t n = (size_t)n_lines;
+            const std::vector<float> hs(seeds, seeds + 3 * n), hg(sign, sign + n);
+            upload_table(e, hs, S->seeds);
+            upload_table(e, hg, S->sign);
+            if (e == hipSuccess) e = hipMalloc((void **)&S->rec, n * ((size_t)max_steps + 1) * STREAM_REC_FLOATS * sizeof(float));
+            if (e == hipSuccess) e = hipMalloc((void **)&S->counts, n * sizeof(int32_t));
+            if (e == hipSuccess) e = hipMalloc((void **)&S->codes, n * sizeof(int32_t));
+        }
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev, hipEventDisableTiming);
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "streamlines: %d lines of %d steps: %s", n_lines, max_steps, hipGetErrorString(e));
+    }
+    if (r != LUDWIG_OK) {
+        ludwig_streamlines_destroy(S);
+        return r;
+    }
+    *out = S;
+    return LUDWIG_OK;
+}
+
+int ludwig_streamlines_trace(LudwigStreamlines *S, int64_t t_coarse)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null streamline set");
+    if (t_coarse < 0) return fail(LUDWIG_ERR_INVALID, "streamlines: t_coarse %lld < 0", (long long)t_coarse);
+    S->traced = true;
+    if (S->n_lines == 0) return LUDWIG_OK;                        // nothing to trace: nothing launched
+    LW_HIP(hipSetDevice(S->device));
+    hipStream_t st = S->levels[0]->stream;
+    uint32_t temp_mask = 0;
+    for (int li = 0; li < S->n_levels; ++li) {
+        LudwigLevel *L = S->levels[li];
+        LW_ENSURE_RHO(L);
+        if (vel_out(L, (t_coarse + 1) * ((int64_t)1 << li) - 1) == L->vel[1]) temp_mask |= 1u << li;
+        if (L->stream != st) {                                    // the trace reads what this level's stream has queued
+            LW_HIP(hipEventRecord(S->ev, L->stream));
+            LW_HIP(hipStreamWaitEvent(st, S->ev, 0));
+        }
+    }
+    StreamArgs a;
+    a.lv = S->table;
+    a.n_levels = S->n_levels;
+    a.temp_mask = temp_mask;
+    a.seeds = S->seeds;
+    a.sign = S->sign;
+    a.n_lines = S->n_lines;
+    a.max_steps = S->max_steps;
+    a.step = S->step;
+    a.min_speed = S->min_speed;
+    a.rec = S->rec;
+    a.counts = S->counts;
+    a.codes = S->codes;
+    hipLaunchKernelGGL(k_streamlines, dim3((unsigned)(((int64_t)S->n_lines * 8 + 63) / 64)), dim3(64), 0, st, a);
+    LW_HIP(hipGetLastError());
+    bool others = false;
+    for (int li = 1; li < S->n_levels; ++li) others = others || S->levels[li]->stream != st;
+    if (others) {                                                 // and nothing queued there later overtakes the trace's reads
+        LW_HIP(hipEventRecord(S->ev, st));
+        for (int li = 1; li < S->n_levels; ++li)
+            if (S->levels[li]->stream != st) LW_HIP(hipStreamWaitEvent(S->levels[li]->stream, S->ev, 0));
+    }
+    return LUDWIG_OK;
+}
+
+int ludwig_streamlines_download(LudwigStreamlines *S, int32_t *counts, int32_t *codes, float *vertices, size_t bytes)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null streamline set");
+    if (!S->traced) return fail(LUDWIG_ERR_STATE, "streamlines: download before ludwig_streamlines_trace");
+    const size_t n = (size_t)S->n_lines, row = ((size_t)S->max_steps + 1) * STREAM_REC_FLOATS * sizeof(float);
+    if (bytes != n * row) return fail(LUDWIG_ERR_INVALID, "streamlines: got %zu bytes, expected %zu", bytes, n * row);
+    if (n == 0) return LUDWIG_OK;
+    if (!counts || !codes || !vertices) return fail(LUDWIG_ERR_INVALID, "null argument");
+    LW_HIP(hipSetDevice(S->device));
+    LW_HIP(hipStreamSynchronize(S->levels[0]->stream));
+    LW_HIP(hipMemcpy(counts, S->counts, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LW_HIP(hipMemcpy(codes, S->codes, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int32_t longest = 0;
+    for (size_t i = 0; i < n; ++i) longest = std::max(longest, counts[i]);
+    if (longest > 0)                                              // the used head of every line's row
+        LW_HIP(hipMemcpy2D(vertices, row, S->rec, row, (size_t)longest * STREAM_REC_FLOATS * sizeof(float), n, hipMemcpyDeviceToHost));
+    return LUDWIG_OK;
+}
+
 int ludwig_halo_pack(const LudwigLevel *L, int field, const int64_t *index_dev, int64_t n, float *dst_dev, void *hip_stream)
 {
     if (!L || (n > 0 && (!index_dev || !dst_dev))) return fail(LUDWIG_ERR_INVALID, "null argument");

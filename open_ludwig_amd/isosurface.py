@@ -250,17 +250,20 @@ class IsoWriter:
 
 
 def read_vtp(path: str) -> Dict[str, np.ndarray]:
-    """the arrays of a file output.write_vtp wrote: Points [n, 3], connectivity, offsets, the point arrays and the cell arrays by name"""
+    """the arrays of a file output.write_vtp or output.write_vtp_lines wrote: Points [n, 3], connectivity, offsets (of the Polys or the
+    Lines, whichever the file holds), the point arrays and the cell arrays by name"""
     from .slices import _NP_TYPE, _decode
     root = ET.parse(path).getroot()
     compressed = root.get("compressor") is not None
     piece = root.find("PolyData").find("Piece")
     out: Dict[str, np.ndarray] = {}
-    for tag in ("Points", "Polys", "PointData", "CellData"):
-        for da in piece.find(tag).findall("DataArray"):
+    for tag in ("Points", "Polys", "Lines", "PointData", "CellData"):
+        section = piece.find(tag)
+        for da in (section.findall("DataArray") if section is not None else ()):
             a = _decode(da.text or "", _NP_TYPE[da.get("type")], compressed)
             k = int(da.get("NumberOfComponents", "1"))
             out[da.get("Name")] = a.reshape(-1, k) if k > 1 else a
     out["NumberOfPoints"] = np.int64(piece.get("NumberOfPoints"))
     out["NumberOfPolys"] = np.int64(piece.get("NumberOfPolys"))
+    out["NumberOfLines"] = np.int64(piece.get("NumberOfLines"))
     return out

@@ -127,6 +127,40 @@ def write_vtp(filename: str, points: np.ndarray, triangles: np.ndarray, density:
     return path
 
 
+def write_vtp_lines(filename: str, points: np.ndarray, offsets: np.ndarray, density: np.ndarray, velocity: np.ndarray, level: np.ndarray,
+                    seed: np.ndarray, direction: np.ndarray, end_code: np.ndarray, compress: bool = True) -> str:
+    """VTK XML PolyData of streamlines (no reference counterpart; streamlines.py): points [n, 3] Float32 in the flow file's frame, line
+    after line; offsets [m] = the end of every line in the point list (each line its points in order); point arrays Density, Velocity,
+    Level (Int32); cell arrays Seed, Direction, EndCode (Int32). Written whole, then renamed. Returns the path."""
+    path = filename if filename.endswith(".vtp") else filename + ".vtp"
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    comp_attr = ' compressor="vtkZLibDataCompressor"' if compress else ""
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    tmp = path + ".part"
+    with open(tmp, "w") as io:
+        io.write('<?xml version="1.0" encoding="utf-8"?>\n')
+        io.write(f'<VTKFile type="PolyData" version="1.0" byte_order="LittleEndian" header_type="UInt64"{comp_attr}>\n')
+        io.write("<PolyData>\n")
+        io.write(f'<Piece NumberOfPoints="{pts.shape[0]}" NumberOfVerts="0" NumberOfLines="{off.shape[0]}" NumberOfStrips="0" '
+                 'NumberOfPolys="0">\n')
+        io.write("<Points>\n" + _data_array("Points", pts, compress, 3) + "</Points>\n")
+        io.write("<Lines>\n")
+        io.write(_data_array("connectivity", np.arange(pts.shape[0], dtype=np.int64), compress))
+        io.write(_data_array("offsets", off, compress))
+        io.write("</Lines>\n<PointData>\n")
+        io.write(_data_array("Density", np.ascontiguousarray(density, dtype=np.float32).reshape(-1), compress))
+        io.write(_data_array("Velocity", np.ascontiguousarray(velocity, dtype=np.float32).reshape(-1, 3), compress, 3))
+        io.write(_data_array("Level", i32(level), compress))
+        io.write("</PointData>\n<CellData>\n")
+        io.write(_data_array("Seed", i32(seed), compress))
+        io.write(_data_array("Direction", i32(direction), compress))
+        io.write(_data_array("EndCode", i32(end_code), compress))
+        io.write("</CellData>\n</Piece>\n</PolyData>\n</VTKFile>\n")
+    os.replace(tmp, path)
+    return path
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # flow export (src/io_vtk.jl)
 # ----------------------------------------------------------------------------------------------------------------

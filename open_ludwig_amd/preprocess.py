@@ -132,6 +132,17 @@ class CaseConfig:
     isosurfaces_interval: int = 1
     isosurfaces_max_triangles: int = 50_000_000
     isosurfaces_surfaces: Tuple["IsoSurfaceSpec", ...] = ()
+    # streamlines, advanced.streamlines (no reference counterpart): lines traced on the device through every level every `interval` coarse
+    # steps from `start_step`, written to stream_<name>_%06d.vtp and stream_<name>.pvd (streamlines.py)
+    streamlines_enabled: bool = False
+    streamlines_start_step: int = 1
+    streamlines_interval: int = 100
+    streamlines_step: float = 0.5
+    streamlines_max_steps: int = 2000
+    streamlines_min_speed: float = 1.0e-6
+    streamlines_direction: str = "both"
+    streamlines_max_vertices: int = 20_000_000
+    streamlines_seeds: Tuple["StreamlineSeeds", ...] = ()
     # flow monitor, advanced.flow_monitor (no reference counterpart; its advanced.diagnostics.stability_check is read by nobody, there or
     # here): a health record of every level at every diagnostics step, written to flow_monitor.csv (monitor.py)
     flow_monitor_enabled: bool = False
@@ -186,6 +197,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     probes = _probes_config(g("advanced", "probes", default=None))
     slices = _slices_config(g("advanced", "slices", default=None))
     isosurfaces = _isosurfaces_config(g("advanced", "isosurfaces", default=None))
+    streamlines = _streamlines_config(g("advanced", "streamlines", default=None))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
     wall_diag = _wall_diagnostics_config(g("advanced", "wall_diagnostics", default=None))
     return CaseConfig(
@@ -243,6 +255,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **probes,
         **slices,
         **isosurfaces,
+        **streamlines,
         **flow_monitor,
         **wall_diag,
         y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
@@ -485,6 +498,74 @@ def _isosurfaces_config(ic) -> dict:
         surfaces.append(IsoSurfaceSpec(name, field, value, bounds))
     return dict(isosurfaces_enabled=True, isosurfaces_start_step=start, isosurfaces_interval=interval, isosurfaces_max_triangles=cap,
                 isosurfaces_surfaces=tuple(surfaces))
+
+
+STREAMLINE_DIRECTIONS = ("forward", "backward", "both")                                          # streamlines.DIRECTIONS
+
+
+@dataclass(frozen=True)
+class StreamlineSeeds:
+    """one group of advanced.streamlines.seeds: its name and its seed points, expanded (semantics: streamlines.py)"""
+    name: str
+    points: Tuple[Tuple[float, float, float], ...]          # STL frame after stl_scale
+
+
+def _streamlines_config(sc) -> dict:
+    """advanced.streamlines: {enabled: false, start_step: 1, interval: 100, step: 0.5, max_steps: 2000, min_speed: 1e-6, direction: both,
+    max_vertices: 20000000, seeds: [{name, points: [[x, y, z], ...]} | {name, line: {from, to, count}}]} -> CaseConfig fields. Absent or
+    disabled: the defaults."""
+    if sc is None:
+        return {}
+    if not isinstance(sc, dict):
+        raise ValueError("advanced.streamlines must be a mapping")
+    if not bool(sc.get("enabled", False)):
+        return {}
+    from .streamlines import expand_group
+    start, interval = int(sc.get("start_step", 1)), int(sc.get("interval", 100))
+    if interval < 1:
+        raise ValueError(f"advanced.streamlines.interval must be >= 1, got {interval}")
+    if start < 1:
+        raise ValueError(f"advanced.streamlines.start_step must be >= 1, got {start}")
+    try:
+        step, min_speed = float(sc.get("step", 0.5)), float(sc.get("min_speed", 1.0e-6))
+    except (TypeError, ValueError):
+        raise ValueError("advanced.streamlines.step and advanced.streamlines.min_speed must be numbers") from None
+    if not (math.isfinite(step) and step > 0.0):
+        raise ValueError(f"advanced.streamlines.step must be positive and finite, got {step}")
+    if not (math.isfinite(min_speed) and min_speed >= 0.0):
+        raise ValueError(f"advanced.streamlines.min_speed must be finite and >= 0, got {min_speed}")
+    max_steps, cap = int(sc.get("max_steps", 2000)), int(sc.get("max_vertices", 20_000_000))
+    if max_steps < 0:
+        raise ValueError(f"advanced.streamlines.max_steps must be >= 0, got {max_steps}")
+    if cap < 1:
+        raise ValueError(f"advanced.streamlines.max_vertices must be >= 1, got {cap}")
+    direction = str(sc.get("direction", "both"))
+    if direction not in STREAMLINE_DIRECTIONS:
+        raise ValueError(f"advanced.streamlines.direction {sc.get('direction')!r} is unknown (one of {', '.join(STREAMLINE_DIRECTIONS)})")
+    raw = sc.get("seeds") or []
+    if not isinstance(raw, (list, tuple)) or not raw:
+        raise ValueError("advanced.streamlines.enabled needs at least one entry in advanced.streamlines.seeds")
+    groups, seen, n_seeds = [], set(), 0
+    for i, gc in enumerate(raw):
+        where = f"advanced.streamlines.seeds[{i}]"
+        if not isinstance(gc, dict):
+            raise ValueError(f"{where} must be a mapping")
+        name = str(gc.get("name", ""))
+        if not name or not all(ch.isalnum() or ch in "_-." for ch in name) or name.startswith("."):
+            raise ValueError(f"{where}.name {name!r} is not a plain file-name stem")
+        if name in seen:
+            raise ValueError(f"{where}.name {name!r} is not unique")
+        seen.add(name)
+        pts = expand_group(gc, where)
+        n_seeds += pts.shape[0]
+        groups.append(StreamlineSeeds(name, tuple(tuple(float(v) for v in p) for p in pts)))
+    lines = n_seeds * (2 if direction == "both" else 1)
+    if lines * (max_steps + 1) > cap:
+        raise ValueError(f"advanced.streamlines: {lines} lines of up to max_steps + 1 = {max_steps + 1} vertices are more than "
+                         f"advanced.streamlines.max_vertices = {cap}")
+    return dict(streamlines_enabled=True, streamlines_start_step=start, streamlines_interval=interval, streamlines_step=step,
+                streamlines_max_steps=max_steps, streamlines_min_speed=min_speed, streamlines_direction=direction,
+                streamlines_max_vertices=cap, streamlines_seeds=tuple(groups))
 
 
 # ----------------------------------------------------------------------------------------------------------------
