@@ -548,6 +548,48 @@ int  ludwig_streamlines_trace(LudwigStreamlines *set, int64_t t_coarse);
  * Synchronizes. LUDWIG_ERR_STATE before the first trace. */
 int  ludwig_streamlines_download(LudwigStreamlines *set, int32_t *counts, int32_t *codes, float *vertices, size_t bytes);
 
+/* ---- tracers: particles advected through the level hierarchy on the device, inside a batch (no reference counterpart) ----
+ * A tracer set is made over a level array, all of it, under the streamline sets' conditions (block_pointer, no ghost blocks, one device).
+ * Float32, no contraction; open_ludwig_amd/tracers.py (advance_host, snapshot_host) restates every bit. Positions are the streamlines' P.
+ * sample_u(P) is the streamlines' sample(P) returning u and the level index only: rho is never read, and no level's rho policy changes.
+ * The set holds n_seeds x generations slots; slot g n_seeds + s has P[3] and an int32 state: -1 empty, 0 alive, 1 outside, 2 obstacle
+ * (the LUDWIG_STREAM_END_* codes), 3 non-finite. The set counts its advances k = 0, 1, ... on the host. Advance k behind coarse step t reads
+ * every level's newest velocity after t (the buffer ludwig_streamlines_trace reads):
+ *   if k % release_every == 0, generation (k / release_every) % generations is the released one;
+ *   every alive slot not of the released generation: u = sample_u(P); Pm = P + (0.5f dt) u per component; um = sample_u(Pm); a failed
+ *   sample: the state takes its code, P stays; Pn = P + dt um; a non-finite component: state 3, P stays; else P = Pn. A dead or empty
+ *   slot is not touched;
+ *   the released generation's slots get P = seed, state 0: overwritten whatever they held, not advanced and not sampled.
+ * Snapshot (changes no state): rec[slot][8] = x, y, z, ux, uy, uz, level index, code. An alive slot is sampled at P: code 0 with values,
+ * or zeros, level -1 and the failing code; any other slot: zeros, level -1, code = its state. The position is always written.
+ * A slot is owned by one lane group: no atomics, no compaction, the result depends on no scheduling. */
+typedef struct LudwigTracers LudwigTracers;   /* opaque */
+enum { LUDWIG_TRACER_EMPTY = -1, LUDWIG_TRACER_ALIVE = 0, LUDWIG_TRACER_OUTSIDE = 1, LUDWIG_TRACER_OBSTACLE = 2, LUDWIG_TRACER_NONFINITE = 3 };
+/* seeds: 3 n_seeds floats; generations >= 1, release_every >= 1 (in advances), dt > 0 and finite (coarse steps per advance, as a float).
+ * n_seeds = 0 is allowed (seeds may be NULL) and never launches. Errors as ludwig_streamlines_create; more than 2^28 - 1 slots:
+ * LUDWIG_ERR_INVALID. */
+int  ludwig_tracers_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_seeds, const float *seeds, int32_t generations,
+                           int32_t release_every, float dt, LudwigTracers **out);
+/* frees the set, not the levels */
+void ludwig_tracers_destroy(LudwigTracers *set);
+/* one advance outside a batch, behind coarse step t_coarse: one launch on the first level's stream, ordered after everything queued on the
+ * other levels' streams, which in turn wait for it. Writes only the set's own buffers. */
+int  ludwig_tracers_advance(LudwigTracers *set, int64_t t_coarse);
+/* snapshot on the newest velocity after coarse step t_coarse, ordered as an advance */
+int  ludwig_tracers_snapshot(LudwigTracers *set, int64_t t_coarse);
+/* the last snapshot: records [n_seeds generations][8] floats, bytes = their size; n_advances (may be NULL): advances so far.
+ * Synchronizes. LUDWIG_ERR_STATE before the first snapshot. */
+int  ludwig_tracers_download(LudwigTracers *set, float *records, size_t bytes, int64_t *n_advances);
+/* ludwig_execute_timestep_batch_loads (forces may be NULL too) that also advances `tracers` behind every coarse step start_step +
+ * k interval of the batch: the host has then issued every launch of that step and none of the next; with level streams the first
+ * level's stream waits for all the others, runs the advance, and all the others wait for it (ordering only). tracers == NULL: the _loads
+ * call itself. LUDWIG_ERR_INVALID before anything is stepped: the set's levels are not exactly the batch's (same handles, same order),
+ * or interval < 1. */
+int  ludwig_execute_timestep_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                           const LudwigStepFlags *flags, const LudwigBatchSamplers *samplers, LudwigForceSeries *forces,
+                                           int64_t force_start_step, int32_t force_interval, LudwigTracers *tracers, int64_t start_step,
+                                           int32_t interval);
+
 /* ---- subgrid model: the WALE eddy viscosity the step collides with, and its time-averaged measures (no reference counterpart for the
  * output; the model is perform_timestep_v2!'s, src/physics_kernels.jl:251-300) ----
  * Per cell of the blocks this device owns, from one velocity buffer u: the gradient in lattice units g_ij = 0.5f (u_i(+e_j) - u_i(-e_j))

@@ -254,6 +254,36 @@ streamlines_download!(counts::Vector{Int32}, codes::Vector{Int32}, vertices::Arr
     GC.@preserve counts codes vertices check(ccall((:ludwig_streamlines_download, LIB), Cint,
         (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Csize_t), s, counts, codes, vertices, sizeof(vertices)))
 
+# tracers (no reference counterpart): particles advected through ALL levels on the device, inside a batch
+const TRACER_EMPTY = Int32(-1)
+const TRACER_ALIVE = Int32(0)
+const TRACER_OUTSIDE = Int32(1)
+const TRACER_OBSTACLE = Int32(2)
+const TRACER_NONFINITE = Int32(3)
+"""a tracer set over every level of `grids` (the streamline sets' conditions): seeds 3 x n Float32 in cell units of the first level,
+`generations` slots per seed, one release every `release_every` advances, dt = coarse steps per advance. Free it with
+`tracers_destroy`."""
+function tracers_create(grids::Vector{DeviceLevel}, seeds::Matrix{Float32}, generations::Integer, release_every::Integer, dt::Real)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles seeds check(ccall((:ludwig_tracers_create, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Ptr{Float32}, Int32, Int32, Cfloat, Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int32(size(seeds, 2)), seeds, Int32(generations), Int32(release_every), Float32(dt), out))
+    return out[]
+end
+tracers_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_tracers_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""one advance behind coarse step `t_coarse`, outside a batch (one launch, queued)"""
+tracers_advance!(s::Ptr{Cvoid}, t_coarse::Integer) = check(ccall((:ludwig_tracers_advance, LIB), Cint, (Ptr{Cvoid}, Int64), s, Int64(t_coarse)))
+"""snapshot every slot on the newest velocity after coarse step `t_coarse` (one launch, queued; changes no state)"""
+tracers_snapshot!(s::Ptr{Cvoid}, t_coarse::Integer) = check(ccall((:ludwig_tracers_snapshot, LIB), Cint, (Ptr{Cvoid}, Int64), s, Int64(t_coarse)))
+"""the last snapshot into records (8 x n_slots Float32: x, y, z, ux, uy, uz, level index, code); returns the advances so far"""
+function tracers_download!(records::Matrix{Float32}, s::Ptr{Cvoid})
+    n = Ref{Int64}(0)
+    GC.@preserve records check(ccall((:ludwig_tracers_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Ref{Int64}),
+                                     s, records, sizeof(records), n))
+    return Int(n[])
+end
+
 # surface statistics (no reference counterpart): 7 float64 sums per triangle of p, p^2, tau, |tau|, |tau|^2 at its nearest fluid cell
 """a surface set on `grid`: per triangle its nearest fluid cell (0-based reference block index, -1 = none; cell x + 8y + 64z), wall
 distance in lattice units and normal (3 x n); tau and the two scales from `sp`. Free it with `surface_stats_destroy`."""
@@ -500,6 +530,20 @@ function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch
                                         (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{BatchSamplers}, Ptr{Cvoid}, Int64, Int32),
                                         handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, sp, forces,
                                         Int64(start_step), Int32(interval)))
+end
+
+"""the call above that also advances the tracer set `tracers` behind the coarse steps start_step + k interval of the batch; `forces`
+may be C_NULL"""
+function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                                 s::Union{BatchSamplers,Nothing}, forces::Ptr{Cvoid}, force_start_step::Integer, force_interval::Integer,
+                                 tracers::Ptr{Cvoid}, start_step::Integer, interval::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    sp = s === nothing ? C_NULL : Ref(s)
+    GC.@preserve handles sp check(ccall((:ludwig_execute_timestep_batch_tracers, LIB), Cint,
+                                        (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{BatchSamplers}, Ptr{Cvoid}, Int64, Int32,
+                                         Ptr{Cvoid}, Int64, Int32),
+                                        handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, sp, forces,
+                                        Int64(force_start_step), Int32(force_interval), tracers, Int64(start_step), Int32(interval)))
 end
 
 end # module

@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
     "ludwig_slices_create", "ludwig_slices_destroy", "ludwig_slices_sample", "ludwig_slices_download",
     "ludwig_streamlines_create", "ludwig_streamlines_destroy", "ludwig_streamlines_trace", "ludwig_streamlines_download",
+    "ludwig_tracers_create", "ludwig_tracers_destroy", "ludwig_tracers_advance", "ludwig_tracers_snapshot", "ludwig_tracers_download",
+    "ludwig_execute_timestep_batch_tracers",
     "ludwig_level_monitor",
     "ludwig_level_isosurface_extract", "ludwig_level_isosurface_download",
     "ludwig_level_wall_census", "ludwig_wall_surface_create", "ludwig_wall_surface_destroy", "ludwig_wall_surface_compute",
@@ -227,6 +229,11 @@ def load() -> C.CDLL:
         "ludwig_streamlines_destroy": (None, [vp]),
         "ludwig_streamlines_trace": (C.c_int, [vp, i64]),
         "ludwig_streamlines_download": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),
+        "ludwig_tracers_create": (C.c_int, [vp, i32, i32, vp, i32, i32, f32, C.POINTER(vp)]),
+        "ludwig_tracers_destroy": (None, [vp]),
+        "ludwig_tracers_advance": (C.c_int, [vp, i64]),
+        "ludwig_tracers_snapshot": (C.c_int, [vp, i64]),
+        "ludwig_tracers_download": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_int64)]),
         "ludwig_level_isosurface_extract": (C.c_int, [vp, i32, i32, f32, f32, vp, vp, vp, i64, C.POINTER(C.c_int64)]),
         "ludwig_level_isosurface_download": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]),
         "ludwig_level_wall_census": (C.c_int, [vp, i64, C.POINTER(WallCensus)]),
@@ -240,6 +247,8 @@ def load() -> C.CDLL:
         "ludwig_force_series_download": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(C.c_int32)]),
         "ludwig_execute_timestep_batch_loads": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers),
                                                           vp, i64, i32]),
+        "ludwig_execute_timestep_batch_tracers": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers),
+                                                            vp, i64, i32, vp, i64, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

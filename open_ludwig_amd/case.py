@@ -23,6 +23,7 @@ from . import monitor as monitor_mod
 from . import probes as probes_mod
 from . import slices as slices_mod
 from . import streamlines as stream_mod
+from . import tracers as tracer_mod
 from . import statistics as stats_mod
 from . import subgrid as subgrid_mod
 from . import surface_stats as surface_mod
@@ -71,10 +72,11 @@ class HipStepper:
         self._fseries = None
         self._surface_plan = None              # (mesh, params, plan) of the surface statistics, shared with the force series
         self.stream_set = None                 # streamlines_setup
+        self.tracer_set = None                 # tracers_setup
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.probes is None and self.forces is None:
-            execute_timestep_batch(self.dev, t_start, n, u_curr, params, surface=self.surface)
+            execute_timestep_batch(self.dev, t_start, n, u_curr, params, surface=self.surface, tracers=self.tracer_set)
             return
         # sampled inside the C batch, the rings drained after it; a batch with more samples than a ring holds is cut where the first one
         # fills (the same inlet speed: the same steps, the same bits)
@@ -85,7 +87,8 @@ class HipStepper:
                 seg_end = min(seg_end, fseries_mod.segment_end(t, end, P.start_step, P.interval, P.capacity))
             if F is not None:
                 seg_end = min(seg_end, fseries_mod.segment_end(t, end, F.start_step, F.interval, F.capacity))
-            execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P, surface=self.surface, forces=F)
+            execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P, surface=self.surface, forces=F,
+                                   tracers=self.tracer_set)
             if P is not None:
                 self._series.append(*P.download())
             if F is not None:
@@ -255,6 +258,21 @@ class HipStepper:
         self.stream_set.trace(t_coarse)
         return self.stream_set.download()
 
+    # -- tracers (tracers.py; no reference counterpart) --
+    def tracers_setup(self, seeds, generations: int = 1, release_every: int = 1, start_step: int = 1, interval: int = 1) -> None:
+        """one device set over every level: seeds [n, 3] float32 in cell units of level 1 (streamlines.seed_positions). From now on
+        every batch advances it behind the coarse steps start_step + k interval, inside the C call."""
+        tracer_mod.check_schedule(start_step, interval, release_every, generations)
+        if self.tracer_set is not None:
+            self.tracer_set.close()
+        self.tracer_set = tracer_mod.DeviceTracers(self.dev, seeds, generations, release_every, start_step, interval)
+
+    def tracers_snapshot(self, t_coarse: int):
+        """(records [n_slots, 8], advances so far) on the newest state of all levels after coarse step t_coarse (the last batch must
+        have ended there); changes nothing of the set"""
+        self.tracer_set.snapshot(t_coarse)
+        return self.tracer_set.download()
+
     # -- subgrid model (subgrid.py; no reference counterpart for the output) --
     def subgrid_fields(self, level: int, vel_name: str):
         """(nu_t [8,8,8,nb], branch code as a float [8,8,8,nb]) of a level from its `vel_name` buffer (Float32)"""
@@ -280,6 +298,9 @@ class HipStepper:
         if self.stream_set is not None:
             self.stream_set.close()
             self.stream_set = None
+        if self.tracer_set is not None:
+            self.tracer_set.close()
+            self.tracer_set = None
         for d in self.dev:
             d.close()
 
@@ -836,6 +857,11 @@ class DistributedStepper:
         raise RuntimeError("advanced.streamlines is enabled, but a distributed run cannot trace streamlines yet: a line crosses the "
                            "ranks' blocks, and each rank holds only its own (DESIGN section 8, Next)")
 
+    # -- tracers: not over ranks, for the streamlines' reason --
+    def tracers_setup(self, *args, **kwargs) -> None:
+        raise RuntimeError("advanced.tracers is enabled, but a distributed run cannot advect tracers yet: a particle crosses the ranks' "
+                           "blocks, and each rank holds only its own (DESIGN section 8, Next)")
+
     # -- subgrid model: every rank works on its owned blocks after batch(); the face stencil is the gradient fields', so their argument
     # holds unchanged (the 'vel' halo ghosts are current for both buffers) --
     def subgrid_fields(self, level: int, vel_name: str):
@@ -925,6 +951,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     downloaded fields (streamlines.trace_host). Each group is written to stream_<name>_%06d.vtp, listed in stream_<name>.pvd; lines of
     fewer than two vertices are left out of the file and counted in the log (streamlines.py). A stepper whose streamlines_setup raises
     (the distributed one) ends the run before the first step.
+    With cfg.tracers_enabled, the seed groups' particles are advanced behind the coarse steps start_step + k interval INSIDE the batches
+    where the stepper offers tracers_setup - no batch is cut for an advance - and batches are cut only after the snapshot steps
+    start_step + k output_interval, as for slices; a stepper without tracers_setup goes through tracers.HostTracers on downloaded
+    velocity, cutting at every advance step. Each snapshot writes tracers_<name>_%06d.vtp per group, listed in tracers_<name>.pvd, and
+    logs one line per group (tracers.py). A stepper whose tracers_setup raises (the distributed one) ends the run before the first step.
     With cfg.flow_monitor_enabled, a monitor.Record of every level is taken at every diagnostics step and after the last step, from the
     state at batch end (where rho_min is taken; no batch is cut) - on the device where the stepper offers monitor, else from downloaded
     fields (monitor.host_monitor); flow_monitor.csv gains one row per level and the warnings go to `log`. With
@@ -976,6 +1007,24 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                 if hasattr(st, "close"):
                     st.close()
                 raise
+    tracers_on = bool(cfg.tracers_enabled)
+    tr_start, tr_interval, tr_out = cfg.tracers_start_step, cfg.tracers_interval, cfg.tracers_output_interval
+    tr_host = None                       # the host fallback (a stepper without tracers_setup)
+    if tracers_on:
+        tr_plan = tracer_mod.TracerPlan([(s.name, np.asarray(s.points, dtype=np.float64)) for s in cfg.tracers_seeds], params.mesh_offset,
+                                        grids[0].dx)
+        if hasattr(st, "tracers_setup"):
+            try:
+                st.tracers_setup(tr_plan.seeds, cfg.tracers_generations, cfg.tracers_release_every, tr_start, tr_interval)
+            except Exception:
+                if hasattr(st, "close"):
+                    st.close()
+                raise
+        else:
+            tr_host = tracer_mod.HostTracers(tr_plan.seeds, cfg.tracers_generations, cfg.tracers_release_every, tr_interval)
+        warn = tracer_mod.jump_warning(tr_interval, float(cfg.u_lattice), len(grids))
+        if warn and log:
+            log(warn)
     wall_on = bool(cfg.wall_diagnostics_enabled)
     if wall_on and not hasattr(st, "wall_diagnostics_setup"):
         if hasattr(st, "close"):
@@ -1038,6 +1087,9 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
         if stream_on:
             stream_writer = stream_mod.StreamlineWriter(out_dir, stream_plan, params.time_scale)
+        if tracers_on:
+            tracer_writer = tracer_mod.TracerWriter(out_dir, tr_plan, params.time_scale, cfg.tracers_generations, cfg.tracers_release_every,
+                                                    tr_start, tr_interval)
         if iso_on:
             iso_writer = iso_mod.IsoWriter(out_dir, [s.name for s in cfg.isosurfaces_surfaces], params.time_scale)
         if probes_on:
@@ -1124,6 +1176,21 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             for gi, name in enumerate(stream_plan.names):
                 log(f"streamlines {name!r}: step {step}: {stream_mod.summary(stream_plan, gi, counts, codes)}")
 
+    def take_tracers(step):
+        """the advance of the host fallback behind coarse step `step`, and at a snapshot step the snapshot: files out, one log line
+        per group"""
+        levels = tracer_mod.stepper_levels(st, grids, step) if tr_host is not None else None
+        if tr_host is not None:
+            tr_host.advance(levels)
+        if not stats_mod.is_sample_step(step, tr_start, tr_out):
+            return
+        rec, n_adv = (tr_host.snapshot(levels), tr_host.n_advances) if tr_host is not None else st.tracers_snapshot(step)
+        if writing:
+            tracer_writer.write(step, rec, n_adv)
+        if log:
+            for gi, name in enumerate(tr_plan.names):
+                log(f"tracers {name!r}: step {step}: {tracer_mod.summary(tr_plan, gi, rec, cfg.tracers_generations)}")
+
     def wall_values(state_step):
         """the wall-surface values of the state after coarse step state_step, evaluated once per step (collective in a distributed run)"""
         if wall_taken[0] != state_step:
@@ -1186,7 +1253,7 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if stats_on or surf_host is not None or slices_on or iso_on or stream_on:
+            if stats_on or surf_host is not None or slices_on or iso_on or stream_on or tracers_on:
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
@@ -1199,6 +1266,9 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     cuts.update(stats_mod.sample_steps(t, batch_end, iso_start, iso_interval))
                 if stream_on:
                     cuts.update(stats_mod.sample_steps(t, batch_end, stream_start, stream_interval))
+                if tracers_on:           # on the device an advance cuts nothing: only the snapshot steps do
+                    tr_cuts = set(stats_mod.sample_steps(t, batch_end, tr_start, tr_interval if tr_host is not None else tr_out))
+                    cuts.update(tr_cuts)
                 seg = t
                 for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
@@ -1224,6 +1294,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         take_isosurfaces(s_step)
                     if stream_on and stats_mod.is_sample_step(s_step, stream_start, stream_interval):
                         take_streamlines(s_step)
+                    if tracers_on and s_step in tr_cuts:
+                        take_tracers(s_step)
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)

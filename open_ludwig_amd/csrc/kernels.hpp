@@ -1456,6 +1456,8 @@ __device__ __forceinline__ int stream_block(const StreamLevel &L, int x, int y, 
 // sample(P) by the group of eight; c = the lane's corner. Returns the end code (0: found) - the same in all eight lanes - and
 // rho, ux, uy, uz in q, the level index in li.
 // `mine` = the table entry of level n_levels - 1 - c (the lane's level in the first round of the locate), kept in registers.
+// RHO = false (the tracers) leaves rho out of the gather and the lerp: q[0] is then not written and the level's rho is never read.
+template <bool RHO = true>
 __device__ __forceinline__ int stream_sample(const StreamArgs &a, const StreamLevel &mine, int c, float px, float py, float pz, float q[4],
                                              int &li)
 {
@@ -1495,7 +1497,7 @@ __device__ __forceinline__ int stream_sample(const StreamArgs &a, const StreamLe
         fluid = L.obstacle[(int64_t)b * CELLS + cell] == 0;
         if (fluid) {
             const float *vel = L.vel[(a.temp_mask >> found) & 1u];
-            v[0] = L.rho[(int64_t)b * CELLS + cell];
+            if (RHO) v[0] = L.rho[(int64_t)b * CELLS + cell];
 #pragma unroll
             for (int k = 0; k < 3; ++k) v[1 + k] = vel[((int64_t)b * 3 + k) * CELLS + cell];
         }
@@ -1504,7 +1506,7 @@ __device__ __forceinline__ int stream_sample(const StreamArgs &a, const StreamLe
     if (!base_fluid) return STREAM_END_OBSTACLE;
     const float wx = g[0] - floorf(g[0]), wy = g[1] - floorf(g[1]), wz = g[2] - floorf(g[2]);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = RHO ? 0 : 1; k < 4; ++k) {
         const float v0 = __shfl(v[k], 0, 8);
         float t = fluid ? v[k] : v0;
         t = stream_group_lerp(t, c, 1, wx);
@@ -1550,6 +1552,94 @@ __global__ __launch_bounds__(64) void k_streamlines(const StreamArgs a)
         a.counts[line] = k;
         a.codes[line] = code;
     }
+}
+
+// ---- tracers (ludwig_tracers_*; no reference counterpart; include/ludwig_hip.h states the definition and open_ludwig_amd/tracers.py
+// restates it in numpy bit for bit) ----
+// Particles that live across coarse steps: slot g n_seeds + s holds generation g of seed s, a position and a state (-1 empty, 0 alive,
+// 1 outside, 2 obstacle, 3 non-finite). An advance is two samples (start and midpoint), each the streamlines' chain of dependent loads,
+// so the streamlines' mapping is kept: eight lanes per slot, locate split over levels, one corner per lane, three shuffle rounds; the
+// sample is stream_sample<false> (velocity only: the finest level's rho store is elided inside a batch and is never read here). A slot
+// belongs to one group of eight lanes and nothing else writes it: no atomics, no compaction, the result depends on no scheduling. The
+// state is read before anything else and is the same word in all eight lanes, so a group leaves or stays together and a shuffle always
+// meets its partners. Writes: pos and state of the own slot (lane 0), rec of the own slot (lanes 0 and 1); every index into them is
+// slot < n_slots, and the seed index is slot % n_seeds.
+struct TracerArgs {
+    StreamArgs s;                // lv, n_levels, temp_mask; the rest unused
+    const float *seeds;          // [n_seeds][3]
+    float *pos;                  // [n_slots][3]
+    int32_t *state;              // [n_slots]
+    float *rec;                  // [n_slots][8] (snapshot)
+    int32_t n_seeds, n_slots;
+    int32_t released;            // the generation this advance releases, -1: none
+    float dt;
+};
+
+constexpr int TRACER_EMPTY = -1, TRACER_ALIVE = 0, TRACER_NONFINITE = 3;
+
+__global__ __launch_bounds__(64) void k_tracers_advance(const TracerArgs a)
+{
+    const int64_t lane = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const int64_t slot64 = lane >> 3;
+    const int c = (int)(lane & 7);
+    if (slot64 >= a.n_slots) return;                                 // a whole group leaves together
+    const int slot = (int)slot64;
+    const int gen = slot / a.n_seeds, seed = slot - gen * a.n_seeds;
+    if (gen == a.released) {                                         // overwritten, not advanced, whatever the slot held
+        if (c < 3) a.pos[3 * (int64_t)slot + c] = a.seeds[3 * seed + c];
+        if (c == 3) a.state[slot] = TRACER_ALIVE;
+        return;
+    }
+    if (a.state[slot] != TRACER_ALIVE) return;                       // a dead or empty slot is not touched
+    const float px = a.pos[3 * (int64_t)slot], py = a.pos[3 * (int64_t)slot + 1], pz = a.pos[3 * (int64_t)slot + 2];
+    const StreamLevel mine = a.s.lv[max(a.s.n_levels - 1 - c, 0)];
+    float q[4], qm[4];
+    int li = 0, lm = 0;
+    int code = stream_sample<false>(a.s, mine, c, px, py, pz, q, li);
+    if (!code) {
+        const float hh = 0.5f * a.dt;
+        const float mx = px + hh * q[1], my = py + hh * q[2], mz = pz + hh * q[3];
+        code = stream_sample<false>(a.s, mine, c, mx, my, mz, qm, lm);
+    }
+    if (code) {                                                      // P stays
+        if (c == 0) a.state[slot] = code;
+        return;
+    }
+    const float nx = px + a.dt * qm[1], ny = py + a.dt * qm[2], nz = pz + a.dt * qm[3];
+    if (c != 0) return;
+    if (!(isfinite(nx) && isfinite(ny) && isfinite(nz))) {
+        a.state[slot] = TRACER_NONFINITE;
+        return;
+    }
+    a.pos[3 * (int64_t)slot] = nx;
+    a.pos[3 * (int64_t)slot + 1] = ny;
+    a.pos[3 * (int64_t)slot + 2] = nz;
+}
+
+// rec[slot] = x, y, z, ux, uy, uz, level index, code: an alive slot sampled at P (code 0; a failed sample: zeros, level -1, its code),
+// any other slot zeros, level -1 and its state. Changes nothing of the set's state.
+__global__ __launch_bounds__(64) void k_tracers_snapshot(const TracerArgs a)
+{
+    const int64_t lane = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const int64_t slot64 = lane >> 3;
+    const int c = (int)(lane & 7);
+    if (slot64 >= a.n_slots) return;
+    const int slot = (int)slot64;
+    const float px = a.pos[3 * (int64_t)slot], py = a.pos[3 * (int64_t)slot + 1], pz = a.pos[3 * (int64_t)slot + 2];
+    int code = a.state[slot];
+    float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int li = -1;
+    if (code == TRACER_ALIVE) {
+        const StreamLevel mine = a.s.lv[max(a.s.n_levels - 1 - c, 0)];
+        code = stream_sample<false>(a.s, mine, c, px, py, pz, q, li);
+        if (code) {
+            q[1] = q[2] = q[3] = 0.0f;
+            li = -1;
+        }
+    }
+    float4 *rec = (float4 *)(a.rec + (int64_t)slot * STREAM_REC_FLOATS);
+    if (c == 0) rec[0] = make_float4(px, py, pz, q[1]);
+    if (c == 1) rec[1] = make_float4(q[2], q[3], (float)li, (float)code);
 }
 
 // ---- iso-surfaces (ludwig_level_isosurface_*; no reference counterpart; open_ludwig_amd/isosurface.py states the definition and

@@ -2039,8 +2039,18 @@ struct ForceSampler {
     int64_t start_step = 0;
     int32_t interval = 1;
 };
+// the tracer set a batch advances (ludwig_execute_timestep_batch_tracers): after coarse steps start_step + k interval
+struct TracerSampler {
+    LudwigTracers *set = nullptr;
+    int64_t start_step = 0;
+    int32_t interval = 1;
+};
+static int tracers_launch_advance(LudwigTracers *S, int64_t t_coarse, hipStream_t st);
+static hipEvent_t tracers_event(LudwigTracers *S);
+static bool tracers_empty(const LudwigTracers *S);
 static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs = nullptr);
+                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs = nullptr,
+                      const TracerSampler *ts = nullptr);
 
 int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                                   const LudwigStepFlags *flags)
@@ -2048,6 +2058,23 @@ int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, 
     const int r = check_batch_levels(levels, n_levels, batch_size, flags);
     if (r) return r;
     return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr);
+}
+
+// one advance of a batch's tracer set behind coarse step t: with level streams, a full join around the launch (see batch_impl)
+static int batch_tracers_advance(LudwigLevel *const *levels, int32_t n_levels, LudwigTracers *T, int64_t t, bool concurrent)
+{
+    hipStream_t st = levels[0]->stream;
+    if (!concurrent || tracers_empty(T)) return tracers_launch_advance(T, t, st);      // one stream, or nothing to launch: no event
+    hipEvent_t ev = tracers_event(T);
+    for (int i = 1; i < n_levels; ++i) {
+        LW_HIP(hipEventRecord(ev, levels[i]->stream));
+        LW_HIP(hipStreamWaitEvent(st, ev, 0));
+    }
+    const int rc = tracers_launch_advance(T, t, st);
+    if (rc) return rc;
+    LW_HIP(hipEventRecord(ev, st));
+    for (int i = 1; i < n_levels; ++i) LW_HIP(hipStreamWaitEvent(levels[i]->stream, ev, 0));
+    return LUDWIG_OK;
 }
 
 // Level streams. The reference steps its levels strictly one after the other (src/solver_control.jl:21-143), and every launch
@@ -2064,12 +2091,16 @@ int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, 
 // r02_level_streams_with_priorities_ab_one_box.txt): 3-level sphere 0.419 -> 0.393 ms per coarse step, real wing 1.011 -> 0.949,
 // 4-level sphere 1.72 -> 1.52; without the priorities 0.402 / 0.982 / 1.58 (and on another box the 4-level case got slower).
 // LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
+// Tracers (ts): after the host has issued every launch of coarse step t and none of t + 1, an advanced step joins all level streams -
+// the first level's stream waits for what the others have queued, runs the advance, and the others wait for it before they go on. That
+// only adds ordering; at advanced steps it gives up the overlap of level 1's step t + 1 with the finer levels' tail of step t.
 static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs)
+                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs, const TracerSampler *ts)
 {
     LudwigProbes *probes = s ? s->probes : nullptr;
     LudwigSurfaceStats *surface = s ? s->surface : nullptr;
     LudwigForceSeries *forces = fs ? fs->set : nullptr;
+    LudwigTracers *tracers = ts ? ts->set : nullptr;
     const bool concurrent = n_levels > 1 && !env::batch_serial();
     hipStream_t user_stream = levels[0]->stream;
     if (concurrent) {
@@ -2131,17 +2162,18 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         const int64_t t = t_start + o;
         if (!probes && !surface && !forces) {
             rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent);
-            continue;
+        } else {
+            BatchHook ph;
+            ph.P = probes;
+            ph.S = surface;
+            ph.t = t;
+            if (probes && step_sampled(t, s->probes_start_step, s->probes_interval)) ph.slot = probes_open_slot(probes, t);
+            ph.surface = surface && step_sampled(t, s->surface_start_step, s->surface_interval);
+            ph.F = forces;
+            ph.forces = forces && step_sampled(t, fs->start_step, fs->interval);
+            rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
         }
-        BatchHook ph;
-        ph.P = probes;
-        ph.S = surface;
-        ph.t = t;
-        if (probes && step_sampled(t, s->probes_start_step, s->probes_interval)) ph.slot = probes_open_slot(probes, t);
-        ph.surface = surface && step_sampled(t, s->surface_start_step, s->surface_interval);
-        ph.F = forces;
-        ph.forces = forces && step_sampled(t, fs->start_step, fs->interval);
-        rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
+        if (rc == LUDWIG_OK && tracers && step_sampled(t, ts->start_step, ts->interval)) rc = batch_tracers_advance(levels, n_levels, tracers, t, concurrent);
     }
     if (concurrent) {
         hipError_t e = hipSuccess;
@@ -3072,15 +3104,30 @@ int ludwig_force_series_download(LudwigForceSeries *F, double *sums, int64_t *co
     return LUDWIG_OK;
 }
 
+static int check_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, const TracerSampler *ts);
+static int batch_loads_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                               const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
+                               int32_t interval, const TracerSampler *ts);
+
 int ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                                         const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
                                         int32_t interval)
 {
     if (!fs) return ludwig_execute_timestep_batch_sampled(levels, n_levels, t_start, batch_size, u_curr, flags, s);
+    return batch_loads_tracers(levels, n_levels, t_start, batch_size, u_curr, flags, s, fs, start_step, interval, nullptr);
+}
+
+// ludwig_execute_timestep_batch_loads with a force series, a tracer set or both: every refusal comes before anything is stepped
+static int batch_loads_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                               const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
+                               int32_t interval, const TracerSampler *ts)
+{
     int r = check_batch_levels(levels, n_levels, batch_size, flags);
     if (r) return r;
     if (s && !s->probes && !s->surface) s = nullptr;
     if (s && (r = check_batch_samplers(levels, n_levels, t_start, batch_size, s))) return r;
+    if (ts && (r = check_batch_tracers(levels, n_levels, ts))) return r;
+    if (!fs) return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s, nullptr, ts);
     if (interval < 1) return fail(LUDWIG_ERR_INVALID, "force series: interval %d < 1", interval);
     bool in_batch = false;
     for (int i = 0; i < n_levels; ++i) in_batch = in_batch || levels[i] == fs->level;
@@ -3094,7 +3141,7 @@ int ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_le
     f.set = fs;
     f.start_step = start_step;
     f.interval = interval;
-    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s, &f);
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s, &f, ts);
 }
 
 // ---- slices (ludwig_slices_*; no reference counterpart) ----
@@ -3270,6 +3317,49 @@ int ludwig_slices_download(LudwigSlices *S, float *values, size_t bytes)
     return LUDWIG_OK;
 }
 
+// ---- what the sets that locate points on the hierarchy themselves share (streamlines, tracers) ----
+// the creators' checks of the level array (`set` = "streamlines", "tracers"; `what` = "a line", "a particle")
+static int check_locator_levels(const char *set, const char *what, LudwigLevel *const *levels, int32_t n_levels)
+{
+    for (int li = 0; li < n_levels; ++li) {
+        const LudwigLevel *L = levels[li];
+        if (!L) return fail(LUDWIG_ERR_INVALID, "%s: level %d is null", set, li);
+        if (L->device != levels[0]->device) return fail(LUDWIG_ERR_STATE, "%s: levels on different devices", set);
+        if (L->n_owned != L->n_blocks)
+            return fail(LUDWIG_ERR_STATE, "%s: level %d holds ghost blocks (%d of %d owned): %s cannot cross ranks", set, li, L->n_owned,
+                        L->n_blocks, what);
+        if (L->h_block_pointer.size() != (size_t)L->gdx * L->gdy * L->gdz || (L->n_blocks > 0 && L->h_block_pointer.empty()))
+            return fail(LUDWIG_ERR_STATE, "%s: level %d was created without block_pointer", set, li);
+        if ((int64_t)L->gdx * 8 > (1 << 24) || (int64_t)L->gdy * 8 > (1 << 24) || (int64_t)L->gdz * 8 > (1 << 24))
+            return fail(LUDWIG_ERR_INVALID, "%s: level %d has more cells per axis than float32 counts exactly", set, li);
+        // the kernel trusts a positive entry as a block index
+        for (const int32_t v : L->h_block_pointer)
+            if (v < 0 || v > L->n_blocks) return fail(LUDWIG_ERR_STATE, "%s: level %d: block_pointer entry %d out of range", set, li, v);
+    }
+    return LUDWIG_OK;
+}
+
+// every level's block_pointer (bp[li], in the library's block order) and the table of StreamLevel entries on the device; with_rho =
+// false leaves the rho pointers null (the tracers never read rho)
+static void upload_locator_table(hipError_t &e, LudwigLevel *const *levels, int32_t n_levels, bool with_rho, std::vector<int32_t *> &bp,
+                                 StreamLevel *&table_dev)
+{
+    std::vector<StreamLevel> table(n_levels);
+    for (int li = 0; li < n_levels && e == hipSuccess; ++li) {
+        const LudwigLevel *L = levels[li];
+        if (!L->h_block_pointer.empty()) upload_table(e, L->h_block_pointer, bp[li]);
+        StreamLevel &t = table[li];
+        t.bp = bp[li];
+        t.obstacle = L->obstacle;
+        t.rho = with_rho ? L->rho : nullptr;
+        t.vel[0] = L->vel[0];
+        t.vel[1] = L->vel[1];
+        t.gx = L->gdx; t.gy = L->gdy; t.gz = L->gdz;
+        t.n_blocks = L->n_blocks;
+    }
+    upload_table(e, table, table_dev);
+}
+
 // ---- streamlines (ludwig_streamlines_*; no reference counterpart) ----
 // Per level its block_pointer on the device (internal block order, as the level keeps it) inside one table of StreamLevel entries; the
 // records [n_lines][max_steps + 1][8], counts and codes. One event orders the trace after the other levels' streams and them after it.
@@ -3314,21 +3404,7 @@ int ludwig_streamlines_create(LudwigLevel *const *levels, int32_t n_levels, int3
         return fail(LUDWIG_ERR_INVALID, "streamlines: %d lines of %d steps are more than 2^31 - 1 records", n_lines, max_steps);
     for (int32_t i = 0; i < n_lines; ++i)
         if (sign[i] != 1.0f && sign[i] != -1.0f) return fail(LUDWIG_ERR_INVALID, "streamlines: sign[%d] = %g is neither 1 nor -1", i, (double)sign[i]);
-    for (int li = 0; li < n_levels; ++li) {
-        const LudwigLevel *L = levels[li];
-        if (!L) return fail(LUDWIG_ERR_INVALID, "streamlines: level %d is null", li);
-        if (L->device != levels[0]->device) return fail(LUDWIG_ERR_STATE, "streamlines: levels on different devices");
-        if (L->n_owned != L->n_blocks)
-            return fail(LUDWIG_ERR_STATE, "streamlines: level %d holds ghost blocks (%d of %d owned): a line cannot cross ranks", li, L->n_owned,
-                        L->n_blocks);
-        if (L->h_block_pointer.size() != (size_t)L->gdx * L->gdy * L->gdz || (L->n_blocks > 0 && L->h_block_pointer.empty()))
-            return fail(LUDWIG_ERR_STATE, "streamlines: level %d was created without block_pointer", li);
-        if ((int64_t)L->gdx * 8 > (1 << 24) || (int64_t)L->gdy * 8 > (1 << 24) || (int64_t)L->gdz * 8 > (1 << 24))
-            return fail(LUDWIG_ERR_INVALID, "streamlines: level %d has more cells per axis than float32 counts exactly", li);
-        // the kernel trusts a positive entry as a block index
-        for (const int32_t v : L->h_block_pointer)
-            if (v < 0 || v > L->n_blocks) return fail(LUDWIG_ERR_STATE, "streamlines: level %d: block_pointer entry %d out of range", li, v);
-    }
+    if (int rl = check_locator_levels("streamlines", "a line", levels, n_levels)) return rl;
     LudwigStreamlines *S = new (std::nothrow) LudwigStreamlines;
     if (!S) return fail(LUDWIG_ERR_ALLOC, "streamlines: out of host memory");
     S->device = levels[0]->device;
@@ -3341,21 +3417,8 @@ int ludwig_streamlines_create(LudwigLevel *const *levels, int32_t n_levels, int3
     S->bp.assign(n_levels, nullptr);
     int r = set_device(S->device);
     hipError_t e = hipSuccess;
-    std::vector<StreamLevel> table(n_levels);
-    for (int li = 0; li < n_levels && r == LUDWIG_OK && e == hipSuccess; ++li) {
-        const LudwigLevel *L = levels[li];
-        if (!L->h_block_pointer.empty()) upload_table(e, L->h_block_pointer, S->bp[li]);
-        StreamLevel &t = table[li];
-        t.bp = S->bp[li];
-        t.obstacle = L->obstacle;
-        t.rho = L->rho;
-        t.vel[0] = L->vel[0];
-        t.vel[1] = L->vel[1];
-        t.gx = L->gdx; t.gy = L->gdy; t.gz = L->gdz;
-        t.n_blocks = L->n_blocks;
-    }
     if (r == LUDWIG_OK) {
-        upload_table(e, table, S->table);
+        upload_locator_table(e, levels, n_levels, true, S->bp, S->table);
         if (n_lines > 0) {
             const size_t n = (size_t)n_lines;
             const std::vector<float> hs(seeds, seeds + 3 * n), hg(sign, sign + n);
@@ -3436,6 +3499,210 @@ int ludwig_streamlines_download(LudwigStreamlines *S, int32_t *counts, int32_t *
     if (longest > 0)                                              // the used head of every line's row
         LW_HIP(hipMemcpy2D(vertices, row, S->rec, row, (size_t)longest * STREAM_REC_FLOATS * sizeof(float), n, hipMemcpyDeviceToHost));
     return LUDWIG_OK;
+}
+
+// ---- tracers (ludwig_tracers_*; no reference counterpart) ----
+// The streamlines' level table (every level's block_pointer on the device) plus what persists: positions and states of n_seeds x
+// generations slots, the snapshot records, and on the host the count of advances, which alone decides the released generation.
+struct LudwigTracers {
+    int device = 0;
+    int n_levels = 0, n_seeds = 0, generations = 0, release_every = 0;
+    int64_t n_slots = 0, n_advances = 0;
+    float dt = 0.0f;
+    std::vector<LudwigLevel *> levels;
+    std::vector<int32_t *> bp;                  // per level, device
+    StreamLevel *table = nullptr;               // [n_levels], device
+    float *seeds = nullptr, *pos = nullptr, *rec = nullptr;
+    int32_t *state = nullptr;
+    hipEvent_t ev = nullptr;
+    bool snapshot = false;
+};
+
+void ludwig_tracers_destroy(LudwigTracers *S)
+{
+    if (!S) return;
+    (void)hipSetDevice(S->device);
+    for (int32_t *q : S->bp)
+        if (q) (void)hipFree(q);
+    void *bufs[] = {S->table, S->seeds, S->pos, S->rec, S->state};
+    for (void *q : bufs)
+        if (q) (void)hipFree(q);
+    if (S->ev) (void)hipEventDestroy(S->ev);
+    delete S;
+}
+
+int ludwig_tracers_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_seeds, const float *seeds, int32_t generations,
+                          int32_t release_every, float dt, LudwigTracers **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels || (n_seeds > 0 && !seeds)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > 30) return fail(LUDWIG_ERR_INVALID, "tracers: n_levels %d not in 1..30", n_levels);
+    if (n_seeds < 0) return fail(LUDWIG_ERR_INVALID, "tracers: n_seeds %d < 0", n_seeds);
+    if (generations < 1) return fail(LUDWIG_ERR_INVALID, "tracers: generations %d < 1", generations);
+    if (release_every < 1) return fail(LUDWIG_ERR_INVALID, "tracers: release_every %d < 1", release_every);
+    if (!(dt > 0.0f) || !std::isfinite(dt)) return fail(LUDWIG_ERR_INVALID, "tracers: dt %g must be positive and finite", (double)dt);
+    // eight lanes per slot, lane numbers and record offsets in 32 bits with room to spare
+    if ((int64_t)n_seeds * (int64_t)generations > (int64_t)INT32_MAX / 8)
+        return fail(LUDWIG_ERR_INVALID, "tracers: %d seeds of %d generations are more than 2^28 - 1 slots", n_seeds, generations);
+    if (int rl = check_locator_levels("tracers", "a particle", levels, n_levels)) return rl;
+    LudwigTracers *S = new (std::nothrow) LudwigTracers;
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "tracers: out of host memory");
+    S->device = levels[0]->device;
+    S->n_levels = n_levels;
+    S->n_seeds = n_seeds;
+    S->generations = generations;
+    S->release_every = release_every;
+    S->n_slots = (int64_t)n_seeds * generations;
+    S->dt = dt;
+    S->levels.assign(levels, levels + n_levels);
+    S->bp.assign(n_levels, nullptr);
+    int r = set_device(S->device);
+    hipError_t e = hipSuccess;
+    if (r == LUDWIG_OK) {
+        upload_locator_table(e, levels, n_levels, false, S->bp, S->table);      // a tracer carries no rho
+        if (S->n_slots > 0) {
+            const size_t n = (size_t)S->n_slots;
+            const std::vector<float> hs(seeds, seeds + 3 * (size_t)n_seeds);
+            const std::vector<int32_t> empty(n, TRACER_EMPTY);
+            const std::vector<float> zero(3 * n, 0.0f);
+            upload_table(e, hs, S->seeds);
+            upload_table(e, zero, S->pos);
+            upload_table(e, empty, S->state);
+            if (e == hipSuccess) e = hipMalloc((void **)&S->rec, n * STREAM_REC_FLOATS * sizeof(float));
+        }
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev, hipEventDisableTiming);
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "tracers: %d seeds of %d generations: %s", n_seeds, generations, hipGetErrorString(e));
+    }
+    if (r != LUDWIG_OK) {
+        ludwig_tracers_destroy(S);
+        return r;
+    }
+    *out = S;
+    return LUDWIG_OK;
+}
+
+static hipEvent_t tracers_event(LudwigTracers *S) { return S->ev; }
+static bool tracers_empty(const LudwigTracers *S) { return S->n_slots == 0; }
+
+// the kernel's arguments for the levels' newest velocity after coarse step t_coarse (the buffer ludwig_streamlines_trace chooses)
+static TracerArgs tracers_args(const LudwigTracers *S, int64_t t_coarse)
+{
+    TracerArgs a{};
+    a.s.lv = S->table;
+    a.s.n_levels = S->n_levels;
+    for (int li = 0; li < S->n_levels; ++li)
+        if (vel_out(S->levels[li], (t_coarse + 1) * ((int64_t)1 << li) - 1) == S->levels[li]->vel[1]) a.s.temp_mask |= 1u << li;
+    a.seeds = S->seeds;
+    a.pos = S->pos;
+    a.state = S->state;
+    a.rec = S->rec;
+    a.n_seeds = S->n_seeds;
+    a.n_slots = (int32_t)S->n_slots;
+    a.released = -1;
+    a.dt = S->dt;
+    return a;
+}
+
+// advance k = n_advances on stream st; the caller has ordered st behind the levels' steps. A set without slots launches nothing.
+static int tracers_launch_advance(LudwigTracers *S, int64_t t_coarse, hipStream_t st)
+{
+    const int64_t k = S->n_advances++;
+    if (S->n_slots == 0) return LUDWIG_OK;
+    TracerArgs a = tracers_args(S, t_coarse);
+    if (k % S->release_every == 0) a.released = (int32_t)((k / S->release_every) % S->generations);
+    hipLaunchKernelGGL(k_tracers_advance, dim3((unsigned)((S->n_slots * 8 + 63) / 64)), dim3(64), 0, st, a);
+    LW_HIP(hipGetLastError());
+    return LUDWIG_OK;
+}
+
+// the first level's stream waits for what the other levels' streams have queued (outside a batch they are usually the same stream)
+static int tracers_join(LudwigTracers *S, hipStream_t st)
+{
+    for (int li = 0; li < S->n_levels; ++li)
+        if (S->levels[li]->stream != st) {
+            LW_HIP(hipEventRecord(S->ev, S->levels[li]->stream));
+            LW_HIP(hipStreamWaitEvent(st, S->ev, 0));
+        }
+    return LUDWIG_OK;
+}
+
+// and nothing queued there later overtakes the kernel's reads
+static int tracers_release(LudwigTracers *S, hipStream_t st)
+{
+    bool others = false;
+    for (int li = 1; li < S->n_levels; ++li) others = others || S->levels[li]->stream != st;
+    if (!others) return LUDWIG_OK;
+    LW_HIP(hipEventRecord(S->ev, st));
+    for (int li = 1; li < S->n_levels; ++li)
+        if (S->levels[li]->stream != st) LW_HIP(hipStreamWaitEvent(S->levels[li]->stream, S->ev, 0));
+    return LUDWIG_OK;
+}
+
+int ludwig_tracers_advance(LudwigTracers *S, int64_t t_coarse)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null tracer set");
+    if (t_coarse < 0) return fail(LUDWIG_ERR_INVALID, "tracers: t_coarse %lld < 0", (long long)t_coarse);
+    if (S->n_slots == 0) { ++S->n_advances; return LUDWIG_OK; }
+    LW_HIP(hipSetDevice(S->device));
+    hipStream_t st = S->levels[0]->stream;
+    int r = tracers_join(S, st);
+    if (r) return r;
+    if ((r = tracers_launch_advance(S, t_coarse, st))) return r;
+    return tracers_release(S, st);
+}
+
+int ludwig_tracers_snapshot(LudwigTracers *S, int64_t t_coarse)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null tracer set");
+    if (t_coarse < 0) return fail(LUDWIG_ERR_INVALID, "tracers: t_coarse %lld < 0", (long long)t_coarse);
+    S->snapshot = true;
+    if (S->n_slots == 0) return LUDWIG_OK;
+    LW_HIP(hipSetDevice(S->device));
+    hipStream_t st = S->levels[0]->stream;
+    const int r = tracers_join(S, st);
+    if (r) return r;
+    const TracerArgs a = tracers_args(S, t_coarse);
+    hipLaunchKernelGGL(k_tracers_snapshot, dim3((unsigned)((S->n_slots * 8 + 63) / 64)), dim3(64), 0, st, a);
+    LW_HIP(hipGetLastError());
+    return tracers_release(S, st);
+}
+
+int ludwig_tracers_download(LudwigTracers *S, float *records, size_t bytes, int64_t *n_advances)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null tracer set");
+    if (!S->snapshot) return fail(LUDWIG_ERR_STATE, "tracers: download before ludwig_tracers_snapshot");
+    const size_t want = (size_t)S->n_slots * STREAM_REC_FLOATS * sizeof(float);
+    if (bytes != want) return fail(LUDWIG_ERR_INVALID, "tracers: got %zu bytes, expected %zu", bytes, want);
+    if (n_advances) *n_advances = S->n_advances;
+    if (S->n_slots == 0) return LUDWIG_OK;
+    if (!records) return fail(LUDWIG_ERR_INVALID, "null argument");
+    LW_HIP(hipSetDevice(S->device));
+    LW_HIP(hipStreamSynchronize(S->levels[0]->stream));
+    LW_HIP(hipMemcpy(records, S->rec, want, hipMemcpyDeviceToHost));
+    return LUDWIG_OK;
+}
+
+static int check_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, const TracerSampler *ts)
+{
+    if (ts->interval < 1) return fail(LUDWIG_ERR_INVALID, "tracers: interval %d < 1", ts->interval);
+    if (ts->set->n_levels != n_levels) return fail(LUDWIG_ERR_INVALID, "tracers: set made over %d levels, batch of %d", ts->set->n_levels, n_levels);
+    for (int i = 0; i < n_levels; ++i)
+        if (ts->set->levels[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "tracers: set made over other levels (level %d)", i + 1);
+    return LUDWIG_OK;
+}
+
+int ludwig_execute_timestep_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                          const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs,
+                                          int64_t force_start_step, int32_t force_interval, LudwigTracers *tracers, int64_t start_step,
+                                          int32_t interval)
+{
+    if (!tracers) return ludwig_execute_timestep_batch_loads(levels, n_levels, t_start, batch_size, u_curr, flags, s, fs, force_start_step, force_interval);
+    TracerSampler ts;
+    ts.set = tracers;
+    ts.start_step = start_step;
+    ts.interval = interval;
+    return batch_loads_tracers(levels, n_levels, t_start, batch_size, u_curr, flags, s, fs, force_start_step, force_interval, &ts);
 }
 
 int ludwig_halo_pack(const LudwigLevel *L, int field, const int64_t *index_dev, int64_t n, float *dst_dev, void *hip_stream)

@@ -250,8 +250,9 @@ class IsoWriter:
 
 
 def read_vtp(path: str) -> Dict[str, np.ndarray]:
-    """the arrays of a file output.write_vtp or output.write_vtp_lines wrote: Points [n, 3], connectivity, offsets (of the Polys or the
-    Lines, whichever the file holds), the point arrays and the cell arrays by name"""
+    """the arrays of a file output.write_vtp, write_vtp_lines or write_vtp_tracers wrote: Points [n, 3], connectivity, offsets (of the
+    Polys or the Lines, whichever the file holds), the point arrays and the cell arrays by name; a file with a Verts section (the
+    tracers') also gives verts_connectivity, verts_offsets and NumberOfVerts"""
     from .slices import _NP_TYPE, _decode
     root = ET.parse(path).getroot()
     compressed = root.get("compressor") is not None
@@ -263,6 +264,11 @@ def read_vtp(path: str) -> Dict[str, np.ndarray]:
             a = _decode(da.text or "", _NP_TYPE[da.get("type")], compressed)
             k = int(da.get("NumberOfComponents", "1"))
             out[da.get("Name")] = a.reshape(-1, k) if k > 1 else a
+    verts = piece.find("Verts")
+    if verts is not None:
+        for da in verts.findall("DataArray"):
+            out["verts_" + da.get("Name")] = _decode(da.text or "", _NP_TYPE[da.get("type")], compressed)
+        out["NumberOfVerts"] = np.int64(piece.get("NumberOfVerts"))
     out["NumberOfPoints"] = np.int64(piece.get("NumberOfPoints"))
     out["NumberOfPolys"] = np.int64(piece.get("NumberOfPolys"))
     out["NumberOfLines"] = np.int64(piece.get("NumberOfLines"))

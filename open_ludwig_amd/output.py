@@ -161,6 +161,42 @@ def write_vtp_lines(filename: str, points: np.ndarray, offsets: np.ndarray, dens
     return path
 
 
+def write_vtp_tracers(filename: str, points: np.ndarray, velocity: np.ndarray, level: np.ndarray, particle_id: np.ndarray, seed: np.ndarray,
+                      age: np.ndarray, line_connectivity: np.ndarray, line_offsets: np.ndarray, compress: bool = True) -> str:
+    """VTK XML PolyData of tracer particles (no reference counterpart; tracers.py): points [n, 3] Float32 in the flow file's frame, one
+    `Verts` cell per point; `Lines` cells = streaklines (connectivity of point indices, offsets = the end of every line in it); point
+    arrays Velocity, Level, ParticleId, Seed, Age (Int32). Cells carry no arrays. Written whole, then renamed. Returns the path."""
+    path = filename if filename.endswith(".vtp") else filename + ".vtp"
+    pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    conn = np.ascontiguousarray(line_connectivity, dtype=np.int64).reshape(-1)
+    off = np.ascontiguousarray(line_offsets, dtype=np.int64).reshape(-1)
+    comp_attr = ' compressor="vtkZLibDataCompressor"' if compress else ""
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    n = pts.shape[0]
+    tmp = path + ".part"
+    with open(tmp, "w") as io:
+        io.write('<?xml version="1.0" encoding="utf-8"?>\n')
+        io.write(f'<VTKFile type="PolyData" version="1.0" byte_order="LittleEndian" header_type="UInt64"{comp_attr}>\n')
+        io.write("<PolyData>\n")
+        io.write(f'<Piece NumberOfPoints="{n}" NumberOfVerts="{n}" NumberOfLines="{off.shape[0]}" NumberOfStrips="0" NumberOfPolys="0">\n')
+        io.write("<Points>\n" + _data_array("Points", pts, compress, 3) + "</Points>\n")
+        io.write("<Verts>\n")
+        io.write(_data_array("connectivity", np.arange(n, dtype=np.int64), compress))
+        io.write(_data_array("offsets", np.arange(1, n + 1, dtype=np.int64), compress))
+        io.write("</Verts>\n<Lines>\n")
+        io.write(_data_array("connectivity", conn, compress))
+        io.write(_data_array("offsets", off, compress))
+        io.write("</Lines>\n<PointData>\n")
+        io.write(_data_array("Velocity", np.ascontiguousarray(velocity, dtype=np.float32).reshape(-1, 3), compress, 3))
+        io.write(_data_array("Level", i32(level), compress))
+        io.write(_data_array("ParticleId", i32(particle_id), compress))
+        io.write(_data_array("Seed", i32(seed), compress))
+        io.write(_data_array("Age", i32(age), compress))
+        io.write("</PointData>\n</Piece>\n</PolyData>\n</VTKFile>\n")
+    os.replace(tmp, path)
+    return path
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # flow export (src/io_vtk.jl)
 # ----------------------------------------------------------------------------------------------------------------

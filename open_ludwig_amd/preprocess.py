@@ -143,6 +143,17 @@ class CaseConfig:
     streamlines_direction: str = "both"
     streamlines_max_vertices: int = 20_000_000
     streamlines_seeds: Tuple["StreamlineSeeds", ...] = ()
+    # tracers, advanced.tracers (no reference counterpart): particles advected on the device inside every batch, one advance every
+    # `interval` coarse steps from `start_step`, one release per seed every `release_every` advances into a ring of `generations`; every
+    # `output_interval` coarse steps a snapshot goes to tracers_<name>_%06d.vtp and tracers_<name>.pvd (tracers.py)
+    tracers_enabled: bool = False
+    tracers_start_step: int = 1
+    tracers_interval: int = 1
+    tracers_release_every: int = 10
+    tracers_generations: int = 64
+    tracers_output_interval: int = 100
+    tracers_max_particles: int = 4_000_000
+    tracers_seeds: Tuple["StreamlineSeeds", ...] = ()
     # flow monitor, advanced.flow_monitor (no reference counterpart; its advanced.diagnostics.stability_check is read by nobody, there or
     # here): a health record of every level at every diagnostics step, written to flow_monitor.csv (monitor.py)
     flow_monitor_enabled: bool = False
@@ -198,6 +209,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     slices = _slices_config(g("advanced", "slices", default=None))
     isosurfaces = _isosurfaces_config(g("advanced", "isosurfaces", default=None))
     streamlines = _streamlines_config(g("advanced", "streamlines", default=None))
+    tracers = _tracers_config(g("advanced", "tracers", default=None), int(g("basic", "simulation", "steps", required=True)))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
     wall_diag = _wall_diagnostics_config(g("advanced", "wall_diagnostics", default=None))
     return CaseConfig(
@@ -256,6 +268,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **slices,
         **isosurfaces,
         **streamlines,
+        **tracers,
         **flow_monitor,
         **wall_diag,
         y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
@@ -566,6 +579,54 @@ def _streamlines_config(sc) -> dict:
     return dict(streamlines_enabled=True, streamlines_start_step=start, streamlines_interval=interval, streamlines_step=step,
                 streamlines_max_steps=max_steps, streamlines_min_speed=min_speed, streamlines_direction=direction,
                 streamlines_max_vertices=cap, streamlines_seeds=tuple(groups))
+
+
+def _tracers_config(tc, steps: int) -> dict:
+    """advanced.tracers: {enabled: false, start_step: 1, interval: 1, release_every: 10, generations: 64, output_interval: 100,
+    max_particles: 4000000, seeds: [{name, points: [[x, y, z], ...]} | {name, line: {from, to, count}}]} -> CaseConfig fields. interval:
+    coarse steps per advance (= dt); release_every: in advances; output_interval: in coarse steps, a multiple of interval. Absent or
+    disabled: the defaults."""
+    if tc is None:
+        return {}
+    if not isinstance(tc, dict):
+        raise ValueError("advanced.tracers must be a mapping")
+    if not bool(tc.get("enabled", False)):
+        return {}
+    from .streamlines import expand_group
+    from .tracers import check_capacity
+    try:
+        start, interval = int(tc.get("start_step", 1)), int(tc.get("interval", 1))
+        release, gens = int(tc.get("release_every", 10)), int(tc.get("generations", 64))
+        out_interval, cap = int(tc.get("output_interval", 100)), int(tc.get("max_particles", 4_000_000))
+    except (TypeError, ValueError):
+        raise ValueError("advanced.tracers: start_step, interval, release_every, generations, output_interval and max_particles must be "
+                         "integers") from None
+    for key, v in (("interval", interval), ("start_step", start), ("release_every", release), ("generations", gens),
+                   ("output_interval", out_interval), ("max_particles", cap)):
+        if v < 1:
+            raise ValueError(f"advanced.tracers.{key} must be >= 1, got {v}")
+    if out_interval % interval != 0:
+        raise ValueError(f"advanced.tracers.output_interval {out_interval} must be a multiple of advanced.tracers.interval {interval}")
+    raw = tc.get("seeds") or []
+    if not isinstance(raw, (list, tuple)) or not raw:
+        raise ValueError("advanced.tracers.enabled needs at least one entry in advanced.tracers.seeds")
+    groups, seen, n_seeds = [], set(), 0
+    for i, gc in enumerate(raw):
+        where = f"advanced.tracers.seeds[{i}]"
+        if not isinstance(gc, dict):
+            raise ValueError(f"{where} must be a mapping")
+        name = str(gc.get("name", ""))
+        if not name or not all(ch.isalnum() or ch in "_-." for ch in name) or name.startswith("."):
+            raise ValueError(f"{where}.name {name!r} is not a plain file-name stem")
+        if name in seen:
+            raise ValueError(f"{where}.name {name!r} is not unique")
+        seen.add(name)
+        pts = expand_group(gc, where)
+        n_seeds += pts.shape[0]
+        groups.append(StreamlineSeeds(name, tuple(tuple(float(v) for v in p) for p in pts)))
+    check_capacity(n_seeds, gens, cap, steps, start, interval, release)
+    return dict(tracers_enabled=True, tracers_start_step=start, tracers_interval=interval, tracers_release_every=release,
+                tracers_generations=gens, tracers_output_interval=out_interval, tracers_max_particles=cap, tracers_seeds=tuple(groups))
 
 
 # ----------------------------------------------------------------------------------------------------------------

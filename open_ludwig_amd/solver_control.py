@@ -37,7 +37,7 @@ def recursive_step(grids: Sequence[DeviceLevel], current_lvl: int, t_sub: int, p
 
 
 def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_size: int, u_curr,
-                           params: SolverParams, native: bool = True, probes=None, surface=None, forces=None) -> None:
+                           params: SolverParams, native: bool = True, probes=None, surface=None, forces=None, tracers=None) -> None:
     """execute_timestep_batch! (src/solver_control.jl:145-165); t_start is 1-based like the reference's loop.
 
     native=True (default): the whole batch is one C call (ludwig_execute_timestep_batch runs the same recursion inside
@@ -48,7 +48,9 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
     surface: a surface_stats.DeviceSurfaceStats on one of `grids`, sampled after every coarse step start_step + k interval (native:
     inside the C batch, ludwig_execute_timestep_batch_sampled; else through its accumulate() after the coarse step).
     forces: a force_series.DeviceForceSeries on one of `grids`, sampled after every coarse step start_step + k interval (native: inside
-    the C batch, ludwig_execute_timestep_batch_loads; else through its sample() after the coarse step)."""
+    the C batch, ludwig_execute_timestep_batch_loads; else through its sample() after the coarse step).
+    tracers: a tracers.DeviceTracers made over `grids`, advanced behind every coarse step start_step + k interval (native: inside the C
+    batch, ludwig_execute_timestep_batch_tracers; else through its advance() after the coarse step) - the same bits either way."""
     if native:
         import ctypes as C
         from . import _lib
@@ -58,7 +60,18 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
             smp = _lib.BatchSamplers(probes.handle.value if probes is not None else None, probes.start_step if probes is not None else 0,
                                      probes.interval if probes is not None else 1, surface.handle.value if surface is not None else None,
                                      surface.start_step if surface is not None else 0, surface.interval if surface is not None else 1)
-        if forces is not None:
+        if tracers is not None:
+            any_sampler = probes is not None or surface is not None
+            if any_sampler and surface is None and forces is None:
+                smp = _lib.BatchSamplers(probes.handle.value, probes.start_step, probes.interval, None, 0, 1)
+            _lib.check(_lib.load().ludwig_execute_timestep_batch_tracers(arr, len(grids), int(t_start), int(batch_size),
+                                                                         float(np.float32(u_curr)), C.byref(fl),
+                                                                         C.byref(smp) if any_sampler else None,
+                                                                         forces.handle if forces is not None else None,
+                                                                         forces.start_step if forces is not None else 0,
+                                                                         forces.interval if forces is not None else 1, tracers.handle,
+                                                                         tracers.start_step, tracers.interval))
+        elif forces is not None:
             _lib.check(_lib.load().ludwig_execute_timestep_batch_loads(arr, len(grids), int(t_start), int(batch_size),
                                                                        float(np.float32(u_curr)), C.byref(fl), C.byref(smp), forces.handle,
                                                                        forces.start_step, forces.interval))
@@ -84,6 +97,8 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
             surface.accumulate(t_sub_after(surface.level_index, t))
         if forces is not None and forces.is_sample_step(t):
             forces.sample(t_sub_after(forces.level_index, t), t)
+        if tracers is not None and tracers.is_advance_step(t):
+            tracers.advance(t)
     grids[0].synchronize()                             # KernelAbstractions.synchronize(backend)
 
 
