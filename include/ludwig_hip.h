@@ -222,6 +222,30 @@ int  ludwig_save_old(LudwigLevel *level, int64_t t_sub);
 int  ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                    float u_curr, const LudwigStepFlags *flags);
 
+/* What a batch observes while it steps: a list of tagged entries, each a set (made by ludwig_probes_create, ludwig_surface_stats_create,
+ * ludwig_force_series_create or ludwig_tracers_create, below) observed at coarse steps start_step + k interval, k >= 0. */
+enum { LUDWIG_OBSERVE_PROBES = 0, LUDWIG_OBSERVE_SURFACE = 1, LUDWIG_OBSERVE_FORCES = 2, LUDWIG_OBSERVE_TRACERS = 3 };
+typedef struct LudwigBatchObserver {
+    int32_t kind;        /* LUDWIG_OBSERVE_* */
+    void   *set;         /* LudwigProbes* / LudwigSurfaceStats* / LudwigForceSeries* / LudwigTracers*; NULL: entry ignored */
+    int64_t start_step;  /* observed at coarse steps start_step + k interval, k >= 0 */
+    int32_t interval;
+} LudwigBatchObserver;
+/* ludwig_execute_timestep_batch with the sets of `observers` observed inside the batch, in any order, at most one per kind.
+ * n_observers = 0 (observers may then be NULL) is ludwig_execute_timestep_batch itself; an entry with a null set is skipped, its
+ * start_step and interval unread. Probes, the surface set and the force series: one launch (the force series: its reduction tree) per
+ * level concerned on that level's own stream, right after its last sub-step of an observed coarse step; the probes' ring slot is opened
+ * only then. Tracers: one advance behind an observed coarse step, when the host has issued every launch of that step and none of the
+ * next; with level streams the first level's stream waits for all the others, runs the advance, and all the others wait for it (ordering
+ * only). Everything is refused before anything is stepped, in this order: the levels; LUDWIG_ERR_INVALID with "observer" in the message
+ * for n_observers < 0, observers NULL with n_observers > 0, an unknown kind, or two non-null entries of one kind; then per set
+ * LUDWIG_ERR_INVALID for interval < 1, probes or tracers not made over exactly these levels (same handles, same order), a surface or
+ * force set whose level is not in `levels`, and LUDWIG_ERR_STATE if the batch's probe samples or force records would overflow the free
+ * ring. */
+int  ludwig_execute_timestep_batch_observed(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
+                                            float u_curr, const LudwigStepFlags *flags, const LudwigBatchObserver *observers,
+                                            int32_t n_observers);
+
 /* KernelAbstractions.synchronize(backend) (src/solver_control.jl:164) */
 int  ludwig_sync(const LudwigLevel *level);
 
@@ -412,10 +436,7 @@ int  ludwig_probes_sample(LudwigProbes *probes, int32_t level_index, int64_t t_s
 /* the samples taken since the last download, oldest first: values [n][n_probes][4], steps [n] (coarse steps); *n_samples = n.
  * Synchronizes the streams of the probed levels, then empties the ring. LUDWIG_ERR_INVALID when n > max_samples. */
 int  ludwig_probes_download(LudwigProbes *probes, float *values, int64_t *steps, int32_t max_samples, int32_t *n_samples);
-/* ludwig_execute_timestep_batch with the probes sampled inside the batch: at coarse steps start_step + k interval (k >= 0), one
- * launch per probed level on that level's own stream, right after its last sub-step of the coarse step. probes = NULL is
- * ludwig_execute_timestep_batch itself. Fails before stepping anything with LUDWIG_ERR_STATE if the batch's samples would overflow
- * the free ring, with LUDWIG_ERR_INVALID if the set was made over other levels or interval < 1. */
+/* ludwig_execute_timestep_batch_observed with one LUDWIG_OBSERVE_PROBES entry (probes, start_step, interval) */
 int  ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                           float u_curr, const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step,
                                           int32_t interval);
@@ -443,7 +464,7 @@ int  ludwig_surface_stats_accumulate(LudwigSurfaceStats *stats, int64_t t_sub);
  * level's stream */
 int  ludwig_surface_stats_download(LudwigSurfaceStats *stats, double *sums, size_t bytes, int64_t *n_samples);
 
-/* what a batch samples: each set at coarse steps start + k interval (k >= 0); a null set is not sampled */
+/* a probes and a surface entry of ludwig_execute_timestep_batch_observed, as the three calls below take them */
 typedef struct LudwigBatchSamplers {
     LudwigProbes       *probes;
     int64_t             probes_start_step;
@@ -452,10 +473,7 @@ typedef struct LudwigBatchSamplers {
     int64_t             surface_start_step;
     int32_t             surface_interval;
 } LudwigBatchSamplers;
-/* ludwig_execute_timestep_batch with the samplers of s sampled inside the batch: the probes as ludwig_execute_timestep_batch_probes
- * does, the surface set with one launch on its level's own stream, right after that level's last sub-step of a sampled coarse step.
- * s = NULL, or both sets null, is ludwig_execute_timestep_batch itself. Fails before stepping anything with LUDWIG_ERR_INVALID if
- * the surface set's level is not in `levels` or its interval < 1, and as ludwig_execute_timestep_batch_probes for the probes. */
+/* ludwig_execute_timestep_batch_observed with the LUDWIG_OBSERVE_PROBES and LUDWIG_OBSERVE_SURFACE entries of s (s may be NULL) */
 int  ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                            float u_curr, const LudwigStepFlags *flags, const LudwigBatchSamplers *s);
 
@@ -484,10 +502,7 @@ int  ludwig_force_series_sample(LudwigForceSeries *set, int64_t t_sub, int64_t t
  * then empties the ring. LUDWIG_ERR_INVALID when n > max_samples. */
 int  ludwig_force_series_download(LudwigForceSeries *set, double *sums, int64_t *covered, int64_t *steps, int32_t max_samples,
                                   int32_t *n_samples);
-/* ludwig_execute_timestep_batch_sampled (s may be NULL) with the force series fs sampled inside the batch: at coarse steps
- * start_step + k interval (k >= 0), on its level's own stream, right after that level's last sub-step of the coarse step. fs = NULL is
- * ludwig_execute_timestep_batch_sampled itself. Fails before stepping anything with LUDWIG_ERR_STATE if the batch's records would
- * overflow the free ring, with LUDWIG_ERR_INVALID if the set's level is not in `levels` or interval < 1. */
+/* ludwig_execute_timestep_batch_observed with the entries of s (may be NULL) and a LUDWIG_OBSERVE_FORCES entry (fs, start_step, interval) */
 int  ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                          float u_curr, const LudwigStepFlags *flags, const LudwigBatchSamplers *s,
                                          LudwigForceSeries *fs, int64_t start_step, int32_t interval);
@@ -580,11 +595,8 @@ int  ludwig_tracers_snapshot(LudwigTracers *set, int64_t t_coarse);
 /* the last snapshot: records [n_seeds generations][8] floats, bytes = their size; n_advances (may be NULL): advances so far.
  * Synchronizes. LUDWIG_ERR_STATE before the first snapshot. */
 int  ludwig_tracers_download(LudwigTracers *set, float *records, size_t bytes, int64_t *n_advances);
-/* ludwig_execute_timestep_batch_loads (forces may be NULL too) that also advances `tracers` behind every coarse step start_step +
- * k interval of the batch: the host has then issued every launch of that step and none of the next; with level streams the first
- * level's stream waits for all the others, runs the advance, and all the others wait for it (ordering only). tracers == NULL: the _loads
- * call itself. LUDWIG_ERR_INVALID before anything is stepped: the set's levels are not exactly the batch's (same handles, same order),
- * or interval < 1. */
+/* ludwig_execute_timestep_batch_observed with the entries of samplers (may be NULL), a LUDWIG_OBSERVE_FORCES entry (forces,
+ * force_start_step, force_interval) and a LUDWIG_OBSERVE_TRACERS entry (tracers, start_step, interval) */
 int  ludwig_execute_timestep_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
                                            const LudwigStepFlags *flags, const LudwigBatchSamplers *samplers, LudwigForceSeries *forces,
                                            int64_t force_start_step, int32_t force_interval, LudwigTracers *tracers, int64_t start_step,

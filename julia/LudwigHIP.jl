@@ -45,6 +45,11 @@ struct BatchSamplers           # LudwigBatchSamplers
     surface::Ptr{Cvoid}; surface_start_step::Int64; surface_interval::Int32
 end
 
+const OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS = Int32.(0:3)   # LUDWIG_OBSERVE_*
+struct BatchObserver           # LudwigBatchObserver
+    kind::Int32; set::Ptr{Cvoid}; start_step::Int64; interval::Int32
+end
+
 mutable struct DeviceLevel
     handle::Ptr{Cvoid}
     level_id::Int; tau::Float32; n_blocks::Int
@@ -501,49 +506,43 @@ function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch
                                      handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags))
 end
 
-"""execute_timestep_batch! with the probes of `probes` sampled inside the batch at coarse steps start_step + k interval"""
+"""execute_timestep_batch! with the sets of `observers` observed inside the batch, each at the coarse steps start_step + k interval of
+its own entry; an entry whose set is C_NULL is ignored, an empty vector is the call above"""
 function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
-                                 probes::Ptr{Cvoid}, start_step::Integer, interval::Integer)
+                                 observers::Vector{BatchObserver})
     handles = Ptr{Cvoid}[g.handle for g in grids]
-    GC.@preserve handles check(ccall((:ludwig_execute_timestep_batch_probes, LIB), Cint,
-                                     (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{Cvoid}, Int64, Int32),
-                                     handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, probes,
-                                     Int64(start_step), Int32(interval)))
+    GC.@preserve handles observers check(ccall((:ludwig_execute_timestep_batch_observed, LIB), Cint,
+                                               (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{BatchObserver}, Int32),
+                                               handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, observers,
+                                               Int32(length(observers))))
 end
 
-"""execute_timestep_batch! with the probe set and the surface set of `s` sampled inside the batch (either may be C_NULL)"""
-function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
-                                 s::BatchSamplers)
-    handles = Ptr{Cvoid}[g.handle for g in grids]
-    GC.@preserve handles check(ccall((:ludwig_execute_timestep_batch_sampled, LIB), Cint,
-                                     (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ref{BatchSamplers}),
-                                     handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, s))
-end
+# The methods from before the observer list keep their signatures: each builds its entries (a set may be C_NULL) and calls the one above.
+entry(kind::Int32, set::Ptr{Cvoid}, start_step::Integer, interval::Integer) = BatchObserver(kind, set, Int64(start_step), Int32(interval))
+entries(s::BatchSamplers) = [entry(OBSERVE_PROBES, s.probes, s.probes_start_step, s.probes_interval),
+                             entry(OBSERVE_SURFACE, s.surface, s.surface_start_step, s.surface_interval)]
+entries(::Nothing) = BatchObserver[]
 
-"""execute_timestep_batch! with the sets of `s` and the force series `forces` (at coarse steps start_step + k interval) sampled inside
-the batch; `s = nothing` is the C call's `s = NULL`: the force series alone"""
-function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
-                                 s::Union{BatchSamplers,Nothing}, forces::Ptr{Cvoid}, start_step::Integer, interval::Integer)
-    handles = Ptr{Cvoid}[g.handle for g in grids]
-    sp = s === nothing ? C_NULL : Ref(s)
-    GC.@preserve handles sp check(ccall((:ludwig_execute_timestep_batch_loads, LIB), Cint,
-                                        (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{BatchSamplers}, Ptr{Cvoid}, Int64, Int32),
-                                        handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, sp, forces,
-                                        Int64(start_step), Int32(interval)))
-end
+"""the probes of `probes` sampled inside the batch: one OBSERVE_PROBES entry"""
+execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                        probes::Ptr{Cvoid}, start_step::Integer, interval::Integer) =
+    execute_timestep_batch!(grids, t_start, batch_size, u_curr, flags, [entry(OBSERVE_PROBES, probes, start_step, interval)])
 
-"""the call above that also advances the tracer set `tracers` behind the coarse steps start_step + k interval of the batch; `forces`
-may be C_NULL"""
-function execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
-                                 s::Union{BatchSamplers,Nothing}, forces::Ptr{Cvoid}, force_start_step::Integer, force_interval::Integer,
-                                 tracers::Ptr{Cvoid}, start_step::Integer, interval::Integer)
-    handles = Ptr{Cvoid}[g.handle for g in grids]
-    sp = s === nothing ? C_NULL : Ref(s)
-    GC.@preserve handles sp check(ccall((:ludwig_execute_timestep_batch_tracers, LIB), Cint,
-                                        (Ptr{Ptr{Cvoid}}, Int32, Int64, Int32, Cfloat, Ref{StepFlags}, Ptr{BatchSamplers}, Ptr{Cvoid}, Int64, Int32,
-                                         Ptr{Cvoid}, Int64, Int32),
-                                        handles, Int32(length(grids)), Int64(t_start), Int32(batch_size), u_curr, flags, sp, forces,
-                                        Int64(force_start_step), Int32(force_interval), tracers, Int64(start_step), Int32(interval)))
-end
+"""the probe set and the surface set of `s`: an OBSERVE_PROBES and an OBSERVE_SURFACE entry"""
+execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags, s::BatchSamplers) =
+    execute_timestep_batch!(grids, t_start, batch_size, u_curr, flags, entries(s))
+
+"""the entries of `s` (`nothing`: none) and an OBSERVE_FORCES entry for the force series `forces`"""
+execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                        s::Union{BatchSamplers,Nothing}, forces::Ptr{Cvoid}, start_step::Integer, interval::Integer) =
+    execute_timestep_batch!(grids, t_start, batch_size, u_curr, flags, [entries(s); entry(OBSERVE_FORCES, forces, start_step, interval)])
+
+"""the entries of `s` (`nothing`: none), an OBSERVE_FORCES entry and an OBSERVE_TRACERS entry for the tracer set `tracers`"""
+execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                        s::Union{BatchSamplers,Nothing}, forces::Ptr{Cvoid}, force_start_step::Integer, force_interval::Integer,
+                        tracers::Ptr{Cvoid}, start_step::Integer, interval::Integer) =
+    execute_timestep_batch!(grids, t_start, batch_size, u_curr, flags,
+                            [entries(s); entry(OBSERVE_FORCES, forces, force_start_step, force_interval);
+                             entry(OBSERVE_TRACERS, tracers, start_step, interval)])
 
 end # module

@@ -35,13 +35,16 @@ SUBGRID_SUM_NAMES = {"nu": 0, "nunu": 1, "eps": 2}
 # enum LudwigPart
 PART_ALL, PART_BOUNDARY, PART_INTERIOR = 0, 1, 2
 
+# LUDWIG_OBSERVE_*: the kind of a BatchObserver entry
+OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS = range(4)
+
 # every symbol include/ludwig_hip.h declares (tests check the .so exports exactly these)
 EXPORTED_SYMBOLS = [
     "ludwig_abi_version", "ludwig_last_error", "ludwig_device_count",
     "ludwig_level_create", "ludwig_level_destroy", "ludwig_level_set_stream", "ludwig_level_add_post_collision_readers", "ludwig_level_set_order",
     "ludwig_level_upload", "ludwig_level_download", "ludwig_level_field_ptr",
     "ludwig_init_equilibrium", "ludwig_step", "ludwig_stream_collide", "ludwig_bouzidi_correction",
-    "ludwig_save_old", "ludwig_execute_timestep_batch", "ludwig_sync", "ludwig_halo_pack", "ludwig_halo_unpack", "ludwig_level_info",
+    "ludwig_save_old", "ludwig_execute_timestep_batch", "ludwig_execute_timestep_batch_observed", "ludwig_sync", "ludwig_halo_pack", "ludwig_halo_unpack", "ludwig_level_info",
     "ludwig_map_surface_stresses", "ludwig_level_rho_min", "ludwig_level_block_order",
     "ludwig_stream_create", "ludwig_stream_destroy", "ludwig_level_field_layout", "ludwig_level_set_rho_store",
     "ludwig_comm_unique_id", "ludwig_comm_create", "ludwig_comm_destroy", "ludwig_comm_allreduce_f32",
@@ -106,6 +109,10 @@ class SurfaceParams(C.Structure):
         ("dx", C.c_float), ("tau", C.c_float), ("offset_x", C.c_float), ("offset_y", C.c_float), ("offset_z", C.c_float),
         ("pressure_scale", C.c_float), ("stress_scale", C.c_float), ("search_radius", C.c_int32),
     ]
+
+
+class BatchObserver(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("set", C.c_void_p), ("start_step", C.c_int64), ("interval", C.c_int32)]
 
 
 class BatchSamplers(C.Structure):
@@ -173,6 +180,8 @@ def load() -> C.CDLL:
         "ludwig_bouzidi_correction": (C.c_int, [vp, i64, f32]),
         "ludwig_save_old": (C.c_int, [vp, i64]),
         "ludwig_execute_timestep_batch": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags)]),
+        "ludwig_execute_timestep_batch_observed": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags),
+                                                             C.POINTER(BatchObserver), i32]),
         "ludwig_sync": (C.c_int, [vp]),
         "ludwig_halo_pack": (C.c_int, [vp, i32, vp, i64, vp, vp]),
         "ludwig_halo_unpack": (C.c_int, [vp, i32, vp, i64, vp, vp]),

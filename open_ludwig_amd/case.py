@@ -45,9 +45,9 @@ class DiagRow:
 
 
 def _close_observers(st) -> None:
-    """close a stepper's probe, surface, slice, wall-surface and force-series sets (each may be None)"""
-    for name in ("probes", "surface", "slices", "wall_surface", "forces"):
-        obs = getattr(st, name)
+    """close a stepper's probe, surface, slice, wall-surface, force-series, streamline and tracer sets (each may be None or absent)"""
+    for name in ("probes", "surface", "slices", "wall_surface", "forces", "stream_set", "tracer_set"):
+        obs = getattr(st, name, None)
         if obs is not None:
             obs.close()
             setattr(st, name, None)
@@ -295,12 +295,6 @@ class HipStepper:
 
     def close(self):
         _close_observers(self)
-        if self.stream_set is not None:
-            self.stream_set.close()
-            self.stream_set = None
-        if self.tracer_set is not None:
-            self.tracer_set.close()
-            self.tracer_set = None
         for d in self.dev:
             d.close()
 

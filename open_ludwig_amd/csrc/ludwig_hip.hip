@@ -1943,17 +1943,26 @@ static int force_series_launch(LudwigForceSeries *F, int64_t t_sub, int64_t t_co
     return LUDWIG_OK;
 }
 
-// Sampling inside a batch (ludwig_execute_timestep_batch_sampled): the coarse step being run, the probes' ring slot (-1 = not sampled)
-// and whether the surface set samples this step.
+// What a batch observes (ludwig_execute_timestep_batch_observed): one typed slot per LUDWIG_OBSERVE_* kind, a null set is not observed.
+struct ObserverSchedule {
+    int64_t start_step = 0;
+    int32_t interval = 1;
+    bool due(int64_t t) const { return step_sampled(t, start_step, interval); }
+};
+struct BatchObservers {
+    struct : ObserverSchedule { LudwigProbes *set = nullptr; } probes;
+    struct : ObserverSchedule { LudwigSurfaceStats *set = nullptr; } surface;
+    struct : ObserverSchedule { LudwigForceSeries *set = nullptr; } forces;
+    struct : ObserverSchedule { LudwigTracers *set = nullptr; } tracers;
+};
+// The observers inside one coarse step: the step being run, the probes' ring slot (-1 = not sampled) and whether the surface set and
+// the force series sample this step.
 struct BatchHook {
-    LudwigProbes *P = nullptr;
-    LudwigSurfaceStats *S = nullptr;
-    LudwigForceSeries *F = nullptr;
+    const BatchObservers *obs = nullptr;
     int64_t t = 0;
     int slot = -1;
     bool surface = false, forces = false;
 };
-static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub);
 
 static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-based*/, int64_t t_sub, const LudwigLevel *parent,
                           float parent_tau, float temporal_weight, float u_vel, const LudwigStepFlags *fl, bool concurrent,
@@ -2010,9 +2019,10 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         // on its own stream, behind the step (and behind the event its children wait for) and ahead of the next write to either
         const int64_t m = (int64_t)1 << (lvl - 1);
         if (t_sub == m * ph->t + m - 1) {
-            if (ph->slot >= 0 && (rc = probes_launch(ph->P, lvl - 1, ph->slot, t_sub))) return rc;
-            if (ph->surface && ph->S->level == L && (rc = surface_stats_launch(ph->S, t_sub))) return rc;
-            if (ph->forces && ph->F->level == L && (rc = force_series_launch(ph->F, t_sub, ph->t))) return rc;
+            const BatchObservers &o = *ph->obs;
+            if (ph->slot >= 0 && (rc = probes_launch(o.probes.set, lvl - 1, ph->slot, t_sub))) return rc;
+            if (ph->surface && o.surface.set->level == L && (rc = surface_stats_launch(o.surface.set, t_sub))) return rc;
+            if (ph->forces && o.forces.set->level == L && (rc = force_series_launch(o.forces.set, t_sub, ph->t))) return rc;
         }
     }
     if (has_children) {
@@ -2020,172 +2030,6 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         if ((rc = recursive_step(levels, n_levels, lvl + 1, 2 * t_sub + 1, L, L->tau, 0.5f, u_vel, fl, concurrent, ph))) return rc;
     }
     return LUDWIG_OK;
-}
-
-static int check_batch_levels(LudwigLevel *const *levels, int32_t n_levels, int32_t batch_size, const LudwigStepFlags *flags)
-{
-    if (!levels || !flags || n_levels < 1 || batch_size < 0) return fail(LUDWIG_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n_levels; ++i) {
-        if (!levels[i]) return fail(LUDWIG_ERR_INVALID, "null level %d", i + 1);
-        if (levels[i]->device != levels[0]->device || levels[i]->stream != levels[0]->stream)
-            return fail(LUDWIG_ERR_INVALID, "all levels must share one device and one stream");
-    }
-    return LUDWIG_OK;
-}
-
-// the force series a batch samples (ludwig_execute_timestep_batch_loads): at coarse steps start_step + k interval
-struct ForceSampler {
-    LudwigForceSeries *set = nullptr;
-    int64_t start_step = 0;
-    int32_t interval = 1;
-};
-// the tracer set a batch advances (ludwig_execute_timestep_batch_tracers): after coarse steps start_step + k interval
-struct TracerSampler {
-    LudwigTracers *set = nullptr;
-    int64_t start_step = 0;
-    int32_t interval = 1;
-};
-static int tracers_launch_advance(LudwigTracers *S, int64_t t_coarse, hipStream_t st);
-static hipEvent_t tracers_event(LudwigTracers *S);
-static bool tracers_empty(const LudwigTracers *S);
-static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs = nullptr,
-                      const TracerSampler *ts = nullptr);
-
-int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                                  const LudwigStepFlags *flags)
-{
-    const int r = check_batch_levels(levels, n_levels, batch_size, flags);
-    if (r) return r;
-    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr);
-}
-
-// one advance of a batch's tracer set behind coarse step t: with level streams, a full join around the launch (see batch_impl)
-static int batch_tracers_advance(LudwigLevel *const *levels, int32_t n_levels, LudwigTracers *T, int64_t t, bool concurrent)
-{
-    hipStream_t st = levels[0]->stream;
-    if (!concurrent || tracers_empty(T)) return tracers_launch_advance(T, t, st);      // one stream, or nothing to launch: no event
-    hipEvent_t ev = tracers_event(T);
-    for (int i = 1; i < n_levels; ++i) {
-        LW_HIP(hipEventRecord(ev, levels[i]->stream));
-        LW_HIP(hipStreamWaitEvent(st, ev, 0));
-    }
-    const int rc = tracers_launch_advance(T, t, st);
-    if (rc) return rc;
-    LW_HIP(hipEventRecord(ev, st));
-    for (int i = 1; i < n_levels; ++i) LW_HIP(hipStreamWaitEvent(levels[i]->stream, ev, 0));
-    return LUDWIG_OK;
-}
-
-// Level streams. The reference steps its levels strictly one after the other (src/solver_control.jl:21-143), and every launch
-// of a small level leaves most of the 256 CUs idle. The data dependencies are weaker than the call order: coupling is one-way,
-// coarse -> fine, and a child reads its parent's buffers only in its interface pass (k_interface_sources / _links, once per
-// pair of sub-steps). So each level gets a HIP stream of its own and two events:
-//   * a child's sub-step waits for its parent's step (parent->ev_stepped) before it interpolates from it;
-//   * a parent's NEXT step - which overwrites the buffer holding its old state, rho and rho_old - waits until the child's
-//     interface pass has read them (ev_consumed, recorded on the child's stream right after that pass).
-// Launches are still issued in the reference's order; the GPU then runs level 1's step t + 1 under the finer levels' sub-steps
-// of step t, and a middle level's second sub-step under its children's first pair. Same kernels, same inputs: same bits.
-// The finest level is the critical chain (2^(n-1) sub-steps per coarse step): its stream gets the highest priority, the others the
-// lowest, so the coarser levels only fill what it leaves free. Measured on one box, alternating (profiles/
-// r02_level_streams_with_priorities_ab_one_box.txt): 3-level sphere 0.419 -> 0.393 ms per coarse step, real wing 1.011 -> 0.949,
-// 4-level sphere 1.72 -> 1.52; without the priorities 0.402 / 0.982 / 1.58 (and on another box the 4-level case got slower).
-// LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
-// Tracers (ts): after the host has issued every launch of coarse step t and none of t + 1, an advanced step joins all level streams -
-// the first level's stream waits for what the others have queued, runs the advance, and the others wait for it before they go on. That
-// only adds ordering; at advanced steps it gives up the overlap of level 1's step t + 1 with the finer levels' tail of step t.
-static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                      const LudwigStepFlags *flags, const LudwigBatchSamplers *s, const ForceSampler *fs, const TracerSampler *ts)
-{
-    LudwigProbes *probes = s ? s->probes : nullptr;
-    LudwigSurfaceStats *surface = s ? s->surface : nullptr;
-    LudwigForceSeries *forces = fs ? fs->set : nullptr;
-    LudwigTracers *tracers = ts ? ts->set : nullptr;
-    const bool concurrent = n_levels > 1 && !env::batch_serial();
-    hipStream_t user_stream = levels[0]->stream;
-    if (concurrent) {
-        LW_HIP(hipSetDevice(levels[0]->device));
-        LW_HIP(hipStreamSynchronize(user_stream));             // everything queued before the batch is done
-        // 1. every level gets its stream and its two events - or none does: a half-made set is destroyed again, so that a later
-        //    batch never finds a level with a stream but no events. The levels keep the caller's stream until all of it exists.
-        int pr_least = 0, pr_greatest = 0;
-        LW_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
-        const int pr_mode = env::level_stream_priority();
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < n_levels && e == hipSuccess; ++i) {
-            LudwigLevel *L = levels[i];
-            if (L->own_stream && L->ev_stepped && L->ev_consumed) continue;
-            // the finest level is the critical chain (2^(n-1) sub-steps per coarse step): its stream gets the highest priority, the
-            // coarser levels fill what it leaves free (graded priorities: no better)
-            // LUDWIG_LEVEL_STREAM_PRIORITY=2: graded - the finest level highest, its parent (whose stream carries the finest level's interface
-            // pass since round 3) one below, the rest lowest
-            int pr = pr_mode == 0 ? pr_least : (i == n_levels - 1 ? pr_greatest : pr_least);
-            if (pr_mode == 2) pr = std::min(pr_least, pr_greatest + (n_levels - 1 - i));
-            if (!L->own_stream) e = hipStreamCreateWithPriority(&L->own_stream, hipStreamNonBlocking, pr);
-            if (e == hipSuccess && !L->ev_stepped) e = hipEventCreateWithFlags(&L->ev_stepped, hipEventDisableTiming);
-            if (e == hipSuccess && !L->ev_consumed) e = hipEventCreateWithFlags(&L->ev_consumed, hipEventDisableTiming);
-        }
-        if (e != hipSuccess) {
-            for (int i = 0; i < n_levels; ++i) {
-                LudwigLevel *L = levels[i];
-                if (L->own_stream && L->ev_stepped && L->ev_consumed) continue;      // complete from an earlier batch: keep
-                hipEvent_t *evs[] = {&L->ev_stepped, &L->ev_consumed};
-                for (hipEvent_t *ev : evs)
-                    if (*ev) { (void)hipEventDestroy(*ev); *ev = nullptr; }
-                if (L->own_stream) { (void)hipStreamDestroy(L->own_stream); L->own_stream = nullptr; }
-            }
-            return fail(LUDWIG_ERR_HIP, "batch: level streams: %s", hipGetErrorString(e));
-        }
-        // 2. switch over; one way back for every early return
-        auto restore = [&]() { for (int j = 0; j < n_levels; ++j) levels[j]->stream = user_stream; };
-        for (int i = 0; i < n_levels; ++i) {
-            LudwigLevel *L = levels[i];
-            L->ev_consumed_set = false;
-            L->waited_parent = nullptr;
-            L->parent_wait = nullptr;
-            L->pair_ready.valid = false;
-            L->pair_done_set[0] = L->pair_done_set[1] = false;      // the previous batch ended with every stream idle
-            L->stream = L->own_stream;
-        }
-        for (int i = 0; i + 1 < n_levels; ++i) {
-            LudwigLevel *L = levels[i];
-            if (!L->rho_eager) {                               // children interpolate from rho after every step
-                L->rho_eager = true;
-                const int r = ensure_rho(L);
-                if (r) { restore(); return r; }
-            }
-        }
-    }
-    for (int i = 0; i < n_levels; ++i) levels[i]->rho_old_pending = false;      // (only an aborted batch could have left one)
-    int rc = LUDWIG_OK;
-    for (int32_t o = 0; o < batch_size && rc == LUDWIG_OK; ++o) {
-        const int64_t t = t_start + o;
-        if (!probes && !surface && !forces) {
-            rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent);
-        } else {
-            BatchHook ph;
-            ph.P = probes;
-            ph.S = surface;
-            ph.t = t;
-            if (probes && step_sampled(t, s->probes_start_step, s->probes_interval)) ph.slot = probes_open_slot(probes, t);
-            ph.surface = surface && step_sampled(t, s->surface_start_step, s->surface_interval);
-            ph.F = forces;
-            ph.forces = forces && step_sampled(t, fs->start_step, fs->interval);
-            rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
-        }
-        if (rc == LUDWIG_OK && tracers && step_sampled(t, ts->start_step, ts->interval)) rc = batch_tracers_advance(levels, n_levels, tracers, t, concurrent);
-    }
-    if (concurrent) {
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < n_levels; ++i) {
-            const hipError_t ei = hipStreamSynchronize(levels[i]->own_stream);
-            if (e == hipSuccess) e = ei;
-            levels[i]->stream = user_stream;
-        }
-        if (rc == LUDWIG_OK && e != hipSuccess) return fail(LUDWIG_ERR_HIP, "batch: %s", hipGetErrorString(e));
-    }
-    if (rc) return rc;
-    return ludwig_sync(levels[0]);
 }
 
 int ludwig_sync(const LudwigLevel *L)
@@ -2866,53 +2710,6 @@ int ludwig_probes_download(LudwigProbes *P, float *values, int64_t *steps, int32
     return LUDWIG_OK;
 }
 
-int ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                                         const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval)
-{
-    LudwigBatchSamplers s{};
-    s.probes = probes;
-    s.probes_start_step = start_step;
-    s.probes_interval = interval;
-    return ludwig_execute_timestep_batch_sampled(levels, n_levels, t_start, batch_size, u_curr, flags, &s);
-}
-
-static int check_batch_samplers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, const LudwigBatchSamplers *s);
-
-int ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                                          const LudwigStepFlags *flags, const LudwigBatchSamplers *s)
-{
-    int r = check_batch_levels(levels, n_levels, batch_size, flags);
-    if (r) return r;
-    if (!s || (!s->probes && !s->surface)) return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr);
-    if ((r = check_batch_samplers(levels, n_levels, t_start, batch_size, s))) return r;
-    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s);
-}
-
-// what ludwig_execute_timestep_batch_sampled refuses before it steps anything (s with at least one set)
-static int check_batch_samplers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, const LudwigBatchSamplers *s)
-{
-    if (LudwigProbes *probes = s->probes) {
-        const int32_t interval = s->probes_interval;
-        const int64_t start_step = s->probes_start_step;
-        if (interval < 1) return fail(LUDWIG_ERR_INVALID, "probes: interval %d < 1", interval);
-        if (probes->n_levels != n_levels) return fail(LUDWIG_ERR_INVALID, "probes: set made over %d levels, batch of %d", probes->n_levels, n_levels);
-        for (int i = 0; i < n_levels; ++i)
-            if (probes->levels[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "probes: set made over other levels (level %d)", i + 1);
-        // nothing is stepped when the batch's samples would not fit
-        const int64_t k = batch_size > 0 ? samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
-        if ((int64_t)probes->slot_step.size() + k > probes->capacity)
-            return fail(LUDWIG_ERR_STATE, "probes: %lld samples of this batch overflow the ring (%d of %d used): download first", (long long)k,
-                        (int)probes->slot_step.size(), probes->capacity);
-    }
-    if (const LudwigSurfaceStats *S = s->surface) {
-        if (s->surface_interval < 1) return fail(LUDWIG_ERR_INVALID, "surface statistics: interval %d < 1", s->surface_interval);
-        bool in_batch = false;
-        for (int i = 0; i < n_levels; ++i) in_batch = in_batch || levels[i] == S->level;
-        if (!in_batch) return fail(LUDWIG_ERR_INVALID, "surface statistics: the set's level is not in the batch");
-    }
-    return LUDWIG_OK;
-}
-
 void ludwig_surface_stats_destroy(LudwigSurfaceStats *S)
 {
     if (!S) return;
@@ -3102,46 +2899,6 @@ int ludwig_force_series_download(LudwigForceSeries *F, double *sums, int64_t *co
     }
     F->slot_step.clear();
     return LUDWIG_OK;
-}
-
-static int check_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, const TracerSampler *ts);
-static int batch_loads_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                               const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
-                               int32_t interval, const TracerSampler *ts);
-
-int ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                                        const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
-                                        int32_t interval)
-{
-    if (!fs) return ludwig_execute_timestep_batch_sampled(levels, n_levels, t_start, batch_size, u_curr, flags, s);
-    return batch_loads_tracers(levels, n_levels, t_start, batch_size, u_curr, flags, s, fs, start_step, interval, nullptr);
-}
-
-// ludwig_execute_timestep_batch_loads with a force series, a tracer set or both: every refusal comes before anything is stepped
-static int batch_loads_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
-                               const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
-                               int32_t interval, const TracerSampler *ts)
-{
-    int r = check_batch_levels(levels, n_levels, batch_size, flags);
-    if (r) return r;
-    if (s && !s->probes && !s->surface) s = nullptr;
-    if (s && (r = check_batch_samplers(levels, n_levels, t_start, batch_size, s))) return r;
-    if (ts && (r = check_batch_tracers(levels, n_levels, ts))) return r;
-    if (!fs) return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s, nullptr, ts);
-    if (interval < 1) return fail(LUDWIG_ERR_INVALID, "force series: interval %d < 1", interval);
-    bool in_batch = false;
-    for (int i = 0; i < n_levels; ++i) in_batch = in_batch || levels[i] == fs->level;
-    if (!in_batch) return fail(LUDWIG_ERR_INVALID, "force series: the set's level is not in the batch");
-    // nothing is stepped when the batch's records would not fit
-    const int64_t k = batch_size > 0 ? samples_in(t_start, t_start + batch_size - 1, start_step, interval) : 0;
-    if ((int64_t)fs->slot_step.size() + k > fs->capacity)
-        return fail(LUDWIG_ERR_STATE, "force series: %lld records of this batch overflow the ring (%d of %d used): download first", (long long)k,
-                    (int)fs->slot_step.size(), fs->capacity);
-    ForceSampler f;
-    f.set = fs;
-    f.start_step = start_step;
-    f.interval = interval;
-    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, s, &f, ts);
 }
 
 // ---- slices (ludwig_slices_*; no reference counterpart) ----
@@ -3582,9 +3339,6 @@ int ludwig_tracers_create(LudwigLevel *const *levels, int32_t n_levels, int32_t 
     return LUDWIG_OK;
 }
 
-static hipEvent_t tracers_event(LudwigTracers *S) { return S->ev; }
-static bool tracers_empty(const LudwigTracers *S) { return S->n_slots == 0; }
-
 // the kernel's arguments for the levels' newest velocity after coarse step t_coarse (the buffer ludwig_streamlines_trace chooses)
 static TracerArgs tracers_args(const LudwigTracers *S, int64_t t_coarse)
 {
@@ -3683,13 +3437,257 @@ int ludwig_tracers_download(LudwigTracers *S, float *records, size_t bytes, int6
     return LUDWIG_OK;
 }
 
-static int check_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, const TracerSampler *ts)
+// ---- the batch (ludwig_execute_timestep_batch*): what it refuses, how it runs, its entry points ----
+static int check_batch_levels(LudwigLevel *const *levels, int32_t n_levels, int32_t batch_size, const LudwigStepFlags *flags)
 {
-    if (ts->interval < 1) return fail(LUDWIG_ERR_INVALID, "tracers: interval %d < 1", ts->interval);
-    if (ts->set->n_levels != n_levels) return fail(LUDWIG_ERR_INVALID, "tracers: set made over %d levels, batch of %d", ts->set->n_levels, n_levels);
-    for (int i = 0; i < n_levels; ++i)
-        if (ts->set->levels[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "tracers: set made over other levels (level %d)", i + 1);
+    if (!levels || !flags || n_levels < 1 || batch_size < 0) return fail(LUDWIG_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n_levels; ++i) {
+        if (!levels[i]) return fail(LUDWIG_ERR_INVALID, "null level %d", i + 1);
+        if (levels[i]->device != levels[0]->device || levels[i]->stream != levels[0]->stream)
+            return fail(LUDWIG_ERR_INVALID, "all levels must share one device and one stream");
+    }
     return LUDWIG_OK;
+}
+
+// the set was made over exactly these levels (probes, tracers)
+static int check_made_over(const char *what, const std::vector<LudwigLevel *> &made_over, LudwigLevel *const *levels, int32_t n_levels)
+{
+    if ((int)made_over.size() != n_levels)
+        return fail(LUDWIG_ERR_INVALID, "%s: set made over %d levels, batch of %d", what, (int)made_over.size(), n_levels);
+    for (int i = 0; i < n_levels; ++i)
+        if (made_over[i] != levels[i]) return fail(LUDWIG_ERR_INVALID, "%s: set made over other levels (level %d)", what, i + 1);
+    return LUDWIG_OK;
+}
+
+// the set's level is one of the batch's (surface, forces)
+static int check_level_in_batch(const char *what, const LudwigLevel *level, LudwigLevel *const *levels, int32_t n_levels)
+{
+    bool in_batch = false;
+    for (int i = 0; i < n_levels; ++i) in_batch = in_batch || levels[i] == level;
+    return in_batch ? LUDWIG_OK : fail(LUDWIG_ERR_INVALID, "%s: the set's level is not in the batch", what);
+}
+
+// nothing is stepped when what this batch adds to a ring would not fit (probes, forces)
+static int check_ring_room(const char *what, const char *items, size_t used, int capacity, const ObserverSchedule &o, int64_t t_start,
+                           int32_t batch_size)
+{
+    const int64_t k = batch_size > 0 ? samples_in(t_start, t_start + batch_size - 1, o.start_step, o.interval) : 0;
+    if ((int64_t)used + k <= capacity) return LUDWIG_OK;
+    return fail(LUDWIG_ERR_STATE, "%s: %lld %s of this batch overflow the ring (%d of %d used): download first", what, (long long)k, items,
+                (int)used, capacity);
+}
+
+// Every refusal of a batch beyond its levels', before anything is stepped: the list itself, then each set in the fixed order probes,
+// surface, tracers, forces. Fills `obs` from the entries with a set.
+static int check_batch_observers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
+                                 const LudwigBatchObserver *observers, int32_t n_observers, BatchObservers *obs)
+{
+    if (n_observers < 0) return fail(LUDWIG_ERR_INVALID, "batch: %d observer entries", n_observers);
+    if (n_observers > 0 && !observers) return fail(LUDWIG_ERR_INVALID, "batch: null observer list of %d entries", n_observers);
+    const LudwigBatchObserver *of_kind[LUDWIG_OBSERVE_TRACERS + 1] = {};
+    for (int i = 0; i < n_observers; ++i) {
+        const LudwigBatchObserver &e = observers[i];
+        if (!e.set) continue;
+        if (e.kind < 0 || e.kind > LUDWIG_OBSERVE_TRACERS) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d of unknown kind %d", i, e.kind);
+        if (of_kind[e.kind]) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d is the second of kind %d", i, e.kind);
+        of_kind[e.kind] = &e;
+    }
+    int r;
+    if (const LudwigBatchObserver *e = of_kind[LUDWIG_OBSERVE_PROBES]) {
+        LudwigProbes *P = static_cast<LudwigProbes *>(e->set);
+        obs->probes = {{e->start_step, e->interval}, P};
+        if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "probes: interval %d < 1", e->interval);
+        if ((r = check_made_over("probes", P->levels, levels, n_levels))) return r;
+        if ((r = check_ring_room("probes", "samples", P->slot_step.size(), P->capacity, obs->probes, t_start, batch_size))) return r;
+    }
+    if (const LudwigBatchObserver *e = of_kind[LUDWIG_OBSERVE_SURFACE]) {
+        LudwigSurfaceStats *S = static_cast<LudwigSurfaceStats *>(e->set);
+        obs->surface = {{e->start_step, e->interval}, S};
+        if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "surface statistics: interval %d < 1", e->interval);
+        if ((r = check_level_in_batch("surface statistics", S->level, levels, n_levels))) return r;
+    }
+    if (const LudwigBatchObserver *e = of_kind[LUDWIG_OBSERVE_TRACERS]) {
+        LudwigTracers *T = static_cast<LudwigTracers *>(e->set);
+        obs->tracers = {{e->start_step, e->interval}, T};
+        if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "tracers: interval %d < 1", e->interval);
+        if ((r = check_made_over("tracers", T->levels, levels, n_levels))) return r;
+    }
+    if (const LudwigBatchObserver *e = of_kind[LUDWIG_OBSERVE_FORCES]) {
+        LudwigForceSeries *F = static_cast<LudwigForceSeries *>(e->set);
+        obs->forces = {{e->start_step, e->interval}, F};
+        if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "force series: interval %d < 1", e->interval);
+        if ((r = check_level_in_batch("force series", F->level, levels, n_levels))) return r;
+        if ((r = check_ring_room("force series", "records", F->slot_step.size(), F->capacity, obs->forces, t_start, batch_size))) return r;
+    }
+    return LUDWIG_OK;
+}
+
+// one advance of a batch's tracer set behind coarse step t: with level streams, a full join around the launch (see batch_impl)
+static int batch_tracers_advance(LudwigLevel *const *levels, int32_t n_levels, LudwigTracers *T, int64_t t, bool concurrent)
+{
+    hipStream_t st = levels[0]->stream;
+    if (!concurrent || T->n_slots == 0) return tracers_launch_advance(T, t, st);      // one stream, or nothing to launch: no event
+    for (int i = 1; i < n_levels; ++i) {
+        LW_HIP(hipEventRecord(T->ev, levels[i]->stream));
+        LW_HIP(hipStreamWaitEvent(st, T->ev, 0));
+    }
+    const int rc = tracers_launch_advance(T, t, st);
+    if (rc) return rc;
+    LW_HIP(hipEventRecord(T->ev, st));
+    for (int i = 1; i < n_levels; ++i) LW_HIP(hipStreamWaitEvent(levels[i]->stream, T->ev, 0));
+    return LUDWIG_OK;
+}
+
+// Level streams. The reference steps its levels strictly one after the other (src/solver_control.jl:21-143), and every launch
+// of a small level leaves most of the 256 CUs idle. The data dependencies are weaker than the call order: coupling is one-way,
+// coarse -> fine, and a child reads its parent's buffers only in its interface pass (k_interface_sources / _links, once per
+// pair of sub-steps). So each level gets a HIP stream of its own and two events:
+//   * a child's sub-step waits for its parent's step (parent->ev_stepped) before it interpolates from it;
+//   * a parent's NEXT step - which overwrites the buffer holding its old state, rho and rho_old - waits until the child's
+//     interface pass has read them (ev_consumed, recorded on the child's stream right after that pass).
+// Launches are still issued in the reference's order; the GPU then runs level 1's step t + 1 under the finer levels' sub-steps
+// of step t, and a middle level's second sub-step under its children's first pair. Same kernels, same inputs: same bits.
+// The finest level is the critical chain (2^(n-1) sub-steps per coarse step): its stream gets the highest priority, the others the
+// lowest, so the coarser levels only fill what it leaves free. Measured on one box, alternating (profiles/
+// r02_level_streams_with_priorities_ab_one_box.txt): 3-level sphere 0.419 -> 0.393 ms per coarse step, real wing 1.011 -> 0.949,
+// 4-level sphere 1.72 -> 1.52; without the priorities 0.402 / 0.982 / 1.58 (and on another box the 4-level case got slower).
+// LUDWIG_BATCH_SERIAL=1 keeps everything on one stream; LUDWIG_LEVEL_STREAM_PRIORITY=0 gives every level the same priority.
+// Tracers: after the host has issued every launch of coarse step t and none of t + 1, an advanced step joins all level streams -
+// the first level's stream waits for what the others have queued, runs the advance, and the others wait for it before they go on. That
+// only adds ordering; at advanced steps it gives up the overlap of level 1's step t + 1 with the finer levels' tail of step t.
+static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                      const LudwigStepFlags *flags, const BatchObservers &obs)
+{
+    const bool concurrent = n_levels > 1 && !env::batch_serial();
+    hipStream_t user_stream = levels[0]->stream;
+    if (concurrent) {
+        LW_HIP(hipSetDevice(levels[0]->device));
+        LW_HIP(hipStreamSynchronize(user_stream));             // everything queued before the batch is done
+        // 1. every level gets its stream and its two events - or none does: a half-made set is destroyed again, so that a later
+        //    batch never finds a level with a stream but no events. The levels keep the caller's stream until all of it exists.
+        int pr_least = 0, pr_greatest = 0;
+        LW_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
+        const int pr_mode = env::level_stream_priority();
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < n_levels && e == hipSuccess; ++i) {
+            LudwigLevel *L = levels[i];
+            if (L->own_stream && L->ev_stepped && L->ev_consumed) continue;
+            // the finest level is the critical chain (2^(n-1) sub-steps per coarse step): its stream gets the highest priority, the
+            // coarser levels fill what it leaves free (graded priorities: no better)
+            // LUDWIG_LEVEL_STREAM_PRIORITY=2: graded - the finest level highest, its parent (whose stream carries the finest level's interface
+            // pass since round 3) one below, the rest lowest
+            int pr = pr_mode == 0 ? pr_least : (i == n_levels - 1 ? pr_greatest : pr_least);
+            if (pr_mode == 2) pr = std::min(pr_least, pr_greatest + (n_levels - 1 - i));
+            if (!L->own_stream) e = hipStreamCreateWithPriority(&L->own_stream, hipStreamNonBlocking, pr);
+            if (e == hipSuccess && !L->ev_stepped) e = hipEventCreateWithFlags(&L->ev_stepped, hipEventDisableTiming);
+            if (e == hipSuccess && !L->ev_consumed) e = hipEventCreateWithFlags(&L->ev_consumed, hipEventDisableTiming);
+        }
+        if (e != hipSuccess) {
+            for (int i = 0; i < n_levels; ++i) {
+                LudwigLevel *L = levels[i];
+                if (L->own_stream && L->ev_stepped && L->ev_consumed) continue;      // complete from an earlier batch: keep
+                hipEvent_t *evs[] = {&L->ev_stepped, &L->ev_consumed};
+                for (hipEvent_t *ev : evs)
+                    if (*ev) { (void)hipEventDestroy(*ev); *ev = nullptr; }
+                if (L->own_stream) { (void)hipStreamDestroy(L->own_stream); L->own_stream = nullptr; }
+            }
+            return fail(LUDWIG_ERR_HIP, "batch: level streams: %s", hipGetErrorString(e));
+        }
+        // 2. switch over; one way back for every early return
+        auto restore = [&]() { for (int j = 0; j < n_levels; ++j) levels[j]->stream = user_stream; };
+        for (int i = 0; i < n_levels; ++i) {
+            LudwigLevel *L = levels[i];
+            L->ev_consumed_set = false;
+            L->waited_parent = nullptr;
+            L->parent_wait = nullptr;
+            L->pair_ready.valid = false;
+            L->pair_done_set[0] = L->pair_done_set[1] = false;      // the previous batch ended with every stream idle
+            L->stream = L->own_stream;
+        }
+        for (int i = 0; i + 1 < n_levels; ++i) {
+            LudwigLevel *L = levels[i];
+            if (!L->rho_eager) {                               // children interpolate from rho after every step
+                L->rho_eager = true;
+                const int r = ensure_rho(L);
+                if (r) { restore(); return r; }
+            }
+        }
+    }
+    for (int i = 0; i < n_levels; ++i) levels[i]->rho_old_pending = false;      // (only an aborted batch could have left one)
+    int rc = LUDWIG_OK;
+    for (int32_t o = 0; o < batch_size && rc == LUDWIG_OK; ++o) {
+        const int64_t t = t_start + o;
+        BatchHook ph;
+        ph.obs = &obs;
+        ph.t = t;
+        if (obs.probes.set && obs.probes.due(t)) ph.slot = probes_open_slot(obs.probes.set, t);
+        ph.surface = obs.surface.set && obs.surface.due(t);
+        ph.forces = obs.forces.set && obs.forces.due(t);
+        rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
+        if (rc == LUDWIG_OK && obs.tracers.set && obs.tracers.due(t)) rc = batch_tracers_advance(levels, n_levels, obs.tracers.set, t, concurrent);
+    }
+    if (concurrent) {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < n_levels; ++i) {
+            const hipError_t ei = hipStreamSynchronize(levels[i]->own_stream);
+            if (e == hipSuccess) e = ei;
+            levels[i]->stream = user_stream;
+        }
+        if (rc == LUDWIG_OK && e != hipSuccess) return fail(LUDWIG_ERR_HIP, "batch: %s", hipGetErrorString(e));
+    }
+    if (rc) return rc;
+    return ludwig_sync(levels[0]);
+}
+
+int ludwig_execute_timestep_batch_observed(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                           const LudwigStepFlags *flags, const LudwigBatchObserver *observers, int32_t n_observers)
+{
+    BatchObservers obs;
+    int r = check_batch_levels(levels, n_levels, batch_size, flags);
+    if (r) return r;
+    if ((r = check_batch_observers(levels, n_levels, t_start, batch_size, observers, n_observers, &obs))) return r;
+    return batch_impl(levels, n_levels, t_start, batch_size, u_curr, flags, obs);
+}
+
+int ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                  const LudwigStepFlags *flags)
+{
+    return ludwig_execute_timestep_batch_observed(levels, n_levels, t_start, batch_size, u_curr, flags, nullptr, 0);
+}
+
+// The four entry points from before the observer list: each fills its entries (a null set: a null entry) and forwards.
+int ludwig_execute_timestep_batch_probes(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                         const LudwigStepFlags *flags, LudwigProbes *probes, int64_t start_step, int32_t interval)
+{
+    const LudwigBatchObserver o = {LUDWIG_OBSERVE_PROBES, probes, start_step, interval};
+    return ludwig_execute_timestep_batch_observed(levels, n_levels, t_start, batch_size, u_curr, flags, &o, 1);
+}
+
+// the probes and surface entries of s (null: two null entries)
+static void sampler_entries(const LudwigBatchSamplers *s, LudwigBatchObserver *o)
+{
+    const LudwigBatchSamplers none = {};
+    if (!s) s = &none;
+    o[0] = {LUDWIG_OBSERVE_PROBES, s->probes, s->probes_start_step, s->probes_interval};
+    o[1] = {LUDWIG_OBSERVE_SURFACE, s->surface, s->surface_start_step, s->surface_interval};
+}
+
+int ludwig_execute_timestep_batch_sampled(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                          const LudwigStepFlags *flags, const LudwigBatchSamplers *s)
+{
+    LudwigBatchObserver o[2];
+    sampler_entries(s, o);
+    return ludwig_execute_timestep_batch_observed(levels, n_levels, t_start, batch_size, u_curr, flags, o, 2);
+}
+
+int ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
+                                        const LudwigStepFlags *flags, const LudwigBatchSamplers *s, LudwigForceSeries *fs, int64_t start_step,
+                                        int32_t interval)
+{
+    LudwigBatchObserver o[3];
+    sampler_entries(s, o);
+    o[2] = {LUDWIG_OBSERVE_FORCES, fs, start_step, interval};
+    return ludwig_execute_timestep_batch_observed(levels, n_levels, t_start, batch_size, u_curr, flags, o, 3);
 }
 
 int ludwig_execute_timestep_batch_tracers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size, float u_curr,
@@ -3697,12 +3695,11 @@ int ludwig_execute_timestep_batch_tracers(LudwigLevel *const *levels, int32_t n_
                                           int64_t force_start_step, int32_t force_interval, LudwigTracers *tracers, int64_t start_step,
                                           int32_t interval)
 {
-    if (!tracers) return ludwig_execute_timestep_batch_loads(levels, n_levels, t_start, batch_size, u_curr, flags, s, fs, force_start_step, force_interval);
-    TracerSampler ts;
-    ts.set = tracers;
-    ts.start_step = start_step;
-    ts.interval = interval;
-    return batch_loads_tracers(levels, n_levels, t_start, batch_size, u_curr, flags, s, fs, force_start_step, force_interval, &ts);
+    LudwigBatchObserver o[4];
+    sampler_entries(s, o);
+    o[2] = {LUDWIG_OBSERVE_FORCES, fs, force_start_step, force_interval};
+    o[3] = {LUDWIG_OBSERVE_TRACERS, tracers, start_step, interval};
+    return ludwig_execute_timestep_batch_observed(levels, n_levels, t_start, batch_size, u_curr, flags, o, 4);
 }
 
 int ludwig_halo_pack(const LudwigLevel *L, int field, const int64_t *index_dev, int64_t n, float *dst_dev, void *hip_stream)

@@ -26,6 +26,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import statistics as stats_mod
 from .blocks import BLOCK_SIZE
 
 F32 = np.float32
@@ -222,9 +223,7 @@ def host_extract_levels(stepper, grids, field: str, value, t_coarse: int, boxes,
 
 
 def check_schedule(start_step: int, interval: int) -> Tuple[int, int]:
-    if int(start_step) < 1 or int(interval) < 1:
-        raise ValueError(f"isosurfaces: start_step {start_step} and interval {interval} must be >= 1")
-    return int(start_step), int(interval)
+    return stats_mod.check_schedule("isosurfaces", start_step, interval)
 
 
 # ---- files ----

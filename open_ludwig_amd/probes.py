@@ -26,7 +26,7 @@ import numpy as np
 
 from ._lib import Handle
 from .blocks import BLOCK_SIZE
-from .statistics import is_sample_step         # noqa: F401  (one rule for every observer's sampled steps)
+from .statistics import is_sample_step         # (one rule for every observer's sampled steps)
 
 F32 = np.float32
 QUANTITIES = ("rho", "ux", "uy", "uz")
@@ -182,6 +182,9 @@ class DeviceProbes(Handle):
         _lib.check(self._lib.ludwig_probes_create(arr, len(levels), plan.n, li.ctypes.data, bl.ctypes.data, ce.ctypes.data, w.ctypes.data,
                                                   self.capacity, C.byref(h)))
         self._h = h
+
+    def is_sample_step(self, t: int) -> bool:
+        return is_sample_step(t, self.start_step, self.interval)
 
     def sample(self, level_index: int, t_sub: int) -> None:
         from . import _lib

@@ -40,6 +40,7 @@ import numpy as np
 from ._lib import Handle
 from .blocks import BLOCK_SIZE
 from .preprocess import SLICE_MAX_POINTS, SlicePlane, slice_axis_points
+from . import statistics as stats_mod
 from .probes import gather, trilinear
 
 F32 = np.float32
@@ -224,14 +225,11 @@ def host_sample(stepper, plans: Sequence[SlicePlan], grids: Sequence, t_coarse: 
 
 def check_schedule(start_step: int, interval: int) -> Tuple[int, int]:
     """(start_step, interval) of a stepper's slice set; ValueError below 1"""
-    if int(start_step) < 1 or int(interval) < 1:
-        raise ValueError(f"slices: start_step {start_step} and interval {interval} must be >= 1")
-    return int(start_step), int(interval)
+    return stats_mod.check_schedule("slices", start_step, interval)
 
 
 def check_sample_step(t_coarse: int, start_step: int, interval: int) -> None:
-    from .statistics import is_sample_step
-    if not is_sample_step(int(t_coarse), start_step, interval):
+    if not stats_mod.is_sample_step(int(t_coarse), start_step, interval):
         raise ValueError(f"slices: coarse step {t_coarse} is no sampled step (start_step {start_step}, interval {interval})")
 
 

@@ -40,64 +40,41 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
                            params: SolverParams, native: bool = True, probes=None, surface=None, forces=None, tracers=None) -> None:
     """execute_timestep_batch! (src/solver_control.jl:145-165); t_start is 1-based like the reference's loop.
 
-    native=True (default): the whole batch is one C call (ludwig_execute_timestep_batch runs the same recursion inside
+    native=True (default): the whole batch is one C call (ludwig_execute_timestep_batch_observed runs the same recursion inside
     the library, so a multi-level coarse step is not paced by Python). native=False: the recursion of this module, call
     by call - the two are tested to give identical results.
-    probes: a probes.DeviceProbes made over `grids`, sampled after every coarse step start_step + k interval (native: inside the C
-    batch, ludwig_execute_timestep_batch_probes; else through its sample() after the coarse step) - the same bits either way.
-    surface: a surface_stats.DeviceSurfaceStats on one of `grids`, sampled after every coarse step start_step + k interval (native:
-    inside the C batch, ludwig_execute_timestep_batch_sampled; else through its accumulate() after the coarse step).
-    forces: a force_series.DeviceForceSeries on one of `grids`, sampled after every coarse step start_step + k interval (native: inside
-    the C batch, ludwig_execute_timestep_batch_loads; else through its sample() after the coarse step).
-    tracers: a tracers.DeviceTracers made over `grids`, advanced behind every coarse step start_step + k interval (native: inside the C
-    batch, ludwig_execute_timestep_batch_tracers; else through its advance() after the coarse step) - the same bits either way."""
+    Each observer is observed at the coarse steps start_step + k interval of its own schedule (native: inside the C batch, as one entry
+    of the call's observer list; else through the set's own call after the coarse step) - the same bits either way:
+    probes: a probes.DeviceProbes made over `grids`, sampled on every level that holds probes;
+    surface: a surface_stats.DeviceSurfaceStats on one of `grids`, accumulated;
+    forces: a force_series.DeviceForceSeries on one of `grids`, sampled;
+    tracers: a tracers.DeviceTracers made over `grids`, advanced."""
     if native:
         import ctypes as C
         from . import _lib
         arr = (C.c_void_p * len(grids))(*[g.handle for g in grids])
         fl = params.to_c()
-        if surface is not None or forces is not None:
-            smp = _lib.BatchSamplers(probes.handle.value if probes is not None else None, probes.start_step if probes is not None else 0,
-                                     probes.interval if probes is not None else 1, surface.handle.value if surface is not None else None,
-                                     surface.start_step if surface is not None else 0, surface.interval if surface is not None else 1)
-        if tracers is not None:
-            any_sampler = probes is not None or surface is not None
-            if any_sampler and surface is None and forces is None:
-                smp = _lib.BatchSamplers(probes.handle.value, probes.start_step, probes.interval, None, 0, 1)
-            _lib.check(_lib.load().ludwig_execute_timestep_batch_tracers(arr, len(grids), int(t_start), int(batch_size),
-                                                                         float(np.float32(u_curr)), C.byref(fl),
-                                                                         C.byref(smp) if any_sampler else None,
-                                                                         forces.handle if forces is not None else None,
-                                                                         forces.start_step if forces is not None else 0,
-                                                                         forces.interval if forces is not None else 1, tracers.handle,
-                                                                         tracers.start_step, tracers.interval))
-        elif forces is not None:
-            _lib.check(_lib.load().ludwig_execute_timestep_batch_loads(arr, len(grids), int(t_start), int(batch_size),
-                                                                       float(np.float32(u_curr)), C.byref(fl), C.byref(smp), forces.handle,
-                                                                       forces.start_step, forces.interval))
-        elif surface is not None:
-            _lib.check(_lib.load().ludwig_execute_timestep_batch_sampled(arr, len(grids), int(t_start), int(batch_size),
-                                                                         float(np.float32(u_curr)), C.byref(fl), C.byref(smp)))
-        elif probes is None:
-            _lib.check(_lib.load().ludwig_execute_timestep_batch(arr, len(grids), int(t_start), int(batch_size),
-                                                                 float(np.float32(u_curr)), C.byref(fl)))
-        else:
-            _lib.check(_lib.load().ludwig_execute_timestep_batch_probes(arr, len(grids), int(t_start), int(batch_size),
-                                                                        float(np.float32(u_curr)), C.byref(fl), probes.handle,
-                                                                        probes.start_step, probes.interval))
+        sets = ((_lib.OBSERVE_PROBES, probes), (_lib.OBSERVE_SURFACE, surface), (_lib.OBSERVE_FORCES, forces), (_lib.OBSERVE_TRACERS, tracers))
+        obs = [_lib.BatchObserver(kind, s.handle.value, s.start_step, s.interval) for kind, s in sets if s is not None]
+        _lib.check(_lib.load().ludwig_execute_timestep_batch_observed(arr, len(grids), int(t_start), int(batch_size),
+                                                                      float(np.float32(u_curr)), C.byref(fl),
+                                                                      (_lib.BatchObserver * len(obs))(*obs), len(obs)))
         return
-    from .statistics import t_sub_after
+    from .statistics import is_sample_step, t_sub_after
+
+    def due(s, t):
+        return s is not None and is_sample_step(t, s.start_step, s.interval)
     for t_offset in range(batch_size):
         t = t_start + t_offset
         recursive_step(grids, 1, t, None, np.float32(0.5), u_curr, params)
-        if probes is not None and t >= probes.start_step and (t - probes.start_step) % probes.interval == 0:
+        if due(probes, t):
             for lvl in probes.levels_with_probes:
                 probes.sample(lvl, t_sub_after(lvl, t))
-        if surface is not None and surface.is_sample_step(t):
+        if due(surface, t):
             surface.accumulate(t_sub_after(surface.level_index, t))
-        if forces is not None and forces.is_sample_step(t):
+        if due(forces, t):
             forces.sample(t_sub_after(forces.level_index, t), t)
-        if tracers is not None and tracers.is_advance_step(t):
+        if due(tracers, t):
             tracers.advance(t)
     grids[0].synchronize()                             # KernelAbstractions.synchronize(backend)
 

@@ -7,7 +7,7 @@ of the sums into mean rho, mean u, the Reynolds stresses R_ij = <u_i u_j> - <u_i
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Tuple
 
 import numpy as np
 
@@ -24,6 +24,13 @@ def t_sub_after(level_index: int, t_coarse: int) -> int:
 
 def is_sample_step(step: int, start_step: int, interval: int) -> bool:
     return step >= start_step and (step - start_step) % interval == 0
+
+
+def check_schedule(what: str, start_step: int, interval: int) -> Tuple[int, int]:
+    """(start_step, interval) of an observer's schedule as ints; ValueError below 1"""
+    if int(start_step) < 1 or int(interval) < 1:
+        raise ValueError(f"{what}: start_step {start_step} and interval {interval} must be >= 1")
+    return int(start_step), int(interval)
 
 
 def sample_steps(first: int, last: int, start_step: int, interval: int) -> List[int]:

@@ -40,6 +40,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import statistics as stats_mod
 from ._lib import Handle
 from .blocks import BLOCK_SIZE
 from .probes import trilinear
@@ -316,9 +317,7 @@ class SeedPlan:
 
 
 def check_schedule(start_step: int, interval: int) -> Tuple[int, int]:
-    if int(start_step) < 1 or int(interval) < 1:
-        raise ValueError(f"streamlines: start_step {start_step} and interval {interval} must be >= 1")
-    return int(start_step), int(interval)
+    return stats_mod.check_schedule("streamlines", start_step, interval)
 
 
 # ---- files ----

@@ -24,6 +24,7 @@ import numpy as np
 from . import forces as forces_mod
 from ._lib import Handle
 from .blocks import BLOCK_SIZE
+from .statistics import is_sample_step
 
 F32 = np.float32
 COMPONENTS = ("p", "pp", "tau_x", "tau_y", "tau_z", "tau_mag", "tau_mag2")
@@ -148,7 +149,7 @@ class DeviceSurfaceStats(Handle):
         self._h = h
 
     def is_sample_step(self, t: int) -> bool:
-        return t >= self.start_step and (t - self.start_step) % self.interval == 0
+        return is_sample_step(t, self.start_step, self.interval)
 
     def reset(self) -> None:
         from . import _lib

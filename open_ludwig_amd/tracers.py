@@ -38,6 +38,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import statistics as stats_mod
 from ._lib import Handle
 from .streamlines import END_OBSTACLE, END_OUTSIDE, expand_group, host_levels, sample_host, seed_positions, to_domain
 
@@ -129,8 +130,7 @@ def snapshot_host(levels: Sequence[tuple], P: np.ndarray, state: np.ndarray) -> 
 
 # ---- host bookkeeping ----
 def check_schedule(start_step: int, interval: int, release_every: int = 1, generations: int = 1) -> None:
-    if int(start_step) < 1 or int(interval) < 1:
-        raise ValueError(f"tracers: start_step {start_step} and interval {interval} must be >= 1")
+    stats_mod.check_schedule("tracers", start_step, interval)
     if int(release_every) < 1 or int(generations) < 1:
         raise ValueError(f"tracers: release_every {release_every} and generations {generations} must be >= 1")
 
@@ -202,7 +202,7 @@ class DeviceTracers(Handle):
         return self.n_seeds * self.generations
 
     def is_advance_step(self, t_coarse: int) -> bool:
-        return t_coarse >= self.start_step and (t_coarse - self.start_step) % self.interval == 0
+        return stats_mod.is_sample_step(t_coarse, self.start_step, self.interval)
 
     def advance(self, t_coarse: int) -> None:
         """queue one advance behind coarse step t_coarse, outside a batch"""

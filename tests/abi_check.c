@@ -41,6 +41,12 @@ int main(int argc, char **argv)
     SIZE(LudwigHaloPlanDesc);
     FIELD(LudwigHaloPlanDesc, n_peers); FIELD(LudwigHaloPlanDesc, peer_ranks); FIELD(LudwigHaloPlanDesc, send_count); FIELD(LudwigHaloPlanDesc, recv_count);
     FIELD(LudwigHaloPlanDesc, send_index); FIELD(LudwigHaloPlanDesc, recv_index);
+    SIZE(LudwigBatchObserver);
+    FIELD(LudwigBatchObserver, kind); FIELD(LudwigBatchObserver, set); FIELD(LudwigBatchObserver, start_step); FIELD(LudwigBatchObserver, interval);
+    printf("enum LUDWIG_OBSERVE_PROBES %d\n", (int)LUDWIG_OBSERVE_PROBES);
+    printf("enum LUDWIG_OBSERVE_SURFACE %d\n", (int)LUDWIG_OBSERVE_SURFACE);
+    printf("enum LUDWIG_OBSERVE_FORCES %d\n", (int)LUDWIG_OBSERVE_FORCES);
+    printf("enum LUDWIG_OBSERVE_TRACERS %d\n", (int)LUDWIG_OBSERVE_TRACERS);
     printf("enum LUDWIG_HALO_GROUPS %d\n", (int)LUDWIG_HALO_GROUPS);
     printf("enum LUDWIG_UNIQUE_ID_BYTES %d\n", (int)LUDWIG_UNIQUE_ID_BYTES);
     printf("enum LUDWIG_FIELD_COUNT %d\n", (int)LUDWIG_FIELD_COUNT);

@@ -129,21 +129,24 @@ def abi_report(tmp_path_factory):
 
 def test_header_is_c99_and_struct_layouts_match_ctypes(abi_report):
     pairs = {"LudwigLevelHost": _lib.LevelHost, "LudwigStepFlags": _lib.StepFlags, "LudwigSurfaceParams": _lib.SurfaceParams,
-             "LudwigLevelInfo": _lib.LevelInfo, "LudwigHaloPlanDesc": _lib.HaloPlanDesc}
+             "LudwigLevelInfo": _lib.LevelInfo, "LudwigHaloPlanDesc": _lib.HaloPlanDesc, "LudwigBatchObserver": _lib.BatchObserver}
     for cname, cls in pairs.items():
         assert abi_report["struct"][cname] == C.sizeof(cls), cname
         want = [(n, getattr(cls, n).offset, getattr(cls, n).size) for n, _ in cls._fields_]
         assert abi_report["field"][cname] == want, cname          # same names, same order, same offsets and sizes
     assert abi_report["enum"] == {"LUDWIG_FIELD_COUNT": len(_lib.FIELD_NAMES), "LUDWIG_WALL_DIST": _lib.WALL_DIST,
                                   "LUDWIG_PART_INTERIOR": _lib.PART_INTERIOR, "LUDWIG_HALO_GROUPS": len(_lib.HALO_GROUPS),
-                                  "LUDWIG_UNIQUE_ID_BYTES": _lib.UNIQUE_ID_BYTES}
+                                  "LUDWIG_UNIQUE_ID_BYTES": _lib.UNIQUE_ID_BYTES,
+                                  "LUDWIG_OBSERVE_PROBES": _lib.OBSERVE_PROBES, "LUDWIG_OBSERVE_SURFACE": _lib.OBSERVE_SURFACE,
+                                  "LUDWIG_OBSERVE_FORCES": _lib.OBSERVE_FORCES, "LUDWIG_OBSERVE_TRACERS": _lib.OBSERVE_TRACERS}
 
 
 def test_julia_binding_structs_match_the_header(abi_report):
     """julia/LudwigHIP.jl cannot run here (no Julia in the image); its struct definitions are at least layout-checked
     against what gcc makes of the header, and every symbol it ccalls must be one the header declares."""
     text = open(os.path.join(ROOT, "julia", "LudwigHIP.jl")).read()
-    for jname, cname in (("LevelHost", "LudwigLevelHost"), ("StepFlags", "LudwigStepFlags"), ("HaloPlanDesc", "LudwigHaloPlanDesc")):
+    for jname, cname in (("LevelHost", "LudwigLevelHost"), ("StepFlags", "LudwigStepFlags"), ("HaloPlanDesc", "LudwigHaloPlanDesc"),
+                         ("BatchObserver", "LudwigBatchObserver")):
         fields, size = _julia_struct_layout(text, jname)
         assert fields == abi_report["field"][cname], jname
         assert size == abi_report["struct"][cname], jname
@@ -179,6 +182,19 @@ def test_multi_gpu_entry_points_reject_bad_arguments_without_a_device():
     assert lib.ludwig_level_field_layout(None, 0, None, None, None) == -1
     lib.ludwig_comm_destroy(None)
     lib.ludwig_halo_plan_destroy(None)                                                               # destroying nothing is a no-op
+
+
+def test_observed_batch_rejects_bad_arguments_without_a_device():
+    """ludwig_execute_timestep_batch_observed refuses its levels and flags before it looks at the observer list or touches a GPU (what it
+    refuses in the list itself needs a live level: tests/test_gpu_batch_observed.py)."""
+    lib = _lib.load()
+    fl = _lib.StepFlags()
+    obs = (_lib.BatchObserver * 1)(_lib.BatchObserver(_lib.OBSERVE_PROBES, None, 0, 0))
+    batch = lib.ludwig_execute_timestep_batch_observed
+    assert batch(None, 1, 1, 1, 0.0, C.byref(fl), obs, 1) == -1 and b"bad argument" in lib.ludwig_last_error()
+    assert batch((C.c_void_p * 1)(None), 1, 1, 1, 0.0, C.byref(fl), obs, 1) == -1 and b"null level 1" in lib.ludwig_last_error()
+    assert batch((C.c_void_p * 1)(None), 0, 1, 1, 0.0, C.byref(fl), obs, 1) == -1 and b"bad argument" in lib.ludwig_last_error()
+    assert batch((C.c_void_p * 1)(None), 1, 1, 1, 0.0, None, obs, 1) == -1 and b"bad argument" in lib.ludwig_last_error()
 
 
 def test_side_buffer_set_is_made_completely_or_not_at_all(tmp_path):

@@ -203,7 +203,10 @@ def test_header_exports_and_julia_list_the_probe_calls():
     lib = _lib.load()
     for name in new:
         assert re.search(r"\b" + name + r"\s*\(", header) and name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name)
-        assert f"(:{name}, LIB)" in jl, name
+        # the binding reaches an in-batch observer through the observed batch call, as an entry of the observer's kind
+        called = "ludwig_execute_timestep_batch_observed" if name.startswith("ludwig_execute_timestep_batch_") else name
+        assert f"(:{called}, LIB)" in jl, name
+    assert "entry(OBSERVE_PROBES, probes, start_step, interval)" in jl
     assert lib.ludwig_abi_version() == 1
 
 

@@ -180,7 +180,10 @@ def test_header_bindings_and_julia_list_the_new_calls():
     for name in NEW_CALLS:
         assert re.search(r"\b%s\(" % name, header), name
         assert name in _lib.EXPORTED_SYMBOLS, name
-        assert re.search(r"ccall\(\(:%s, LIB\)" % name, jl), name
+        # the binding reaches an in-batch observer through the observed batch call, as an entry of the observer's kind
+        called = "ludwig_execute_timestep_batch_observed" if name.startswith("ludwig_execute_timestep_batch_") else name
+        assert re.search(r"ccall\(\(:%s, LIB\)" % called, jl), name
+    assert "entry(OBSERVE_SURFACE, s.surface, s.surface_start_step, s.surface_interval)" in jl
     assert "typedef struct LudwigBatchSamplers" in header and "struct BatchSamplers" in jl
     lib = _lib.load()
     assert lib.ludwig_abi_version() == 1
