@@ -223,11 +223,13 @@ int  ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels,
                                    float u_curr, const LudwigStepFlags *flags);
 
 /* What a batch observes while it steps: a list of tagged entries, each a set (made by ludwig_probes_create, ludwig_surface_stats_create,
- * ludwig_force_series_create or ludwig_tracers_create, below) observed at coarse steps start_step + k interval, k >= 0. */
-enum { LUDWIG_OBSERVE_PROBES = 0, LUDWIG_OBSERVE_SURFACE = 1, LUDWIG_OBSERVE_FORCES = 2, LUDWIG_OBSERVE_TRACERS = 3 };
+ * ludwig_force_series_create, ludwig_tracers_create or ludwig_flux_planes_create, below) observed at coarse steps start_step + k interval,
+ * k >= 0. */
+enum { LUDWIG_OBSERVE_PROBES = 0, LUDWIG_OBSERVE_SURFACE = 1, LUDWIG_OBSERVE_FORCES = 2, LUDWIG_OBSERVE_TRACERS = 3,
+       LUDWIG_OBSERVE_FLUXES = 4 };
 typedef struct LudwigBatchObserver {
     int32_t kind;        /* LUDWIG_OBSERVE_* */
-    void   *set;         /* LudwigProbes* / LudwigSurfaceStats* / LudwigForceSeries* / LudwigTracers*; NULL: entry ignored */
+    void   *set;         /* LudwigProbes* / LudwigSurfaceStats* / LudwigForceSeries* / LudwigTracers* / LudwigFluxPlanes*; NULL: ignored */
     int64_t start_step;  /* observed at coarse steps start_step + k interval, k >= 0 */
     int32_t interval;
 } LudwigBatchObserver;
@@ -241,7 +243,10 @@ typedef struct LudwigBatchObserver {
  * for n_observers < 0, observers NULL with n_observers > 0, an unknown kind, or two non-null entries of one kind; then per set
  * LUDWIG_ERR_INVALID for interval < 1, probes or tracers not made over exactly these levels (same handles, same order), a surface or
  * force set whose level is not in `levels`, and LUDWIG_ERR_STATE if the batch's probe samples or force records would overflow the free
- * ring. */
+ * ring. Flux planes (checked last): the ring slot is opened when an observed coarse step begins, every level that holds points launches
+ * its reduction on its own stream right after its last sub-step of that step - no stream join, no host synchronisation;
+ * LUDWIG_ERR_INVALID for interval < 1 or a set not made over exactly these levels, LUDWIG_ERR_STATE if the batch's records would
+ * overflow the free ring. */
 int  ludwig_execute_timestep_batch_observed(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                             float u_curr, const LudwigStepFlags *flags, const LudwigBatchObserver *observers,
                                             int32_t n_observers);
@@ -506,6 +511,42 @@ int  ludwig_force_series_download(LudwigForceSeries *set, double *sums, int64_t 
 int  ludwig_execute_timestep_batch_loads(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                          float u_curr, const LudwigStepFlags *flags, const LudwigBatchSamplers *s,
                                          LudwigForceSeries *fs, int64_t start_step, int32_t interval);
+
+/* ---- flux planes: integrals over axis-aligned planes per sampled coarse step (no reference counterpart) ----
+ * A set is made over a level array. Plane k has the normal axis normal[k] (0, 1, 2: x, y, z) and the points plane_start[k] ..
+ * plane_start[k + 1] - 1 (plane_start[0] = 0), in its point order. Point p with valid[p] != 0 lives on level level_index[p] (0-based)
+ * and has the probes' stencil: 8 corners c = dx + 2 dy + 4 dz (reference block index blocks[8p + c], cell cells[8p + c] = x + 8 y +
+ * 64 z), every corner that is no fluid cell of the level already replaced by the base cell, and weights[3p + 0..2] in [0, 1]. A point
+ * with valid[p] == 0 is skipped and its other entries are unread.
+ * A sample of a valid point is rho, ux, uy, uz by the probes' trilinear rule (x, then y, then z, every lerp (1 - w) a + w b) in float32
+ * without contraction, read from the level's newest state after the coarse step (vel_temp after an even sub-step, vel after an odd
+ * one; rho as a download would return it). Its integrands, float32 without contraction, in exactly this operand order:
+ *     un = u[normal]   m = rho * un   q = (ux*ux + uy*uy) + uz*uz   c[0..7] = rho, un, m, m*ux, m*uy, m*uz, rho*q, m*q
+ * For every (plane, level) pair the valid points of that plane on that level, in point order, are reduced per row: widened to float64
+ * and added in the force series' balanced tree (adjacent pairs halved, +0.0 appended wherever a length is odd, no addition once one
+ * value is left); the count of points is an int64 sum. A plane's record is the float64 left-to-right sum of its per-level records
+ * from the coarsest level to the finest, skipping levels that hold none of its points (counts added as integers); a plane without a
+ * valid point gives +0.0 and 0. No atomics: a record depends on nothing but the state and the point order. Each level reduces its own
+ * points on its own stream, so no level waits for another. Lattice units throughout: the area element, the plane's direction and every
+ * physical scale are the caller's.
+ * Per-level records wait in a device ring [capacity][n_planes][n_levels] until they are downloaded. Creating the set makes every level
+ * that holds a point store rho after every step (see ludwig_level_set_rho_store). n_planes = 0, or no valid point, is allowed and
+ * launches nothing. A level may hold at most 2^31 / 512 blocks; entries of `levels` that no valid point refers to may be NULL. */
+typedef struct LudwigFluxPlanes LudwigFluxPlanes;   /* opaque */
+int  ludwig_flux_planes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_planes, const int32_t *plane_start,
+                               const int32_t *normal, const int32_t *level_index, const int32_t *blocks, const int32_t *cells,
+                               const float *weights, const uint8_t *valid, int32_t capacity, LudwigFluxPlanes **out);
+/* frees the set, not the levels; it does not touch them, so it may come before or after their destruction */
+void ludwig_flux_planes_destroy(LudwigFluxPlanes *set);
+/* between batches: one ring slot filed under coarse step t_coarse; every level that holds points reduces them, as left by its last
+ * sub-step of that step ((t_coarse + 1) 2^level_index - 1), on its stream; no host synchronisation. LUDWIG_ERR_STATE when the ring is
+ * full. */
+int  ludwig_flux_planes_sample(LudwigFluxPlanes *set, int64_t t_coarse);
+/* the n samples taken since the last download, oldest first: sums[(i n_planes + k) 8 + 0..7], counts[i n_planes + k], steps[i].
+ * Synchronizes the streams of the levels that hold points, adds each plane's levels in order, then empties the ring.
+ * LUDWIG_ERR_INVALID when n > max_samples. */
+int  ludwig_flux_planes_download(LudwigFluxPlanes *set, double *sums, int64_t *counts, int64_t *steps, int32_t max_samples,
+                                 int32_t *n_samples);
 
 /* ---- slices: planar grids of points sampled after a coarse step (no reference counterpart) ----
  * A slice set is made over a level array. Point p with valid[p] != 0 lives on level level_index[p] (0-based) and has the probes'

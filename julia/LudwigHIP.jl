@@ -45,7 +45,7 @@ struct BatchSamplers           # LudwigBatchSamplers
     surface::Ptr{Cvoid}; surface_start_step::Int64; surface_interval::Int32
 end
 
-const OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS = Int32.(0:3)   # LUDWIG_OBSERVE_*
+const OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS, OBSERVE_FLUXES = Int32.(0:4)   # LUDWIG_OBSERVE_*
 struct BatchObserver           # LudwigBatchObserver
     kind::Int32; set::Ptr{Cvoid}; start_step::Int64; interval::Int32
 end
@@ -335,6 +335,34 @@ function force_series_download!(sums::Matrix{Float64}, covered::Vector{Int64}, s
     n = Ref{Int32}(0)
     GC.@preserve sums covered steps check(ccall((:ludwig_force_series_download, LIB), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int32, Ref{Int32}), s, sums, covered, steps, Int32(length(steps)), n))
+    return Int(n[])
+end
+
+# flux planes (no reference counterpart): per plane and sampled coarse step the eight sums of rho, un, m, m ux, m uy, m uz, rho q, m q
+# (m = rho un, q = |u|^2) over its valid points and their count; pass the set to a batch as entry(OBSERVE_FLUXES, set, start_step, interval)
+"""a flux-plane set over `grids`: plane k has the normal axis `normal[k]` (0, 1, 2) and the points `plane_start[k]` .. `plane_start[k+1]`-1
+(0-based, `plane_start[1]` = 0); per point its 0-based level, the probes' stencil (8 x n blocks and cells, 3 x n weights) and `valid`;
+a ring of `capacity` samples. Free it with `flux_planes_destroy`."""
+function flux_planes_create(grids::Vector{DeviceLevel}, plane_start::Vector{Int32}, normal::Vector{Int32}, level::Vector{Int32},
+                            blocks::Matrix{Int32}, cells::Matrix{Int32}, weights::Matrix{Float32}, valid::Vector{UInt8}, capacity::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles plane_start normal level blocks cells weights valid check(ccall((:ludwig_flux_planes_create, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Ptr{UInt8}, Int32,
+         Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int32(length(normal)), plane_start, normal, level, blocks, cells, weights, valid, Int32(capacity), out))
+    return out[]
+end
+flux_planes_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_flux_planes_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""between batches: one sample of the state after coarse step `t_coarse` (every level that holds points, queued on its stream)"""
+flux_planes_sample!(s::Ptr{Cvoid}, t_coarse::Integer) =
+    check(ccall((:ludwig_flux_planes_sample, LIB), Cint, (Ptr{Cvoid}, Int64), s, Int64(t_coarse)))
+"""the samples taken since the last download into sums (8 x n_planes x capacity), counts (n_planes x capacity) and steps (capacity);
+returns how many; empties the ring"""
+function flux_planes_download!(sums::Array{Float64,3}, counts::Matrix{Int64}, steps::Vector{Int64}, s::Ptr{Cvoid})
+    n = Ref{Int32}(0)
+    GC.@preserve sums counts steps check(ccall((:ludwig_flux_planes_download, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Int32, Ref{Int32}), s, sums, counts, steps, Int32(length(steps)), n))
     return Int(n[])
 end
 

@@ -36,7 +36,7 @@ SUBGRID_SUM_NAMES = {"nu": 0, "nunu": 1, "eps": 2}
 PART_ALL, PART_BOUNDARY, PART_INTERIOR = 0, 1, 2
 
 # LUDWIG_OBSERVE_*: the kind of a BatchObserver entry
-OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS = range(4)
+OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS, OBSERVE_FLUXES = range(5)
 
 # every symbol include/ludwig_hip.h declares (tests check the .so exports exactly these)
 EXPORTED_SYMBOLS = [
@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_wall_surface_download",
     "ludwig_force_series_create", "ludwig_force_series_destroy", "ludwig_force_series_sample", "ludwig_force_series_download",
     "ludwig_execute_timestep_batch_loads",
+    "ludwig_flux_planes_create", "ludwig_flux_planes_destroy", "ludwig_flux_planes_sample", "ludwig_flux_planes_download",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -256,6 +257,10 @@ def load() -> C.CDLL:
         "ludwig_force_series_download": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(C.c_int32)]),
         "ludwig_execute_timestep_batch_loads": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers),
                                                           vp, i64, i32]),
+        "ludwig_flux_planes_create": (C.c_int, [C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp)]),
+        "ludwig_flux_planes_destroy": (None, [vp]),
+        "ludwig_flux_planes_sample": (C.c_int, [vp, i64]),
+        "ludwig_flux_planes_download": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(C.c_int32)]),
         "ludwig_execute_timestep_batch_tracers": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers),
                                                             vp, i64, i32, vp, i64, i32]),
     }

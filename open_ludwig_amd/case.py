@@ -16,6 +16,7 @@ from typing import Callable, List, Optional
 
 import numpy as np
 
+from . import flux_planes as flux_mod
 from . import force_series as fseries_mod
 from . import forces as forces_mod
 from . import isosurface as iso_mod
@@ -45,8 +46,9 @@ class DiagRow:
 
 
 def _close_observers(st) -> None:
-    """close a stepper's probe, surface, slice, wall-surface, force-series, streamline and tracer sets (each may be None or absent)"""
-    for name in ("probes", "surface", "slices", "wall_surface", "forces", "stream_set", "tracer_set"):
+    """close a stepper's probe, surface, slice, wall-surface, force-series, streamline, tracer and flux-plane sets (each may be None or
+    absent)"""
+    for name in ("probes", "surface", "slices", "wall_surface", "forces", "stream_set", "tracer_set", "fluxes"):
         obs = getattr(st, name, None)
         if obs is not None:
             obs.close()
@@ -73,26 +75,29 @@ class HipStepper:
         self._surface_plan = None              # (mesh, params, plan) of the surface statistics, shared with the force series
         self.stream_set = None                 # streamlines_setup
         self.tracer_set = None                 # tracers_setup
+        self.fluxes = None                     # flux_planes_setup
+        self._flux_series = None
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
-        if self.probes is None and self.forces is None:
+        if self.probes is None and self.forces is None and self.fluxes is None:
             execute_timestep_batch(self.dev, t_start, n, u_curr, params, surface=self.surface, tracers=self.tracer_set)
             return
         # sampled inside the C batch, the rings drained after it; a batch with more samples than a ring holds is cut where the first one
         # fills (the same inlet speed: the same steps, the same bits)
-        P, F, t, end = self.probes, self.forces, t_start, t_start + n - 1
+        P, F, X, t, end = self.probes, self.forces, self.fluxes, t_start, t_start + n - 1
         while t <= end:
             seg_end = end
-            if P is not None:
-                seg_end = min(seg_end, fseries_mod.segment_end(t, end, P.start_step, P.interval, P.capacity))
-            if F is not None:
-                seg_end = min(seg_end, fseries_mod.segment_end(t, end, F.start_step, F.interval, F.capacity))
+            for ring in (P, F, X):
+                if ring is not None:
+                    seg_end = min(seg_end, fseries_mod.segment_end(t, end, ring.start_step, ring.interval, ring.capacity))
             execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P, surface=self.surface, forces=F,
-                                   tracers=self.tracer_set)
+                                   tracers=self.tracer_set, fluxes=X)
             if P is not None:
                 self._series.append(*P.download())
             if F is not None:
                 self._fseries.append(*F.download())
+            if X is not None:
+                self._flux_series.append(*X.download())
             t = seg_end + 1
 
     # -- probes (no reference counterpart) --
@@ -148,6 +153,20 @@ class HipStepper:
     def force_series_new(self):
         """the same, of the records drained since the last force_series_new() only (what run_case writes after a batch)"""
         return self._fseries.take_new()
+
+    # -- flux planes (no reference counterpart) --
+    def flux_planes_setup(self, plans, start_step: int = 1, interval: int = 1, capacity: int = 64) -> None:
+        """reduce the planes of `plans` (flux_planes.plan_flux_plane over this stepper's grids) at coarse steps start_step + k interval,
+        inside every batch"""
+        if self.fluxes is not None:
+            self.fluxes.close()
+        self.fluxes = flux_mod.DeviceFluxPlanes(plans, self.dev, capacity, max(int(start_step), 1), interval)
+        self._flux_series = flux_mod.Series(len(plans))
+
+    def flux_planes_new(self):
+        """(coarse steps [n] int64, sums [n, n_planes, 8] Float64, counts [n, n_planes] int64) of the samples drained since the last
+        flux_planes_new() (what run_case writes after a batch)"""
+        return self._flux_series.take_new()
 
     # -- slices (no reference counterpart) --
     def slices_setup(self, plans, start_step: int = 1, interval: int = 1) -> None:
@@ -851,6 +870,11 @@ class DistributedStepper:
         raise RuntimeError("advanced.streamlines is enabled, but a distributed run cannot trace streamlines yet: a line crosses the "
                            "ranks' blocks, and each rank holds only its own (DESIGN section 8, Next)")
 
+    # -- flux planes: not over ranks - a record is one tree over a plane's points in point order, not a sum of per-rank parts --
+    def flux_planes_setup(self, *args, **kwargs) -> None:
+        raise RuntimeError("advanced.flux_planes is enabled, but a distributed run cannot integrate flux planes yet: a record is one "
+                           "fixed tree over a plane's points in point order, not a sum of the ranks' parts")
+
     # -- tracers: not over ranks, for the streamlines' reason --
     def tracers_setup(self, *args, **kwargs) -> None:
         raise RuntimeError("advanced.tracers is enabled, but a distributed run cannot advect tracers yet: a particle crosses the ranks' "
@@ -965,6 +989,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     batches at the coarse steps start_step + k interval (force_series.py) and forces_series.csv gains one row per sampled step after
     every batch, with that batch's inlet speed; `log` gets the mean and rms of Cd, Cl, Cmy over the rows after ramp_steps at the end. No
     batch is cut for it beyond the ring's capacity. Device only: a stepper without force_series_setup raises.
+    With cfg.flux_planes_enabled (advanced.flux_planes), every plane and every box face is reduced at the coarse steps start_step + k
+    interval (flux_planes.py): inside the batches where the stepper offers flux_planes_setup - no batch is cut beyond the ring's capacity -
+    else from downloaded fields (flux_planes.host_sample), cutting batches there as for slices; after every batch fluxes.csv gains one row
+    per plane and sampled step and flux_boxes.csv one per box. A stepper whose flux_planes_setup raises (the distributed one) ends the run
+    before the first step.
     With cfg.statistics_subgrid the model's sums are sampled at exactly the flow statistics' sampled steps (same
     reset) and flow_mean_%06d.vtu gains subgrid.MEAN_ARRAYS after its own arrays. Device only: a stepper without subgrid_fields raises."""
     import time as _time
@@ -978,6 +1007,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     sl_start, sl_interval = cfg.slices_start_step, cfg.slices_interval
     # a plane outside the domain is refused before anything is allocated on a device
     splans = [slices_mod.plan_slice(spec, grids, params.mesh_offset) for spec in cfg.slices_planes] if slices_on else []
+    # a flux plane outside the domain is refused before anything is allocated on a device
+    fplans = [flux_mod.plan_flux_plane(spec, grids, params.mesh_offset) for spec in cfg.flux_planes_planes] if cfg.flux_planes_enabled else []
     st = stepper_factory(grids)
     iso_on = bool(cfg.isosurfaces_enabled)
     iso_start, iso_interval = cfg.isosurfaces_start_step, cfg.isosurfaces_interval
@@ -1019,6 +1050,18 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         warn = tracer_mod.jump_warning(tr_interval, float(cfg.u_lattice), len(grids))
         if warn and log:
             log(warn)
+    flux_on = bool(cfg.flux_planes_enabled)
+    fx_start, fx_interval = cfg.flux_planes_start_step, cfg.flux_planes_interval
+    dev_fluxes = flux_on and hasattr(st, "flux_planes_setup")      # else the host fallback from downloaded fields
+    if dev_fluxes:
+        try:
+            st.flux_planes_setup(fplans, fx_start, fx_interval, max(cfg.async_depth, 1))
+        except Exception:
+            if hasattr(st, "close"):
+                st.close()
+            raise
+    if flux_on and cfg.flux_planes_boxes and cfg.symmetric_analysis and log:
+        log("flux planes: symmetric_analysis is on; the control-volume force of a box is that of the modelled half, not doubled")
     wall_on = bool(cfg.wall_diagnostics_enabled)
     if wall_on and not hasattr(st, "wall_diagnostics_setup"):
         if hasattr(st, "close"):
@@ -1077,6 +1120,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         if fseries_on:
             with open(os.path.join(out_dir, "forces_series.csv"), "w") as io:
                 io.write(fseries_mod.csv_header() + "\n")
+        if flux_on:
+            with open(os.path.join(out_dir, "fluxes.csv"), "w") as io:
+                io.write(flux_mod.FLUXES_CSV_HEADER + "\n")
+            if cfg.flux_planes_boxes:
+                with open(os.path.join(out_dir, "flux_boxes.csv"), "w") as io:
+                    io.write(flux_mod.BOXES_CSV_COMMENT + "\n" + flux_mod.BOXES_CSV_HEADER + "\n")
         if slices_on:
             slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
         if stream_on:
@@ -1233,6 +1282,27 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         if writing and lines:
             with open(os.path.join(out_dir, "forces_series.csv"), "a") as io:
                 io.writelines(l + "\n" for l in lines)
+    flux_host = []                       # the host fallback's samples of the batch: (step, sums, counts)
+    flux_box_cd = {}                     # box name -> Cd of the rows after the ramp
+
+    def flush_fluxes():
+        """append the samples the batch that has just ended took to fluxes.csv and flux_boxes.csv"""
+        if dev_fluxes:
+            f_steps, f_sums, f_counts = st.flux_planes_new()
+        else:
+            f_steps = np.array([s for s, _, _ in flux_host], dtype=np.int64)
+            f_sums, f_counts = [a for _, a, _ in flux_host], [c for _, _, c in flux_host]
+            flux_host.clear()
+        plane_rows, box_rows, box_values = flux_mod.csv_rows(fplans, cfg.flux_planes_boxes, f_steps, f_sums, f_counts, params)
+        for step, name, b in box_values:
+            if step > cfg.ramp_steps:
+                flux_box_cd.setdefault(name, []).append(b.Cd)
+        if writing and plane_rows:
+            with open(os.path.join(out_dir, "fluxes.csv"), "a") as io:
+                io.writelines(l + "\n" for l in plane_rows)
+        if writing and box_rows:
+            with open(os.path.join(out_dir, "flux_boxes.csv"), "a") as io:
+                io.writelines(l + "\n" for l in box_rows)
     t0 = last_diag = _time.time()
     total_cells = sum(g.n_blocks * 512 for g in grids)
     fr = None
@@ -1247,7 +1317,7 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if stats_on or surf_host is not None or slices_on or iso_on or stream_on or tracers_on:
+            if stats_on or surf_host is not None or slices_on or iso_on or stream_on or tracers_on or (flux_on and not dev_fluxes):
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
@@ -1263,6 +1333,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                 if tracers_on:           # on the device an advance cuts nothing: only the snapshot steps do
                     tr_cuts = set(stats_mod.sample_steps(t, batch_end, tr_start, tr_interval if tr_host is not None else tr_out))
                     cuts.update(tr_cuts)
+                if flux_on and not dev_fluxes:      # on the device a sample cuts nothing
+                    cuts.update(stats_mod.sample_steps(t, batch_end, fx_start, fx_interval))
                 seg = t
                 for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
@@ -1290,6 +1362,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         take_streamlines(s_step)
                     if tracers_on and s_step in tr_cuts:
                         take_tracers(s_step)
+                    if flux_on and not dev_fluxes and stats_mod.is_sample_step(s_step, fx_start, fx_interval):
+                        flux_host.append((s_step, *flux_mod.host_sample(st, fplans, s_step)))
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)
@@ -1297,6 +1371,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                 st.batch(t, actual, u_curr, sp)
             if fseries_on:
                 flush_force_series(u_curr)
+            if flux_on:
+                flush_fluxes()
             monitored = wall_done = False
             if batch_end % cfg.diag_freq < actual or batch_end == total_steps:
                 diag_step = (batch_end // cfg.diag_freq) * cfg.diag_freq
@@ -1406,6 +1482,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             for name, k in (("Cd", 0), ("Cl", 1), ("Cmy", 2)):
                 m, r = fseries_mod.mean_rms(c[k] for c in fseries_coeffs)
                 log(f"force series {name}: mean {m:.6f} rms {r:.6f} over {len(fseries_coeffs)} rows after step {cfg.ramp_steps}")
+        if fseries_on and flux_on and log:
+            surface_cd, _ = fseries_mod.mean_rms(c[0] for c in fseries_coeffs)
+            for name, cds in flux_box_cd.items():
+                m, _ = fseries_mod.mean_rms(cds)
+                log(f"flux box {name!r}: mean control-volume Cd {m:.6f} over {len(cds)} rows after step {cfg.ramp_steps} "
+                    f"(surface Cd {surface_cd:.6f})")
     finally:
         if hasattr(st, "close"):
             st.close()

@@ -2246,35 +2246,138 @@ __global__ __launch_bounds__(256) void k_force_chunks(ForceRecord *__restrict__ 
     slab[blockIdx.x] = o;
 }
 
+// One workgroup's node of a tree of records {double s[ROWS]; long long <CNT>;} (the force series' and the flux planes'): records
+// in[chunk * 512 ..] of n -> the caller's lane 0 (true) holds their node in `a`; missing records are +0.0. part / pc: LDS.
+template <typename Rec, int ROWS, long long Rec::*CNT>
+__device__ __forceinline__ bool tree_combine(Rec &a, const Rec *__restrict__ in, int64_t n, int64_t chunk, double (*part)[ROWS], long long *pc)
+{
+    const int t = (int)threadIdx.x;
+    const int64_t i = chunk * CELLS + 2 * t;
+    Rec b;
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) a.s[k] = b.s[k] = 0.0;
+    a.*CNT = b.*CNT = 0;
+    if (i < n) a = in[i];
+    if (i + 1 < n) b = in[i + 1];
+    a.*CNT += b.*CNT;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a.*CNT += __shfl_xor(a.*CNT, o, 64);
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) a.s[k] = force_wave_sum(n > 1 ? a.s[k] + b.s[k] : a.s[k], n);
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < ROWS; ++k) part[t >> 6][k] = a.s[k];
+        pc[t >> 6] = a.*CNT;
+    }
+    __syncthreads();
+    if (t != 0) return false;
+#pragma unroll
+    for (int k = 0; k < ROWS; ++k) a.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], n);
+    a.*CNT = (pc[0] + pc[1]) + (pc[2] + pc[3]);
+    return true;
+}
+
 __global__ __launch_bounds__(256) void k_force_combine(ForceRecord *__restrict__ out, const ForceRecord *__restrict__ in, int64_t n)
 {
     __shared__ double part[4][9];
     __shared__ long long cov[4];
+    ForceRecord o;
+    if (tree_combine<ForceRecord, 9, &ForceRecord::covered>(o, in, n, (int64_t)blockIdx.x, part, cov)) out[blockIdx.x] = o;
+}
+
+// ---- flux planes (ludwig_flux_planes_*; no reference counterpart) ----
+// The points of one level lie in lists, one per (plane, level) pair that holds any: the plane's valid points on that level in point
+// order. Point p has the probes' stencil: cell[8 p + c] = internal block * 512 + cell of corner c (a corner that is no fluid cell
+// already replaced by the base cell), w[3 p + a] the weights. Per point, float32 with -ffp-contract=off: rho, ux, uy, uz by the probes'
+// trilinear rule (probe_lerp: x, then y, then z), un = u[axis], m = rho * un, q = (ux ux + uy uy) + uz uz and the eight rows rho, un,
+// m, m ux, m uy, m uz, rho q, m q. Each row is widened to double and summed over its list in the force series' balanced tree
+// (force_wave_sum, force_join_waves: "add iff count > half"), the count of points is an integer sum. No atomics.
+// A FluxChunk is one workgroup's work in either kernel: elements start + 512 chunk .. of a list of n - points of the level's
+// arrays in k_flux_chunks, records of the slab in k_flux_combine - reduce to one record, written to slab[dst] or, where dst < 0 (the
+// list's last stage), to the ring slot's record ~dst.
+struct FluxRecord {
+    double s[8];                   // sums of rho, un, m, m ux, m uy, m uz, rho q, m q
+    long long count;
+};
+struct FluxChunk {
+    int32_t start, n, chunk, dst, axis, pad;
+};
+constexpr int FLUX_ROWS = 8;
+
+__device__ __forceinline__ void flux_contributions(float c[FLUX_ROWS], int64_t p, int axis, const int32_t *__restrict__ cell,
+                                                   const float *__restrict__ w, const float *__restrict__ rho,
+                                                   const float *__restrict__ vel)
+{
+    int64_t e[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e[k] = cell[8 * p + k];
+    const float wx = w[3 * p], wy = w[3 * p + 1], wz = w[3 * p + 2];
+    float res[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = k == 0 ? rho[e[j]] : vel[((e[j] >> 9) * 3 + (k - 1)) * CELLS + (e[j] & 511)];
+        const float x00 = probe_lerp(v[0], v[1], wx), x10 = probe_lerp(v[2], v[3], wx);
+        const float x01 = probe_lerp(v[4], v[5], wx), x11 = probe_lerp(v[6], v[7], wx);
+        const float y0 = probe_lerp(x00, x10, wy), y1 = probe_lerp(x01, x11, wy);
+        res[k] = probe_lerp(y0, y1, wz);
+    }
+    const float r = res[0], ux = res[1], uy = res[2], uz = res[3];
+    const float un = axis == 0 ? ux : (axis == 1 ? uy : uz);
+    const float m = r * un;
+    const float q = (ux * ux + uy * uy) + uz * uz;
+    c[0] = r; c[1] = un; c[2] = m; c[3] = m * ux; c[4] = m * uy; c[5] = m * uz; c[6] = r * q; c[7] = m * q;
+}
+
+__device__ __forceinline__ void flux_store(FluxRecord *__restrict__ slab, FluxRecord *__restrict__ slot, int32_t dst, const FluxRecord &o)
+{
+    FluxRecord *out = dst >= 0 ? slab + dst : slot + ~dst;
+    *out = o;
+}
+
+__global__ __launch_bounds__(256) void k_flux_chunks(FluxRecord *__restrict__ slab, FluxRecord *__restrict__ slot,
+                                                     const FluxChunk *__restrict__ chunks, const int32_t *__restrict__ cell,
+                                                     const float *__restrict__ w, const float *__restrict__ rho,
+                                                     const float *__restrict__ vel)
+{
+    __shared__ double part[4][FLUX_ROWS];
+    __shared__ int cnt[4];
+    const FluxChunk d = chunks[blockIdx.x];
     const int t = (int)threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * CELLS + 2 * t;
-    ForceRecord a, b;
+    const int64_t N = d.n, i = (int64_t)d.chunk * CELLS + 2 * t;
+    float c0[FLUX_ROWS], c1[FLUX_ROWS];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) a.s[k] = b.s[k] = 0.0;
-    a.covered = b.covered = 0;
-    if (i < n) a = in[i];
-    if (i + 1 < n) b = in[i + 1];
-    a.covered += b.covered;
+    for (int k = 0; k < FLUX_ROWS; ++k) c0[k] = c1[k] = 0.0f;
+    const bool k0 = i < N, k1 = i + 1 < N;
+    if (k0) flux_contributions(c0, d.start + i, d.axis, cell, w, rho, vel);
+    if (k1) flux_contributions(c1, d.start + i + 1, d.axis, cell, w, rho, vel);
+    const int n_in = __popcll(__ballot(k0)) + __popcll(__ballot(k1));
+    double s[FLUX_ROWS];
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) a.covered += __shfl_xor(a.covered, o, 64);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) a.s[k] = force_wave_sum(n > 1 ? a.s[k] + b.s[k] : a.s[k], n);
+    for (int k = 0; k < FLUX_ROWS; ++k) s[k] = force_wave_sum(N > 1 ? (double)c0[k] + (double)c1[k] : (double)c0[k], N);
     if ((t & 63) == 0) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) part[t >> 6][k] = a.s[k];
-        cov[t >> 6] = a.covered;
+        for (int k = 0; k < FLUX_ROWS; ++k) part[t >> 6][k] = s[k];
+        cnt[t >> 6] = n_in;
     }
     __syncthreads();
     if (t != 0) return;
-    ForceRecord o;
+    FluxRecord o;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) o.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], n);
-    o.covered = (cov[0] + cov[1]) + (cov[2] + cov[3]);
-    out[blockIdx.x] = o;
+    for (int k = 0; k < FLUX_ROWS; ++k) o.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], N);
+    o.count = (long long)((cnt[0] + cnt[1]) + (cnt[2] + cnt[3]));
+    flux_store(slab, slot, d.dst, o);
+}
+
+__global__ __launch_bounds__(256) void k_flux_combine(FluxRecord *__restrict__ slab, FluxRecord *__restrict__ slot,
+                                                      const FluxChunk *__restrict__ chunks)
+{
+    __shared__ double part[4][FLUX_ROWS];
+    __shared__ long long cnt[4];
+    const FluxChunk d = chunks[blockIdx.x];
+    FluxRecord o;
+    if (tree_combine<FluxRecord, FLUX_ROWS, &FluxRecord::count>(o, slab + d.start, d.n, d.chunk, part, cnt)) flux_store(slab, slot, d.dst, o);
 }
 
 // ---- wall diagnostics (ludwig_level_wall_census, ludwig_wall_surface_*; no reference counterpart: the reference reads y_plus_target

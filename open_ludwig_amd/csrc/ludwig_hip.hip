@@ -1943,6 +1943,58 @@ static int force_series_launch(LudwigForceSeries *F, int64_t t_sub, int64_t t_co
     return LUDWIG_OK;
 }
 
+// ---- flux planes (ludwig_flux_planes_*; no reference counterpart) ----
+// A set over a level array. Per level: the valid points it holds, list after list (one list per plane with points there, in plane
+// order; within a list in point order), the chunk table of k_flux_chunks, one table per further stage of k_flux_combine, and a slab for
+// the records of every stage but a list's last, which goes into the ring [capacity][n_planes][n_levels]. A (plane, level) pair without
+// points has no list and its ring record is never written or read. The host keeps the coarse step of every used slot.
+struct LudwigFluxPlanes {
+    int device = 0;
+    int n_levels = 0, n_planes = 0, capacity = 0;
+    std::vector<LudwigLevel *> levels;          // as given; an entry without points may be null
+    struct PerLevel {
+        int n = 0;                              // points
+        int32_t *cell = nullptr;                // [n][8] internal block * 512 + cell
+        float *w = nullptr;                     // [n][3]
+        FluxChunk *table = nullptr;             // every stage's workgroups, stage after stage
+        std::vector<int> stage_groups;          // workgroups of each stage (the first: k_flux_chunks)
+        FluxRecord *slab = nullptr;
+    };
+    std::vector<PerLevel> per;
+    std::vector<uint8_t> has_list;              // [n_planes][n_levels]
+    FluxRecord *ring = nullptr;
+    std::vector<int64_t> slot_step;             // coarse step of each used slot, oldest first
+};
+
+// a new slot for coarse step t (the caller has checked that there is one)
+static int flux_planes_open_slot(LudwigFluxPlanes *P, int64_t t)
+{
+    P->slot_step.push_back(t);
+    return (int)P->slot_step.size() - 1;
+}
+
+// level li's lists of the state sub-step t_sub wrote, reduced into ring slot `slot` on the level's stream
+static int flux_planes_launch(LudwigFluxPlanes *P, int li, int slot, int64_t t_sub)
+{
+    const LudwigFluxPlanes::PerLevel &q = P->per[li];
+    if (q.n == 0) return LUDWIG_OK;                       // a level without points launches nothing
+    LudwigLevel *L = P->levels[li];
+    LW_ENSURE_RHO(L);                                     // a no-op on these levels, which store it every step since the set was made
+    FluxRecord *dst = P->ring + (size_t)slot * P->n_planes * P->n_levels;
+    const FluxChunk *tab = q.table;
+    for (size_t s = 0; s < q.stage_groups.size(); ++s) {
+        const int g = q.stage_groups[s];
+        if (s == 0)
+            hipLaunchKernelGGL(k_flux_chunks, dim3((unsigned)g), dim3(CELLS / 2), 0, L->stream, q.slab, dst, tab, q.cell, q.w, L->rho,
+                               vel_out(L, t_sub));
+        else
+            hipLaunchKernelGGL(k_flux_combine, dim3((unsigned)g), dim3(CELLS / 2), 0, L->stream, q.slab, dst, tab);
+        LW_HIP(hipGetLastError());
+        tab += g;
+    }
+    return LUDWIG_OK;
+}
+
 // What a batch observes (ludwig_execute_timestep_batch_observed): one typed slot per LUDWIG_OBSERVE_* kind, a null set is not observed.
 struct ObserverSchedule {
     int64_t start_step = 0;
@@ -1954,14 +2006,16 @@ struct BatchObservers {
     struct : ObserverSchedule { LudwigSurfaceStats *set = nullptr; } surface;
     struct : ObserverSchedule { LudwigForceSeries *set = nullptr; } forces;
     struct : ObserverSchedule { LudwigTracers *set = nullptr; } tracers;
+    struct : ObserverSchedule { LudwigFluxPlanes *set = nullptr; } fluxes;
 };
 // The observers inside one coarse step: the step being run, the probes' ring slot (-1 = not sampled) and whether the surface set and
-// the force series sample this step.
+// the force series sample this step, and the flux planes' ring slot (-1 = not sampled).
 struct BatchHook {
     const BatchObservers *obs = nullptr;
     int64_t t = 0;
     int slot = -1;
     bool surface = false, forces = false;
+    int flux_slot = -1;
 };
 
 static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-based*/, int64_t t_sub, const LudwigLevel *parent,
@@ -2014,7 +2068,7 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         LW_HIP(hipEventRecord(L->ev_stepped, L->stream));
         ++L->stepped_gen;
     }
-    if (ph && (ph->slot >= 0 || ph->surface || ph->forces)) {
+    if (ph && (ph->slot >= 0 || ph->surface || ph->forces || ph->flux_slot >= 0)) {
         // the level's last sub-step of a sampled coarse step: the probes and the surface sets of this level read its newest rho / vel
         // on its own stream, behind the step (and behind the event its children wait for) and ahead of the next write to either
         const int64_t m = (int64_t)1 << (lvl - 1);
@@ -2023,6 +2077,7 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
             if (ph->slot >= 0 && (rc = probes_launch(o.probes.set, lvl - 1, ph->slot, t_sub))) return rc;
             if (ph->surface && o.surface.set->level == L && (rc = surface_stats_launch(o.surface.set, t_sub))) return rc;
             if (ph->forces && o.forces.set->level == L && (rc = force_series_launch(o.forces.set, t_sub, ph->t))) return rc;
+            if (ph->flux_slot >= 0 && (rc = flux_planes_launch(o.fluxes.set, lvl - 1, ph->flux_slot, t_sub))) return rc;
         }
     }
     if (has_children) {
@@ -2901,6 +2956,174 @@ int ludwig_force_series_download(LudwigForceSeries *F, double *sums, int64_t *co
     return LUDWIG_OK;
 }
 
+// ---- flux planes (ludwig_flux_planes_*) ----
+void ludwig_flux_planes_destroy(LudwigFluxPlanes *P)
+{
+    if (!P) return;
+    (void)hipSetDevice(P->device);
+    for (LudwigFluxPlanes::PerLevel &q : P->per) {
+        if (q.cell) (void)hipFree(q.cell);
+        if (q.w) (void)hipFree(q.w);
+        if (q.table) (void)hipFree(q.table);
+        if (q.slab) (void)hipFree(q.slab);
+    }
+    if (P->ring) (void)hipFree(P->ring);
+    delete P;
+}
+
+int ludwig_flux_planes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_planes, const int32_t *plane_start,
+                              const int32_t *plane_axis, const int32_t *level_index, const int32_t *blocks, const int32_t *cells,
+                              const float *weights, const uint8_t *valid, int32_t capacity, LudwigFluxPlanes **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels || n_planes < 0 || (n_planes > 0 && (!plane_start || !plane_axis))) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > 64) return fail(LUDWIG_ERR_INVALID, "flux planes: n_levels %d not in 1..64", n_levels);
+    if (capacity < 1) return fail(LUDWIG_ERR_INVALID, "flux planes: capacity %d < 1", capacity);
+    const int64_t n_points = n_planes > 0 ? plane_start[n_planes] : 0;
+    if (n_planes > 0 && plane_start[0] != 0) return fail(LUDWIG_ERR_INVALID, "flux planes: plane_start[0] = %d, not 0", plane_start[0]);
+    for (int32_t k = 0; k < n_planes; ++k) {
+        if (plane_start[k + 1] < plane_start[k]) return fail(LUDWIG_ERR_INVALID, "flux planes: plane_start decreases at plane %d", k);
+        if (plane_axis[k] < 0 || plane_axis[k] > 2) return fail(LUDWIG_ERR_INVALID, "flux planes: plane %d: normal axis %d not in 0..2", k, plane_axis[k]);
+    }
+    if (n_points > 0 && (!level_index || !blocks || !cells || !weights || !valid)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if ((int64_t)capacity * n_planes * n_levels * (int64_t)sizeof(FluxRecord) > ((int64_t)1 << 34))
+        return fail(LUDWIG_ERR_INVALID, "flux planes: ring of %d x %d x %d records too large", capacity, n_planes, n_levels);
+    // everything is checked before anything is allocated
+    const LudwigLevel *first = nullptr;
+    for (int64_t p = 0; p < n_points; ++p) {
+        if (!valid[p]) continue;
+        const int r = check_stencil_point("flux point", "flux planes", (int32_t)p, levels, n_levels, level_index, blocks, cells, weights, first);
+        if (r) return r;
+    }
+    if (first)
+        if (const int r = check_one_device("flux planes", levels, n_levels, first)) return r;
+    LudwigFluxPlanes *P = new (std::nothrow) LudwigFluxPlanes;
+    if (!P) return fail(LUDWIG_ERR_ALLOC, "flux planes: out of host memory");
+    P->n_levels = n_levels;
+    P->n_planes = n_planes;
+    P->capacity = capacity;
+    P->levels.assign(levels, levels + n_levels);
+    P->per.resize(n_levels);
+    P->has_list.assign((size_t)n_planes * n_levels, 0);
+    if (!first) {                                          // no valid point: nothing on the device, records of zeros
+        *out = P;
+        return LUDWIG_OK;
+    }
+    P->device = first->device;
+    int r = set_device(P->device);
+    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
+        std::vector<int32_t> hc;
+        std::vector<float> hw;
+        std::vector<std::vector<FluxChunk>> stages(1);
+        const LudwigLevel *L = levels[li];
+        int32_t slab = 0;                                  // records so far in the level's slab
+        for (int32_t k = 0; k < n_planes; ++k) {
+            const int32_t start = (int32_t)(hc.size() / 8);
+            for (int64_t p = plane_start[k]; p < plane_start[k + 1]; ++p) {
+                if (!valid[p] || level_index[p] != li) continue;
+                for (int c = 0; c < 8; ++c) hc.push_back(internal_cell(L, blocks[8 * p + c], cells[8 * p + c]));
+                for (int a = 0; a < 3; ++a) hw.push_back(weights[3 * p + a]);
+            }
+            int32_t n = (int32_t)(hc.size() / 8) - start;
+            if (n == 0) continue;
+            P->has_list[(size_t)k * n_levels + li] = 1;
+            const int32_t final_dst = ~(k * n_levels + li);
+            // the list's stages: n elements from `from` (points, then slab records) -> ceil(n / 512) records
+            int32_t from = start;
+            for (size_t s = 0;; ++s) {
+                if (stages.size() <= s) stages.emplace_back();
+                const int32_t m = (n + CELLS - 1) / CELLS;
+                for (int32_t c = 0; c < m; ++c) stages[s].push_back({from, n, c, m == 1 ? final_dst : slab + c, plane_axis[k], 0});
+                if (m == 1) break;
+                from = slab;
+                slab += m;
+                n = m;
+            }
+        }
+        LudwigFluxPlanes::PerLevel &q = P->per[li];
+        q.n = (int)(hc.size() / 8);
+        if (q.n == 0) continue;
+        std::vector<FluxChunk> table;
+        for (const std::vector<FluxChunk> &st : stages) {
+            q.stage_groups.push_back((int)st.size());
+            table.insert(table.end(), st.begin(), st.end());
+        }
+        hipError_t e = hipSuccess;
+        upload_table(e, hc, q.cell);
+        upload_table(e, hw, q.w);
+        upload_table(e, table, q.table);
+        if (e == hipSuccess && slab > 0) e = hipMalloc((void **)&q.slab, (size_t)slab * sizeof(FluxRecord));
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "flux planes: level %d tables: %s", li, hipGetErrorString(e));
+        // a sample reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now on
+        if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(levels[li], 1);
+    }
+    if (r == LUDWIG_OK) {
+        const hipError_t e = hipMalloc((void **)&P->ring, (size_t)capacity * n_planes * n_levels * sizeof(FluxRecord));
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "flux planes: ring of %d records: %s", capacity, hipGetErrorString(e));
+    }
+    if (r != LUDWIG_OK) {
+        ludwig_flux_planes_destroy(P);
+        return r;
+    }
+    *out = P;
+    return LUDWIG_OK;
+}
+
+int ludwig_flux_planes_sample(LudwigFluxPlanes *P, int64_t t_coarse)
+{
+    if (!P) return fail(LUDWIG_ERR_INVALID, "null flux plane set");
+    if (t_coarse < 0) return fail(LUDWIG_ERR_INVALID, "flux planes: t_coarse %lld < 0", (long long)t_coarse);
+    if ((int)P->slot_step.size() >= P->capacity)
+        return fail(LUDWIG_ERR_STATE, "flux planes: ring full (%d records): download first", P->capacity);
+    if (P->ring) LW_HIP(hipSetDevice(P->device));
+    const int slot = flux_planes_open_slot(P, t_coarse);
+    for (int li = 0; li < P->n_levels; ++li) {
+        // the level's last sub-step of coarse step t_coarse
+        const int r = flux_planes_launch(P, li, slot, ((t_coarse + 1) << li) - 1);
+        if (r) return r;
+    }
+    return LUDWIG_OK;
+}
+
+int ludwig_flux_planes_download(LudwigFluxPlanes *P, double *sums, int64_t *counts, int64_t *steps, int32_t max_samples, int32_t *n_samples)
+{
+    if (!P || !n_samples || max_samples < 0 || (max_samples > 0 && (!steps || (P->n_planes > 0 && (!sums || !counts)))))
+        return fail(LUDWIG_ERR_INVALID, "null argument");
+    const int n = (int)P->slot_step.size();
+    if (n > max_samples) return fail(LUDWIG_ERR_INVALID, "flux planes: %d records waiting, room for %d", n, max_samples);
+    *n_samples = n;
+    if (n == 0) return LUDWIG_OK;
+    const size_t per_slot = (size_t)P->n_planes * P->n_levels;
+    std::vector<FluxRecord> rec(n * per_slot);
+    if (P->ring && per_slot > 0) {
+        LW_HIP(hipSetDevice(P->device));
+        for (int li = 0; li < P->n_levels; ++li)
+            if (P->per[li].n > 0) LW_HIP(hipStreamSynchronize(P->levels[li]->stream));
+        LW_HIP(hipMemcpy(rec.data(), P->ring, rec.size() * sizeof(FluxRecord), hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < P->n_planes; ++k) {
+            // the levels that hold points of the plane, coarsest first, added left to right; none: +0.0 and 0
+            double s[FLUX_ROWS] = {};
+            int64_t count = 0;
+            bool any = false;
+            for (int li = 0; li < P->n_levels; ++li) {
+                if (!P->has_list[(size_t)k * P->n_levels + li]) continue;
+                const FluxRecord &q = rec[i * per_slot + (size_t)k * P->n_levels + li];
+                for (int j = 0; j < FLUX_ROWS; ++j) s[j] = any ? s[j] + q.s[j] : q.s[j];
+                count += q.count;
+                any = true;
+            }
+            for (int j = 0; j < FLUX_ROWS; ++j) sums[((size_t)i * P->n_planes + k) * FLUX_ROWS + j] = s[j];
+            counts[(size_t)i * P->n_planes + k] = count;
+        }
+        steps[i] = P->slot_step[i];
+    }
+    P->slot_step.clear();
+    return LUDWIG_OK;
+}
+
 // ---- slices (ludwig_slices_*; no reference counterpart) ----
 // Per level: its points in the order of their base cells (lanes of one wave read neighbouring cells), each with its base cell
 // (internal block * 512 + cell), weights, replaced-corner mask and place in the set. One device result [n_rows][n_points], zero
@@ -3478,17 +3701,17 @@ static int check_ring_room(const char *what, const char *items, size_t used, int
 }
 
 // Every refusal of a batch beyond its levels', before anything is stepped: the list itself, then each set in the fixed order probes,
-// surface, tracers, forces. Fills `obs` from the entries with a set.
+// surface, tracers, forces, fluxes. Fills `obs` from the entries with a set.
 static int check_batch_observers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                  const LudwigBatchObserver *observers, int32_t n_observers, BatchObservers *obs)
 {
     if (n_observers < 0) return fail(LUDWIG_ERR_INVALID, "batch: %d observer entries", n_observers);
     if (n_observers > 0 && !observers) return fail(LUDWIG_ERR_INVALID, "batch: null observer list of %d entries", n_observers);
-    const LudwigBatchObserver *of_kind[LUDWIG_OBSERVE_TRACERS + 1] = {};
+    const LudwigBatchObserver *of_kind[LUDWIG_OBSERVE_FLUXES + 1] = {};
     for (int i = 0; i < n_observers; ++i) {
         const LudwigBatchObserver &e = observers[i];
         if (!e.set) continue;
-        if (e.kind < 0 || e.kind > LUDWIG_OBSERVE_TRACERS) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d of unknown kind %d", i, e.kind);
+        if (e.kind < 0 || e.kind > LUDWIG_OBSERVE_FLUXES) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d of unknown kind %d", i, e.kind);
         if (of_kind[e.kind]) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d is the second of kind %d", i, e.kind);
         of_kind[e.kind] = &e;
     }
@@ -3518,6 +3741,13 @@ static int check_batch_observers(LudwigLevel *const *levels, int32_t n_levels, i
         if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "force series: interval %d < 1", e->interval);
         if ((r = check_level_in_batch("force series", F->level, levels, n_levels))) return r;
         if ((r = check_ring_room("force series", "records", F->slot_step.size(), F->capacity, obs->forces, t_start, batch_size))) return r;
+    }
+    if (const LudwigBatchObserver *e = of_kind[LUDWIG_OBSERVE_FLUXES]) {
+        LudwigFluxPlanes *P = static_cast<LudwigFluxPlanes *>(e->set);
+        obs->fluxes = {{e->start_step, e->interval}, P};
+        if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "flux planes: interval %d < 1", e->interval);
+        if ((r = check_made_over("flux planes", P->levels, levels, n_levels))) return r;
+        if ((r = check_ring_room("flux planes", "records", P->slot_step.size(), P->capacity, obs->fluxes, t_start, batch_size))) return r;
     }
     return LUDWIG_OK;
 }
@@ -3623,6 +3853,7 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         if (obs.probes.set && obs.probes.due(t)) ph.slot = probes_open_slot(obs.probes.set, t);
         ph.surface = obs.surface.set && obs.surface.due(t);
         ph.forces = obs.forces.set && obs.forces.due(t);
+        if (obs.fluxes.set && obs.fluxes.due(t)) ph.flux_slot = flux_planes_open_slot(obs.fluxes.set, t);
         rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
         if (rc == LUDWIG_OK && obs.tracers.set && obs.tracers.due(t)) rc = batch_tracers_advance(levels, n_levels, obs.tracers.set, t, concurrent);
     }

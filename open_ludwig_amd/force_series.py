@@ -101,14 +101,17 @@ def host_record(mesh, plan: SurfacePlan, rho: np.ndarray, vel: np.ndarray, tau, 
 
 class Series:
     """the host copy of a force series: appended after every drain into buffers that double when full, so a run's appends cost O(1)
-    each; take_new() hands out what came since the last take_new() (what run_case writes after a batch), arrays() the whole history"""
+    each; take_new() hands out what came since the last take_new() (what run_case writes after a batch), arrays() the whole history.
+    Per record Float64 sums of shape sums_shape and Int64 counts of shape count_shape (the force series: 9 sums, one coverage count;
+    flux_planes.Series: per plane)"""
 
-    def __init__(self):
+    def __init__(self, sums_shape: Tuple[int, ...] = (9,), count_shape: Tuple[int, ...] = ()):
         self._n = 0
         self._taken = 0
+        self._sums_shape, self._count_shape = tuple(sums_shape), tuple(count_shape)
         self._steps = np.empty(64, np.int64)
-        self._sums = np.empty((64, 9), np.float64)
-        self._cov = np.empty(64, np.int64)
+        self._sums = np.empty((64,) + self._sums_shape, np.float64)
+        self._cov = np.empty((64,) + self._count_shape, np.int64)
 
     def append(self, steps: np.ndarray, sums: np.ndarray, covered: np.ndarray) -> None:
         k = len(steps)
@@ -120,8 +123,8 @@ class Series:
                                                   for a in (self._steps, self._sums, self._cov))
         sl = slice(self._n, self._n + k)
         self._steps[sl] = steps
-        self._sums[sl] = np.asarray(sums, dtype=np.float64).reshape(-1, 9)
-        self._cov[sl] = covered
+        self._sums[sl] = np.asarray(sums, dtype=np.float64).reshape((-1,) + self._sums_shape)
+        self._cov[sl] = np.asarray(covered).reshape((-1,) + self._count_shape)
         self._n += k
 
     def _range(self, lo: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

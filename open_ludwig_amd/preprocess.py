@@ -154,6 +154,14 @@ class CaseConfig:
     tracers_output_interval: int = 100
     tracers_max_particles: int = 4_000_000
     tracers_seeds: Tuple["StreamlineSeeds", ...] = ()
+    # flux planes, advanced.flux_planes (no reference counterpart): mass, momentum, pressure and kinetic-energy flux through planes and
+    # boxes, reduced on the device inside every batch at the coarse steps start_step + k interval and written to fluxes.csv and
+    # flux_boxes.csv (flux_planes.py); flux_planes_planes holds the planes and then every box's six faces
+    flux_planes_enabled: bool = False
+    flux_planes_start_step: int = 1
+    flux_planes_interval: int = 1
+    flux_planes_planes: Tuple["FluxPlane", ...] = ()
+    flux_planes_boxes: Tuple["FluxBox", ...] = ()
     # flow monitor, advanced.flow_monitor (no reference counterpart; its advanced.diagnostics.stability_check is read by nobody, there or
     # here): a health record of every level at every diagnostics step, written to flow_monitor.csv (monitor.py)
     flow_monitor_enabled: bool = False
@@ -210,6 +218,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     isosurfaces = _isosurfaces_config(g("advanced", "isosurfaces", default=None))
     streamlines = _streamlines_config(g("advanced", "streamlines", default=None))
     tracers = _tracers_config(g("advanced", "tracers", default=None), int(g("basic", "simulation", "steps", required=True)))
+    flux_planes = _flux_planes_config(g("advanced", "flux_planes", default=None))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
     wall_diag = _wall_diagnostics_config(g("advanced", "wall_diagnostics", default=None))
     return CaseConfig(
@@ -269,6 +278,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **isosurfaces,
         **streamlines,
         **tracers,
+        **flux_planes,
         **flow_monitor,
         **wall_diag,
         y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
@@ -444,6 +454,124 @@ def _slices_config(sc) -> dict:
                 raise ValueError(f"{where}: {n} points, more than {SLICE_MAX_POINTS} per plane")
         planes.append(SlicePlane(name, "xyz".index(normal), position, bounds, spacing, tuple(f for f in SLICE_FIELDS if f in fields)))
     return dict(slices_enabled=True, slices_start_step=start, slices_interval=interval, slices_planes=tuple(planes))
+
+
+@dataclass(frozen=True)
+class FluxPlane:
+    """one plane of advanced.flux_planes.planes, or one face of a box (semantics: flux_planes.py)"""
+    name: str
+    normal: int                                             # axis: 0 = x, 1 = y, 2 = z
+    position: float                                         # STL frame after stl_scale
+    bounds: Optional[Tuple[Tuple[float, float], Tuple[float, float]]] = None   # the two in-plane axes in x, y, z order; None: the domain
+    spacing: Optional[float] = None                         # None: dx of the finest level
+    direction: int = 1                                      # +1: flux along the +axis counts positive; -1: along the -axis
+    box: Optional[str] = None                               # the box this plane is a face of
+
+
+@dataclass(frozen=True)
+class FluxBox:
+    """one box of advanced.flux_planes.boxes: its faces are the FluxPlanes <name>_xmin .. <name>_zmax with outward directions"""
+    name: str
+    bounds: Tuple[Tuple[float, float], Tuple[float, float], Tuple[float, float]]
+    spacing: Optional[float] = None
+
+
+def _file_stem(where: str, name: str, seen: set) -> None:
+    if not name or not all(ch.isalnum() or ch in "_-." for ch in name) or name.startswith("."):
+        raise ValueError(f"{where}.name {name!r} is not a plain file-name stem")
+    if name in seen:
+        raise ValueError(f"{where}.name {name!r} is not unique")
+    seen.add(name)
+
+
+def _flux_spacing(where: str, spacing) -> Optional[float]:
+    if spacing is None:
+        return None
+    spacing = float(spacing)
+    if not (math.isfinite(spacing) and spacing > 0):
+        raise ValueError(f"{where}: spacing {spacing} must be > 0")
+    return spacing
+
+
+def _flux_bounds(where: str, bounds, n: int, shape: str):
+    ok = isinstance(bounds, (list, tuple)) and len(bounds) == n and all(isinstance(b, (list, tuple)) and len(b) == 2 for b in bounds)
+    if not ok:
+        raise ValueError(f"{where}: bounds must be {shape}, got {bounds!r}")
+    bounds = tuple((float(b[0]), float(b[1])) for b in bounds)
+    for lo, hi in bounds:
+        if not (math.isfinite(lo) and math.isfinite(hi)) or not lo < hi:
+            raise ValueError(f"{where}: bounds {list(map(list, bounds))} must be finite with lower < upper")
+    return bounds
+
+
+def flux_box_faces(box: FluxBox) -> Tuple[FluxPlane, ...]:
+    """the six faces of a box, xmin, xmax, ymin, ymax, zmin, zmax, each with the outward direction"""
+    faces = []
+    for a in range(3):
+        inplane = tuple(box.bounds[b] for b in range(3) if b != a)
+        for side, d in ((0, -1), (1, 1)):
+            faces.append(FluxPlane(f"{box.name}_{'xyz'[a]}{('min', 'max')[side]}", a, box.bounds[a][side], inplane, box.spacing, d, box.name))
+    return tuple(faces)
+
+
+def _flux_planes_config(fc) -> dict:
+    """advanced.flux_planes: {enabled: false, start_step: 1, interval: 1, planes: [{name, normal, position, bounds?, spacing?,
+    direction?}], boxes: [{name, bounds: [[x0, x1], [y0, y1], [z0, z1]], spacing?}]} -> CaseConfig fields. Absent or disabled: the
+    defaults. What needs the domain (a plane outside it, the default bounds' point count) is checked when the plane is planned
+    (flux_planes.flux_grid)."""
+    if fc is None:
+        return {}
+    if not isinstance(fc, dict):
+        raise ValueError("advanced.flux_planes must be a mapping")
+    if not bool(fc.get("enabled", False)):
+        return {}
+    start, interval = int(fc.get("start_step", 1)), int(fc.get("interval", 1))
+    if interval < 1:
+        raise ValueError(f"advanced.flux_planes.interval must be >= 1, got {interval}")
+    if start < 1:
+        raise ValueError(f"advanced.flux_planes.start_step must be >= 1, got {start}")
+    raw_planes, raw_boxes = fc.get("planes") or [], fc.get("boxes") or []
+    if not isinstance(raw_planes, (list, tuple)) or not isinstance(raw_boxes, (list, tuple)) or not (raw_planes or raw_boxes):
+        raise ValueError("advanced.flux_planes.enabled needs at least one plane or box")
+    planes, boxes, seen = [], [], set()
+    for i, pc in enumerate(raw_planes):
+        where = f"advanced.flux_planes.planes[{i}]"
+        if not isinstance(pc, dict):
+            raise ValueError(f"{where} must be a mapping")
+        name = str(pc.get("name", ""))
+        _file_stem(where, name, seen)
+        where = f"advanced.flux_planes plane {name!r}"
+        normal = str(pc.get("normal", "")).lower()
+        if normal not in ("x", "y", "z"):
+            raise ValueError(f"{where}: normal {pc.get('normal')!r} is not x, y or z")
+        if "position" not in pc:
+            raise ValueError(f"{where}: position is required")
+        position = float(pc["position"])
+        if not math.isfinite(position):
+            raise ValueError(f"{where}: position {position} is not finite")
+        bounds = pc.get("bounds")
+        if bounds is not None:
+            bounds = _flux_bounds(where, bounds, 2, "[[a0, a1], [b0, b1]]")
+        spacing = _flux_spacing(where, pc.get("spacing"))
+        direction = pc.get("direction", 1)
+        if isinstance(direction, bool) or direction not in (1, -1):
+            raise ValueError(f"{where}: direction {direction!r} is not 1 or -1")
+        planes.append(FluxPlane(name, "xyz".index(normal), position, bounds, spacing, int(direction)))
+    for i, bc in enumerate(raw_boxes):
+        where = f"advanced.flux_planes.boxes[{i}]"
+        if not isinstance(bc, dict):
+            raise ValueError(f"{where} must be a mapping")
+        name = str(bc.get("name", ""))
+        _file_stem(where, name, seen)
+        where = f"advanced.flux_planes box {name!r}"
+        bounds = _flux_bounds(where, bc.get("bounds"), 3, "[[x0, x1], [y0, y1], [z0, z1]]")
+        boxes.append(FluxBox(name, bounds, _flux_spacing(where, bc.get("spacing"))))
+    for b in boxes:
+        for f in flux_box_faces(b):
+            _file_stem(f"advanced.flux_planes box {b.name!r} face", f.name, seen)
+            planes.append(f)
+    return dict(flux_planes_enabled=True, flux_planes_start_step=start, flux_planes_interval=interval, flux_planes_planes=tuple(planes),
+                flux_planes_boxes=tuple(boxes))
 
 
 ISOSURFACE_FIELDS = ("density", "velocity_magnitude", "q_criterion", "vorticity_magnitude")      # isosurface.FIELDS
