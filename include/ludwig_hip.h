@@ -223,13 +223,13 @@ int  ludwig_execute_timestep_batch(LudwigLevel *const *levels, int32_t n_levels,
                                    float u_curr, const LudwigStepFlags *flags);
 
 /* What a batch observes while it steps: a list of tagged entries, each a set (made by ludwig_probes_create, ludwig_surface_stats_create,
- * ludwig_force_series_create, ludwig_tracers_create or ludwig_flux_planes_create, below) observed at coarse steps start_step + k interval,
- * k >= 0. */
+ * ludwig_force_series_create, ludwig_tracers_create, ludwig_flux_planes_create or ludwig_modes_create, below) observed at coarse steps
+ * start_step + k interval, k >= 0. */
 enum { LUDWIG_OBSERVE_PROBES = 0, LUDWIG_OBSERVE_SURFACE = 1, LUDWIG_OBSERVE_FORCES = 2, LUDWIG_OBSERVE_TRACERS = 3,
-       LUDWIG_OBSERVE_FLUXES = 4 };
+       LUDWIG_OBSERVE_FLUXES = 4, LUDWIG_OBSERVE_MODES = 5 };
 typedef struct LudwigBatchObserver {
     int32_t kind;        /* LUDWIG_OBSERVE_* */
-    void   *set;         /* LudwigProbes* / LudwigSurfaceStats* / LudwigForceSeries* / LudwigTracers* / LudwigFluxPlanes*; NULL: ignored */
+    void   *set;         /* LudwigProbes* / LudwigSurfaceStats* / LudwigForceSeries* / LudwigTracers* / LudwigFluxPlanes* / LudwigModes*; NULL: ignored */
     int64_t start_step;  /* observed at coarse steps start_step + k interval, k >= 0 */
     int32_t interval;
 } LudwigBatchObserver;
@@ -246,7 +246,11 @@ typedef struct LudwigBatchObserver {
  * ring. Flux planes (checked last): the ring slot is opened when an observed coarse step begins, every level that holds points launches
  * its reduction on its own stream right after its last sub-step of that step - no stream join, no host synchronisation;
  * LUDWIG_ERR_INVALID for interval < 1 or a set not made over exactly these levels, LUDWIG_ERR_STATE if the batch's records would
- * overflow the free ring. */
+ * overflow the free ring. Modes (checked after the flux planes): at an observed coarse step t the table row is ((t - start_step) /
+ * interval) % n_rows; every level with owned blocks launches its sample on its own stream right after its last sub-step of that step -
+ * no stream join, no event, no host synchronisation; LUDWIG_ERR_INVALID for interval < 1 or a set not made over exactly these levels,
+ * LUDWIG_ERR_STATE unless the batch's observed steps give exactly the rows count, count + 1, ... of every level (count: its samples
+ * since the last reset) and all of them are below n_rows: a batch never runs past the end of a window, the caller cuts there. */
 int  ludwig_execute_timestep_batch_observed(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                             float u_curr, const LudwigStepFlags *flags, const LudwigBatchObserver *observers,
                                             int32_t n_observers);
@@ -547,6 +551,36 @@ int  ludwig_flux_planes_sample(LudwigFluxPlanes *set, int64_t t_coarse);
  * LUDWIG_ERR_INVALID when n > max_samples. */
 int  ludwig_flux_planes_download(LudwigFluxPlanes *set, double *sums, int64_t *counts, int64_t *steps, int32_t max_samples,
                                  int32_t *n_samples);
+
+/* ---- Fourier modes: weighted running sums of rho and u per cell, for an on-the-fly DFT (no reference counterpart) ----
+ * The library knows only a weight table W[n_rows][n_columns] of Float64 (row-major: W[r][m] = weights[r n_columns + m]), copied to the
+ * device once; what the columns mean - a window, cosines and sines of chosen frequencies - is the caller's (open_ludwig_amd/modes.py).
+ * A set is made over a level array, all of it. Per level with owned blocks it holds 4 n_columns Float64 sums per cell (32 n_columns B):
+ * rho, ux, uy, uz per column. One sample of a level with table row r does, per cell of every owned block and every column m,
+ *     S[m][q] = S[m][q] + W[r][m] * double(v_q)
+ * - one float64 multiply, then one float64 add, never fused - with rho as ludwig_level_download(LUDWIG_RHO) would return it and the
+ * velocity buffer sub-step t_sub wrote (vel_temp if t_sub is even, vel if odd): the conventions of ludwig_level_stats_accumulate.
+ * Obstacle cells are accumulated like any other, non-finite values propagate by IEEE rules, so acc = acc + W[r][m] * double(v) on the
+ * host reproduces every bit. Creating the set makes every level store rho after every step (see ludwig_level_set_rho_store). A level
+ * created with n_owned < 0, or without owned blocks, is accepted, counts its samples and does nothing. */
+typedef struct LudwigModes LudwigModes;   /* opaque */
+/* 1 <= n_columns <= 33, 1 <= n_rows <= 65 536, no null level, one device: LUDWIG_ERR_INVALID otherwise. Everything is checked before
+ * anything is allocated, and the set is made for every level or not at all; a failed allocation names the bytes asked for. The sums
+ * start at zero. */
+int  ludwig_modes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_columns, int32_t n_rows, const double *weights,
+                         LudwigModes **out);
+/* frees the set, not the levels */
+void ludwig_modes_destroy(LudwigModes *set);
+/* zero the sums (queued on each level's stream) and every level's sample count */
+int  ludwig_modes_reset(LudwigModes *set);
+/* one sample of level level_index (0-based) after its sub-step t_sub with table row `row`, queued on the level's stream, no host
+ * synchronisation. Rows come in order with none skipped: row must equal the level's sample count since the last reset
+ * (LUDWIG_ERR_STATE, naming both); row < 0 or row >= n_rows: LUDWIG_ERR_INVALID. */
+int  ludwig_modes_accumulate(LudwigModes *set, int32_t level_index, int64_t t_sub, int32_t row);
+/* the four sums of one column in the reference layout [8,8,8,n_blocks,4] Float64 (rho, ux, uy, uz), reference block order, ghost
+ * blocks zero; bytes = 4096 n_blocks 4; *n_samples (may be NULL) = the level's samples since the last reset. Synchronizes the level's
+ * stream. */
+int  ludwig_modes_download(LudwigModes *set, int32_t level_index, int32_t column, double *host, size_t bytes, int32_t *n_samples);
 
 /* ---- slices: planar grids of points sampled after a coarse step (no reference counterpart) ----
  * A slice set is made over a level array. Point p with valid[p] != 0 lives on level level_index[p] (0-based) and has the probes'

@@ -46,6 +46,7 @@ struct BatchSamplers           # LudwigBatchSamplers
 end
 
 const OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS, OBSERVE_FLUXES = Int32.(0:4)   # LUDWIG_OBSERVE_*
+const OBSERVE_MODES = Int32(5)
 struct BatchObserver           # LudwigBatchObserver
     kind::Int32; set::Ptr{Cvoid}; start_step::Int64; interval::Int32
 end
@@ -366,6 +367,33 @@ function flux_planes_download!(sums::Array{Float64,3}, counts::Matrix{Int64}, st
     return Int(n[])
 end
 
+# Fourier modes (no reference counterpart): per cell and table column the running sums of rho, ux, uy, uz times one row of a weight table
+# per sample; pass the set to a batch as entry(OBSERVE_MODES, set, start_step, interval) - the row of an observed step t is then
+# ((t - start_step) / interval) % n_rows, and a batch must not run past the end of a window
+"""a mode set over `grids` with the weight table `W` (n_columns x n_rows: one table row per Julia column, as the C table is row-major;
+1 <= n_columns <= 33, 1 <= n_rows <= 65536). Free it with `modes_destroy`."""
+function modes_create(grids::Vector{DeviceLevel}, W::Matrix{Float64})
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles W check(ccall((:ludwig_modes_create, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int32(size(W, 1)), Int32(size(W, 2)), W, out))
+    return out[]
+end
+modes_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_modes_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""zero the sums and every level's sample count (queued on the levels' streams)"""
+modes_reset!(s::Ptr{Cvoid}) = check(ccall((:ludwig_modes_reset, LIB), Cint, (Ptr{Cvoid},), s))
+"""between batches: one sample of level `level_index` (0-based) after its sub-step `t_sub` with table row `row` (0-based, in order)"""
+modes_accumulate!(s::Ptr{Cvoid}, level_index::Integer, t_sub::Integer, row::Integer) =
+    check(ccall((:ludwig_modes_accumulate, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Int32), s, Int32(level_index), Int64(t_sub), Int32(row)))
+"""the sums of one column (0-based) of a level into `sums` (8 x 8 x 8 x n_blocks x 4: rho, ux, uy, uz); returns the level's samples"""
+function modes_download!(sums::Array{Float64,5}, s::Ptr{Cvoid}, level_index::Integer, column::Integer)
+    n = Ref{Int32}(0)
+    GC.@preserve sums check(ccall((:ludwig_modes_download, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Csize_t, Ref{Int32}),
+                                  s, Int32(level_index), Int32(column), sums, Csize_t(sizeof(sums)), n))
+    return Int(n[])
+end
+
 # wall diagnostics (no reference counterpart: Y_PLUS_TARGET is read and never used): the wall model's y+, u_tau and modelled shear
 """LudwigWallCensus of include/ludwig_hip.h: counts, the Float32 bits of the least / greatest y+, 194 bins (eight per octave)"""
 struct WallCensus
@@ -572,5 +600,10 @@ execute_timestep_batch!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::In
     execute_timestep_batch!(grids, t_start, batch_size, u_curr, flags,
                             [entries(s); entry(OBSERVE_FORCES, forces, force_start_step, force_interval);
                              entry(OBSERVE_TRACERS, tracers, start_step, interval)])
+
+"""the Fourier modes of `modes` accumulated inside the batch: one OBSERVE_MODES entry"""
+execute_timestep_batch_modes!(grids::Vector{DeviceLevel}, t_start::Int, batch_size::Int, u_curr::Float32, flags::StepFlags,
+                              modes::Ptr{Cvoid}, start_step::Integer, interval::Integer) =
+    execute_timestep_batch!(grids, t_start, batch_size, u_curr, flags, [entry(OBSERVE_MODES, modes, start_step, interval)])
 
 end # module

@@ -37,6 +37,7 @@ PART_ALL, PART_BOUNDARY, PART_INTERIOR = 0, 1, 2
 
 # LUDWIG_OBSERVE_*: the kind of a BatchObserver entry
 OBSERVE_PROBES, OBSERVE_SURFACE, OBSERVE_FORCES, OBSERVE_TRACERS, OBSERVE_FLUXES = range(5)
+OBSERVE_MODES = 5
 
 # every symbol include/ludwig_hip.h declares (tests check the .so exports exactly these)
 EXPORTED_SYMBOLS = [
@@ -70,6 +71,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_force_series_create", "ludwig_force_series_destroy", "ludwig_force_series_sample", "ludwig_force_series_download",
     "ludwig_execute_timestep_batch_loads",
     "ludwig_flux_planes_create", "ludwig_flux_planes_destroy", "ludwig_flux_planes_sample", "ludwig_flux_planes_download",
+    "ludwig_modes_create", "ludwig_modes_destroy", "ludwig_modes_reset", "ludwig_modes_accumulate", "ludwig_modes_download",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -261,6 +263,11 @@ def load() -> C.CDLL:
         "ludwig_flux_planes_destroy": (None, [vp]),
         "ludwig_flux_planes_sample": (C.c_int, [vp, i64]),
         "ludwig_flux_planes_download": (C.c_int, [vp, vp, vp, vp, i32, C.POINTER(C.c_int32)]),
+        "ludwig_modes_create": (C.c_int, [C.POINTER(vp), i32, i32, i32, vp, C.POINTER(vp)]),
+        "ludwig_modes_destroy": (None, [vp]),
+        "ludwig_modes_reset": (C.c_int, [vp]),
+        "ludwig_modes_accumulate": (C.c_int, [vp, i32, i64, i32]),
+        "ludwig_modes_download": (C.c_int, [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_int32)]),
         "ludwig_execute_timestep_batch_tracers": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers),
                                                             vp, i64, i32, vp, i64, i32]),
     }
@@ -303,6 +310,48 @@ class Handle:
             self.close()
         except Exception:
             pass
+
+
+class ModeSet(Handle):
+    """ludwig_modes_*: running sums of rho and u per cell times the rows of a weight table W [n_rows, n_columns] (Float64), over every
+    level of `levels` (DeviceLevel). start_step / interval: the coarse steps a batch samples, and what row_of() counts rows from."""
+    _destroy, _closed = "ludwig_modes_destroy", "mode set closed"
+
+    def __init__(self, levels, W, start_step: int = 1, interval: int = 1):
+        import numpy as np
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2:
+            raise ValueError(f"modes: the weight table must be [n_rows, n_columns], got shape {W.shape}")
+        if int(interval) < 1:
+            raise ValueError(f"modes: interval {interval} < 1")
+        self._lib = load()
+        self.levels = list(levels)
+        self.W = W
+        self.n_rows, self.n_columns = int(W.shape[0]), int(W.shape[1])
+        self.start_step, self.interval = int(start_step), int(interval)
+        arr = (C.c_void_p * len(self.levels))(*[(lv.handle if lv is not None else None) for lv in self.levels])
+        h = C.c_void_p()
+        check(self._lib.ludwig_modes_create(arr, len(self.levels), self.n_columns, self.n_rows, W.ctypes.data, C.byref(h)))
+        self._h = h
+
+    def row_of(self, t_coarse: int) -> int:
+        return ((int(t_coarse) - self.start_step) // self.interval) % self.n_rows
+
+    def reset(self) -> None:
+        check(self._lib.ludwig_modes_reset(self.handle))
+
+    def accumulate(self, level_index: int, t_sub: int, row: int) -> None:
+        """one sample of a level after its sub-step t_sub with table row `row` (queued on the level's stream)"""
+        check(self._lib.ludwig_modes_accumulate(self.handle, int(level_index), int(t_sub), int(row)))
+
+    def download(self, level_index: int, column: int):
+        """(Float64 sums [8,8,8,n_blocks,4] of one column in the reference layout: rho, ux, uy, uz; samples); ghost blocks are 0"""
+        import numpy as np
+        a = np.empty((8, 8, 8, self.levels[level_index].n_blocks, 4), dtype=np.float64, order="F")
+        n = C.c_int32(0)
+        check(self._lib.ludwig_modes_download(self.handle, int(level_index), int(column), a.ctypes.data if a.size else None, a.nbytes,
+                                              C.byref(n)))
+        return a, int(n.value)
 
 
 def device_count() -> int:

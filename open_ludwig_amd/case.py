@@ -20,6 +20,7 @@ from . import flux_planes as flux_mod
 from . import force_series as fseries_mod
 from . import forces as forces_mod
 from . import isosurface as iso_mod
+from . import modes as modes_mod
 from . import monitor as monitor_mod
 from . import probes as probes_mod
 from . import slices as slices_mod
@@ -29,6 +30,7 @@ from . import statistics as stats_mod
 from . import subgrid as subgrid_mod
 from . import surface_stats as surface_mod
 from . import wall_diagnostics as wall_mod
+from . import _lib
 from .blocks import adapt
 from .preprocess import CaseConfig, DomainParameters, setup_multilevel_domain, solver_params
 from .solver_control import execute_timestep_batch, ramp_velocity
@@ -46,9 +48,9 @@ class DiagRow:
 
 
 def _close_observers(st) -> None:
-    """close a stepper's probe, surface, slice, wall-surface, force-series, streamline, tracer and flux-plane sets (each may be None or
-    absent)"""
-    for name in ("probes", "surface", "slices", "wall_surface", "forces", "stream_set", "tracer_set", "fluxes"):
+    """close a stepper's probe, surface, slice, wall-surface, force-series, streamline, tracer, flux-plane and mode sets (each may be
+    None or absent)"""
+    for name in ("probes", "surface", "slices", "wall_surface", "forces", "stream_set", "tracer_set", "fluxes", "modes"):
         obs = getattr(st, name, None)
         if obs is not None:
             obs.close()
@@ -77,10 +79,11 @@ class HipStepper:
         self.tracer_set = None                 # tracers_setup
         self.fluxes = None                     # flux_planes_setup
         self._flux_series = None
+        self.modes = None                      # modes_setup
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.probes is None and self.forces is None and self.fluxes is None:
-            execute_timestep_batch(self.dev, t_start, n, u_curr, params, surface=self.surface, tracers=self.tracer_set)
+            execute_timestep_batch(self.dev, t_start, n, u_curr, params, surface=self.surface, tracers=self.tracer_set, modes=self.modes)
             return
         # sampled inside the C batch, the rings drained after it; a batch with more samples than a ring holds is cut where the first one
         # fills (the same inlet speed: the same steps, the same bits)
@@ -91,7 +94,7 @@ class HipStepper:
                 if ring is not None:
                     seg_end = min(seg_end, fseries_mod.segment_end(t, end, ring.start_step, ring.interval, ring.capacity))
             execute_timestep_batch(self.dev, t, seg_end - t + 1, u_curr, params, probes=P, surface=self.surface, forces=F,
-                                   tracers=self.tracer_set, fluxes=X)
+                                   tracers=self.tracer_set, fluxes=X, modes=self.modes)
             if P is not None:
                 self._series.append(*P.download())
             if F is not None:
@@ -167,6 +170,29 @@ class HipStepper:
         """(coarse steps [n] int64, sums [n, n_planes, 8] Float64, counts [n, n_planes] int64) of the samples drained since the last
         flux_planes_new() (what run_case writes after a batch)"""
         return self._flux_series.take_new()
+
+    # -- Fourier modes (modes.py; no reference counterpart) --
+    def modes_setup(self, W, start_step: int = 1, interval: int = 1) -> None:
+        """one device set over every level with the weight table W [n_samples, n_columns] (modes.weight_table). From now on every batch
+        adds the state after the coarse steps start_step + k interval times row k % n_samples, inside the C call; a batch must end with
+        a window at the latest (run_case cuts there) and the caller resets before the next one."""
+        if self.modes is not None:
+            self.modes.close()
+        self.modes = _lib.ModeSet(self.dev, W, max(int(start_step), 1), interval)
+
+    def modes_reset(self) -> None:
+        self.modes.reset()
+
+    def modes_sample(self, t_coarse: int) -> None:
+        """between batches: add every level's newest state after coarse step t_coarse with the row of that step (queued)"""
+        row = modes_mod.row_of(t_coarse, self.modes.start_step, self.modes.interval, self.modes.n_rows)
+        for lvl in range(len(self.dev)):
+            self.modes.accumulate(lvl, stats_mod.t_sub_after(lvl, t_coarse), row)
+
+    def modes_sums(self, level: int):
+        """(the sums of every table column [n_columns][8,8,8,nb,4] Float64 in the reference layout: rho, ux, uy, uz; samples)"""
+        got = [self.modes.download(level, m) for m in range(self.modes.n_columns)]
+        return [a for a, _ in got], got[0][1]
 
     # -- slices (no reference counterpart) --
     def slices_setup(self, plans, start_step: int = 1, interval: int = 1) -> None:
@@ -363,6 +389,9 @@ class DistributedStepper:
         self.wall_surface = None               # this rank's wall-surface set (None: it holds no copy of the finest level)
         self._forces_cfg = None                # force_series_setup: (mesh, plan, params, start_step, interval, capacity)
         self.forces = None                     # this rank's force-series set (None: it holds no copy of the finest level)
+        self._modes_cfg = None                 # modes_setup: (W, start_step, interval)
+        self.modes = None                      # this rank's mode set over the levels it owns blocks of (None: it owns none)
+        self._modes_levels = []                # those levels' indices
 
     def _level_owner(self, level: int) -> np.ndarray:
         g = self.host[level]
@@ -442,15 +471,19 @@ class DistributedStepper:
             self._wall_surface_create()
         if self._forces_cfg is not None:
             self._forces_create()
+        if self._modes_cfg is not None:
+            self._modes_create()
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.runner is None:
             self._start(params)
         self.runner.params = params
-        P, S, F = self.probes, self.surface, self.forces
+        P, S, F, M = self.probes, self.surface, self.forces, self.modes
         fin = len(self.host) - 1
         for t in range(t_start, t_start + n):
             self.runner.step(t, u_curr)
+            if M is not None and stats_mod.is_sample_step(t, M.start_step, M.interval):
+                self._modes_accumulate(t)      # owned blocks only: no ghost is read, nothing to join
             if S is not None and S.is_sample_step(t):
                 self.runner._join(fin)
                 S.accumulate(stats_mod.t_sub_after(fin, t))
@@ -845,6 +878,52 @@ class DistributedStepper:
         sums = self.stats_sums(level)
         return None if sums is None else stats_mod.finalize(*sums)
 
+    # -- Fourier modes: every rank accumulates the blocks it owns, inside batch() after each coarse step's level steps; the sums are
+    # gathered like the statistics'. No ghost is read, so no halo group changes --
+    def modes_setup(self, W, start_step: int = 1, interval: int = 1) -> None:
+        self._modes_cfg = (np.ascontiguousarray(W, dtype=np.float64), max(int(start_step), 1), int(interval))
+        if self.runner is not None:
+            self._modes_create()
+
+    def _modes_create(self) -> None:
+        if self.modes is not None:
+            self.modes.close()
+            self.modes = None
+        held = self._held()
+        self._modes_levels = [lvl for lvl, _ in held]
+        if held:
+            self.modes = _lib.ModeSet([lv for _, lv in held], *self._modes_cfg)
+
+    def _modes_accumulate(self, t_coarse: int) -> None:
+        M = self.modes
+        row = modes_mod.row_of(t_coarse, M.start_step, M.interval, M.n_rows)
+        for i, lvl in enumerate(self._modes_levels):
+            M.accumulate(i, stats_mod.t_sub_after(lvl, t_coarse), row)
+
+    def modes_reset(self) -> None:
+        if self.modes is not None:
+            self.modes.reset()
+
+    def modes_sample(self, t_coarse: int) -> None:
+        """between batches: every rank adds its owned blocks' newest state after coarse step t_coarse"""
+        if self.modes is not None:
+            self._modes_accumulate(t_coarse)
+
+    def modes_sums(self, level: int):
+        """(the sums of every table column of the GLOBAL level, samples), assembled on rank 0 (None elsewhere); collective"""
+        mine = None
+        if self.modes is not None and level in self._modes_levels:
+            i = self._modes_levels.index(level)
+            got = [self.modes.download(i, m) for m in range(self.modes.n_columns)]
+            mine = self._owned_blocks(self.runner.views[level], [a for a, _ in got]) + (got[0][1],)
+        parts = self._gather(mine)
+        if parts is None:
+            return None
+        out = [np.zeros((8, 8, 8, self.host[level].n_blocks, 4), dtype=np.float64, order="F") for _ in range(self._modes_cfg[0].shape[1])]
+        self._scatter_blocks(parts, out)
+        n = ([0] + [part[2] for part in parts if part is not None])[-1]
+        return out, n
+
     # -- velocity-gradient fields: every rank computes on its owned blocks after batch() (its 'vel' halo ghosts are current for
     # both buffers: each level step exchanges the buffer it wrote, and nothing writes that buffer again before the next such step) --
     def gradient_fields(self, level: int, vel_name: str, scale):
@@ -995,7 +1074,13 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     per plane and sampled step and flux_boxes.csv one per box. A stepper whose flux_planes_setup raises (the distributed one) ends the run
     before the first step.
     With cfg.statistics_subgrid the model's sums are sampled at exactly the flow statistics' sampled steps (same
-    reset) and flow_mean_%06d.vtu gains subgrid.MEAN_ARRAYS after its own arrays. Device only: a stepper without subgrid_fields raises."""
+    reset) and flow_mean_%06d.vtu gains subgrid.MEAN_ARRAYS after its own arrays. Device only: a stepper without subgrid_fields raises.
+    With cfg.fourier_modes_enabled (advanced.fourier_modes), every level's rho and u are accumulated against the weight table of
+    modes.plan_modes at the coarse steps start_step + k interval, inside the batches; window j covers the samples start_step + (j N + n)
+    interval, n < N = samples. Batches are cut at a window's last step only - one cut per window, none for the samples. There the sums
+    are downloaded, flow_modes_%06d.vtu (output.export_modes_mesh) and one flow_modes.csv row per mode and level are written, and with
+    `repeat` the sums are reset for the next window (without it the set is closed). A window unfinished at the end of the run writes
+    nothing and says so in `log`. Device only: a stepper without modes_setup raises."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
@@ -1009,7 +1094,15 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     splans = [slices_mod.plan_slice(spec, grids, params.mesh_offset) for spec in cfg.slices_planes] if slices_on else []
     # a flux plane outside the domain is refused before anything is allocated on a device
     fplans = [flux_mod.plan_flux_plane(spec, grids, params.mesh_offset) for spec in cfg.flux_planes_planes] if cfg.flux_planes_enabled else []
+    modes_on = bool(cfg.fourier_modes_enabled)
+    # a frequency the sampling cannot resolve is refused before anything is allocated on a device
+    mplan = modes_mod.plan_modes(cfg, params, log) if modes_on else None
     st = stepper_factory(grids)
+    if modes_on and not hasattr(st, "modes_setup"):
+        if hasattr(st, "close"):
+            st.close()
+        raise RuntimeError(f"advanced.fourier_modes is enabled, but {type(st).__name__} offers no modes_setup: the Fourier modes are "
+                           "accumulated on the device only")
     iso_on = bool(cfg.isosurfaces_enabled)
     iso_start, iso_interval = cfg.isosurfaces_start_step, cfg.isosurfaces_interval
     if iso_on and hasattr(st, "isosurfaces_setup"):
@@ -1106,6 +1199,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         st.wall_diagnostics_setup(mesh, params, splan if surf_on else None)      # one plan for both surface observers
     if fseries_on:                       # after the surface statistics: one plan for both
         st.force_series_setup(mesh, params, cfg.forces_series_start_step, cfg.forces_series_interval, max(batch, 1))
+    if modes_on:
+        st.modes_setup(mplan.W, mplan.start_step, mplan.interval)
     wall_band = cfg.wall_diagnostics_band
     wall_taken = [None, None]            # the coarse step of the last wall-surface values, and the values
     if writing:
@@ -1126,6 +1221,9 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             if cfg.flux_planes_boxes:
                 with open(os.path.join(out_dir, "flux_boxes.csv"), "w") as io:
                     io.write(flux_mod.BOXES_CSV_COMMENT + "\n" + flux_mod.BOXES_CSV_HEADER + "\n")
+        if modes_on:
+            with open(os.path.join(out_dir, "flow_modes.csv"), "w") as io:
+                io.write(modes_mod.CSV_HEADER + "\n")
         if slices_on:
             slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
         if stream_on:
@@ -1303,6 +1401,37 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
         if writing and box_rows:
             with open(os.path.join(out_dir, "flux_boxes.csv"), "a") as io:
                 io.writelines(l + "\n" for l in box_rows)
+    modes_live = [modes_on]              # False once a window has ended without `repeat`
+
+    def take_modes(step):
+        """the window that ends with coarse step `step`: sums down, files out, then the reset for the next window (collective in a
+        distributed run)"""
+        first = step - (mplan.samples - 1) * mplan.interval
+        finals = {}
+        for lvl in range(len(grids)):
+            got = st.modes_sums(lvl)                                                                  # collective
+            if got is None:
+                continue
+            if got[1] != mplan.samples:
+                raise RuntimeError(f"fourier modes: level {lvl + 1} holds {got[1]} samples at step {step}, the window has {mplan.samples}")
+            finals[lvl] = modes_mod.finalize(np.stack(got[0]), mplan.W)
+        if writing and finals:
+            out_mod.export_modes_mesh(step, grids, finals.__getitem__, (first, step, mplan.samples, mplan.interval), mplan.frequencies_hz,
+                                      out_dir)
+            with open(os.path.join(out_dir, "flow_modes.csv"), "a") as io:
+                for k in range(mplan.n_modes):
+                    for lvl, g in enumerate(grids):
+                        io.write(modes_mod.csv_row(mplan, first, step, k, g.level_id,
+                                                   *modes_mod.level_energy(finals[lvl][1][k], g.obstacle)) + "\n")
+        if log:
+            log(f"fourier modes: window of steps {first}..{step} ({mplan.samples} samples) written at step {step}")
+        if mplan.repeat:
+            st.modes_reset()
+        else:
+            modes_live[0] = False
+            if st.modes is not None:
+                st.modes.close()
+                st.modes = None
     t0 = last_diag = _time.time()
     total_cells = sum(g.n_blocks * 512 for g in grids)
     fr = None
@@ -1317,7 +1446,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if stats_on or surf_host is not None or slices_on or iso_on or stream_on or tracers_on or (flux_on and not dev_fluxes):
+            if (stats_on or surf_host is not None or slices_on or iso_on or stream_on or tracers_on or (flux_on and not dev_fluxes)
+                    or modes_live[0]):
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
@@ -1335,6 +1465,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     cuts.update(tr_cuts)
                 if flux_on and not dev_fluxes:      # on the device a sample cuts nothing
                     cuts.update(stats_mod.sample_steps(t, batch_end, fx_start, fx_interval))
+                mode_cuts = set()
+                if modes_live[0]:        # a sample cuts nothing: only a window's last step does (the first one alone without `repeat`)
+                    ends = modes_mod.window_end_steps(t, batch_end, mplan.start_step, mplan.interval, mplan.samples)
+                    mode_cuts = set(ends if mplan.repeat else ends[:1])
+                    cuts.update(mode_cuts)
                 seg = t
                 for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
@@ -1364,6 +1499,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         take_tracers(s_step)
                     if flux_on and not dev_fluxes and stats_mod.is_sample_step(s_step, fx_start, fx_interval):
                         flux_host.append((s_step, *flux_mod.host_sample(st, fplans, s_step)))
+                    if s_step in mode_cuts:
+                        take_modes(s_step)
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)
@@ -1478,6 +1615,11 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             t = batch_end + 1
         if probes_on:
             flush_probes()
+        if modes_live[0] and log:
+            done = modes_mod.window_end_steps(1, total_steps, mplan.start_step, mplan.interval, mplan.samples)
+            began = (done[-1] + mplan.interval) if done else mplan.start_step
+            if began <= total_steps:
+                log(f"fourier modes: the window that began at step {began} is unfinished at step {total_steps}: nothing written for it")
         if fseries_on and log:
             for name, k in (("Cd", 0), ("Cl", 1), ("Cmy", 2)):
                 m, r = fseries_mod.mean_rms(c[k] for c in fseries_coeffs)

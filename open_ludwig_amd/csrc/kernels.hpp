@@ -1111,6 +1111,37 @@ __global__ __launch_bounds__(256) void k_accumulate_stats(double *__restrict__ s
     }
 }
 
+// ---- Fourier modes (ludwig_modes_*; no reference counterpart) ----
+// sums: [internal block][M][MODE_FIELDS][512] doubles - per weight column m the running sums of rho, ux, uy, uz times w[m]; w: the M
+// weights of this sample, one row of the set's table; rho, vel as k_accumulate_stats reads them, and the same shape: one workgroup per
+// owned block, two x-consecutive cells per lane, float2 loads, double2 read-modify-writes, no LDS, no atomics. w is read with an index
+// every lane shares, so a row sits in scalar registers. Per sum one float64 multiply and then one float64 add (the library is built
+// without contraction): acc = acc + w[m] * double(v) on the host reproduces every bit, non-finite values included.
+constexpr int MODE_FIELDS = 4;
+constexpr int MODE_MAX_COLUMNS = 33;
+__global__ __launch_bounds__(256) void k_accumulate_modes(double *__restrict__ sums, const double *__restrict__ w, int n_columns,
+                                                          const float *__restrict__ rho, const float *__restrict__ vel)
+{
+    const int64_t b = blockIdx.x;
+    const int c = 2 * (int)threadIdx.x;
+    const float2 r = *(const float2 *)(rho + b * CELLS + c);
+    const float *v = vel + b * 3 * CELLS + c;
+    const float2 vx = *(const float2 *)v, vy = *(const float2 *)(v + CELLS), vz = *(const float2 *)(v + 2 * CELLS);
+    const double val[MODE_FIELDS][2] = {{r.x, r.y}, {vx.x, vx.y}, {vy.x, vy.y}, {vz.x, vz.y}};
+    double *s = sums + b * n_columns * (MODE_FIELDS * CELLS) + c;
+    for (int m = 0; m < n_columns; ++m) {
+        const double wm = w[m];
+#pragma unroll
+        for (int q = 0; q < MODE_FIELDS; ++q) {
+            double2 *p = (double2 *)(s + (m * MODE_FIELDS + q) * CELLS);
+            double2 a = *p;
+            a.x = a.x + wm * val[q][0];
+            a.y = a.y + wm * val[q][1];
+            *p = a;
+        }
+    }
+}
+
 // ---- velocity-gradient fields (ludwig_level_gradient_fields_*; the gradient is compute_velocity_gradients, reference
 // src/physics_utils.jl:44-82, the one the WALE model uses) ----
 // out: [internal block][GRAD_COMPONENTS][512] floats - vorticity x, y, z and Q; vel: [block][3][512]; obstacle: [block][512].

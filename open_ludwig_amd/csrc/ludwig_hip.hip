@@ -1995,6 +1995,40 @@ static int flux_planes_launch(LudwigFluxPlanes *P, int li, int slot, int64_t t_s
     return LUDWIG_OK;
 }
 
+// ---- Fourier modes (ludwig_modes_*; no reference counterpart) ----
+// A set over a level array: the weight table [n_rows][n_columns] on the device and, per level with owned blocks, the sums
+// [n_blocks][n_columns][MODE_FIELDS][512] in the internal block order (ghost blocks stay zero). The library knows nothing of
+// frequencies: a sample adds the state times one table row. The host counts each level's samples; rows come in order.
+struct LudwigModes {
+    int device = 0;
+    int n_levels = 0, n_columns = 0, n_rows = 0;
+    std::vector<LudwigLevel *> levels;          // as given
+    double *table = nullptr;
+    std::vector<double *> sums;                 // per level; null: no owned blocks
+    std::vector<size_t> sums_count;             // doubles in each
+    std::vector<int64_t> count;                 // samples of each level since the last reset
+};
+
+// the table row of sampled coarse step t
+static int64_t modes_row_of(int64_t t, int64_t start_step, int32_t interval, int n_rows)
+{
+    return ((t - start_step) / interval) % n_rows;
+}
+
+// one sample of level li with table row `row` of the state sub-step t_sub wrote, on the level's stream (the caller has checked the row)
+static int modes_launch(LudwigModes *S, int li, int64_t t_sub, int64_t row)
+{
+    if (S->sums[li]) {
+        LudwigLevel *L = S->levels[li];
+        LW_ENSURE_RHO(L);                                 // a no-op on these levels, which store it every step since the set was made
+        hipLaunchKernelGGL(k_accumulate_modes, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, S->sums[li],
+                           (const double *)(S->table + (size_t)row * S->n_columns), S->n_columns, (const float *)L->rho, vel_out(L, t_sub));
+        LW_HIP(hipGetLastError());
+    }
+    ++S->count[li];
+    return LUDWIG_OK;
+}
+
 // What a batch observes (ludwig_execute_timestep_batch_observed): one typed slot per LUDWIG_OBSERVE_* kind, a null set is not observed.
 struct ObserverSchedule {
     int64_t start_step = 0;
@@ -2007,15 +2041,17 @@ struct BatchObservers {
     struct : ObserverSchedule { LudwigForceSeries *set = nullptr; } forces;
     struct : ObserverSchedule { LudwigTracers *set = nullptr; } tracers;
     struct : ObserverSchedule { LudwigFluxPlanes *set = nullptr; } fluxes;
+    struct : ObserverSchedule { LudwigModes *set = nullptr; } modes;
 };
 // The observers inside one coarse step: the step being run, the probes' ring slot (-1 = not sampled) and whether the surface set and
-// the force series sample this step, and the flux planes' ring slot (-1 = not sampled).
+// the force series sample this step, the flux planes' ring slot (-1 = not sampled) and the modes' table row (-1 = not sampled).
 struct BatchHook {
     const BatchObservers *obs = nullptr;
     int64_t t = 0;
     int slot = -1;
     bool surface = false, forces = false;
     int flux_slot = -1;
+    int64_t modes_row = -1;
 };
 
 static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-based*/, int64_t t_sub, const LudwigLevel *parent,
@@ -2068,7 +2104,7 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
         LW_HIP(hipEventRecord(L->ev_stepped, L->stream));
         ++L->stepped_gen;
     }
-    if (ph && (ph->slot >= 0 || ph->surface || ph->forces || ph->flux_slot >= 0)) {
+    if (ph && (ph->slot >= 0 || ph->surface || ph->forces || ph->flux_slot >= 0 || ph->modes_row >= 0)) {
         // the level's last sub-step of a sampled coarse step: the probes and the surface sets of this level read its newest rho / vel
         // on its own stream, behind the step (and behind the event its children wait for) and ahead of the next write to either
         const int64_t m = (int64_t)1 << (lvl - 1);
@@ -2078,6 +2114,7 @@ static int recursive_step(LudwigLevel *const *levels, int n_levels, int lvl /*1-
             if (ph->surface && o.surface.set->level == L && (rc = surface_stats_launch(o.surface.set, t_sub))) return rc;
             if (ph->forces && o.forces.set->level == L && (rc = force_series_launch(o.forces.set, t_sub, ph->t))) return rc;
             if (ph->flux_slot >= 0 && (rc = flux_planes_launch(o.fluxes.set, lvl - 1, ph->flux_slot, t_sub))) return rc;
+            if (ph->modes_row >= 0 && (rc = modes_launch(o.modes.set, lvl - 1, t_sub, ph->modes_row))) return rc;
         }
     }
     if (has_children) {
@@ -3124,6 +3161,121 @@ int ludwig_flux_planes_download(LudwigFluxPlanes *P, double *sums, int64_t *coun
     return LUDWIG_OK;
 }
 
+// ---- Fourier modes (ludwig_modes_*) ----
+void ludwig_modes_destroy(LudwigModes *S)
+{
+    if (!S) return;
+    (void)hipSetDevice(S->device);
+    if (S->table) (void)hipFree(S->table);
+    for (double *p : S->sums)
+        if (p) (void)hipFree(p);
+    delete S;
+}
+
+int ludwig_modes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_columns, int32_t n_rows, const double *weights,
+                        LudwigModes **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels || !weights) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > 64) return fail(LUDWIG_ERR_INVALID, "modes: n_levels %d not in 1..64", n_levels);
+    if (n_columns < 1 || n_columns > MODE_MAX_COLUMNS)
+        return fail(LUDWIG_ERR_INVALID, "modes: %d columns not in 1..%d", n_columns, MODE_MAX_COLUMNS);
+    if (n_rows < 1 || n_rows > 65536) return fail(LUDWIG_ERR_INVALID, "modes: %d rows not in 1..65536", n_rows);
+    // everything is checked before anything is allocated
+    for (int li = 0; li < n_levels; ++li) {
+        if (!levels[li]) return fail(LUDWIG_ERR_INVALID, "modes: level %d is null", li + 1);
+        if (levels[li]->device != levels[0]->device) return fail(LUDWIG_ERR_INVALID, "modes: levels on different devices");
+    }
+    LudwigModes *S = new (std::nothrow) LudwigModes;
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "modes: out of host memory");
+    S->device = levels[0]->device;
+    S->n_levels = n_levels;
+    S->n_columns = n_columns;
+    S->n_rows = n_rows;
+    S->levels.assign(levels, levels + n_levels);
+    S->sums.assign((size_t)n_levels, nullptr);
+    S->sums_count.assign((size_t)n_levels, 0);
+    S->count.assign((size_t)n_levels, 0);
+    int r = set_device(S->device);
+    if (r == LUDWIG_OK) {
+        const size_t bytes = (size_t)n_rows * n_columns * sizeof(double);
+        hipError_t e = hipMalloc((void **)&S->table, bytes);
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "modes: hipMalloc(%zu bytes) for the weight table failed: %s", bytes, hipGetErrorString(e));
+        else if ((e = hipMemcpy(S->table, weights, bytes, hipMemcpyHostToDevice)) != hipSuccess)
+            r = fail(LUDWIG_ERR_HIP, "modes: weight table: %s", hipGetErrorString(e));
+    }
+    // all or nothing across levels: a level that fails takes the sums of the levels before it along
+    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
+        LudwigLevel *L = levels[li];
+        if (L->n_owned == 0) continue;                    // no owned blocks: accepted, does nothing
+        const size_t n = (size_t)L->n_blocks * n_columns * MODE_FIELDS * CELLS;
+        r = dev_alloc(L, &S->sums[li], n);
+        if (r != LUDWIG_OK) break;
+        S->sums_count[li] = n;
+        // zeroed on the level's stream: ahead of every sample, which is queued there (or on a batch's level stream, which starts behind it)
+        const hipError_t e = hipMemsetAsync(S->sums[li], 0, n * sizeof(double), L->stream);
+        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "modes: level %d: %s", li + 1, hipGetErrorString(e));
+    }
+    // a sample reads rho after the level's last sub-step of every sampled coarse step: every level stores it every step from now on
+    // (+4 of 216 B per cell where the store was elided), so a batch never replays it
+    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) r = ludwig_level_set_rho_store(levels[li], 1);
+    if (r != LUDWIG_OK) {
+        const std::string msg = g_err;                    // (freeing must not replace the message)
+        for (int li = 0; li < n_levels; ++li)
+            if (S->sums[li]) levels[li]->device_bytes -= (int64_t)(S->sums_count[li] * sizeof(double));
+        ludwig_modes_destroy(S);
+        g_err = msg;
+        return r;
+    }
+    *out = S;
+    return LUDWIG_OK;
+}
+
+int ludwig_modes_reset(LudwigModes *S)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null mode set");
+    LW_HIP(hipSetDevice(S->device));
+    for (int li = 0; li < S->n_levels; ++li) {
+        S->count[li] = 0;
+        if (S->sums[li]) LW_HIP(hipMemsetAsync(S->sums[li], 0, S->sums_count[li] * sizeof(double), S->levels[li]->stream));
+    }
+    return LUDWIG_OK;
+}
+
+int ludwig_modes_accumulate(LudwigModes *S, int32_t level_index, int64_t t_sub, int32_t row)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null mode set");
+    if (level_index < 0 || level_index >= S->n_levels)
+        return fail(LUDWIG_ERR_INVALID, "modes: level index %d not in 0..%d", level_index, S->n_levels - 1);
+    if (t_sub < 0) return fail(LUDWIG_ERR_INVALID, "modes: t_sub %lld < 0", (long long)t_sub);
+    if (row < 0 || row >= S->n_rows) return fail(LUDWIG_ERR_INVALID, "modes: row %d not in 0..%d", row, S->n_rows - 1);
+    if (row != S->count[level_index])
+        return fail(LUDWIG_ERR_STATE, "modes: row %d given, level %d has %lld samples: rows come in order", row, level_index + 1,
+                    (long long)S->count[level_index]);
+    LW_HIP(hipSetDevice(S->device));
+    return modes_launch(S, level_index, t_sub, row);
+}
+
+int ludwig_modes_download(LudwigModes *S, int32_t level_index, int32_t column, double *host, size_t bytes, int32_t *n_samples)
+{
+    if (!S || (!host && bytes > 0)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (level_index < 0 || level_index >= S->n_levels)
+        return fail(LUDWIG_ERR_INVALID, "modes: level index %d not in 0..%d", level_index, S->n_levels - 1);
+    if (column < 0 || column >= S->n_columns) return fail(LUDWIG_ERR_INVALID, "modes: column %d not in 0..%d", column, S->n_columns - 1);
+    const LudwigLevel *L = S->levels[level_index];
+    const size_t want = (size_t)L->sk * sizeof(double) * MODE_FIELDS;
+    if (bytes != want) return fail(LUDWIG_ERR_INVALID, "modes: got %zu bytes, expected %zu", bytes, want);
+    if (n_samples) *n_samples = (int32_t)S->count[level_index];
+    if (want == 0) return LUDWIG_OK;
+    if (!S->sums[level_index]) {                          // no owned blocks: every block is a ghost
+        memset(host, 0, bytes);
+        return LUDWIG_OK;
+    }
+    return download_components(L, (const double *)S->sums[level_index], S->n_columns * MODE_FIELDS, column * MODE_FIELDS, MODE_FIELDS, host,
+                               "modes download");
+}
+
 // ---- slices (ludwig_slices_*; no reference counterpart) ----
 // Per level: its points in the order of their base cells (lanes of one wave read neighbouring cells), each with its base cell
 // (internal block * 512 + cell), weights, replaced-corner mask and place in the set. One device result [n_rows][n_points], zero
@@ -3701,17 +3853,17 @@ static int check_ring_room(const char *what, const char *items, size_t used, int
 }
 
 // Every refusal of a batch beyond its levels', before anything is stepped: the list itself, then each set in the fixed order probes,
-// surface, tracers, forces, fluxes. Fills `obs` from the entries with a set.
+// surface, tracers, forces, fluxes, modes. Fills `obs` from the entries with a set.
 static int check_batch_observers(LudwigLevel *const *levels, int32_t n_levels, int64_t t_start, int32_t batch_size,
                                  const LudwigBatchObserver *observers, int32_t n_observers, BatchObservers *obs)
 {
     if (n_observers < 0) return fail(LUDWIG_ERR_INVALID, "batch: %d observer entries", n_observers);
     if (n_observers > 0 && !observers) return fail(LUDWIG_ERR_INVALID, "batch: null observer list of %d entries", n_observers);
-    const LudwigBatchObserver *of_kind[LUDWIG_OBSERVE_FLUXES + 1] = {};
+    const LudwigBatchObserver *of_kind[LUDWIG_OBSERVE_MODES + 1] = {};
     for (int i = 0; i < n_observers; ++i) {
         const LudwigBatchObserver &e = observers[i];
         if (!e.set) continue;
-        if (e.kind < 0 || e.kind > LUDWIG_OBSERVE_FLUXES) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d of unknown kind %d", i, e.kind);
+        if (e.kind < 0 || e.kind > LUDWIG_OBSERVE_MODES) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d of unknown kind %d", i, e.kind);
         if (of_kind[e.kind]) return fail(LUDWIG_ERR_INVALID, "batch: observer entry %d is the second of kind %d", i, e.kind);
         of_kind[e.kind] = &e;
     }
@@ -3748,6 +3900,28 @@ static int check_batch_observers(LudwigLevel *const *levels, int32_t n_levels, i
         if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "flux planes: interval %d < 1", e->interval);
         if ((r = check_made_over("flux planes", P->levels, levels, n_levels))) return r;
         if ((r = check_ring_room("flux planes", "records", P->slot_step.size(), P->capacity, obs->fluxes, t_start, batch_size))) return r;
+    }
+    if (const LudwigBatchObserver *e = of_kind[LUDWIG_OBSERVE_MODES]) {
+        LudwigModes *S = static_cast<LudwigModes *>(e->set);
+        obs->modes = {{e->start_step, e->interval}, S};
+        if (e->interval < 1) return fail(LUDWIG_ERR_INVALID, "modes: interval %d < 1", e->interval);
+        if ((r = check_made_over("modes", S->levels, levels, n_levels))) return r;
+        // the batch's due steps must give exactly the rows count, count + 1, ... of every level, all of them inside the window
+        const int64_t last = t_start + batch_size - 1;
+        const int64_t k = batch_size > 0 ? samples_in(t_start, last, e->start_step, e->interval) : 0;
+        if (k > 0) {
+            const int64_t lo = std::max(t_start, e->start_step);
+            const int64_t first_due = e->start_step + (lo - e->start_step + e->interval - 1) / e->interval * e->interval;
+            const int64_t row = modes_row_of(first_due, e->start_step, e->interval, S->n_rows);
+            for (int i = 0; i < n_levels; ++i) {
+                if (S->count[i] != row)
+                    return fail(LUDWIG_ERR_STATE, "modes: step %lld is row %lld of the window, level %d has %lld samples", (long long)first_due,
+                                (long long)row, i + 1, (long long)S->count[i]);
+                if (row + k > S->n_rows)
+                    return fail(LUDWIG_ERR_STATE, "modes: %lld samples of this batch from row %lld run past the window of %d rows: cut the "
+                                "batch at the window's last step", (long long)k, (long long)row, S->n_rows);
+            }
+        }
     }
     return LUDWIG_OK;
 }
@@ -3854,6 +4028,7 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         ph.surface = obs.surface.set && obs.surface.due(t);
         ph.forces = obs.forces.set && obs.forces.due(t);
         if (obs.fluxes.set && obs.fluxes.due(t)) ph.flux_slot = flux_planes_open_slot(obs.fluxes.set, t);
+        if (obs.modes.set && obs.modes.due(t)) ph.modes_row = modes_row_of(t, obs.modes.start_step, obs.modes.interval, obs.modes.set->n_rows);
         rc = recursive_step(levels, n_levels, 1, t, nullptr, 0.5f, 0.0f, u_curr, flags, concurrent, &ph);
         if (rc == LUDWIG_OK && obs.tracers.set && obs.tracers.due(t)) rc = batch_tracers_advance(levels, n_levels, obs.tracers.set, t, concurrent);
     }

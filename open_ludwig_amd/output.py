@@ -345,6 +345,37 @@ def export_mean_mesh(t_step: int, grids, stats_of_level, window: Tuple[int, int,
                      cd, compress, field_data=fd)
 
 
+def export_modes_mesh(t_step: int, grids, modes_of_level, window: Tuple[int, int, int, int], frequencies_hz: Sequence[float], out_dir: str,
+                      compress: bool = True) -> Optional[str]:
+    """<out_dir>/flow_modes_%06d.vtu: the Fourier modes of a finished window (no reference counterpart; modes.py) on the mesh of
+    flow_%06d.vtu - same blocks (select_export_blocks), points and cell order. modes_of_level(lvl) -> modes.finalize of that level's
+    sums: (mean [8,8,8,nb,4], amplitude [K,8,8,8,nb,4], phase [K,8,8,8,nb,4]) with the components rho, ux, uy, uz. Cell arrays, Float32:
+    DensityMean, VelocityMean, then per mode k DensityAmp_<k>, VelocityAmp_<k>, DensityPhase_<k>, VelocityPhase_<k>; then Obstacle (UInt8)
+    and Level (Int32). window = (first step, last step, samples, interval), written as Int64 FieldData beside ModesFrequencyHz (Float64)."""
+    valid = select_export_blocks([g.active_block_coords for g in grids])
+    if not valid:
+        return None
+    geo = _flow_geometry(grids, valid)
+    K = len(frequencies_hz)
+    f32 = lambda a: np.asarray(a).astype(np.float32)
+
+    def arrays(lvl):
+        mean, amp, phase = modes_of_level(lvl)
+        out = [f32(mean[..., 0]), f32(mean[..., 1:4])]
+        for k in range(K):
+            out += [f32(amp[k][..., 0]), f32(amp[k][..., 1:4]), f32(phase[k][..., 0]), f32(phase[k][..., 1:4])]
+        return out + [np.asarray(grids[lvl].obstacle).astype(bool)]
+    names = ["DensityMean", "VelocityMean"]
+    for k in range(K):
+        names += [f"DensityAmp_{k}", f"VelocityAmp_{k}", f"DensityPhase_{k}", f"VelocityPhase_{k}"]
+    got = _gather_cells(geo, arrays, (np.float32,) * (2 + 4 * K) + (np.uint8,), (1, 3) * (1 + 2 * K) + (1,))
+    cd = list(zip(names, got[:-1])) + [("Obstacle", got[-1]), ("Level", geo["Level"])]
+    fd = [(name, np.array([v], dtype=np.int64)) for name, v in zip(("ModesFirstStep", "ModesLastStep", "ModesSamples", "ModesInterval"), window)]
+    fd.append(("ModesFrequencyHz", np.asarray(frequencies_hz, dtype=np.float64)))
+    return write_vtu(os.path.join(out_dir, "flow_modes_%06d" % t_step), geo["points"], geo["connectivity"], geo["offsets"], geo["types"],
+                     cd, compress, field_data=fd)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # surface export + CSV (src/forces/io.jl)
 # ----------------------------------------------------------------------------------------------------------------

@@ -162,6 +162,17 @@ class CaseConfig:
     flux_planes_interval: int = 1
     flux_planes_planes: Tuple["FluxPlane", ...] = ()
     flux_planes_boxes: Tuple["FluxBox", ...] = ()
+    # Fourier modes, advanced.fourier_modes (no reference counterpart): per cell the windowed DFT of rho and u at a few frequencies,
+    # accumulated on the device inside every batch at the coarse steps start_step + k interval; every `samples` samples a window ends and
+    # flow_modes_%06d.vtu and flow_modes.csv rows are written (modes.py). frequencies in Hz, strouhal as f L / U of the case
+    fourier_modes_enabled: bool = False
+    fourier_modes_start_step: int = 1
+    fourier_modes_interval: int = 1
+    fourier_modes_samples: int = 256
+    fourier_modes_window: str = "hann"
+    fourier_modes_frequencies: Tuple[float, ...] = ()
+    fourier_modes_strouhal: Tuple[float, ...] = ()
+    fourier_modes_repeat: bool = True
     # flow monitor, advanced.flow_monitor (no reference counterpart; its advanced.diagnostics.stability_check is read by nobody, there or
     # here): a health record of every level at every diagnostics step, written to flow_monitor.csv (monitor.py)
     flow_monitor_enabled: bool = False
@@ -219,6 +230,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     streamlines = _streamlines_config(g("advanced", "streamlines", default=None))
     tracers = _tracers_config(g("advanced", "tracers", default=None), int(g("basic", "simulation", "steps", required=True)))
     flux_planes = _flux_planes_config(g("advanced", "flux_planes", default=None))
+    fourier_modes = _fourier_modes_config(g("advanced", "fourier_modes", default=None))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
     wall_diag = _wall_diagnostics_config(g("advanced", "wall_diagnostics", default=None))
     return CaseConfig(
@@ -279,6 +291,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **streamlines,
         **tracers,
         **flux_planes,
+        **fourier_modes,
         **flow_monitor,
         **wall_diag,
         y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
@@ -572,6 +585,44 @@ def _flux_planes_config(fc) -> dict:
             planes.append(f)
     return dict(flux_planes_enabled=True, flux_planes_start_step=start, flux_planes_interval=interval, flux_planes_planes=tuple(planes),
                 flux_planes_boxes=tuple(boxes))
+
+
+def _fourier_modes_config(mc) -> dict:
+    """advanced.fourier_modes: {enabled: false, start_step: 1, interval: 1, samples: 256, window: hann, frequencies: [Hz, ...],
+    strouhal: [St, ...], repeat: true} -> CaseConfig fields. Absent or disabled: the defaults (nothing is allocated, launched or
+    written). What needs the case's scales - the Strouhal conversion, the Nyquist limit - is checked by modes.plan_modes."""
+    if mc is None:
+        return {}
+    if not isinstance(mc, dict):
+        raise ValueError("advanced.fourier_modes must be a mapping")
+    if not bool(mc.get("enabled", False)):
+        return {}
+    start, interval, samples = int(mc.get("start_step", 1)), int(mc.get("interval", 1)), int(mc.get("samples", 256))
+    if interval < 1:
+        raise ValueError(f"advanced.fourier_modes.interval must be >= 1, got {interval}")
+    if start < 1:
+        raise ValueError(f"advanced.fourier_modes.start_step must be >= 1, got {start}")
+    if not 1 <= samples <= 65536:
+        raise ValueError(f"advanced.fourier_modes.samples must be in 1..65536, got {samples}")
+    window = str(mc.get("window", "hann")).lower()
+    if window not in ("hann", "rectangular"):
+        raise ValueError(f"advanced.fourier_modes.window must be hann or rectangular, got {mc.get('window')!r}")
+    lists = {}
+    for key in ("frequencies", "strouhal"):
+        raw = mc.get(key) or []
+        if not isinstance(raw, (list, tuple)):
+            raise ValueError(f"advanced.fourier_modes.{key} must be a list of numbers")
+        vals = tuple(float(v) for v in raw)
+        for v in vals:
+            if not (math.isfinite(v) and v > 0.0):
+                raise ValueError(f"advanced.fourier_modes.{key}: {v} must be finite and > 0")
+        lists[key] = vals
+    n = len(lists["frequencies"]) + len(lists["strouhal"])
+    if not 1 <= n <= 16:
+        raise ValueError(f"advanced.fourier_modes: frequencies and strouhal must name 1 to 16 modes in all, got {n}")
+    return dict(fourier_modes_enabled=True, fourier_modes_start_step=start, fourier_modes_interval=interval, fourier_modes_samples=samples,
+                fourier_modes_window=window, fourier_modes_frequencies=lists["frequencies"], fourier_modes_strouhal=lists["strouhal"],
+                fourier_modes_repeat=bool(mc.get("repeat", True)))
 
 
 ISOSURFACE_FIELDS = ("density", "velocity_magnitude", "q_criterion", "vorticity_magnitude")      # isosurface.FIELDS

@@ -37,7 +37,8 @@ def recursive_step(grids: Sequence[DeviceLevel], current_lvl: int, t_sub: int, p
 
 
 def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_size: int, u_curr,
-                           params: SolverParams, native: bool = True, probes=None, surface=None, forces=None, tracers=None, fluxes=None) -> None:
+                           params: SolverParams, native: bool = True, probes=None, surface=None, forces=None, tracers=None, fluxes=None,
+                           modes=None) -> None:
     """execute_timestep_batch! (src/solver_control.jl:145-165); t_start is 1-based like the reference's loop.
 
     native=True (default): the whole batch is one C call (ludwig_execute_timestep_batch_observed runs the same recursion inside
@@ -49,14 +50,16 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
     surface: a surface_stats.DeviceSurfaceStats on one of `grids`, accumulated;
     forces: a force_series.DeviceForceSeries on one of `grids`, sampled;
     tracers: a tracers.DeviceTracers made over `grids`, advanced;
-    fluxes: a flux_planes.DeviceFluxPlanes made over `grids`, sampled on every level that holds points."""
+    fluxes: a flux_planes.DeviceFluxPlanes made over `grids`, sampled on every level that holds points;
+    modes: a _lib.ModeSet made over `grids`, accumulated on every level with the table row of the step (a batch must not run past the
+    end of a window: the caller cuts there)."""
     if native:
         import ctypes as C
         from . import _lib
         arr = (C.c_void_p * len(grids))(*[g.handle for g in grids])
         fl = params.to_c()
         sets = ((_lib.OBSERVE_PROBES, probes), (_lib.OBSERVE_SURFACE, surface), (_lib.OBSERVE_FORCES, forces), (_lib.OBSERVE_TRACERS, tracers),
-                (_lib.OBSERVE_FLUXES, fluxes))
+                (_lib.OBSERVE_FLUXES, fluxes), (_lib.OBSERVE_MODES, modes))
         obs = [_lib.BatchObserver(kind, s.handle.value, s.start_step, s.interval) for kind, s in sets if s is not None]
         _lib.check(_lib.load().ludwig_execute_timestep_batch_observed(arr, len(grids), int(t_start), int(batch_size),
                                                                       float(np.float32(u_curr)), C.byref(fl),
@@ -80,6 +83,9 @@ def execute_timestep_batch(grids: Sequence[DeviceLevel], t_start: int, batch_siz
             tracers.advance(t)
         if due(fluxes, t):
             fluxes.sample(t)
+        if due(modes, t):
+            for lvl in range(len(grids)):
+                modes.accumulate(lvl, t_sub_after(lvl, t), modes.row_of(t))
     grids[0].synchronize()                             # KernelAbstractions.synchronize(backend)
 
 
