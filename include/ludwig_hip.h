@@ -289,6 +289,23 @@ int  ludwig_level_rho_min(const LudwigLevel *level, float *rho_min);
  * (LUDWIG_EAGER_RHO=1 in the environment does it for every level), 0 lets the library elide again. Results never depend on it. */
 int  ludwig_level_set_rho_store(LudwigLevel *level, int every_step);
 
+/* ---- record step (no reference counterpart; DESIGN.md section 3.1 "Record step") ----
+ * The post-collision state of a plain cell is a function of 11 floats (rho, u, the six components of the non-equilibrium stress and
+ * 1 - omega). A level every cell of which is plain keeps those between steps instead of f, vel and rho - 44 B written and 44 B read per
+ * cell update against 240 - and turns them back into populations, bit for bit, before anything reads, hands out or writes f, vel or rho.
+ * Results never depend on it; LUDWIG_RECORD_STEP=0 in the environment turns it off.
+ *
+ * ludwig_record_step_rule: the rule, as a function of what a level is (no device needed). 1 = such a level steps by records: every
+ * block is owned (n_owned == n_blocks > 0: one rank, no ghost blocks), the level has no parent, no saved state for temporal
+ * interpolation, no f_post_collision and no wall model, and every block's flags word (LUDWIG internal: bit 0 all 26 neighbours present,
+ * bit 1 obstacle, bit 2 sponge, bit 3 near-wall, bit 4 post-collision readers) is exactly 1. 0 = f path; -1 = bad arguments. On top of it
+ * a step goes by records only as a whole-level launch (LUDWIG_PART_ALL) outside batches that run in-batch observers or several levels,
+ * and never once a writable pointer into the level was handed out, a halo plan was made for it or another level used it as its parent. */
+int  ludwig_record_step_rule(const int32_t *block_flags, int32_t n_blocks, int32_t n_owned, int32_t has_parent,
+                             int32_t has_temporal_storage, int32_t has_post_collision, int32_t wall_model_active);
+/* how many of the level's steps so far went by records (0 on a level the rule excludes) */
+int  ludwig_level_record_steps(const LudwigLevel *level, int64_t *n_steps);
+
 /* ---- time-averaged statistics (no reference counterpart) ----
  * Per cell of the blocks this device owns, in double precision: S_rho += rho, S_u[i] += u_i, S_uu[m] += u_i u_j (m = xx, yy, zz, xy,
  * yz, xz: VTK's symmetric-tensor order). Each sum is a plain sequential addition in sample order, so a float64 replay on the host

@@ -122,6 +122,20 @@ function rho_min(d::DeviceLevel)
     return v[]
 end
 
+# record step (no reference counterpart): plain levels keep 11 collision values per cell between steps instead of f, vel and rho;
+# LUDWIG_RECORD_STEP=0 in the environment turns it off, results never depend on it
+"""how many of the level's steps so far went by records (0 on a level the rule excludes)"""
+function record_steps(d::DeviceLevel)
+    n = Ref{Int64}(0)
+    check(ccall((:ludwig_level_record_steps, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), d.handle, n))
+    return n[]
+end
+"""the rule as a function of what a level is: `flags` = the per-block flags words (1 = all neighbours present and nothing else)"""
+function record_step_rule(flags::Vector{Int32}, n_owned::Integer; has_parent=false, has_temporal=false, has_post=false, wall_model=false)
+    return ccall((:ludwig_record_step_rule, LIB), Cint, (Ptr{Int32}, Int32, Int32, Int32, Int32, Int32, Int32), flags, length(flags), n_owned,
+                 has_parent, has_temporal, has_post, wall_model) == 1
+end
+
 # time-averaged statistics (no reference counterpart): double-precision sums of rho, u_i and u_i u_j over the owned cells
 const STAT_RHO, STAT_VEL, STAT_VEL2 = Int32(0), Int32(1), Int32(2)      # K = 1, 3, 6 (xx, yy, zz, xy, yz, xz)
 """zero the sums (allocates them on the first call)"""

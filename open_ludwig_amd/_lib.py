@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_execute_timestep_batch_loads",
     "ludwig_flux_planes_create", "ludwig_flux_planes_destroy", "ludwig_flux_planes_sample", "ludwig_flux_planes_download",
     "ludwig_modes_create", "ludwig_modes_destroy", "ludwig_modes_reset", "ludwig_modes_accumulate", "ludwig_modes_download",
+    "ludwig_record_step_rule", "ludwig_level_record_steps",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -196,6 +197,8 @@ def load() -> C.CDLL:
         "ludwig_stream_destroy": (C.c_int, [i32, vp]),
         "ludwig_level_field_layout": (C.c_int, [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "ludwig_level_set_rho_store": (C.c_int, [vp, i32]),
+        "ludwig_record_step_rule": (C.c_int, [vp, i32, i32, i32, i32, i32, i32]),
+        "ludwig_level_record_steps": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "ludwig_comm_unique_id": (C.c_int, [vp]),
         "ludwig_comm_create": (C.c_int, [vp, i32, i32, i32, C.POINTER(vp)]),
         "ludwig_comm_destroy": (None, [vp]),

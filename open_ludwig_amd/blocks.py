@@ -315,6 +315,12 @@ class DeviceLevel(_lib.Handle):
         """True: rho is stored by every step like the reference's kernel (src/physics_kernels.jl:243-246); False: elided when unread"""
         _lib.check(self._lib.ludwig_level_set_rho_store(self.handle, 1 if every_step else 0))
 
+    def record_steps(self) -> int:
+        """how many of this level's steps went by 11-float records instead of populations (0 on a level the rule excludes)"""
+        n = C.c_int64()
+        _lib.check(self._lib.ludwig_level_record_steps(self.handle, C.byref(n)))
+        return int(n.value)
+
     def rho_min(self) -> float:
         """rho_min of compute_flow_stats (src/diagnostics.jl:56-94) over the owned, non-obstacle cells, reduced on the device"""
         v = C.c_float()

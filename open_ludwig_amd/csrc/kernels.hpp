@@ -59,6 +59,10 @@ struct SCParams {
     // non-null: copy_to_old!'s rho part fused into this launch - every cell saves its old rho here before storing the new one
     // (whole-level launches of a level without ghost blocks only; ludwig_hip.hip "rho_old in the step")
     float *rho_old_save;
+    // non-null (k_records_from_populations, k_step_records): the step stores each cell's 11-float collision record here and leaves f_out, vel_out
+    // and rho unwritten ("Record step" below)
+    float *rec_out;
+    const float *rec_in;      // k_step_records, k_materialise: the records read
 };
 
 template <int K, int N, class F>
@@ -310,10 +314,108 @@ __device__ __forceinline__ WaleState wale_state(float g11, float g12, float g13,
     return w;
 }
 
+// The regularized post-collision value of population K, reference src/physics_kernels.jl:324-349 without the wall-model term: a
+// function of the cell's 11 collision values and nothing else. ONE source for the three places that form it - finish_cell (which
+// stores it), the record step (which evaluates it at the source cell instead of loading it) and k_materialise - so under
+// -ffp-contract=off all three give the same bits.
+template <int K>
+__device__ __forceinline__ float collide_value(float rho, float ux_eq, float uy_eq, float uz_eq, float Pi_xx, float Pi_yy, float Pi_zz,
+                                               float Pi_xy, float Pi_yz, float Pi_zx, float one_m_omega)
+{
+    constexpr int cx = CX(K), cy = CY(K), cz = CZ(K);
+    constexpr float w_k = WEIGHT(K);
+    constexpr float cx_f = (float)cx, cy_f = (float)cy, cz_f = (float)cz;
+    const float usq_eq = ux_eq * ux_eq + uy_eq * uy_eq + uz_eq * uz_eq;
+    const float cu = cdot<K>(ux_eq, uy_eq, uz_eq);
+    const float feq = rho * w_k * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * usq_eq);
+    constexpr float Q_xx = cx_f * cx_f - CS2_PHYSICS, Q_yy = cy_f * cy_f - CS2_PHYSICS, Q_zz = cz_f * cz_f - CS2_PHYSICS;
+    // Pi_xy*cx*cy + Pi_yz*cy*cz + Pi_zx*cz*cx, left-associated, zero terms dropped
+    float od = 0.0f;
+    bool od_empty = true;
+    acc_signed<cx * cy>(od, od_empty, Pi_xy);
+    acc_signed<cy * cz>(od, od_empty, Pi_yz);
+    acc_signed<cz * cx>(od, od_empty, Pi_zx);
+    float inner = Pi_xx * Q_xx + Pi_yy * Q_yy + Pi_zz * Q_zz;
+    if constexpr (cx * cy != 0 || cy * cz != 0 || cz * cx != 0) inner = inner + 2.0f * od;   // else + 2*0: exact no-op
+    const float f_neq_reg = (w_k * 4.5f) * inner;
+    return feq + one_m_omega * f_neq_reg;
+}
+
+// ---- Record step: storage ----
+// A plain cell's post-collision state is collide_value of 11 floats: rho, u (= u_eq without the wall model), the six Pi and
+// 1 - omega. A level that qualifies (ludwig_hip.hip "record step") keeps those instead of the 27 populations, the velocity and the
+// density: 44 B written and 44 B read per cell update against 240. Layout rec[block][z][11][64], plane-major: a wave's plane is one
+// contiguous 2 816-B piece and all 11 components sit at immediate offsets of one per-lane address.
+constexpr int R_COMP = 11;
+constexpr uint32_t R_PLANE_BYTES = R_COMP * 64 * 4, R_BLOCK_BYTES = 8 * R_PLANE_BYTES;
+enum { R_RHO, R_UX, R_UY, R_UZ, R_PXX, R_PYY, R_PZZ, R_PXY, R_PYZ, R_PZX, R_OMO };
+
+__device__ __forceinline__ const char *record_plane(const float *base, int blk, int z)      // wave-uniform arguments -> scalar
+{
+    return reinterpret_cast<const char *>(base) + (uint64_t)(uint32_t)blk * R_BLOCK_BYTES + (uint32_t)z * R_PLANE_BYTES;
+}
+__device__ __forceinline__ void load_record(float (&r)[R_COMP], const char *plane, uint32_t lane4)
+{
+    const float *q = reinterpret_cast<const float *>(plane + lane4);
+#pragma unroll
+    for (int c = 0; c < R_COMP; ++c) r[c] = q[c * 64];
+}
+// Byte offset of plane z of block blk from the array base, as the step kernel addresses a record whose block differs from lane to lane
+// (the y neighbour for the lanes of a face row): 32 bits while the array is below 4 GiB (190 650 blocks), 64 bits (WIDE) beyond. The
+// narrow form is `SGPR base + one VGPR`; a 64-bit per-lane address costs two registers for each of the 15 records a wave may touch.
+template <bool WIDE>
+using record_off_t = std::conditional_t<WIDE, uint64_t, uint32_t>;
+template <bool WIDE>
+__device__ __forceinline__ record_off_t<WIDE> record_offset(int blk, int z)
+{
+    return (record_off_t<WIDE>)(uint32_t)blk * R_BLOCK_BYTES + (uint32_t)z * R_PLANE_BYTES;
+}
+template <class OFF>
+__device__ __forceinline__ void load_record_at(float (&r)[R_COMP], const float *base, OFF off)
+{
+    const float *q = reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + off);
+#pragma unroll
+    for (int c = 0; c < R_COMP; ++c) r[c] = q[c * 64];
+}
+__device__ __forceinline__ void store_record(float *base, const Own own, float rho, float ux, float uy, float uz, float Pi_xx, float Pi_yy,
+                                             float Pi_zz, float Pi_xy, float Pi_yz, float Pi_zx, float one_m_omega)
+{
+    // own.cell4 = (lane + 64 z) * 4: plane z, lane
+    char *plane = const_cast<char *>(record_plane(base, own.b, __builtin_amdgcn_readfirstlane((int)(own.cell4 >> 8))));
+    float *q = reinterpret_cast<float *>(plane + (own.cell4 & 255u));
+    const float v[R_COMP] = {rho, ux, uy, uz, Pi_xx, Pi_yy, Pi_zz, Pi_xy, Pi_yz, Pi_zx, one_m_omega};
+#pragma unroll
+    for (int c = 0; c < R_COMP; ++c) {
+#ifdef LW_NT_STORES
+        __builtin_nontemporal_store(v[c], q + c * 64);
+#else
+        q[c * 64] = v[c];
+#endif
+    }
+}
+// the three populations (cx = -1, 0, +1) that leave the record's cell in the (CY, CZ) row, into fs
+template <int CY_, int CZ_>
+__device__ __forceinline__ void record_row(float (&fs)[Q], const float (&r)[R_COMP])
+{
+    static_for<0, 3>([&](auto ic) {
+        constexpr int k = decltype(ic)::value + 3 * (CY_ + 1) + 9 * (CZ_ + 1);
+        fs[k] = collide_value<k>(r[R_RHO], r[R_UX], r[R_UY], r[R_UZ], r[R_PXX], r[R_PYY], r[R_PZZ], r[R_PXY], r[R_PYZ], r[R_PZX], r[R_OMO]);
+    });
+}
+// The one population that crosses an x face out of the record's cell: cx = +1 (plus) or cx = -1. c * v for c = -1 is -v exactly, so
+// the cx = -1 value is the cx = +1 expression on (-ux, -Pi_xy, -Pi_zx): the same operands meet in the same operations.
+template <int CY_, int CZ_>
+__device__ __forceinline__ float record_face(const float (&r)[R_COMP], bool plus)
+{
+    constexpr int k = 2 + 3 * (CY_ + 1) + 9 * (CZ_ + 1);
+    return collide_value<k>(r[R_RHO], plus ? r[R_UX] : -r[R_UX], r[R_UY], r[R_UZ], r[R_PXX], r[R_PYY], r[R_PZZ],
+                            plus ? r[R_PXY] : -r[R_PXY], r[R_PYZ], plus ? r[R_PZX] : -r[R_PZX], r[R_OMO]);
+}
+
 // Everything after the loads: moments, obstacle bounce, sponge, wall model, WALE, regularized collision, stores.
 // reference src/physics_kernels.jl:144-354. fs = the 27 pulled populations, u?_? = previous-step velocity of the six
 // face neighbours. Shared by the per-wave kernel and the x-run kernel.
-template <bool POST, bool WALL>
+template <bool POST, bool WALL, bool REC_OUT = false>
 __device__ __forceinline__ void finish_cell(const SCParams &p, const int flags, const Own own, float (&fs)[Q],
                                             const float ux_E, const float uy_E, const float uz_E, const float ux_W, const float uy_W, const float uz_W,
                                             const float ux_N, const float uy_N, const float uz_N, const float ux_S, const float uy_S, const float uz_S,
@@ -409,11 +511,13 @@ __device__ __forceinline__ void finish_cell(const SCParams &p, const int flags, 
     }
     const float usq_eq = ux_eq * ux_eq + uy_eq * uy_eq + uz_eq * uz_eq;
 
-    st_f32(p.vel_out, own.b, V_BLOCK_BYTES, own.cell4, ux);
-    st_f32(p.vel_out, own.b, V_BLOCK_BYTES, COMP_BYTES + own.cell4, uy);
-    st_f32(p.vel_out, own.b, V_BLOCK_BYTES, 2 * COMP_BYTES + own.cell4, uz);
-    if (p.rho_old_save) st_f32(p.rho_old_save, own.b, S_BLOCK_BYTES, own.cell4, ld_own(p.rho, own.b, S_BLOCK_BYTES, own.cell4));
-    if (p.store_rho) st_f32(p.rho, own.b, S_BLOCK_BYTES, own.cell4, rho);
+    if constexpr (!REC_OUT) {
+        st_f32(p.vel_out, own.b, V_BLOCK_BYTES, own.cell4, ux);
+        st_f32(p.vel_out, own.b, V_BLOCK_BYTES, COMP_BYTES + own.cell4, uy);
+        st_f32(p.vel_out, own.b, V_BLOCK_BYTES, 2 * COMP_BYTES + own.cell4, uz);
+        if (p.rho_old_save) st_f32(p.rho_old_save, own.b, S_BLOCK_BYTES, own.cell4, ld_own(p.rho, own.b, S_BLOCK_BYTES, own.cell4));
+        if (p.store_rho) st_f32(p.rho, own.b, S_BLOCK_BYTES, own.cell4, rho);
+    }
 
     // ---- WALE eddy viscosity from the previous step's velocity, reference :251-300 ----
     const float g11 = 0.5f * (ux_E - ux_W), g12 = 0.5f * (ux_N - ux_S), g13 = 0.5f * (ux_T - ux_B);
@@ -468,25 +572,17 @@ __device__ __forceinline__ void finish_cell(const SCParams &p, const int flags, 
     // ---- regularized collision + write, reference :324-354 ----
     const float one_m_omega = 1.0f - omega;
     const float one_m_half_omega = 1.0f - 0.5f * omega;
+    if constexpr (REC_OUT) {      // eligible levels only (no wall model: u_eq = u is the stored velocity too), see "Record step"
+        store_record(p.rec_out, own, rho, ux_eq, uy_eq, uz_eq, Pi_xx, Pi_yy, Pi_zz, Pi_xy, Pi_yz, Pi_zx, one_m_omega);
+        return;
+    }
     static_for<0, Q>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        constexpr int cx = CX(k), cy = CY(k), cz = CZ(k);
-        constexpr float w_k = WEIGHT(k);
-        constexpr float cx_f = (float)cx, cy_f = (float)cy, cz_f = (float)cz;
-        const float cu = cdot<k>(ux_eq, uy_eq, uz_eq);
-        const float feq = rho * w_k * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * usq_eq);
-        constexpr float Q_xx = cx_f * cx_f - CS2_PHYSICS, Q_yy = cy_f * cy_f - CS2_PHYSICS, Q_zz = cz_f * cz_f - CS2_PHYSICS;
-        // Pi_xy*cx*cy + Pi_yz*cy*cz + Pi_zx*cz*cx, left-associated, zero terms dropped
-        float od = 0.0f;
-        bool od_empty = true;
-        acc_signed<cx * cy>(od, od_empty, Pi_xy);
-        acc_signed<cy * cz>(od, od_empty, Pi_yz);
-        acc_signed<cz * cx>(od, od_empty, Pi_zx);
-        float inner = Pi_xx * Q_xx + Pi_yy * Q_yy + Pi_zz * Q_zz;
-        if constexpr (cx * cy != 0 || cy * cz != 0 || cz * cx != 0) inner = inner + 2.0f * od;   // else + 2*0: exact no-op
-        const float f_neq_reg = (w_k * 4.5f) * inner;
-        float f_coll = feq + one_m_omega * f_neq_reg;
+        float f_coll = collide_value<k>(rho, ux_eq, uy_eq, uz_eq, Pi_xx, Pi_yy, Pi_zz, Pi_xy, Pi_yz, Pi_zx, one_m_omega);
         if constexpr (WALL) {
+            constexpr float w_k = WEIGHT(k);
+            constexpr float cx_f = (float)CX(k), cy_f = (float)CY(k), cz_f = (float)CZ(k);
+            const float cu = cdot<k>(ux_eq, uy_eq, uz_eq);
             const float force_term = (w_k * 3.0f) * ((cx_f - ux + 3.0f * cu * cx_f) * Fx + (cy_f - uy + 3.0f * cu * cy_f) * Fy +
                                                      (cz_f - uz + 3.0f * cu * cz_f) * Fz);
             f_coll = f_coll + one_m_half_omega * force_term;
@@ -591,8 +687,9 @@ constexpr int ITEM_ID_MASK = (1 << 29) - 1;
 #ifndef LW_MIN_WAVES
 #define LW_MIN_WAVES 5      // waves per SIMD the register allocator must leave room for (96 VGPRs)
 #endif
-template <int NW, bool GENERAL, bool POST, bool WALL, bool RHO_ONLY = false, bool WIDE = false>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE && GENERAL) ? LW_MIN_WAVES - 1 : LW_MIN_WAVES))) void k_stream_collide_xrun(const SCParams p)
+// The body of the kernel; REC_OUT: the result is stored as 11-float records (k_records_from_populations), not as f, vel and rho.
+template <int NW, bool GENERAL, bool POST, bool WALL, bool RHO_ONLY, bool WIDE, bool REC_OUT>
+__device__ __forceinline__ void stream_collide_xrun(const SCParams p)
 {
     __shared__ float xch[NW][24][8];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -723,8 +820,185 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE &
         uS[c] = l.y0 ? uy_edge[c] : s_in;
     }
     if constexpr (GENERAL) { if (needs_patch) patch_missing_sources(p, meta, nbr, l, z, own, fs); }
-    finish_cell<POST, WALL>(p, flags, own, fs, uE[0], uE[1], uE[2], uW[0], uW[1], uW[2], uN[0], uN[1], uN[2], uS[0], uS[1], uS[2],
-                            uT[0], uT[1], uT[2], uB[0], uB[1], uB[2]);
+    finish_cell<POST, WALL, REC_OUT>(p, flags, own, fs, uE[0], uE[1], uE[2], uW[0], uW[1], uW[2], uN[0], uN[1], uN[2], uS[0], uS[1], uS[2],
+                                     uT[0], uT[1], uT[2], uB[0], uB[1], uB[2]);
+}
+template <int NW, bool GENERAL, bool POST, bool WALL, bool RHO_ONLY = false, bool WIDE = false>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((WIDE && GENERAL) ? LW_MIN_WAVES - 1 : LW_MIN_WAVES))) void k_stream_collide_xrun(const SCParams p)
+{
+    stream_collide_xrun<NW, GENERAL, POST, WALL, RHO_ONLY, WIDE, false>(p);
+}
+// The first record step after populations were written (upload, an f-path step, k_materialise): the f path's pull on an eligible
+// level, stored as records. "Record step" below.
+template <int NW, bool WIDE>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_MIN_WAVES))) void k_records_from_populations(const SCParams p)
+{
+    stream_collide_xrun<NW, false, false, false, false, WIDE, true>(p);
+}
+
+// ---- Record step: the kernel that reads records ----
+// Same mapping, same work list and same LDS / DPP x exchange as k_stream_collide_xrun<NW, false, false, false>; what differs is
+// where the 27 pulled populations come from. Lane (x, y) of plane z loads the 9 records at (x, y - cy, z - cz) - the y shift is
+// addressing, as for populations: row (y - cy) & 7 of the own block or of the y neighbour - and evaluates collide_value for the 3
+// x directions of each; the x shift then is the usual lane shift plus face column. The previous step's velocity of the y and z
+// neighbours is in those same records (the centre one, cy = +-1 and cz = +-1), so no velocity is loaded and nothing is shuffled
+// in y. At the outer faces of a run the lanes of the face column load the x neighbour's 9 records and evaluate the one population
+// of each that crosses the face. Every block is all-neighbour, carries no obstacle / sponge / near-wall flag, and the level has no
+// wall model (the host's eligibility rule), so this is finish_cell<false, false> with flags = 0 - the f path's arithmetic, operation
+// by operation - and the result is stored as a record again.
+#ifndef LW_REC_WAVES
+#define LW_REC_WAVES 4      // waves per SIMD the register allocator must leave room for: 128 VGPRs (at 96 it spills 132 B per lane)
+#endif
+#ifndef LW_REC_AHEAD
+#define LW_REC_AHEAD 3      // records whose loads are in flight while one is evaluated (11 registers each)
+#endif
+template <int NW, bool WIDE>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_REC_WAVES))) void k_step_records(const SCParams p)
+{
+    __shared__ float xch[NW][24][8];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int raw = p.items[blockIdx.x * NW + wave];
+    const bool active = raw >= 0;
+    const int item = active ? (raw & ITEM_ID_MASK) : 0;
+    const int b = item >> 3;
+    const int z = item & 7;
+    const int lane = threadIdx.x & 63;
+    LanePos l;
+    l.x = lane & 7; l.y = lane >> 3;
+    l.x0 = l.x == 0; l.x7 = l.x == 7; l.y0 = l.y == 0; l.y7 = l.y == 7;
+    const int32_t *__restrict__ meta = p.meta + (size_t)b * NBR_STRIDE;
+    const NeighbourIds nbr = load_neighbour_ids(meta, z);
+    const Own own{b, (uint32_t)((l.x + 8 * l.y + 64 * z) * 4)};
+    const bool first = !active || (raw & ITEM_LINK_W) == 0, last = !active || (raw & ITEM_LINK_E) == 0;
+    // what crosses the run's outer faces, per wave and side (0: from -x, 1: from +x): slots 0..8 the population of row
+    // j = (cy+1) + 3 (cz+1), 9..11 the velocity. Through LDS, not registers: they would be held across the whole pull otherwise.
+    __shared__ float xedge[NW][2][12][8];
+    float fs[Q];
+    float uc[3], uT[3], uB[3], uN[3], uS[3];
+    if (active) {
+    // ---- the run's outer faces: lanes x = 0 of the first wave read column 7 of the -x neighbour, lanes x = 7 of the last wave
+    // column 0 of the +x neighbour (a lone block does both) ----
+    // Loads are staged: record j is evaluated while those of records j + 1 .. j + LW_REC_AHEAD are in flight, and the scheduler is kept
+    // from merging the stages (sched_barrier) - all 99 loads at once would need 99 registers beside the 27 populations.
+    if ((first && l.x0) || (last && l.x7)) {
+        float r[9][R_COMP];
+        auto load_face = [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int cy = j % 3 - 1, g = 1 - (j / 3 - 1);
+            const bool yo = cy == 1 ? l.y0 : (cy == -1 ? l.y7 : false);
+            const int wX = nbr.id[g][4 - 1], wXY = nbr.id[g][4 - 1 - 3 * cy], eX = nbr.id[g][4 + 1], eXY = nbr.id[g][4 + 1 - 3 * cy];
+            // four wave-uniform offsets, one chosen per lane
+            const auto oW = record_offset<WIDE>(wX, nbr.zs[g]), oWY = record_offset<WIDE>(wXY, nbr.zs[g]);
+            const auto oE = record_offset<WIDE>(eX, nbr.zs[g]), oEY = record_offset<WIDE>(eXY, nbr.zs[g]);
+            const auto off = l.x0 ? (yo ? oWY : oW) : (yo ? oEY : oE);
+            load_record_at(r[j], p.rec_in, off + (uint32_t)(((l.x0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
+        };
+        static_for<0, LW_REC_AHEAD>(load_face);
+        static_for<0, 9>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int cy = j % 3 - 1, cz = j / 3 - 1;
+            if constexpr (j + LW_REC_AHEAD < 9) load_face(std::integral_constant<int, j + LW_REC_AHEAD>{});
+            __builtin_amdgcn_sched_barrier(0);
+            float(&mine)[12][8] = xedge[wave][l.x0 ? 0 : 1];
+            mine[j][l.y] = record_face<cy, cz>(r[j], l.x0);
+            if constexpr (cy == 0 && cz == 0) { mine[9][l.y] = r[j][R_UX]; mine[10][l.y] = r[j][R_UY]; mine[11][l.y] = r[j][R_UZ]; }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    }
+    // ---- the 9 records at (x, y - cy, z - cz) ----
+    {
+        float r[9][R_COMP];
+        auto load_pulled = [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int cy = j % 3 - 1, g = 1 - (j / 3 - 1);
+            const uint32_t lane4 = (uint32_t)((l.x + 8 * ((l.y - cy) & 7)) * 4);
+            if constexpr (cy == 0) {       // the block is wave-uniform: scalar base, the lane's offset inside the plane
+                load_record(r[j], record_plane(p.rec_in, nbr.id[g][4], nbr.zs[g]), lane4);
+            } else {
+                const bool yo = cy == 1 ? l.y0 : l.y7;
+                const auto o0 = record_offset<WIDE>(nbr.id[g][4], nbr.zs[g]), oY = record_offset<WIDE>(nbr.id[g][4 - 3 * cy], nbr.zs[g]);
+                load_record_at(r[j], p.rec_in, (yo ? oY : o0) + lane4);
+            }
+        };
+        static_for<0, LW_REC_AHEAD>(load_pulled);
+        static_for<0, 9>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            constexpr int cy = j % 3 - 1, cz = j / 3 - 1;
+            if constexpr (j + LW_REC_AHEAD < 9) load_pulled(std::integral_constant<int, j + LW_REC_AHEAD>{});
+            __builtin_amdgcn_sched_barrier(0);
+            const float(&q)[R_COMP] = r[j];
+            record_row<cy, cz>(fs, q);
+            if constexpr (cy == 0 && cz == 0) { uc[0] = q[R_UX]; uc[1] = q[R_UY]; uc[2] = q[R_UZ]; }
+            if constexpr (cy == 0 && cz == 1) { uB[0] = q[R_UX]; uB[1] = q[R_UY]; uB[2] = q[R_UZ]; }
+            if constexpr (cy == 0 && cz == -1) { uT[0] = q[R_UX]; uT[1] = q[R_UY]; uT[2] = q[R_UZ]; }
+            if constexpr (cy == 1 && cz == 0) { uS[0] = q[R_UX]; uS[1] = q[R_UY]; uS[2] = q[R_UZ]; }
+            if constexpr (cy == -1 && cz == 0) { uN[0] = q[R_UX]; uN[1] = q[R_UY]; uN[2] = q[R_UZ]; }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    }
+    // ---- publish the face columns the neighbouring waves need ----
+    static_for<0, Q>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        constexpr int cx = CX(k);
+        if constexpr (cx == 1) { if (l.x7) xch[wave][XSLOT(k)][l.y] = fs[k]; }
+        if constexpr (cx == -1) { if (l.x0) xch[wave][XSLOT(k)][l.y] = fs[k]; }
+    });
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (l.x7) xch[wave][18 + c][l.y] = uc[c];
+        if (l.x0) xch[wave][21 + c][l.y] = uc[c];
+    }
+    }   // if (active)
+    __syncthreads();
+    if (!active) return;
+    const int wlo = first ? 0 : wave - 1, whi = last ? NW - 1 : wave + 1;
+    static_for<0, Q>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        constexpr int cx = CX(k);
+        if constexpr (cx == 1) {
+            const float inner = dpp_from_lower_lane(fs[k]);
+            const float edge = first ? xedge[wave][0][k / 3][l.y] : xch[wlo][XSLOT(k)][l.y];
+            fs[k] = l.x0 ? edge : inner;
+        }
+        if constexpr (cx == -1) {
+            const float inner = dpp_from_upper_lane(fs[k]);
+            const float edge = last ? xedge[wave][1][k / 3][l.y] : xch[whi][XSLOT(k)][l.y];
+            fs[k] = l.x7 ? edge : inner;
+        }
+    });
+    float uE[3], uW[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float e_edge = last ? xedge[wave][1][9 + c][l.y] : xch[whi][21 + c][l.y];
+        const float w_edge = first ? xedge[wave][0][9 + c][l.y] : xch[wlo][18 + c][l.y];
+        const float e_in = dpp_from_upper_lane(uc[c]), w_in = dpp_from_lower_lane(uc[c]);   // all lanes active, see k_stream_collide_xrun
+        uE[c] = l.x7 ? e_edge : e_in;
+        uW[c] = l.x0 ? w_edge : w_in;
+    }
+    finish_cell<false, false, true>(p, 0, own, fs, uE[0], uE[1], uE[2], uW[0], uW[1], uW[2], uN[0], uN[1], uN[2], uS[0], uS[1], uS[2],
+                                    uT[0], uT[1], uT[2], uB[0], uB[1], uB[2]);
+}
+
+// A record back into what the f path keeps: the cell's 27 post-collision populations (un-streamed, as f_out holds them), its velocity
+// and its density. One thread per cell; the same collide_value the f path's writer evaluates, so the same bits.
+__global__ __launch_bounds__(256) void k_materialise(const SCParams p, int64_t n_cells)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_cells) return;
+    const int b = (int)(i >> 9);
+    const uint32_t cell = (uint32_t)(i & 511);
+    float r[R_COMP];
+    load_record(r, record_plane(p.rec_in, b, (int)(cell >> 6)), (cell & 63u) * 4);
+    const Own own{b, cell * 4};
+    st_f32(p.vel_out, b, V_BLOCK_BYTES, own.cell4, r[R_UX]);
+    st_f32(p.vel_out, b, V_BLOCK_BYTES, COMP_BYTES + own.cell4, r[R_UY]);
+    st_f32(p.vel_out, b, V_BLOCK_BYTES, 2 * COMP_BYTES + own.cell4, r[R_UZ]);
+    if (p.rho) st_f32(p.rho, b, S_BLOCK_BYTES, own.cell4, r[R_RHO]);      // null: a later step's density is the level's rho
+    static_for<0, Q>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        st_f32(p.f_out, b, F_BLOCK_BYTES, k * COMP_BYTES + own.cell4,
+               collide_value<k>(r[R_RHO], r[R_UX], r[R_UY], r[R_UZ], r[R_PXX], r[R_PYY], r[R_PZZ], r[R_PXY], r[R_PYZ], r[R_PZX], r[R_OMO]));
+    });
 }
 
 // ---- coarse -> fine interface pass (reference src/physics_kernels.jl:122-137 + src/physics_interpolation.jl) ----

@@ -79,6 +79,11 @@ const char *rccl_lib() { return getenv("LUDWIG_RCCL_LIB"); }
 bool halo_self_via_rccl() { return is_set("LUDWIG_HALO_SELF_VIA_RCCL"); }
 // LUDWIG_HALO_TRACE: host microseconds of every exchange call on stderr. Per process (first exchange).
 bool halo_trace() { static const bool v = is_set("LUDWIG_HALO_TRACE"); return v; }
+// LUDWIG_RECORD_STEP=0: plain levels step on the f path too (the record step off, same bits). Per call (every step).
+bool record_step_off() { return flag("LUDWIG_RECORD_STEP") == 0; }
+// LUDWIG_RECORD_ORDER=0/1: the record step launches in the f path's order / with the 8 planes of a run on one XCD (unset: 1). Per
+// level, when its record work list is built (first record step after create or set_order).
+int record_order() { const int v = flag("LUDWIG_RECORD_ORDER"); return v < 0 ? 1 : v; }
 
 }  // namespace env
 
@@ -266,6 +271,19 @@ struct LudwigLevel {
     int32_t *iso_keys = nullptr;
     int64_t iso_capacity = 0;
     int64_t iso_n = -1;                 // triangles of the last extraction (0 after a refusal); -1: none yet
+    // Record step (kernels.hpp "Record step"). A plain level - record_eligible() - steps from 11-float collision records instead of
+    // f / vel / rho: rec[q] plays the role of f[q] and vel[q]. Per parity q, f_valid[q] says f[q] / vel[q] hold what the f path would
+    // hold there and rec_valid[q] the same for rec[q]; a record step into parity q makes rec[q] valid and f[q] / vel[q] stale, and
+    // ensure_populations() brings them back with k_materialise before anything reads or hands them out. rho_in_rec = the parity
+    // whose record holds the density `rho` should hold (the last record step's output), or -1 when `rho` itself is in charge.
+    float *rec[2] = {nullptr, nullptr};     // allocated by the first record step
+    bool f_valid[2] = {true, true}, rec_valid[2] = {false, false};
+    int rho_in_rec = -1;
+    int rec_eligible = -1;                  // the level's part of the rule: -1 unknown (recomputed after set_items / upload_meta)
+    bool rec_banned = false;                // another level reads this one, or the record buffers could not be allocated: f path for good
+    bool rec_hold = false;                  // a batch with in-batch observers or several levels is running: f path meanwhile
+    int32_t *rec_items = nullptr;           // the class-2 work list in the record path's order, see record_items()
+    int64_t n_record_steps = 0;
 };
 
 namespace {
@@ -298,6 +316,35 @@ struct FieldDesc {
 
 int ensure_rho(LudwigLevel *L);
 
+// ---- record step: validity (LudwigLevel::rec) ----
+// The ONE way back from records to populations: f[parity] / vel[parity] (and rho, where that parity's record holds it) are made what
+// the f path would hold there. parity -1 = both. Called by whatever reads them, hands them out or writes into them; a no-op on a
+// level that has taken no record step since.
+int ensure_populations(LudwigLevel *L, int parity)
+{
+    for (int q = 0; q < 2; ++q) {
+        if ((parity >= 0 && parity != q) || L->f_valid[q]) continue;
+        LW_HIP(hipSetDevice(L->device));
+        SCParams p{};
+        p.rec_in = L->rec[q];
+        p.f_out = L->f[q];
+        p.vel_out = L->vel[q];
+        p.rho = L->rho_in_rec == q ? L->rho : nullptr;      // only the last record step's density is the level's rho
+        hipLaunchKernelGGL(k_materialise, dim3((unsigned)((L->sk + 255) / 256)), dim3(256), 0, L->stream, p, L->sk);
+        LW_HIP(hipGetLastError());
+        L->f_valid[q] = true;
+        if (L->rho_in_rec == q) L->rho_in_rec = -1;
+    }
+    return LUDWIG_OK;
+}
+
+// f, vel and rho of both parities as the f path would hold them now (observers and diagnostics read them through raw pointers)
+#define LW_ENSURE_POPULATIONS(L)                                                                          \
+    do {                                                                                                  \
+        const int rp_ = ensure_populations(const_cast<LudwigLevel *>(L), -1);                             \
+        if (rp_) return rp_;                                                                              \
+    } while (0)
+
 int materialize_old(LudwigLevel *L)
 {
     if (L->old_alias < 0) return LUDWIG_OK;
@@ -314,6 +361,11 @@ int materialize_old(LudwigLevel *L)
 // call before anything but a stream-collide step writes `field` (upload, halo unpack, a raw pointer handed out)
 int before_external_write(LudwigLevel *L, int field)
 {
+    {   // the write lands in populations: they are brought up to date first, and no record stands for them afterwards
+        const int r = ensure_populations(L, -1);
+        if (r) return r;
+        L->rec_valid[0] = L->rec_valid[1] = false;
+    }
     // an elided rho is recomputed from the input populations / sponge / obstacle of the last step: produce it before any
     // of them changes (a halo unpack into the OUTPUT buffer of that step, the usual case, does not touch them)
     bool feeds_rho = field == LUDWIG_SPONGE || field == LUDWIG_OBSTACLE || field == LUDWIG_RHO;
@@ -379,6 +431,7 @@ void scan_flags(LudwigLevel *L, int field, const void *host)
 
 int upload_meta(LudwigLevel *L)
 {
+    L->rec_eligible = -1;                     // the per-block flags are part of the record step's rule
     if (L->n_blocks == 0) return LUDWIG_OK;
     LW_HIP(hipMemcpyAsync(L->meta, L->h_meta.data(), L->h_meta.size() * 4, hipMemcpyHostToDevice, L->stream));
     LW_HIP(hipStreamSynchronize(L->stream));
@@ -408,6 +461,10 @@ int set_items(LudwigLevel *L, int part, const int32_t *items, int64_t n)
     // class 2: all-neighbour blocks, class 1: blocks with a missing neighbour - both through the x-run kernel;
     // class 0 (wave-by-wave kernel) only with LUDWIG_NO_XRUN (diagnostics).
     std::vector<int32_t> cls[N_CLASSES];
+    if (part == LUDWIG_PART_ALL) {            // the record step's work list is made from this part's: rebuilt on its next step
+        L->rec_eligible = -1;
+        if (L->rec_items) { (void)hipFree(L->rec_items); L->rec_items = nullptr; }
+    }
     auto is_fast = [&](int b) { return (L->h_meta[(size_t)b * NBR_STRIDE + NBR_FLAGS] & FLAG_ALL_NEIGHBOURS) != 0; };
     for (int64_t i = 0; i < n; ++i) {
         if (items[i] >= 0) {
@@ -864,6 +921,108 @@ static int interface_prepass(LudwigLevel *L, const LudwigLevel *parent, int64_t 
     return interface_launch(L, parent, part, p, t_sub, parent_tau, temporal_weight, true, L->stream);
 }
 
+// ---- record step (kernels.hpp "Record step") ------------------------------------------------------------------------------
+// From now on this level steps on the f path: somebody reads its arrays without asking (another level's interface pass).
+int ban_records(LudwigLevel *L)
+{
+    L->rec_banned = true;
+    const bool behind = !L->f_valid[0] || !L->f_valid[1];
+    const int r = ensure_populations(L, -1);
+    if (r) return r;
+    L->rec_valid[0] = L->rec_valid[1] = false;
+    if (behind) LW_HIP(hipStreamSynchronize(L->stream));      // the reader may sit on another stream; this happens once per level
+    return LUDWIG_OK;
+}
+
+// The level's part of the rule (ludwig_record_step_rule), looked at again after every set_items / upload_meta.
+bool record_level_ok(LudwigLevel *L)
+{
+    if (L->rec_eligible < 0) {
+        std::vector<int32_t> flags((size_t)L->n_blocks);
+        for (int b = 0; b < L->n_blocks; ++b) flags[b] = L->h_meta[(size_t)b * NBR_STRIDE + NBR_FLAGS];
+        const bool one_list = L->n_items_merged[LUDWIG_PART_ALL] == 0 && L->n_items[LUDWIG_PART_ALL][1] == 0 && L->n_items[LUDWIG_PART_ALL][2] > 0;
+        L->rec_eligible = one_list && ludwig_record_step_rule(flags.data(), L->n_blocks, L->n_owned, 0, L->has_temporal ? 1 : 0,
+                                                              (L->has_post || L->bouzidi_enabled) ? 1 : 0, 0) == 1;
+    }
+    return L->rec_eligible == 1;
+}
+
+// The class-2 work list in the order the record step launches it. The f path's order deals the 8 planes of a run of blocks to the 8
+// XCDs (default_items): fine for populations, which no two planes share, but a record plane is wanted by the waves of planes z - 1, z
+// and z + 1. LUDWIG_RECORD_ORDER=1 transposes every 8 x 8 tile of workgroups, so that slot 8 j + x of a tile - XCD x - holds what was slot
+// 8 x + j: all 8 planes of one run on one XCD. Workgroups stay whole, so the link bits hold. profiles/record_step_order.txt.
+int build_record_items(LudwigLevel *L)
+{
+    const int64_t n = L->n_items[LUDWIG_PART_ALL][2];
+    std::vector<int32_t> src((size_t)n), dst;
+    LW_HIP(hipMemcpy(src.data(), L->items[LUDWIG_PART_ALL][2], (size_t)n * 4, hipMemcpyDeviceToHost));
+    dst = src;
+    if (env::record_order() == 1) {
+        const int64_t n_wg = n / XRUN;
+        for (int64_t t0 = 0; t0 + 64 <= n_wg; t0 += 64)
+            for (int j = 0; j < 8; ++j)
+                for (int x = 0; x < 8; ++x)
+                    for (int w = 0; w < XRUN; ++w) dst[(size_t)(t0 + 8 * j + x) * XRUN + w] = src[(size_t)(t0 + 8 * x + j) * XRUN + w];
+    }
+    LW_HIP(hipMalloc((void **)&L->rec_items, (size_t)n * 4));
+    LW_HIP(hipMemcpy(L->rec_items, dst.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    return LUDWIG_OK;
+}
+
+// Does this step go by records? Also makes what the record step needs on its first use.
+int record_step_wanted(LudwigLevel *L, const LudwigLevel *parent, const LudwigStepFlags *fl, int part, bool *yes)
+{
+    *yes = false;
+    if (env::record_step_off() || L->rec_banned || L->rec_hold || L->external_writer || L->rho_old_pending || parent || part != LUDWIG_PART_ALL ||
+        fl->wall_model_active || !record_level_ok(L))
+        return LUDWIG_OK;
+    if (!L->rec[0]) {
+        const size_t bytes = (size_t)L->n_blocks * R_BLOCK_BYTES;
+        float *a = nullptr, *b = nullptr;
+        if (hipMalloc((void **)&a, bytes) != hipSuccess || hipMalloc((void **)&b, bytes) != hipSuccess) {
+            (void)hipGetLastError();                 // no room for the records: the f path needs none
+            if (a) (void)hipFree(a);
+            L->rec_banned = true;
+            return LUDWIG_OK;
+        }
+        L->rec[0] = a; L->rec[1] = b;
+        L->device_bytes += (int64_t)(2 * bytes);
+    }
+    if (!L->rec_items) {
+        const int r = build_record_items(L);
+        if (r) return r;
+    }
+    *yes = true;
+    return LUDWIG_OK;
+}
+
+// One whole-level step in -> out that writes records: from rec[in] where that holds the state, else from f[in] / vel[in].
+int launch_record_step(LudwigLevel *L, SCParams p, int in, int out, int64_t t_sub)
+{
+    if (t_sub != L->last_step_t) { ++L->step_count; L->last_step_t = t_sub; }
+    L->rho_replay[LUDWIG_PART_ALL].stale = false;     // superseded, as by any whole-level step
+    p.items = L->rec_items;
+    p.rec_out = L->rec[out];
+    p.store_rho = 0;
+    const dim3 grid((unsigned)(L->n_items[LUDWIG_PART_ALL][2] / XRUN)), block(64 * XRUN);
+    if (L->rec_valid[in]) {
+        p.rec_in = L->rec[in];
+        // 64-bit per-lane record addresses from 4 GiB of records on (190 650 blocks)
+        if ((uint64_t)L->n_blocks * R_BLOCK_BYTES >= (1ull << 32)) hipLaunchKernelGGL((k_step_records<XRUN, true>), grid, block, 0, L->stream, p);
+        else hipLaunchKernelGGL((k_step_records<XRUN, false>), grid, block, 0, L->stream, p);
+    } else if (L->wide) {
+        hipLaunchKernelGGL((k_records_from_populations<XRUN, true>), grid, block, 0, L->stream, p);
+    } else {
+        hipLaunchKernelGGL((k_records_from_populations<XRUN, false>), grid, block, 0, L->stream, p);
+    }
+    LW_HIP(hipGetLastError());
+    L->rec_valid[out] = true;
+    L->f_valid[out] = false;
+    L->rho_in_rec = out;
+    ++L->n_record_steps;
+    return LUDWIG_OK;
+}
+
 int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_sub, float u_curr, float parent_tau,
                           float temporal_weight, const LudwigStepFlags *fl, int part)
 {
@@ -908,6 +1067,19 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
     p.wall_model = fl->wall_model_active ? 1 : 0;
     p.seed = (int32_t)(t_sub % 1000000);        // reference src/physics_v2.jl:76
     p.sponge_blend = fl->sponge_blend_distributions ? 1 : 0;
+
+    if (parent && !parent->rec_banned) {           // the interface pass reads the parent's arrays: they stay populations
+        const int r = ban_records(const_cast<LudwigLevel *>(parent));
+        if (r) return r;
+    }
+    {
+        bool by_records = false;
+        int r = record_step_wanted(L, parent, fl, part, &by_records);
+        if (r) return r;
+        if (by_records) return launch_record_step(L, p, in, out, t_sub);
+        if ((r = ensure_populations(L, -1))) return r;       // the f path: whatever only a record holds comes back first
+        L->rec_valid[out] = false;
+    }
 
     // lazy rho: who reads rho before this level's next step?
     if (parent && !parent->rho_eager) {            // a child interpolates from its parent's rho after every parent step
@@ -990,6 +1162,10 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
 // Produce `rho` now if the last step left it unwritten (see LudwigLevel::rho_replay).
 int ensure_rho(LudwigLevel *L)
 {
+    if (L->rho_in_rec >= 0) {          // the last step was a record step: rho is component 0 of its records
+        const int r = ensure_populations(L, L->rho_in_rec);
+        if (r) return r;
+    }
     bool any = false;
     for (int a = 0; a < N_PARTS; ++a) any = any || L->rho_replay[a].stale;
     if (!any) return LUDWIG_OK;
@@ -1158,6 +1334,9 @@ void ludwig_level_destroy(LudwigLevel *L)
         if (L->source_mac2[a]) (void)hipFree(L->source_mac2[a]);
     }
     if (L->f_iface) (void)hipFree(L->f_iface);
+    if (L->rec[0]) (void)hipFree(L->rec[0]);
+    if (L->rec[1]) (void)hipFree(L->rec[1]);
+    if (L->rec_items) (void)hipFree(L->rec_items);
     if (L->stats) (void)hipFree(L->stats);
     if (L->grad) (void)hipFree(L->grad);
     if (L->subgrid_fields) (void)hipFree(L->subgrid_fields);
@@ -1621,6 +1800,12 @@ int ludwig_level_download(const LudwigLevel *L, int field, void *host, size_t by
     if (!d.ptr || d.bytes == 0) return fail(LUDWIG_ERR_STATE, "field %d is not allocated on this level", field);
     if (bytes != d.bytes) return fail(LUDWIG_ERR_INVALID, "field %d: got %zu bytes, expected %zu", field, bytes, d.bytes);
     LW_HIP(hipSetDevice(L->device));
+    {   // what a record holds of this field comes back first: one parity for f / vel, the last step's for rho
+        const bool p0 = field == LUDWIG_F || field == LUDWIG_VEL, p1 = field == LUDWIG_F_TEMP || field == LUDWIG_VEL_TEMP;
+        const int r = (p0 || p1) ? ensure_populations(const_cast<LudwigLevel *>(L), p0 ? 0 : 1)
+                                 : (field == LUDWIG_RHO ? LUDWIG_OK : ensure_populations(const_cast<LudwigLevel *>(L), -1));
+        if (r) return r;
+    }
     if (field == LUDWIG_RHO) {
         const int r = ensure_rho(const_cast<LudwigLevel *>(L));
         if (r) return r;
@@ -1688,7 +1873,10 @@ int ludwig_init_equilibrium(LudwigLevel *L)
     const unsigned grid = (unsigned)((L->sk + 255) / 256);
     ++L->version;
     {
-        const int r = ensure_rho(L);                 // init_eq! leaves rho alone: it must hold what the last step made of it
+        int r = ensure_populations(L, -1);           // vel and rho stay what the last step made of them; f is populations from here on
+        if (r) return r;
+        L->rec_valid[0] = L->rec_valid[1] = false;
+        r = ensure_rho(L);                           // init_eq! leaves rho alone: it must hold what the last step made of it
         if (r) return r;
     }
     hipLaunchKernelGGL(k_fill_weights, dim3(grid), dim3(256), 0, L->stream, L->f[0], L->sk);
@@ -1766,6 +1954,7 @@ int32_t internal_cell(const LudwigLevel *L, int32_t b, int32_t x) { return (L->r
 // rho as ludwig_level_download(LUDWIG_RHO) would return it now: an elided store is replayed first, on the level's stream
 #define LW_ENSURE_RHO(L)                                                                                  \
     do {                                                                                                  \
+        LW_ENSURE_POPULATIONS(L);                                                                         \
         const int r_ = ensure_rho(const_cast<LudwigLevel *>(L));                                          \
         if (r_) return r_;                                                                                \
     } while (0)
@@ -2042,6 +2231,7 @@ struct BatchObservers {
     struct : ObserverSchedule { LudwigTracers *set = nullptr; } tracers;
     struct : ObserverSchedule { LudwigFluxPlanes *set = nullptr; } fluxes;
     struct : ObserverSchedule { LudwigModes *set = nullptr; } modes;
+    bool any() const { return probes.set || surface.set || forces.set || tracers.set || fluxes.set || modes.set; }
 };
 // The observers inside one coarse step: the step being run, the probes' ring slot (-1 = not sampled) and whether the surface set and
 // the force series sample this step, the flux planes' ring slot (-1 = not sampled) and the modes' table row (-1 = not sampled).
@@ -2434,6 +2624,7 @@ int ludwig_level_gradient_fields_compute(LudwigLevel *L, int vel_field, float sc
         return LUDWIG_OK;
     }
     LW_HIP(hipSetDevice(L->device));
+    LW_ENSURE_POPULATIONS(L);
     if (!L->grad) {
         const size_t n = (size_t)L->n_blocks * GRAD_COMPONENTS * CELLS;
         const int r = dev_alloc(L, &L->grad, n);
@@ -2605,6 +2796,7 @@ int ludwig_level_subgrid_fields_compute(LudwigLevel *L, int vel_field)
     }
     if (const int r = subgrid_model_known(L, "fields")) return r;
     LW_HIP(hipSetDevice(L->device));
+    LW_ENSURE_POPULATIONS(L);
     if (!L->subgrid_fields) {
         const size_t n = (size_t)L->n_blocks * SUBGRID_FIELD_COMPONENTS * CELLS;
         const int r = dev_alloc(L, &L->subgrid_fields, n);
@@ -2658,6 +2850,7 @@ int ludwig_level_subgrid_stats_accumulate(LudwigLevel *L, int64_t t_sub)
     if (L->n_owned == 0) return LUDWIG_OK;
     if (const int r = subgrid_model_known(L, "statistics")) return r;
     LW_HIP(hipSetDevice(L->device));
+    LW_ENSURE_POPULATIONS(L);
     hipLaunchKernelGGL(k_subgrid<SUBGRID_SUMS>, dim3((unsigned)L->n_owned), dim3(CELLS / 2), 0, L->stream, L->subgrid_sums,
                        (const float *)vel_out(L, t_sub), (const uint8_t *)L->obstacle, (const int32_t *)L->meta, L->c_wale, L->nu_bg);
     LW_HIP(hipGetLastError());
@@ -3738,6 +3931,7 @@ static int tracers_launch_advance(LudwigTracers *S, int64_t t_coarse, hipStream_
 {
     const int64_t k = S->n_advances++;
     if (S->n_slots == 0) return LUDWIG_OK;
+    for (int li = 0; li < S->n_levels; ++li) LW_ENSURE_POPULATIONS(S->levels[li]);
     TracerArgs a = tracers_args(S, t_coarse);
     if (k % S->release_every == 0) a.released = (int32_t)((k / S->release_every) % S->generations);
     hipLaunchKernelGGL(k_tracers_advance, dim3((unsigned)((S->n_slots * 8 + 63) / 64)), dim3(64), 0, st, a);
@@ -3791,6 +3985,7 @@ int ludwig_tracers_snapshot(LudwigTracers *S, int64_t t_coarse)
     hipStream_t st = S->levels[0]->stream;
     const int r = tracers_join(S, st);
     if (r) return r;
+    for (int li = 0; li < S->n_levels; ++li) LW_ENSURE_POPULATIONS(S->levels[li]);
     const TracerArgs a = tracers_args(S, t_coarse);
     hipLaunchKernelGGL(k_tracers_snapshot, dim3((unsigned)((S->n_slots * 8 + 63) / 64)), dim3(64), 0, st, a);
     LW_HIP(hipGetLastError());
@@ -4018,6 +4213,9 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         }
     }
     for (int i = 0; i < n_levels; ++i) levels[i]->rho_old_pending = false;      // (only an aborted batch could have left one)
+    // in-batch observers read f / vel / rho between the steps, and the levels of a nest read each other: such a batch runs the f path
+    const bool hold_records = n_levels > 1 || obs.any();
+    for (int i = 0; i < n_levels; ++i) levels[i]->rec_hold = hold_records;
     int rc = LUDWIG_OK;
     for (int32_t o = 0; o < batch_size && rc == LUDWIG_OK; ++o) {
         const int64_t t = t_start + o;
@@ -4041,6 +4239,7 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
         }
         if (rc == LUDWIG_OK && e != hipSuccess) return fail(LUDWIG_ERR_HIP, "batch: %s", hipGetErrorString(e));
     }
+    for (int i = 0; i < n_levels; ++i) levels[i]->rec_hold = false;
     if (rc) return rc;
     return ludwig_sync(levels[0]);
 }
@@ -4115,6 +4314,7 @@ int ludwig_halo_pack(const LudwigLevel *L, int field, const int64_t *index_dev, 
     const FieldDesc d = field_desc(L, field);
     if (!d.ptr || field == LUDWIG_OBSTACLE) return fail(LUDWIG_ERR_STATE, "field %d cannot be packed", field);
     LW_HIP(hipSetDevice(L->device));
+    LW_ENSURE_POPULATIONS(L);
     if (field == LUDWIG_RHO) {
         bool stale = false;
         for (int a = 0; a < N_PARTS; ++a) stale = stale || L->rho_replay[a].stale;
@@ -4144,6 +4344,23 @@ int ludwig_halo_unpack(LudwigLevel *L, int field, const int64_t *index_dev, int6
     LW_HIP(hipSetDevice(L->device));
     hipLaunchKernelGGL(k_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hip_stream ? (hipStream_t)hip_stream : L->stream, (float *)d.ptr, index_dev, n, src_dev, (const int32_t *)L->d_ref2int, L->sk, d.comps);
     LW_HIP(hipGetLastError());
+    return LUDWIG_OK;
+}
+
+int ludwig_record_step_rule(const int32_t *block_flags, int32_t n_blocks, int32_t n_owned, int32_t has_parent, int32_t has_temporal_storage,
+                            int32_t has_post_collision, int32_t wall_model_active)
+{
+    if (n_blocks < 0 || (n_blocks > 0 && !block_flags)) return fail(LUDWIG_ERR_INVALID, "record step rule: bad argument");
+    if (n_blocks == 0 || n_owned != n_blocks || has_parent || has_temporal_storage || has_post_collision || wall_model_active) return 0;
+    for (int32_t b = 0; b < n_blocks; ++b)
+        if (block_flags[b] != FLAG_ALL_NEIGHBOURS) return 0;       // a missing neighbour, or an obstacle / sponge / near-wall / post bit
+    return 1;
+}
+
+int ludwig_level_record_steps(const LudwigLevel *L, int64_t *n_steps)
+{
+    if (!L || !n_steps) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *n_steps = L->n_record_steps;
     return LUDWIG_OK;
 }
 
@@ -4443,6 +4660,7 @@ int ludwig_halo_plan_create(LudwigLevel *L, LudwigComm *comm, const LudwigHaloPl
     if (out) *out = nullptr;
     if (!L || !desc || !out || desc->n_peers < 0 || (desc->n_peers > 0 && !desc->peer_ranks)) return fail(LUDWIG_ERR_INVALID, "bad argument");
     if (comm && comm->device != L->device) return fail(LUDWIG_ERR_INVALID, "communicator and level live on different devices");
+    if (const int r = ban_records(L)) return r;              // a level whose arrays are exchanged keeps them as populations
     for (int p = 0; p < desc->n_peers; ++p) {
         const int r = desc->peer_ranks[p];
         if (comm ? (r < 0 || r >= comm->world) : r != 0) return fail(LUDWIG_ERR_INVALID, "peer %d: rank %d not in the communicator", p, r);
@@ -4541,6 +4759,7 @@ int ludwig_halo_plan_pack(LudwigHaloPlan *P, int32_t group, int32_t field, void 
 {
     if (!P || group < 0 || group >= LUDWIG_HALO_GROUPS) return fail(LUDWIG_ERR_INVALID, "bad argument");
     LW_HIP(hipSetDevice(P->L->device));
+    LW_ENSURE_POPULATIONS(P->L);
     if (field == LUDWIG_RHO) { const int r = ensure_rho(P->L); if (r) return r; }
     return halo_pack_group(P, group, field, hip_stream ? (hipStream_t)hip_stream : P->L->stream);
 }

@@ -33,13 +33,20 @@ if __name__ == "__main__":
         f.write(f"{'kernel':70s} {'calls':>6s} {'avg_ns':>12s} {'min_ns':>12s} {'max_ns':>12s} {'pct':>7s}\n")
         for k in ks:
             f.write(f"{k['kernel'][:70]:70s} {k['calls']:6d} {k['avg_ns']:12.0f} {k['min_ns']:12d} {k['max_ns']:12d} {k['pct']:7.2f}\n")
-    c = pmc(glob.glob(os.path.join(pmc_root, "pmc_*")), "k_stream_collide")
+    # the 256^3 periodic box steps by records (kernels.hpp "Record step") unless LUDWIG_RECORD_STEP=0: then its launches are
+    # k_step_records and the one k_records_from_populations launch in front of them is not the steady state
+    c = pmc(glob.glob(os.path.join(pmc_root, "pmc_*")), "k_step_records")
+    by_records = bool(c)
+    if not by_records:
+        c = pmc(glob.glob(os.path.join(pmc_root, "pmc_*")), "k_stream_collide")
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from open_ludwig_amd import build as build_mod
     import datetime
     res = {"cells_per_launch": cells, "counters_per_launch": c, "source_digest": build_mod.source_digest(),
            "captured": datetime.datetime.now(datetime.timezone.utc).strftime("%Y-%m-%d %H:%M UTC"),
-           "kernel": "void lw::k_stream_collide_xrun<4, false, false, false, false, false>(lw::SCParams) at 256^3, library default order, rho store elided"}
+           "kernel": ("void lw::k_step_records<4, false>(lw::SCParams) at 256^3, library default order (LUDWIG_RECORD_ORDER=1); the record step stores no rho, vel or f"
+                      if by_records else
+                      "void lw::k_stream_collide_xrun<4, false, false, false, false, false>(lw::SCParams) at 256^3, library default order, rho store elided")}
     if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
         # MI355X_MICROARCH.md "HBM": FETCH_SIZE and WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE tallies 128-B read requests
         # at 64 B -> double it; WRITE_SIZE is exact. Separate --pmc passes (TCC has 4 slots: FETCH 3 + WRITE 2 do not fit).
