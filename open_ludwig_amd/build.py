@@ -14,8 +14,11 @@ OUT = os.path.join(CSRC, "libludwig_hip.so")
 # -ffp-contract=off: the reference's CPU path never fuses a*b+c; parity with it is bit-level (DESIGN.md "Numerics").
 # -DLW_NT_STORES: outputs are pure streaming writes (nothing re-reads them inside the launch); non-temporal stores
 # keep them from evicting the face-layer lines neighbouring workgroups still need (2-4 % measured at 256^3).
+# -fno-slp-vectorize: where packed FP32 pays, the kernels write the pairs by hand (kernels.hpp f32x2). What the SLP pass finds on top
+# of that costs the record step about a hundred register-pair moves and its register budget (128 VGPRs and scratch in some builds,
+# none in others, for the same source), and measured slower with it than without (profiles/packed_finish_vs_parent.txt).
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-               "-fno-fast-math", "-Wall", "-Wno-unused-function", "-DLW_NT_STORES"]
+               "-fno-fast-math", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function", "-DLW_NT_STORES"]
 
 
 def source_digest() -> str:

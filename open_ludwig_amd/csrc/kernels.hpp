@@ -318,27 +318,119 @@ __device__ __forceinline__ WaleState wale_state(float g11, float g12, float g13,
 // function of the cell's 11 collision values and nothing else. ONE source for the three places that form it - finish_cell (which
 // stores it), the record step (which evaluates it at the source cell instead of loading it) and k_materialise - so under
 // -ffp-contract=off all three give the same bits.
+// Two floats in an even-aligned register pair: + - * on it are one v_pk_*_f32 each, IEEE per half like the scalar instruction (and
+// measured to issue at the scalar instruction's cost, profiles/packed_f32_issue_cost.txt). A per-half negation is an operand modifier.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// The equilibrium of a population with weight w_k and c . u = cu, reference src/physics_kernels.jl:310-313 / :330-333. ONE expression
+// for T = float (one population) and T = f32x2 (two populations of the same weight at once, finish_cell's opposite directions).
+template <class T>
+__device__ __forceinline__ T equilibrium_value(float rho, float w_k, T cu, float usq_eq)
+{
+    return rho * w_k * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * usq_eq);
+}
+
+// Two running sums that finish_cell advances side by side. PACKED: one register pair - a term for both is one packed add, a term
+// for one a scalar add on its half. Otherwise two floats. Either way each sum receives its own terms in its own order: the same bits.
+template <bool PACKED>
+struct Chain2;
+template <>
+struct Chain2<true> {
+    f32x2 v = {0.0f, 0.0f};
+    __device__ __forceinline__ void add_both(float a, float b) { v += f32x2{a, b}; }
+    __device__ __forceinline__ void add_first(float a) { v.x += a; }
+    __device__ __forceinline__ void add_second(float b) { v.y += b; }
+    __device__ __forceinline__ float first() const { return v.x; }
+    __device__ __forceinline__ float second() const { return v.y; }
+};
+template <>
+struct Chain2<false> {
+    float s0 = 0.0f, s1 = 0.0f;
+    __device__ __forceinline__ void add_both(float a, float b) { s0 += a; s1 += b; }
+    __device__ __forceinline__ void add_first(float a) { s0 += a; }
+    __device__ __forceinline__ void add_second(float b) { s1 += b; }
+    __device__ __forceinline__ float first() const { return s0; }
+    __device__ __forceinline__ float second() const { return s1; }
+};
+
+// The direction a population moves in, as collide_value takes it. DirConst<K>: all three components known at compile time - zero
+// terms are dropped by `if constexpr`. DirLaneFace: cx = +1 with cy, cz per-lane values (the record step's outer face column, where
+// one wave evaluates the rows of all nine (cy, cz) at once); a zero term is dropped by selecting the unchanged partial sum, never by
+// adding a product with zero, so every lane performs the operations DirConst of its (1, cy, cz) performs: the same bits.
+template <int K>
+struct DirConst {
+    static constexpr int cx = CX(K), cy = CY(K), cz = CZ(K);
+    __device__ __forceinline__ float weight() const { return WEIGHT(K); }
+    __device__ __forceinline__ float q_xx() const { return (float)cx * (float)cx - CS2_PHYSICS; }
+    __device__ __forceinline__ float q_yy() const { return (float)cy * (float)cy - CS2_PHYSICS; }
+    __device__ __forceinline__ float q_zz() const { return (float)cz * (float)cz - CS2_PHYSICS; }
+    // cx*a + cy*b + cz*c, left-associated, zero terms dropped
+    __device__ __forceinline__ float dot(float a, float b, float c) const { return cdot<K>(a, b, c); }
+    // inner + 2 (xy*cx*cy + yz*cy*cz + zx*cz*cx), the sum left-associated, zero terms dropped; all three zero: + 2*0 is an exact no-op
+    __device__ __forceinline__ float add_off_diagonal(float inner, float xy, float yz, float zx) const
+    {
+        float od = 0.0f;
+        bool od_empty = true;
+        acc_signed<cx * cy>(od, od_empty, xy);
+        acc_signed<cy * cz>(od, od_empty, yz);
+        acc_signed<cz * cx>(od, od_empty, zx);
+        if constexpr (cx * cy != 0 || cy * cz != 0 || cz * cx != 0) inner = inner + 2.0f * od;
+        return inner;
+    }
+};
+// acc_signed with a per-lane c
+__device__ __forceinline__ void acc_signed_lane(int c, float &sum, bool &empty, float v)
+{
+    const float t = c > 0 ? v : -v;
+    const float next = empty ? t : sum + t;
+    sum = c != 0 ? next : sum;
+    empty = empty && c == 0;
+}
+struct DirLaneFace {
+    int cy, cz;
+    __device__ __forceinline__ float weight() const
+    {
+        const int n = (cy != 0 ? 1 : 0) + (cz != 0 ? 1 : 0);
+        return n == 0 ? WEIGHT(DIR(1, 0, 0)) : (n == 1 ? WEIGHT(DIR(1, 1, 0)) : WEIGHT(DIR(1, 1, 1)));
+    }
+    __device__ __forceinline__ float q_xx() const { return 1.0f * 1.0f - CS2_PHYSICS; }
+    __device__ __forceinline__ float q_yy() const { return cy != 0 ? 1.0f * 1.0f - CS2_PHYSICS : 0.0f * 0.0f - CS2_PHYSICS; }
+    __device__ __forceinline__ float q_zz() const { return cz != 0 ? 1.0f * 1.0f - CS2_PHYSICS : 0.0f * 0.0f - CS2_PHYSICS; }
+    __device__ __forceinline__ float dot(float a, float b, float c) const
+    {
+        float s = a;
+        bool empty = false;
+        acc_signed_lane(cy, s, empty, b);
+        acc_signed_lane(cz, s, empty, c);
+        return s;
+    }
+    __device__ __forceinline__ float add_off_diagonal(float inner, float xy, float yz, float zx) const
+    {
+        float od = 0.0f;
+        bool od_empty = true;
+        acc_signed_lane(cy, od, od_empty, xy);
+        acc_signed_lane(cy * cz, od, od_empty, yz);
+        acc_signed_lane(cz, od, od_empty, zx);
+        return od_empty ? inner : inner + 2.0f * od;
+    }
+};
+template <class DIRECTION>
+__device__ __forceinline__ float collide_value(const DIRECTION d, float rho, float ux_eq, float uy_eq, float uz_eq, float Pi_xx, float Pi_yy,
+                                               float Pi_zz, float Pi_xy, float Pi_yz, float Pi_zx, float one_m_omega)
+{
+    const float w_k = d.weight();
+    const float usq_eq = ux_eq * ux_eq + uy_eq * uy_eq + uz_eq * uz_eq;
+    const float cu = d.dot(ux_eq, uy_eq, uz_eq);
+    const float feq = equilibrium_value<float>(rho, w_k, cu, usq_eq);
+    const float inner = d.add_off_diagonal(Pi_xx * d.q_xx() + Pi_yy * d.q_yy() + Pi_zz * d.q_zz(), Pi_xy, Pi_yz, Pi_zx);
+    const float f_neq_reg = (w_k * 4.5f) * inner;
+    return feq + one_m_omega * f_neq_reg;
+}
 template <int K>
 __device__ __forceinline__ float collide_value(float rho, float ux_eq, float uy_eq, float uz_eq, float Pi_xx, float Pi_yy, float Pi_zz,
                                                float Pi_xy, float Pi_yz, float Pi_zx, float one_m_omega)
 {
-    constexpr int cx = CX(K), cy = CY(K), cz = CZ(K);
-    constexpr float w_k = WEIGHT(K);
-    constexpr float cx_f = (float)cx, cy_f = (float)cy, cz_f = (float)cz;
-    const float usq_eq = ux_eq * ux_eq + uy_eq * uy_eq + uz_eq * uz_eq;
-    const float cu = cdot<K>(ux_eq, uy_eq, uz_eq);
-    const float feq = rho * w_k * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * usq_eq);
-    constexpr float Q_xx = cx_f * cx_f - CS2_PHYSICS, Q_yy = cy_f * cy_f - CS2_PHYSICS, Q_zz = cz_f * cz_f - CS2_PHYSICS;
-    // Pi_xy*cx*cy + Pi_yz*cy*cz + Pi_zx*cz*cx, left-associated, zero terms dropped
-    float od = 0.0f;
-    bool od_empty = true;
-    acc_signed<cx * cy>(od, od_empty, Pi_xy);
-    acc_signed<cy * cz>(od, od_empty, Pi_yz);
-    acc_signed<cz * cx>(od, od_empty, Pi_zx);
-    float inner = Pi_xx * Q_xx + Pi_yy * Q_yy + Pi_zz * Q_zz;
-    if constexpr (cx * cy != 0 || cy * cz != 0 || cz * cx != 0) inner = inner + 2.0f * od;   // else + 2*0: exact no-op
-    const float f_neq_reg = (w_k * 4.5f) * inner;
-    return feq + one_m_omega * f_neq_reg;
+    return collide_value(DirConst<K>{}, rho, ux_eq, uy_eq, uz_eq, Pi_xx, Pi_yy, Pi_zz, Pi_xy, Pi_yz, Pi_zx, one_m_omega);
 }
 
 // ---- Record step: storage ----
@@ -404,34 +496,40 @@ __device__ __forceinline__ void record_row(float (&fs)[Q], const float (&r)[R_CO
 }
 // The one population that crosses an x face out of the record's cell: cx = +1 (plus) or cx = -1. c * v for c = -1 is -v exactly, so
 // the cx = -1 value is the cx = +1 expression on (-ux, -Pi_xy, -Pi_zx): the same operands meet in the same operations.
-template <int CY_, int CZ_>
-__device__ __forceinline__ float record_face(const float (&r)[R_COMP], bool plus)
+template <class DIRECTION>
+__device__ __forceinline__ float record_face(const DIRECTION d, const float (&r)[R_COMP], bool plus)
 {
-    constexpr int k = 2 + 3 * (CY_ + 1) + 9 * (CZ_ + 1);
-    return collide_value<k>(r[R_RHO], plus ? r[R_UX] : -r[R_UX], r[R_UY], r[R_UZ], r[R_PXX], r[R_PYY], r[R_PZZ],
-                            plus ? r[R_PXY] : -r[R_PXY], r[R_PYZ], plus ? r[R_PZX] : -r[R_PZX], r[R_OMO]);
+    return collide_value(d, r[R_RHO], plus ? r[R_UX] : -r[R_UX], r[R_UY], r[R_UZ], r[R_PXX], r[R_PYY], r[R_PZZ],
+                         plus ? r[R_PXY] : -r[R_PXY], r[R_PYZ], plus ? r[R_PZX] : -r[R_PZX], r[R_OMO]);
 }
 
 // Everything after the loads: moments, obstacle bounce, sponge, wall model, WALE, regularized collision, stores.
 // reference src/physics_kernels.jl:144-354. fs = the 27 pulled populations, u?_? = previous-step velocity of the six
 // face neighbours. Shared by the per-wave kernel and the x-run kernel.
-template <bool POST, bool WALL, bool REC_OUT = false>
+// PACKED: the moment and stress sums and the 27 equilibria in packed FP32 (Chain2, equilibrium_value<f32x2>) - k_step_records. The f
+// path's instantiations are memory-bound and sit at their register limit (96 VGPRs for 5 waves), where the pairs' alignment costs
+// scratch or a wave (k_records_from_populations: 88 VGPRs, 5 waves instead of 6), so they instantiate the same expressions on float.
+template <bool POST, bool WALL, bool REC_OUT = false, bool PACKED = false>
 __device__ __forceinline__ void finish_cell(const SCParams &p, const int flags, const Own own, float (&fs)[Q],
                                             const float ux_E, const float uy_E, const float uz_E, const float ux_W, const float uy_W, const float uz_W,
                                             const float ux_N, const float uy_N, const float uz_N, const float ux_S, const float uy_S, const float uz_S,
                                             const float ux_T, const float uy_T, const float uz_T, const float ux_B, const float uy_B, const float uz_B)
 {
-    // moments in the reference's order: rho += f_k; j += f_k * c_k for k = 1..27
-    float rho = 0.0f, jx = 0.0f, jy = 0.0f, jz = 0.0f;
+    // moments in the reference's order: rho += f_k; j += f_k * c_k for k = 1..27. Four serial chains, each in k order, advanced as
+    // the pairs (rho, jx) and (jy, jz). a - b and a + (-b) are the same operation, so a c = -1 term is the negated value.
+    Chain2<PACKED> m_rx, m_yz;
     static_for<0, Q>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         constexpr int cx = CX(k), cy = CY(k), cz = CZ(k);
         const float val = fs[k];
-        rho += val;
-        if constexpr (cx == 1) jx += val; else if constexpr (cx == -1) jx -= val;
-        if constexpr (cy == 1) jy += val; else if constexpr (cy == -1) jy -= val;
-        if constexpr (cz == 1) jz += val; else if constexpr (cz == -1) jz -= val;
+        if constexpr (cx != 0) m_rx.add_both(val, cx > 0 ? val : -val);
+        else m_rx.add_first(val);
+        if constexpr (cy != 0 && cz != 0) m_yz.add_both(cy > 0 ? val : -val, cz > 0 ? val : -val);
+        else if constexpr (cy != 0) m_yz.add_first(cy > 0 ? val : -val);
+        else if constexpr (cz != 0) m_yz.add_second(cz > 0 ? val : -val);
     });
+    float rho = m_rx.first();
+    const float jx = m_rx.second(), jy = m_yz.first(), jz = m_yz.second();
 
     // the reference stores f_post_collision for every cell of a Bouzidi level (src/physics_kernels.jl:350-352); its only
     // reader is the Bouzidi kernel, at boundary cells and their link neighbours, so blocks that neither hold nor touch a
@@ -554,20 +652,35 @@ __device__ __forceinline__ void finish_cell(const SCParams &p, const int flags, 
     const float omega = 1.0f / jl_max(tau_turb, 0.500001f);
 
     // ---- non-equilibrium stress, reference :305-322 ----
-    float Pi_xx = 0.0f, Pi_yy = 0.0f, Pi_zz = 0.0f, Pi_xy = 0.0f, Pi_yz = 0.0f, Pi_zx = 0.0f;
+    // Six serial chains in k order, advanced as the pairs (Pi_xx, Pi_xy), (Pi_yy, Pi_yz), (Pi_zz, Pi_zx): the second of a pair takes a
+    // term only where the first does, and it is the same f_neq up to the sign.
+    // PACKED: directions k and 26 - k share the weight and have opposite c, so their two equilibria are evaluated at once, at k < 13, on
+    // (cu, -cu), and f_neq of 26 - k waits in fs for its turn. c_opp . u negates every term of c_k . u, and rounding is symmetric in
+    // sign, so it is -cu - except that a sum that cancels is +0 either way, where -cu is -0; 1 + 3 cu and 4.5 cu cu are the same
+    // bits for either zero.
+    Chain2<PACKED> P_x, P_y, P_z;
     static_for<0, Q>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
+        constexpr int k = decltype(kc)::value, ko = OPP(k);
         constexpr int cx = CX(k), cy = CY(k), cz = CZ(k);
-        const float cu = cdot<k>(ux_eq, uy_eq, uz_eq);
-        const float feq = rho * WEIGHT(k) * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * usq_eq);
-        const float f_neq = fs[k] - feq;
-        if constexpr (cx != 0) Pi_xx += f_neq;
-        if constexpr (cy != 0) Pi_yy += f_neq;
-        if constexpr (cz != 0) Pi_zz += f_neq;
-        if constexpr (cx * cy == 1) Pi_xy += f_neq; else if constexpr (cx * cy == -1) Pi_xy -= f_neq;
-        if constexpr (cy * cz == 1) Pi_yz += f_neq; else if constexpr (cy * cz == -1) Pi_yz -= f_neq;
-        if constexpr (cz * cx == 1) Pi_zx += f_neq; else if constexpr (cz * cx == -1) Pi_zx -= f_neq;
+        float f_neq;
+        if constexpr (PACKED && k < ko) {
+            const float cu = cdot<k>(ux_eq, uy_eq, uz_eq);
+            const f32x2 both = f32x2{fs[k], fs[ko]} - equilibrium_value<f32x2>(rho, WEIGHT(k), f32x2{cu, -cu}, usq_eq);
+            f_neq = both.x;
+            fs[ko] = both.y;
+        } else if constexpr (PACKED && k > ko) {
+            f_neq = fs[k];
+        } else {
+            f_neq = fs[k] - equilibrium_value<float>(rho, WEIGHT(k), cdot<k>(ux_eq, uy_eq, uz_eq), usq_eq);
+        }
+        if constexpr (cx * cy != 0) P_x.add_both(f_neq, cx * cy > 0 ? f_neq : -f_neq);
+        else if constexpr (cx != 0) P_x.add_first(f_neq);
+        if constexpr (cy * cz != 0) P_y.add_both(f_neq, cy * cz > 0 ? f_neq : -f_neq);
+        else if constexpr (cy != 0) P_y.add_first(f_neq);
+        if constexpr (cz * cx != 0) P_z.add_both(f_neq, cz * cx > 0 ? f_neq : -f_neq);
+        else if constexpr (cz != 0) P_z.add_first(f_neq);
     });
+    const float Pi_xx = P_x.first(), Pi_xy = P_x.second(), Pi_yy = P_y.first(), Pi_yz = P_y.second(), Pi_zz = P_z.first(), Pi_zx = P_z.second();
 
     // ---- regularized collision + write, reference :324-354 ----
     const float one_m_omega = 1.0f - omega;
@@ -842,12 +955,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_MIN_
 // addressing, as for populations: row (y - cy) & 7 of the own block or of the y neighbour - and evaluates collide_value for the 3
 // x directions of each; the x shift then is the usual lane shift plus face column. The previous step's velocity of the y and z
 // neighbours is in those same records (the centre one, cy = +-1 and cz = +-1), so no velocity is loaded and nothing is shuffled
-// in y. At the outer faces of a run the lanes of the face column load the x neighbour's 9 records and evaluate the one population
-// of each that crosses the face. Every block is all-neighbour, carries no obstacle / sponge / near-wall flag, and the level has no
+// in y. At the outer faces of a run the wave loads the x neighbour's 9 records of its face column, spread over all 64 lanes, and
+// evaluates the one population of each that crosses the face. Every block is all-neighbour, carries no obstacle / sponge / near-wall flag, and the level has no
 // wall model (the host's eligibility rule), so this is finish_cell<false, false> with flags = 0 - the f path's arithmetic, operation
 // by operation - and the result is stored as a record again.
 #ifndef LW_REC_WAVES
-#define LW_REC_WAVES 4      // waves per SIMD the register allocator must leave room for: 128 VGPRs (at 96 it spills 132 B per lane)
+#define LW_REC_WAVES 4      // waves per SIMD the register allocator must leave room for: 128 VGPRs, 107 used (at 96 the allocator spills)
 #endif
 #ifndef LW_REC_AHEAD
 #define LW_REC_AHEAD 3      // records whose loads are in flight while one is evaluated (11 registers each)
@@ -876,35 +989,44 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_REC_
     float fs[Q];
     float uc[3], uT[3], uB[3], uN[3], uS[3];
     if (active) {
-    // ---- the run's outer faces: lanes x = 0 of the first wave read column 7 of the -x neighbour, lanes x = 7 of the last wave
-    // column 0 of the +x neighbour (a lone block does both) ----
-    // Loads are staged: record j is evaluated while those of records j + 1 .. j + LW_REC_AHEAD are in flight, and the scheduler is kept
-    // from merging the stages (sched_barrier) - all 99 loads at once would need 99 registers beside the 27 populations.
+    // ---- the run's outer faces: the first wave needs column 7 of the -x neighbour, the last wave column 0 of the +x neighbour (a
+    // lone block both): per face 9 records x 8 rows, of each the one population that crosses the face ----
+    // Spread over the whole wave: lane (x', y) takes row y of record j = x', j = (cy+1) + 3 (cz+1) = 0..7, so (cy, cz), the source
+    // plane and the block - the x neighbour, or for the row that leaves it in y the y neighbour of the x neighbour - are per-lane
+    // selections among wave-uniform values, and the population is collide_value in its per-lane form (DirLaneFace). 11 loads and one
+    // evaluation with 64 lanes active, where eight lanes used to walk through nine records.
+    auto face_rows = [&](auto sc) {
+        constexpr int side = decltype(sc)::value;                     // 0: from -x, 1: from +x
+        constexpr int jx = side == 0 ? 4 - 1 : 4 + 1;
+        const int j = l.x;
+        const int jz = (j >= 3 ? 1 : 0) + (j >= 6 ? 1 : 0);         // j / 3
+        const int cy = j - 3 * jz - 1, cz = jz - 1, g = 2 - jz;      // g = 1 - cz
+        auto by_g = [&](int v0, int v1, int v2) { return g == 0 ? v0 : (g == 1 ? v1 : v2); };      // values, not lvalues (see source_block)
+        const int bX = by_g(nbr.id[0][jx], nbr.id[1][jx], nbr.id[2][jx]);
+        const int bXlo = by_g(nbr.id[0][jx - 3], nbr.id[1][jx - 3], nbr.id[2][jx - 3]);            // its -y neighbour: cy = +1 rows of y = 0
+        const int bXhi = by_g(nbr.id[0][jx + 3], nbr.id[1][jx + 3], nbr.id[2][jx + 3]);            // its +y neighbour: cy = -1 rows of y = 7
+        const int blk = (cy == 1 && l.y0) ? bXlo : ((cy == -1 && l.y7) ? bXhi : bX);
+        const int zsrc = by_g(nbr.zs[0], nbr.zs[1], nbr.zs[2]);
+        float r[R_COMP];
+        load_record_at(r, p.rec_in, record_offset<WIDE>(blk, zsrc) + (uint32_t)(((side == 0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
+        float(&mine)[12][8] = xedge[wave][side];
+        mine[j][l.y] = record_face(DirLaneFace{cy, cz}, r, side == 0);
+        if (j == 4) { mine[9][l.y] = r[R_UX]; mine[10][l.y] = r[R_UY]; mine[11][l.y] = r[R_UZ]; }      // cy = cz = 0: the face neighbour itself
+    };
+    if (first) face_rows(std::integral_constant<int, 0>{});
+    if (last) face_rows(std::integral_constant<int, 1>{});
+    // the ninth record (cy = cz = +1), in the lanes of the face column: four wave-uniform offsets, one chosen per lane
     if ((first && l.x0) || (last && l.x7)) {
-        float r[9][R_COMP];
-        auto load_face = [&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            constexpr int cy = j % 3 - 1, g = 1 - (j / 3 - 1);
-            const bool yo = cy == 1 ? l.y0 : (cy == -1 ? l.y7 : false);
-            const int wX = nbr.id[g][4 - 1], wXY = nbr.id[g][4 - 1 - 3 * cy], eX = nbr.id[g][4 + 1], eXY = nbr.id[g][4 + 1 - 3 * cy];
-            // four wave-uniform offsets, one chosen per lane
-            const auto oW = record_offset<WIDE>(wX, nbr.zs[g]), oWY = record_offset<WIDE>(wXY, nbr.zs[g]);
-            const auto oE = record_offset<WIDE>(eX, nbr.zs[g]), oEY = record_offset<WIDE>(eXY, nbr.zs[g]);
-            const auto off = l.x0 ? (yo ? oWY : oW) : (yo ? oEY : oE);
-            load_record_at(r[j], p.rec_in, off + (uint32_t)(((l.x0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
-        };
-        static_for<0, LW_REC_AHEAD>(load_face);
-        static_for<0, 9>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            constexpr int cy = j % 3 - 1, cz = j / 3 - 1;
-            if constexpr (j + LW_REC_AHEAD < 9) load_face(std::integral_constant<int, j + LW_REC_AHEAD>{});
-            __builtin_amdgcn_sched_barrier(0);
-            float(&mine)[12][8] = xedge[wave][l.x0 ? 0 : 1];
-            mine[j][l.y] = record_face<cy, cz>(r[j], l.x0);
-            if constexpr (cy == 0 && cz == 0) { mine[9][l.y] = r[j][R_UX]; mine[10][l.y] = r[j][R_UY]; mine[11][l.y] = r[j][R_UZ]; }
-            __builtin_amdgcn_sched_barrier(0);
-        });
+        constexpr int j = 8, cy = 1, g = 0;
+        const int wX = nbr.id[g][4 - 1], wXY = nbr.id[g][4 - 1 - 3 * cy], eX = nbr.id[g][4 + 1], eXY = nbr.id[g][4 + 1 - 3 * cy];
+        const auto oW = record_offset<WIDE>(wX, nbr.zs[g]), oWY = record_offset<WIDE>(wXY, nbr.zs[g]);
+        const auto oE = record_offset<WIDE>(eX, nbr.zs[g]), oEY = record_offset<WIDE>(eXY, nbr.zs[g]);
+        const auto off = l.x0 ? (l.y0 ? oWY : oW) : (l.y0 ? oEY : oE);
+        float r[R_COMP];
+        load_record_at(r, p.rec_in, off + (uint32_t)(((l.x0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
+        xedge[wave][l.x0 ? 0 : 1][j][l.y] = record_face(DirConst<DIR(1, 1, 1)>{}, r, l.x0);
     }
+    __builtin_amdgcn_sched_barrier(0);      // the faces are done before the pull's loads start: their registers are free again
     // ---- the 9 records at (x, y - cy, z - cz) ----
     {
         float r[9][R_COMP];
@@ -975,7 +1097,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_REC_
         uE[c] = l.x7 ? e_edge : e_in;
         uW[c] = l.x0 ? w_edge : w_in;
     }
-    finish_cell<false, false, true>(p, 0, own, fs, uE[0], uE[1], uE[2], uW[0], uW[1], uW[2], uN[0], uN[1], uN[2], uS[0], uS[1], uS[2],
+    finish_cell<false, false, true, true>(p, 0, own, fs, uE[0], uE[1], uE[2], uW[0], uW[1], uW[2], uN[0], uN[1], uN[2], uS[0], uS[1], uS[2],
                                     uT[0], uT[1], uT[2], uB[0], uB[1], uB[2]);
 }
 
