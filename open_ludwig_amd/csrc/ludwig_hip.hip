@@ -9,12 +9,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ludwig_hip.h"
-#include "all_or_nothing.hpp"
+#include "device_memory.hpp"
 #include "kernels.hpp"
 
 using namespace lw;
@@ -39,6 +41,23 @@ int fail(int code, const char *fmt, ...)
         hipError_t e_ = (call);                                                                           \
         if (e_ != hipSuccess) return fail(LUDWIG_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
+
+// Every release of device memory, events and streams in this file happens in these three policies (device_memory.hpp).
+struct HipMem {
+    static int alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static void release(void *p) { (void)hipFree(p); }
+};
+struct HipEventOps {
+    static int create(hipEvent_t *ev, unsigned flags = hipEventDisableTiming) { return (int)hipEventCreateWithFlags(ev, flags); }
+    static int destroy(hipEvent_t ev) { return (int)hipEventDestroy(ev); }
+};
+struct HipStreamOps {
+    static int create(hipStream_t *st, unsigned flags, int priority = 0) { return (int)hipStreamCreateWithPriority(st, flags, priority); }
+    static int destroy(hipStream_t st) { return (int)hipStreamDestroy(st); }
+};
+template <class T> using Dev = lw::DeviceArray<T, HipMem>;
+using HipEvent = lw::DeviceHandle<hipEvent_t, HipEventOps>;
+using HipStream = lw::DeviceHandle<hipStream_t, HipStreamOps>;
 
 constexpr int N_PARTS = 3, N_CLASSES = 3;   // class 1 = blocks with a missing neighbour (GENERAL instantiation), 2 = all-neighbour blocks; 0 unused
 constexpr int XRUN = 4, XRUN_MAX = 4;       // waves per workgroup = blocks of an x-run (8 and 16 were tried in rounds 1-2: slower)
@@ -91,7 +110,7 @@ int record_order() { const int v = flag("LUDWIG_RECORD_ORDER"); return v < 0 ? 1
 
 struct LudwigLevel {
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;         // borrowed: the caller's (ludwig_level_set_stream) or own_stream
     int level_id = 1, n_blocks = 0, n_owned = 0;
     float tau = 1.0f;
     int gdx = 0, gdy = 0, gdz = 0;
@@ -104,12 +123,12 @@ struct LudwigLevel {
     // Translated at the ABI like the block order; only raw pointers see it (ludwig_level_field_layout).
     int64_t sk = 0;        // cells of the level = 512 * n_blocks (the reference's population stride; here only a count)
     bool wide = false;     // 64-bit per-lane addresses: the level's f array is 4 GiB or more (>= 77 672 blocks), or LUDWIG_WIDE_ADDR
-    float *f[2] = {nullptr, nullptr};      // f, f_temp
-    float *vel[2] = {nullptr, nullptr};    // vel, vel_temp
-    float *rho = nullptr, *f_post = nullptr, *f_old = nullptr, *rho_old = nullptr, *vel_old = nullptr;
-    uint8_t *obstacle = nullptr;
-    float *sponge = nullptr, *wall_dist = nullptr;
-    int32_t *meta = nullptr;
+    Dev<float> f[2];                       // f, f_temp
+    Dev<float> vel[2];                     // vel, vel_temp
+    Dev<float> rho, f_post, f_old, rho_old, vel_old;
+    Dev<uint8_t> obstacle;
+    Dev<float> sponge, wall_dist;
+    Dev<int32_t> meta;
     bool has_temporal = false, has_post = false, bouzidi_enabled = false;
     // copy_to_old! without the copies: a pull step never writes its input buffers, so after ludwig_save_old(t_sub) the saved
     // f / vel ARE f[in] / vel[in] until something else writes that buffer. old_alias = that buffer index, or -1 when the
@@ -121,16 +140,16 @@ struct LudwigLevel {
     // ahead, rho is stored by every step.
     bool external_writer = false;
     int n_bc = 0;
-    int4 *bouzidi_links = nullptr;      // every listed link with q > 0 (the q map is static): kernels.hpp BouzidiParams::links
+    Dev<int4> bouzidi_links;            // every listed link with q > 0 (the q map is static): kernels.hpp BouzidiParams::links
     int n_bouzidi_links = 0;
-    uint32_t *post_rows = nullptr;      // [n_blocks][2] bits: the x-rows f_post_collision is read at by the links with q > 0 (SCParams::post_rows)
+    Dev<uint32_t> post_rows;            // [n_blocks][2] bits: the x-rows f_post_collision is read at by the links with q > 0 (SCParams::post_rows)
     std::vector<uint32_t> h_post_rows;  // host copy (ludwig_level_add_post_collision_readers ORs into it)
     int post_mode = 0;                  // 0: rows / blocks with a reader; 1: every block because asked to (flag, environment);
                                         // 2: every block because no cell list is owned and nobody has named the readers yet
     bool post_rows_used = false;        // the last stream-collide stored f_post_collision by rows (valid for q_min >= 0 only)
-    _Float16 *q_map = nullptr;
-    int32_t *cell_block = nullptr;
-    int8_t *cell_x = nullptr, *cell_y = nullptr, *cell_z = nullptr;
+    Dev<_Float16> q_map;
+    Dev<int32_t> cell_block;
+    Dev<int8_t> cell_x, cell_y, cell_z;
     // Block order. The caller's arrays keep the reference's block order (sort of (bx,by,bz) tuples, src/domain.jl:171: bz fastest
     // in memory, x neighbours 2 MB apart at 256^3). The device arrays hold the blocks in the library's own order - owned blocks
     // first, each group sorted with bx FASTEST - so that the four x-consecutive blocks an x-run workgroup steps are consecutive
@@ -140,15 +159,15 @@ struct LudwigLevel {
     // copy through `scratch`, one population at a time), halo pack / unpack (offsets translated in the kernel), set_order.
     std::vector<int32_t> ref2int, int2ref;      // empty = the reference order is kept (LUDWIG_REFERENCE_BLOCK_ORDER, or <= 1 block)
     bool x_fastest_memory = false;              // known while the default launch order is built (before ref2int is attached)
-    int32_t *d_ref2int = nullptr;
-    void *scratch = nullptr;                    // one population in the reference order (sk floats), allocated on first use
+    Dev<int32_t> d_ref2int;
+    Dev<float> scratch;                         // one population in the reference order (sk floats), allocated on first use
     std::vector<int32_t> h_meta;
     std::vector<uint8_t> h_comm_boundary;
-    int32_t *items[N_PARTS][N_CLASSES] = {};
+    Dev<int32_t> items[N_PARTS][N_CLASSES];
     int64_t n_items[N_PARTS][N_CLASSES] = {};
     // small levels step both kinds of blocks in ONE launch (merge_classes): the all-neighbour workgroups followed by the general ones,
     // through the GENERAL instantiation. The separate lists stay for the rho replay and for levels that are not merged.
-    int32_t *items_merged[N_PARTS] = {};
+    Dev<int32_t> items_merged[N_PARTS];
     int64_t n_items_merged[N_PARTS] = {};
     int n_fast_blocks = 0;
     bool general_in_runs[N_PARTS] = {};     // class-1 items are in x-run format (link bits, XRUN waves per workgroup)
@@ -156,19 +175,19 @@ struct LudwigLevel {
     int64_t device_bytes = 0;
     // coarse -> fine interface pass (levels >= 2): links per part, built lazily for the global box of the first step
     int n_iface_blocks = 0;
-    float *f_iface = nullptr;
-    int4 *links[N_PARTS] = {};           // per link: (block << 9) | cell, (gbi << 5) | k, source index
-    int4 *sources[N_PARTS] = {};        // per source cell: 8 parent-cell offsets of its trilinear stencil (-1 = absent), 2 x int4
-    float4 *source_w[N_PARTS] = {};     // per source cell: interpolation weights wx, wy, wz
-    float4 *source_mac[N_PARTS] = {};   // per source cell, rewritten every pass: interpolated rho, ux, uy, uz
-    float4 *source_mac2[N_PARTS] = {};  // the same for the speculated weight of the next sub-step
-    float *f_iface2 = nullptr;
+    Dev<float> f_iface;
+    Dev<int4> links[N_PARTS];            // per link: (block << 9) | cell, (gbi << 5) | k, source index
+    Dev<int4> sources[N_PARTS];         // per source cell: 8 parent-cell offsets of its trilinear stencil (-1 = absent), 2 x int4
+    Dev<float4> source_w[N_PARTS];      // per source cell: interpolation weights wx, wy, wz
+    Dev<float4> source_mac[N_PARTS];    // per source cell, rewritten every pass: interpolated rho, ux, uy, uz
+    Dev<float4> source_mac2[N_PARTS];   // the same for the speculated weight of the next sub-step
+    Dev<float> f_iface2;
     // What a set of interface values was computed from and for; every placement of the pass keeps its record in this one form, so a
     // key cannot be known to one and forgotten by another. The values hold while the parent was not written (parent_version) and
     // the question is asked for the same sub-step (or pair), weight, parent tau and blending mode.
     struct IfaceKey {
         bool valid = false;
-        const LudwigLevel *parent = nullptr;
+        const LudwigLevel *parent = nullptr;      // borrowed
         uint64_t parent_version = 0;
         int64_t step = 0;             // the sub-step the values are for; pair_ready: the pair, t_sub >> 1
         float tw = 0.0f, tau_parent = 0.0f;
@@ -207,8 +226,8 @@ struct LudwigLevel {
     } rho_replay[N_PARTS];              // only [LUDWIG_PART_ALL] is ever stale
     int64_t step_count = 0, last_step_t = -1, last_replay_step = -10;   // a level asked for rho after two steps in a row turns eager
     // ludwig_execute_timestep_batch runs every level on a stream of its own (level_streams below): events that order them
-    hipStream_t own_stream = nullptr;
-    hipEvent_t parent_wait = nullptr;   // set by recursive_step: the parent's step this sub-step's interface pass has to wait for
+    HipStream own_stream;
+    hipEvent_t parent_wait = nullptr;   // borrowed; set by recursive_step: the parent's step this sub-step's interface pass has to wait for
     // rho_old in the step: copy_to_old!'s copy of rho (the one field a step overwrites in place) costs a launch and two transitions on
     // a parent level's stream per step. The batch driver leaves it to the step that follows: every cell saves its old rho before it
     // stores the new one (kernels.hpp rho_old_save). Only whole-level launches of a level without ghost blocks; anything that
@@ -217,31 +236,31 @@ struct LudwigLevel {
     // Parent-side interface pass (level streams, recursive_step): the PARENT's stream computes this level's interface values for
     // the pair of sub-steps 2t, 2t + 1 right after the parent's step t, into set t & 1 of a second pair of side buffers - while this
     // level is still stepping pair t - 1 out of the other set. This level's own stream then carries no interface kernels at all.
-    float *f_iface_b = nullptr, *f_iface2_b = nullptr;             // set 1 (set 0 = f_iface, f_iface2)
-    float4 *mac_b = nullptr, *mac2_b = nullptr;                    // scratch of set 1's pass (LUDWIG_PART_ALL)
+    Dev<float> f_iface_b, f_iface2_b;                              // set 1 (set 0 = f_iface, f_iface2)
+    Dev<float4> mac_b, mac2_b;                                     // scratch of set 1's pass (LUDWIG_PART_ALL)
     IfaceKey pair_ready;                                           // step = the pair; tw = the first sub-step's weight, the second's is 0.5
-    hipEvent_t ev_pair_done[2] = {nullptr, nullptr};               // recorded on THIS level's stream after the second sub-step of a pair
+    HipEvent ev_pair_done[2];                                      // recorded on THIS level's stream after the second sub-step of a pair
     bool pair_done_set[2] = {false, false};
-    hipEvent_t ev_stepped = nullptr;    // recorded on this level's stream after each of its steps (collision + Bouzidi)
-    hipEvent_t ev_consumed = nullptr;   // recorded on the CHILD's stream once its interface pass has read this level's buffers
+    HipEvent ev_stepped;                // recorded on this level's stream after each of its steps (collision + Bouzidi)
+    HipEvent ev_consumed;               // recorded on the CHILD's stream once its interface pass has read this level's buffers
     bool ev_consumed_set = false;
     uint64_t stepped_gen = 0;           // how often ev_stepped has been recorded
-    const LudwigLevel *waited_parent = nullptr;   // the parent step this level's stream has already been made to wait for
+    const LudwigLevel *waited_parent = nullptr;   // borrowed: the parent step this level's stream has already been made to wait for
     uint64_t waited_gen = 0;
     uint64_t version = 0;               // bumped by everything that writes this level's fields
-    const LudwigLevel *iface_parent = nullptr;
+    const LudwigLevel *iface_parent = nullptr;    // borrowed
     std::vector<int32_t> h_block_pointer;   // [gdx,gdy,gdz] 1-based, 0 = absent (src/blocks.jl:111-114)
     int n_links[N_PARTS] = {};
     int n_sources[N_PARTS] = {};
     int iface_dims[3] = {-1, -1, -1};
     // time-averaged statistics (ludwig_level_stats_*): [n_blocks][STAT_COMPONENTS][512] doubles in the internal block order, allocated
     // by the first reset; only the owned blocks are ever accumulated, the ghost blocks stay zero
-    double *stats = nullptr;
+    Dev<double> stats;
     bool stats_ready = false;           // reset has been called
     int64_t stats_n = 0;                // samples accumulated since
     // velocity-gradient fields (ludwig_level_gradient_fields_*): [n_blocks][GRAD_COMPONENTS][512] floats in the internal block order,
     // allocated (and zeroed) by the first compute; only the owned blocks are ever written, the ghost blocks stay zero
-    float *grad = nullptr;
+    Dev<float> grad;
     bool grad_ready = false;            // compute has been called
     // subgrid model (ludwig_level_subgrid_*). The model constants are the step's own: every stream-collide launch of this level records
     // the c_wale and nu_sgs_background it was given, and the observers evaluate with those, so they cannot disagree with the step.
@@ -249,26 +268,26 @@ struct LudwigLevel {
     // [SUBGRID_SUM_COMPONENTS][512] doubles, allocated by the first reset. Internal block order; the ghost blocks stay zero.
     bool wale_known = false;            // a step has run
     float c_wale = 0.0f, nu_bg = 0.0f;
-    float *subgrid_fields = nullptr;
+    Dev<float> subgrid_fields;
     bool subgrid_fields_ready = false;  // compute has been called
-    double *subgrid_sums = nullptr;
+    Dev<double> subgrid_sums;
     bool subgrid_stats_ready = false;   // reset has been called
     int64_t subgrid_n = 0;              // samples accumulated since
     // flow monitor (ludwig_level_monitor): one MonitorRecord per owned block in the reference block order, then the records of every
     // combine stage (512 -> 1) behind them; allocated by the first call
-    MonitorRecord *monitor_slab = nullptr;
+    Dev<MonitorRecord> monitor_slab;
     // wall diagnostics (ludwig_level_wall_census): the one device record, allocated by the first call
-    WallCensusRecord *wall_census = nullptr;
+    Dev<WallCensusRecord> wall_census;
     // iso-surfaces (ludwig_level_isosurface_*): everything is allocated by the first extraction. iso_scalar: [n_blocks][512], the
     // magnitudes that are stored nowhere; counts / offsets / skip: one entry per owned block in the reference block order; the triangle
     // buffers hold iso_capacity triangles and grow when an extraction needs more.
-    float *iso_scalar = nullptr;
-    int32_t *iso_counts = nullptr;
-    int64_t *iso_offsets = nullptr;
-    uint8_t *iso_skip = nullptr;
-    int32_t *d_int2ref = nullptr;       // the internal -> reference block order on the device (a vertex key names reference blocks)
-    float *iso_pos = nullptr, *iso_att = nullptr;
-    int32_t *iso_keys = nullptr;
+    Dev<float> iso_scalar;
+    Dev<int32_t> iso_counts;
+    Dev<int64_t> iso_offsets;
+    Dev<uint8_t> iso_skip;
+    Dev<int32_t> d_int2ref;             // the internal -> reference block order on the device (a vertex key names reference blocks)
+    Dev<float> iso_pos, iso_att;
+    Dev<int32_t> iso_keys;
     int64_t iso_capacity = 0;
     int64_t iso_n = -1;                 // triangles of the last extraction (0 after a refusal); -1: none yet
     // Record step (kernels.hpp "Record step"). A plain level - record_eligible() - steps from 11-float collision records instead of
@@ -276,27 +295,42 @@ struct LudwigLevel {
     // hold there and rec_valid[q] the same for rec[q]; a record step into parity q makes rec[q] valid and f[q] / vel[q] stale, and
     // ensure_populations() brings them back with k_materialise before anything reads or hands them out. rho_in_rec = the parity
     // whose record holds the density `rho` should hold (the last record step's output), or -1 when `rho` itself is in charge.
-    float *rec[2] = {nullptr, nullptr};     // allocated by the first record step
+    Dev<float> rec[2];                      // allocated by the first record step
     bool f_valid[2] = {true, true}, rec_valid[2] = {false, false};
     int rho_in_rec = -1;
     int rec_eligible = -1;                  // the level's part of the rule: -1 unknown (recomputed after set_items / upload_meta)
     bool rec_banned = false;                // another level reads this one, or the record buffers could not be allocated: f path for good
     bool rec_hold = false;                  // a batch with in-batch observers or several levels is running: f path meanwhile
-    int32_t *rec_items = nullptr;           // the class-2 work list in the record path's order, see record_items()
+    Dev<int32_t> rec_items;                 // the class-2 work list in the record path's order, see record_items()
     int64_t n_record_steps = 0;
 };
 
 namespace {
 
 template <class T>
-int dev_alloc(LudwigLevel *L, T **p, size_t count)
+int dev_alloc(LudwigLevel *L, Dev<T> &p, size_t count)
 {
-    *p = nullptr;
-    if (count == 0) return LUDWIG_OK;
-    hipError_t e = hipMalloc((void **)p, count * sizeof(T));
-    if (e != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
+    const int e = p.alloc(count);
+    if (e) return fail(LUDWIG_ERR_ALLOC, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString((hipError_t)e));
     L->device_bytes += (int64_t)(count * sizeof(T));
     return LUDWIG_OK;
+}
+
+// A host table onto the device, unless an earlier table of the chain has failed already (e says so).
+template <class T>
+void upload_table(hipError_t &e, const std::vector<T> &h, Dev<T> &dev)
+{
+    if (e == hipSuccess) e = (hipError_t)dev.alloc(h.size());
+    if (e == hipSuccess && !h.empty()) e = hipMemcpy(dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// what ludwig_level_destroy and every ludwig_*_destroy of a set do: the object's device is current while its members release
+template <class S>
+void destroy_set(S *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    delete s;
 }
 
 int fill(LudwigLevel *L, float *a, int64_t n, float v)
@@ -438,6 +472,21 @@ int upload_meta(LudwigLevel *L)
     return LUDWIG_OK;
 }
 
+// h_post_rows onto the device: into the table the level has, or into a new one that becomes the level's once it is filled
+int upload_post_rows(LudwigLevel *L)
+{
+    if (L->post_rows) {
+        LW_HIP(hipMemcpy(L->post_rows, L->h_post_rows.data(), L->h_post_rows.size() * 4, hipMemcpyHostToDevice));
+        return LUDWIG_OK;
+    }
+    hipError_t e = hipSuccess;
+    Dev<uint32_t> rows;
+    upload_table(e, L->h_post_rows, rows);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "post-collision rows: %s", hipGetErrorString(e));
+    L->post_rows = std::move(rows);
+    return LUDWIG_OK;
+}
+
 bool block_in_part(const LudwigLevel *L, int b, int part)
 {
     if (b >= L->n_owned) return false;
@@ -461,10 +510,6 @@ int set_items(LudwigLevel *L, int part, const int32_t *items, int64_t n)
     // class 2: all-neighbour blocks, class 1: blocks with a missing neighbour - both through the x-run kernel;
     // class 0 (wave-by-wave kernel) only with LUDWIG_NO_XRUN (diagnostics).
     std::vector<int32_t> cls[N_CLASSES];
-    if (part == LUDWIG_PART_ALL) {            // the record step's work list is made from this part's: rebuilt on its next step
-        L->rec_eligible = -1;
-        if (L->rec_items) { (void)hipFree(L->rec_items); L->rec_items = nullptr; }
-    }
     auto is_fast = [&](int b) { return (L->h_meta[(size_t)b * NBR_STRIDE + NBR_FLAGS] & FLAG_ALL_NEIGHBOURS) != 0; };
     for (int64_t i = 0; i < n; ++i) {
         if (items[i] >= 0) {
@@ -474,7 +519,7 @@ int set_items(LudwigLevel *L, int part, const int32_t *items, int64_t n)
         }
     }
     const bool use_xrun = true;
-    L->general_in_runs[part] = true;
+    int64_t n_linked = 0;
     {
         // All-neighbour blocks -> x-run kernel (class 2), XRUN waves per workgroup; a wave is LINKED to the next one when
         // that one holds its +x neighbour block at the same plane (then the face column travels through LDS). Workgroups
@@ -507,9 +552,8 @@ int set_items(LudwigLevel *L, int part, const int32_t *items, int64_t n)
                     cls[c][g + w + 1] |= ITEM_LINK_W;
                 }
         }
-        L->n_linked_items[part] = 0;
         for (int32_t it : cls[2])
-            if (it >= 0 && (it & (ITEM_LINK_E | ITEM_LINK_W))) ++L->n_linked_items[part];
+            if (it >= 0 && (it & (ITEM_LINK_E | ITEM_LINK_W))) ++n_linked;
     }
     std::vector<int32_t> merged;
     if (use_xrun && merge_classes(L, cls[1], cls[2])) {
@@ -518,23 +562,29 @@ int set_items(LudwigLevel *L, int part, const int32_t *items, int64_t n)
         merged = cls[2];
         merged.insert(merged.end(), cls[1].begin(), cls[1].end());
     }
-    if (L->items_merged[part]) { (void)hipFree(L->items_merged[part]); L->items_merged[part] = nullptr; }
-    L->n_items_merged[part] = (int64_t)merged.size();
-    if (!merged.empty()) {
-        LW_HIP(hipMalloc((void **)&L->items_merged[part], merged.size() * 4));
-        LW_HIP(hipMemcpy(L->items_merged[part], merged.data(), merged.size() * 4, hipMemcpyHostToDevice));
-    }
+    // the new lists are made beside the level's; a failure leaves the level stepping on the lists it had
+    hipError_t e = hipSuccess;
+    Dev<int32_t> d_merged, d_cls[N_CLASSES];
+    upload_table(e, merged, d_merged);
     for (int c = 0; c < N_CLASSES; ++c) {
         bool any = false;
         for (int32_t it : cls[c]) any = any || it >= 0;
         if (!any) cls[c].clear();
         while (cls[c].size() % XRUN) cls[c].push_back(-1);
-        if (L->items[part][c]) { (void)hipFree(L->items[part][c]); L->items[part][c] = nullptr; }
+        upload_table(e, cls[c], d_cls[c]);
+    }
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "work lists of part %d: %s", part, hipGetErrorString(e));
+    L->general_in_runs[part] = true;
+    L->n_linked_items[part] = n_linked;
+    L->items_merged[part] = std::move(d_merged);
+    L->n_items_merged[part] = (int64_t)merged.size();
+    for (int c = 0; c < N_CLASSES; ++c) {
+        L->items[part][c] = std::move(d_cls[c]);
         L->n_items[part][c] = (int64_t)cls[c].size();
-        if (!cls[c].empty()) {
-            LW_HIP(hipMalloc((void **)&L->items[part][c], cls[c].size() * 4));
-            LW_HIP(hipMemcpy(L->items[part][c], cls[c].data(), cls[c].size() * 4, hipMemcpyHostToDevice));
-        }
+    }
+    if (part == LUDWIG_PART_ALL) {            // the record step's work list is made from this part's: rebuilt on its next step
+        L->rec_eligible = -1;
+        L->rec_items.reset();
     }
     return LUDWIG_OK;
 }
@@ -645,6 +695,9 @@ int build_interface_links(LudwigLevel *L, const LudwigLevel *parent, int nx_g, i
     LW_HIP(hipStreamSynchronize(L->stream));
     struct Link { int64_t key; int sx, sy, sz; int2 e; };
     std::vector<Link> raw[N_PARTS];
+    // every table is made beside the level's and moved in at the end: a failure leaves the level with the tables it had
+    struct Tables { Dev<int4> links, sources; Dev<float4> w, mac, mac2; int n_links = 0, n_sources = 0; } made[N_PARTS];
+    hipError_t e = hipSuccess;
     for (int b = 0; b < L->n_owned; ++b) {
         const int32_t *row = &L->h_meta[(size_t)b * NBR_STRIDE];
         const int gbi = row[NBR_GBI];
@@ -703,29 +756,33 @@ int build_interface_links(LudwigLevel *L, const LudwigLevel *parent, int nx_g, i
         // read neighbouring parent cells of ONE population array (a few 128-B lines per wave-load instead of ~30) and
         // write neighbouring cells of f_iface.
         std::stable_sort(links.begin(), links.end(), [](const int4 &u, const int4 &v) { return (u.y & 31) < (v.y & 31); });
-        L->ahead[a2].valid = false;
-        void **owned[] = {(void **)&L->links[a2], (void **)&L->sources[a2], (void **)&L->source_w[a2], (void **)&L->source_mac[a2],
-                          (void **)&L->source_mac2[a2]};
-        for (void **q : owned)
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-        L->n_links[a2] = (int)links.size();
-        L->n_sources[a2] = (int)weights.size();
-        if (!links.empty()) {
-            LW_HIP(hipMalloc((void **)&L->links[a2], links.size() * sizeof(int4)));
-            LW_HIP(hipMemcpy(L->links[a2], links.data(), links.size() * sizeof(int4), hipMemcpyHostToDevice));
-            LW_HIP(hipMalloc((void **)&L->sources[a2], corners.size() * sizeof(int4)));
-            LW_HIP(hipMemcpy(L->sources[a2], corners.data(), corners.size() * sizeof(int4), hipMemcpyHostToDevice));
-            LW_HIP(hipMalloc((void **)&L->source_w[a2], weights.size() * sizeof(float4)));
-            LW_HIP(hipMemcpy(L->source_w[a2], weights.data(), weights.size() * sizeof(float4), hipMemcpyHostToDevice));
-            LW_HIP(hipMalloc((void **)&L->source_mac[a2], weights.size() * sizeof(float4)));
-            LW_HIP(hipMalloc((void **)&L->source_mac2[a2], weights.size() * sizeof(float4)));
-
-        }
+        Tables &t = made[a2];
+        t.n_links = (int)links.size();
+        t.n_sources = (int)weights.size();
+        upload_table(e, links, t.links);
+        upload_table(e, corners, t.sources);
+        upload_table(e, weights, t.w);
+        if (e == hipSuccess) e = (hipError_t)t.mac.alloc(weights.size());
+        if (e == hipSuccess) e = (hipError_t)t.mac2.alloc(weights.size());
     }
-    if (!L->f_iface && L->n_iface_blocks > 0) {
-        LW_HIP(hipMalloc((void **)&L->f_iface, (size_t)L->n_iface_blocks * CELLS * Q * sizeof(float)));
-        LW_HIP(hipMalloc((void **)&L->f_iface2, (size_t)L->n_iface_blocks * CELLS * Q * sizeof(float)));
-        L->device_bytes += 2 * (int64_t)L->n_iface_blocks * CELLS * Q * 4;
+    const bool first = !L->f_iface && L->n_iface_blocks > 0;      // the pair of side buffers is sized with the level: made once
+    const size_t n_side = (size_t)L->n_iface_blocks * CELLS * Q;
+    Dev<float> side, side2;
+    if (first && e == hipSuccess) e = (hipError_t)side.alloc(n_side);
+    if (first && e == hipSuccess) e = (hipError_t)side2.alloc(n_side);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "interface links of level %d: %s", L->level_id, hipGetErrorString(e));
+    for (int a2 = 0; a2 < N_PARTS; ++a2) {
+        Tables &t = made[a2];
+        L->ahead[a2].valid = false;
+        L->links[a2] = std::move(t.links); L->sources[a2] = std::move(t.sources); L->source_w[a2] = std::move(t.w);
+        L->source_mac[a2] = std::move(t.mac); L->source_mac2[a2] = std::move(t.mac2);
+        L->n_links[a2] = t.n_links;
+        L->n_sources[a2] = t.n_sources;
+    }
+    if (first) {
+        L->f_iface = std::move(side);
+        L->f_iface2 = std::move(side2);
+        L->device_bytes += 2 * (int64_t)n_side * 4;
     }
     L->iface_parent = parent;
     L->iface_dims[0] = nx_g; L->iface_dims[1] = ny_g; L->iface_dims[2] = nz_g;
@@ -865,16 +922,20 @@ static int interface_launch(LudwigLevel *L, const LudwigLevel *parent, int part,
 static int make_second_iface_set(LudwigLevel *C, size_t n_side, size_t n_src)
 {
     if (C->f_iface_b) return LUDWIG_OK;
-    void **const bufs[4] = {(void **)&C->f_iface_b, (void **)&C->f_iface2_b, (void **)&C->mac_b, (void **)&C->mac2_b};
-    const size_t bytes[4] = {n_side * sizeof(float), n_side * sizeof(float), n_src * sizeof(float4), n_src * sizeof(float4)};
-    hipEvent_t *const evs[2] = {&C->ev_pair_done[0], &C->ev_pair_done[1]};
-    hipError_t e = hipSuccess;
-    const bool made = lw::make_all_or_nothing(
-        bufs, bytes, evs, [&](void **q, size_t n) { return (e = hipMalloc(q, n)) == hipSuccess; }, [](void *q) { (void)hipFree(q); },
-        [&](hipEvent_t *ev) { return (e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) == hipSuccess; },
-        [](hipEvent_t ev) { (void)hipEventDestroy(ev); });
-    if (!made) return fail(LUDWIG_ERR_HIP, "second set of interface side buffers: %s", hipGetErrorString(e));
-    C->device_bytes += (int64_t)(bytes[0] + bytes[1] + bytes[2] + bytes[3]);
+    Dev<float> side, side2;
+    Dev<float4> mac, mac2;
+    HipEvent done[2];
+    int e = side.alloc(n_side);
+    if (!e) e = side2.alloc(n_side);
+    if (!e) e = mac.alloc(n_src);
+    if (!e) e = mac2.alloc(n_src);
+    if (!e) e = done[0].create();
+    if (!e) e = done[1].create();
+    if (e) return fail(LUDWIG_ERR_HIP, "second set of interface side buffers: %s", hipGetErrorString((hipError_t)e));
+    C->f_iface_b = std::move(side); C->f_iface2_b = std::move(side2);
+    C->mac_b = std::move(mac); C->mac2_b = std::move(mac2);
+    C->ev_pair_done[0] = std::move(done[0]); C->ev_pair_done[1] = std::move(done[1]);
+    C->device_bytes += (int64_t)(2 * n_side * sizeof(float) + 2 * n_src * sizeof(float4));
     return LUDWIG_OK;
 }
 
@@ -964,8 +1025,11 @@ int build_record_items(LudwigLevel *L)
                 for (int x = 0; x < 8; ++x)
                     for (int w = 0; w < XRUN; ++w) dst[(size_t)(t0 + 8 * j + x) * XRUN + w] = src[(size_t)(t0 + 8 * x + j) * XRUN + w];
     }
-    LW_HIP(hipMalloc((void **)&L->rec_items, (size_t)n * 4));
-    LW_HIP(hipMemcpy(L->rec_items, dst.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    hipError_t e = hipSuccess;
+    Dev<int32_t> made;
+    upload_table(e, dst, made);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "record work list: %s", hipGetErrorString(e));
+    L->rec_items = std::move(made);
     return LUDWIG_OK;
 }
 
@@ -977,16 +1041,15 @@ int record_step_wanted(LudwigLevel *L, const LudwigLevel *parent, const LudwigSt
         fl->wall_model_active || !record_level_ok(L))
         return LUDWIG_OK;
     if (!L->rec[0]) {
-        const size_t bytes = (size_t)L->n_blocks * R_BLOCK_BYTES;
-        float *a = nullptr, *b = nullptr;
-        if (hipMalloc((void **)&a, bytes) != hipSuccess || hipMalloc((void **)&b, bytes) != hipSuccess) {
+        const size_t n = (size_t)L->n_blocks * R_BLOCK_BYTES / sizeof(float);
+        Dev<float> a, b;
+        if (a.alloc(n) || b.alloc(n)) {
             (void)hipGetLastError();                 // no room for the records: the f path needs none
-            if (a) (void)hipFree(a);
             L->rec_banned = true;
             return LUDWIG_OK;
         }
-        L->rec[0] = a; L->rec[1] = b;
-        L->device_bytes += (int64_t)(2 * bytes);
+        L->rec[0] = std::move(a); L->rec[1] = std::move(b);
+        L->device_bytes += (int64_t)(2 * n * sizeof(float));
     }
     if (!L->rec_items) {
         const int r = build_record_items(L);
@@ -1242,21 +1305,22 @@ int copy_field(LudwigLevel *L, void *dev, void *host, int K, size_t es, bool to_
         LW_HIP(hipStreamSynchronize(L->stream));
         return LUDWIG_OK;
     }
-    if (!L->scratch) LW_HIP(hipMalloc(&L->scratch, (size_t)L->sk * 4));
+    if (!L->scratch) LW_HIP((hipError_t)L->scratch.alloc((size_t)L->sk));
+    void *const scratch = L->scratch;
     const int64_t n = L->sk;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     for (int k = 0; k < K; ++k) {
         char *h = (char *)host + (size_t)k * plane;
         if (to_device) {
-            LW_HIP(hipMemcpyAsync(L->scratch, h, plane, hipMemcpyHostToDevice, L->stream));
-            if (es == 1) hipLaunchKernelGGL(k_component_to_internal<uint8_t>, grid, block, 0, L->stream, (uint8_t *)dev, (const uint8_t *)L->scratch, L->d_ref2int, n, K, k);
-            else if (es == 2) hipLaunchKernelGGL(k_component_to_internal<uint16_t>, grid, block, 0, L->stream, (uint16_t *)dev, (const uint16_t *)L->scratch, L->d_ref2int, n, K, k);
-            else hipLaunchKernelGGL(k_component_to_internal<float>, grid, block, 0, L->stream, (float *)dev, (const float *)L->scratch, L->d_ref2int, n, K, k);
+            LW_HIP(hipMemcpyAsync(scratch, h, plane, hipMemcpyHostToDevice, L->stream));
+            if (es == 1) hipLaunchKernelGGL(k_component_to_internal<uint8_t>, grid, block, 0, L->stream, (uint8_t *)dev, (const uint8_t *)scratch, L->d_ref2int, n, K, k);
+            else if (es == 2) hipLaunchKernelGGL(k_component_to_internal<uint16_t>, grid, block, 0, L->stream, (uint16_t *)dev, (const uint16_t *)scratch, L->d_ref2int, n, K, k);
+            else hipLaunchKernelGGL(k_component_to_internal<float>, grid, block, 0, L->stream, (float *)dev, (const float *)scratch, L->d_ref2int, n, K, k);
         } else {
-            if (es == 1) hipLaunchKernelGGL(k_component_to_reference<uint8_t>, grid, block, 0, L->stream, (uint8_t *)L->scratch, (const uint8_t *)dev, L->d_ref2int, n, K, k);
-            else if (es == 2) hipLaunchKernelGGL(k_component_to_reference<uint16_t>, grid, block, 0, L->stream, (uint16_t *)L->scratch, (const uint16_t *)dev, L->d_ref2int, n, K, k);
-            else hipLaunchKernelGGL(k_component_to_reference<float>, grid, block, 0, L->stream, (float *)L->scratch, (const float *)dev, L->d_ref2int, n, K, k);
-            LW_HIP(hipMemcpyAsync(h, L->scratch, plane, hipMemcpyDeviceToHost, L->stream));
+            if (es == 1) hipLaunchKernelGGL(k_component_to_reference<uint8_t>, grid, block, 0, L->stream, (uint8_t *)scratch, (const uint8_t *)dev, L->d_ref2int, n, K, k);
+            else if (es == 2) hipLaunchKernelGGL(k_component_to_reference<uint16_t>, grid, block, 0, L->stream, (uint16_t *)scratch, (const uint16_t *)dev, L->d_ref2int, n, K, k);
+            else hipLaunchKernelGGL(k_component_to_reference<float>, grid, block, 0, L->stream, (float *)scratch, (const float *)dev, L->d_ref2int, n, K, k);
+            LW_HIP(hipMemcpyAsync(h, scratch, plane, hipMemcpyDeviceToHost, L->stream));
             LW_HIP(hipStreamSynchronize(L->stream));          // pageable destination: the copy must be over before scratch is reused
         }
         LW_HIP(hipGetLastError());
@@ -1269,32 +1333,21 @@ int copy_field(LudwigLevel *L, void *dev, void *host, int K, size_t es, bool to_
 // the reference layout: one component at a time into a plane in the reference block order, which is copied out. A result-file call,
 // so the plane is allocated per call. Synchronous on the level's stream.
 template <class T>
-int download_components(const LudwigLevel *L, const T *dev, int K_total, int first, int K, T *host, const char *what)
+int download_components(const LudwigLevel *L, const T *dev, int K_total, int first, int K, T *host)
 {
     const size_t plane = (size_t)L->sk * sizeof(T);
     LW_HIP(hipSetDevice(L->device));
-    T *tmp = nullptr;
-    LW_HIP(hipMalloc((void **)&tmp, plane));
-    hipError_t e = hipSuccess;
+    Dev<T> tmp;
+    LW_HIP((hipError_t)tmp.alloc((size_t)L->sk));
     const int64_t n = L->sk;
-    for (int k = 0; k < K && e == hipSuccess; ++k) {
-        hipLaunchKernelGGL(k_component_to_reference<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L->stream, tmp, dev, L->d_ref2int, n,
-                           K_total, first + k);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync((char *)host + (size_t)k * plane, tmp, plane, hipMemcpyDeviceToHost, L->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
+    for (int k = 0; k < K; ++k) {
+        hipLaunchKernelGGL(k_component_to_reference<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L->stream, tmp.get(), dev,
+                           L->d_ref2int.get(), n, K_total, first + k);
+        LW_HIP(hipGetLastError());
+        LW_HIP(hipMemcpyAsync((char *)host + (size_t)k * plane, tmp, plane, hipMemcpyDeviceToHost, L->stream));
+        LW_HIP(hipStreamSynchronize(L->stream));
     }
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return LUDWIG_OK;
-}
-
-// A host table onto the device, unless an earlier table of the chain has failed already (e says so).
-template <class T>
-void upload_table(hipError_t &e, const std::vector<T> &h, T *&dev)
-{
-    if (e == hipSuccess) e = hipMalloc((void **)&dev, h.size() * sizeof(T));
-    if (e == hipSuccess) e = hipMemcpy(dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
 }  // namespace
@@ -1315,56 +1368,7 @@ int ludwig_device_count(int *count)
     return LUDWIG_OK;
 }
 
-void ludwig_level_destroy(LudwigLevel *L)
-{
-    if (!L) return;
-    (void)hipSetDevice(L->device);
-    void *ptrs[] = {L->f[0], L->f[1], L->vel[0], L->vel[1], L->rho, L->f_post, L->f_old, L->rho_old, L->vel_old, L->obstacle,
-                    L->sponge, L->wall_dist, L->meta, L->q_map, L->cell_block, L->cell_x, L->cell_y, L->cell_z};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (int a = 0; a < N_PARTS; ++a) {
-        for (int c = 0; c < N_CLASSES; ++c)
-            if (L->items[a][c]) (void)hipFree(L->items[a][c]);
-        if (L->items_merged[a]) (void)hipFree(L->items_merged[a]);
-        if (L->links[a]) (void)hipFree(L->links[a]);
-        if (L->sources[a]) (void)hipFree(L->sources[a]);
-        if (L->source_w[a]) (void)hipFree(L->source_w[a]);
-        if (L->source_mac[a]) (void)hipFree(L->source_mac[a]);
-        if (L->source_mac2[a]) (void)hipFree(L->source_mac2[a]);
-    }
-    if (L->f_iface) (void)hipFree(L->f_iface);
-    if (L->rec[0]) (void)hipFree(L->rec[0]);
-    if (L->rec[1]) (void)hipFree(L->rec[1]);
-    if (L->rec_items) (void)hipFree(L->rec_items);
-    if (L->stats) (void)hipFree(L->stats);
-    if (L->grad) (void)hipFree(L->grad);
-    if (L->subgrid_fields) (void)hipFree(L->subgrid_fields);
-    if (L->subgrid_sums) (void)hipFree(L->subgrid_sums);
-    if (L->monitor_slab) (void)hipFree(L->monitor_slab);
-    if (L->wall_census) (void)hipFree(L->wall_census);
-    {
-        void *iso[] = {L->iso_scalar, L->iso_counts, L->iso_offsets, L->iso_skip, L->d_int2ref, L->iso_pos, L->iso_att, L->iso_keys};
-        for (void *q : iso)
-            if (q) (void)hipFree(q);
-    }
-    if (L->d_ref2int) (void)hipFree(L->d_ref2int);
-    if (L->scratch) (void)hipFree(L->scratch);
-    if (L->own_stream) (void)hipStreamDestroy(L->own_stream);
-    if (L->ev_stepped) (void)hipEventDestroy(L->ev_stepped);
-    if (L->ev_consumed) (void)hipEventDestroy(L->ev_consumed);
-    if (L->bouzidi_links) (void)hipFree(L->bouzidi_links);
-    if (L->post_rows) (void)hipFree(L->post_rows);
-    if (L->f_iface2) (void)hipFree(L->f_iface2);
-    {
-        void *more[] = {L->f_iface_b, L->f_iface2_b, L->mac_b, L->mac2_b};
-        for (void *q : more)
-            if (q) (void)hipFree(q);
-        for (hipEvent_t ev : L->ev_pair_done)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    delete L;
-}
+void ludwig_level_destroy(LudwigLevel *L) { destroy_set(L); }
 
 static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel **out, bool x_fastest_memory);
 
@@ -1444,8 +1448,8 @@ int ludwig_level_create(const LudwigLevelHost *h, int device, LudwigLevel **out)
     LudwigLevel *L = *out;
     L->ref2int.swap(ref2int);
     L->int2ref.swap(int2ref);
-    hipError_t e = hipMalloc((void **)&L->d_ref2int, n * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(L->d_ref2int, L->ref2int.data(), n * sizeof(int32_t), hipMemcpyHostToDevice);
+    hipError_t e = hipSuccess;
+    upload_table(e, L->ref2int, L->d_ref2int);
     if (e != hipSuccess) { ludwig_level_destroy(L); *out = nullptr; return fail(LUDWIG_ERR_HIP, "block order table: %s", hipGetErrorString(e)); }
     return LUDWIG_OK;
 }
@@ -1464,7 +1468,8 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
     if (device < 0 || device >= ndev) return fail(LUDWIG_ERR_INVALID, "device %d out of range (have %d)", device, ndev);
     LW_HIP(hipSetDevice(device));
 
-    LudwigLevel *L = new (std::nothrow) LudwigLevel();
+    std::unique_ptr<LudwigLevel> owner(new (std::nothrow) LudwigLevel());       // the device is current: whatever fails below, it releases
+    LudwigLevel *const L = owner.get();
     if (!L) return fail(LUDWIG_ERR_ALLOC, "host allocation failed");
     L->device = device;
     L->x_fastest_memory = x_fastest_memory;
@@ -1480,37 +1485,35 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
     L->bouzidi_enabled = h->n_boundary_cells > 0 && h->bouzidi_q_map;        // reference src/blocks.jl:152
     L->n_bc = L->bouzidi_enabled ? h->n_boundary_cells : 0;
     L->has_post = h->n_boundary_cells != 0 && nb > 0;                         // reference src/blocks.jl:135 (< 0: forced, multi-GPU)
-    if (L->bouzidi_enabled && (!h->bouzidi_cell_block || !h->bouzidi_cell_x || !h->bouzidi_cell_y || !h->bouzidi_cell_z)) {
-        delete L;
+    if (L->bouzidi_enabled && (!h->bouzidi_cell_block || !h->bouzidi_cell_x || !h->bouzidi_cell_y || !h->bouzidi_cell_z))
         return fail(LUDWIG_ERR_INVALID, "bouzidi cell lists missing");
-    }
 
     int rc = LUDWIG_OK;
 #define LW_TRY(expr) do { if (rc == LUDWIG_OK) rc = (expr); } while (0)
-    LW_TRY(dev_alloc(L, &L->f[0], c * Q));
-    LW_TRY(dev_alloc(L, &L->f[1], c * Q));
-    LW_TRY(dev_alloc(L, &L->vel[0], c * 3));
-    LW_TRY(dev_alloc(L, &L->vel[1], c * 3));
-    LW_TRY(dev_alloc(L, &L->rho, c));
-    if (L->has_post) LW_TRY(dev_alloc(L, &L->f_post, c * Q));
+    LW_TRY(dev_alloc(L, L->f[0], c * Q));
+    LW_TRY(dev_alloc(L, L->f[1], c * Q));
+    LW_TRY(dev_alloc(L, L->vel[0], c * 3));
+    LW_TRY(dev_alloc(L, L->vel[1], c * 3));
+    LW_TRY(dev_alloc(L, L->rho, c));
+    if (L->has_post) LW_TRY(dev_alloc(L, L->f_post, c * Q));
     if (L->has_temporal) {
-        LW_TRY(dev_alloc(L, &L->f_old, c * Q));
-        LW_TRY(dev_alloc(L, &L->rho_old, c));
-        LW_TRY(dev_alloc(L, &L->vel_old, c * 3));
+        LW_TRY(dev_alloc(L, L->f_old, c * Q));
+        LW_TRY(dev_alloc(L, L->rho_old, c));
+        LW_TRY(dev_alloc(L, L->vel_old, c * 3));
     }
-    LW_TRY(dev_alloc(L, &L->obstacle, c));
-    LW_TRY(dev_alloc(L, &L->sponge, c));
-    LW_TRY(dev_alloc(L, &L->wall_dist, c));
-    LW_TRY(dev_alloc(L, &L->meta, nb * NBR_STRIDE));
+    LW_TRY(dev_alloc(L, L->obstacle, c));
+    LW_TRY(dev_alloc(L, L->sponge, c));
+    LW_TRY(dev_alloc(L, L->wall_dist, c));
+    LW_TRY(dev_alloc(L, L->meta, nb * NBR_STRIDE));
     const size_t nptr = (size_t)h->grid_dim_x * h->grid_dim_y * h->grid_dim_z;
     if (L->bouzidi_enabled) {
-        LW_TRY(dev_alloc(L, &L->q_map, c * Q));
-        LW_TRY(dev_alloc(L, &L->cell_block, (size_t)L->n_bc));
-        LW_TRY(dev_alloc(L, &L->cell_x, (size_t)L->n_bc));
-        LW_TRY(dev_alloc(L, &L->cell_y, (size_t)L->n_bc));
-        LW_TRY(dev_alloc(L, &L->cell_z, (size_t)L->n_bc));
+        LW_TRY(dev_alloc(L, L->q_map, c * Q));
+        LW_TRY(dev_alloc(L, L->cell_block, (size_t)L->n_bc));
+        LW_TRY(dev_alloc(L, L->cell_x, (size_t)L->n_bc));
+        LW_TRY(dev_alloc(L, L->cell_y, (size_t)L->n_bc));
+        LW_TRY(dev_alloc(L, L->cell_z, (size_t)L->n_bc));
     }
-    if (rc != LUDWIG_OK) { ludwig_level_destroy(L); return rc; }
+    if (rc != LUDWIG_OK) return rc;
 
     // metadata rows: neighbours 0-based (-1 absent), flags, block coords
     L->h_meta.assign(nb * NBR_STRIDE, 0);
@@ -1519,7 +1522,7 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
         bool all = true;
         for (int d = 0; d < 27; ++d) {
             const int32_t v = h->neighbor_table[b + nb * d];
-            if (v < 0 || v > h->n_blocks) { ludwig_level_destroy(L); return fail(LUDWIG_ERR_INVALID, "neighbor_table[%zu,%d] = %d out of range", b + 1, d + 1, v); }
+            if (v < 0 || v > h->n_blocks) return fail(LUDWIG_ERR_INVALID, "neighbor_table[%zu,%d] = %d out of range", b + 1, d + 1, v);
             row[d] = v - 1;
             if (d != 13 && v == 0) all = false;
         }
@@ -1599,11 +1602,12 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
             // cells that are mostly neighbours along x - their f_post loads and f_out stores share 32-B sectors instead of touching 64
             // different 2-KiB population slices of a few cells (every link writes its own (cell, opp k): the order is free)
             std::sort(bl.begin(), bl.end(), [](const int4 &a, const int4 &c) { return a.y != c.y ? a.y < c.y : a.x < c.x; });
+            hipError_t e = hipSuccess;
+            Dev<int4> links;
+            upload_table(e, bl, links);
+            if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "bouzidi links: %s", hipGetErrorString(e));
+            L->bouzidi_links = std::move(links);
             L->n_bouzidi_links = (int)bl.size();
-            if (!bl.empty()) {
-                LW_HIP(hipMalloc((void **)&L->bouzidi_links, bl.size() * sizeof(int4)));
-                LW_HIP(hipMemcpy(L->bouzidi_links, bl.data(), bl.size() * sizeof(int4), hipMemcpyHostToDevice));
-            }
         }
         if (L->has_post) {
             // where f_post_collision has a reader: blocks that hold a Bouzidi cell or a cell next to one (a link q < 1/2 reads
@@ -1631,8 +1635,8 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
                 auto mark = [&](int cell) { const int row = (cell & (CELLS - 1)) >> 3; L->h_post_rows[(size_t)(cell / CELLS) * 2 + (row >> 5)] |= 1u << (row & 31); };
                 for (const int4 &l : bl) { mark(l.x); if (l.w >= 0) mark(l.w); }
                 if (!everywhere) {
-                    LW_HIP(hipMalloc((void **)&L->post_rows, L->h_post_rows.size() * 4));
-                    LW_HIP(hipMemcpy(L->post_rows, L->h_post_rows.data(), L->h_post_rows.size() * 4, hipMemcpyHostToDevice));
+                    const int r = upload_post_rows(L);
+                    if (r) return r;
                 }
             }
         }
@@ -1644,9 +1648,9 @@ static int level_create_impl(const LudwigLevelHost *h, int device, LudwigLevel *
         return LUDWIG_OK;
     };
     rc = nb > 0 ? init() : LUDWIG_OK;
-    if (rc != LUDWIG_OK) { ludwig_level_destroy(L); return rc; }
+    if (rc != LUDWIG_OK) return rc;
 #undef LW_TRY
-    *out = L;
+    *out = owner.release();
     return LUDWIG_OK;
 }
 
@@ -1674,8 +1678,8 @@ int ludwig_level_add_post_collision_readers(LudwigLevel *L, const int64_t *offse
         if (by_rows) L->h_post_rows[(size_t)b * 2 + (row >> 5)] |= 1u << (row & 31);
     }
     if (by_rows) {
-        if (!L->post_rows) LW_HIP(hipMalloc((void **)&L->post_rows, L->h_post_rows.size() * 4));
-        LW_HIP(hipMemcpy(L->post_rows, L->h_post_rows.data(), L->h_post_rows.size() * 4, hipMemcpyHostToDevice));
+        const int r = upload_post_rows(L);
+        if (r) return r;
     }
     ++L->version;
     return upload_meta(L);
@@ -1731,7 +1735,7 @@ int ludwig_stream_destroy(int device, void *hip_stream)
 {
     if (!hip_stream) return LUDWIG_OK;
     LW_HIP(hipSetDevice(device));
-    LW_HIP(hipStreamDestroy((hipStream_t)hip_stream));
+    LW_HIP((hipError_t)HipStreamOps::destroy((hipStream_t)hip_stream));     // the caller owned it (ludwig_stream_create)
     return LUDWIG_OK;
 }
 
@@ -1999,6 +2003,42 @@ int check_one_device(const char *set, LudwigLevel *const *levels, int32_t n_leve
     return LUDWIG_OK;
 }
 
+// The cell table of a triangle set (`set` = "surface statistics", "force series", "wall surface"), checked before anything is allocated:
+// per triangle, in the caller's order, the nearest fluid cell in the internal block order, or -1 for none.
+int triangle_cells(const char *set, const LudwigLevel *L, const LudwigSurfaceParams *sp, int32_t n_tri, const int32_t *blocks,
+                   const int32_t *cells, std::vector<int32_t> &hc)
+{
+    if (!L || !sp || n_tri < 0 || (n_tri > 0 && (!blocks || !cells))) return fail(LUDWIG_ERR_INVALID, "null argument");
+    // the kernel indexes cells as internal block * 512 + cell in 32 bits
+    if (n_tri > 0 && (int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "%s: level has %d blocks, more than 32-bit cell indices reach", set, L->n_blocks);
+    hc.resize((size_t)n_tri);
+    for (int32_t i = 0; i < n_tri; ++i) {
+        const int32_t b = blocks[i], x = cells[i];
+        if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "%s: triangle %d: block %d not in -1..%d", set, i, b, L->n_blocks - 1);
+        if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "%s: triangle %d: cell %d not in 0..511", set, i, x);
+        hc[i] = b < 0 ? -1 : internal_cell(L, b, x);
+    }
+    return LUDWIG_OK;
+}
+
+// The stencil tables of one level of a probe or flux-plane set: per point 8 corner cells in the internal block order and 3 weights.
+struct StencilTables {
+    std::vector<int32_t> cell;
+    std::vector<float> w;
+    void add(const LudwigLevel *L, int64_t p, const int32_t *blocks, const int32_t *cells, const float *weights)
+    {
+        for (int c = 0; c < 8; ++c) cell.push_back(internal_cell(L, blocks[8 * p + c], cells[8 * p + c]));
+        for (int a = 0; a < 3; ++a) w.push_back(weights[3 * p + a]);
+    }
+    int points() const { return (int)(cell.size() / 8); }
+    void upload(hipError_t &e, Dev<int32_t> &d_cell, Dev<float> &d_w) const
+    {
+        upload_table(e, cell, d_cell);
+        upload_table(e, w, d_w);
+    }
+};
+
 // whether coarse step t is one of start_step, start_step + interval, ...; and how many of first..last are
 bool step_sampled(int64_t t, int64_t start_step, int32_t interval)
 {
@@ -2021,15 +2061,15 @@ int64_t samples_in(int64_t first, int64_t last, int64_t start_step, int32_t inte
 struct LudwigProbes {
     int device = 0;
     int n_levels = 0, n_probes = 0, capacity = 0;
-    std::vector<LudwigLevel *> levels;          // as given; an entry without probes may be null (a rank that holds no copy of it)
+    std::vector<LudwigLevel *> levels;          // borrowed, as given; an entry without probes may be null (a rank that holds no copy of it)
     struct PerLevel {
         int n = 0;
-        int32_t *cell = nullptr;                // [n][8] internal block * 512 + cell
-        float *w = nullptr;                     // [n][3]
-        int32_t *col = nullptr;                 // [n] place in the set
+        Dev<int32_t> cell;                      // [n][8] internal block * 512 + cell
+        Dev<float> w;                           // [n][3]
+        Dev<int32_t> col;                       // [n] place in the set
     };
     std::vector<PerLevel> per;
-    float *ring = nullptr;
+    Dev<float> ring;
     std::vector<int64_t> slot_step;             // coarse step of each used slot, oldest first
     std::vector<uint64_t> slot_levels;          // bit li: level li has written its probes into the slot
 };
@@ -2071,12 +2111,12 @@ static int probes_launch(LudwigProbes *P, int li, int slot, int64_t t_sub)
 // Per triangle, in the caller's order: the nearest fluid cell in the internal block order (-1: none), and [4][n] floats of wall distance
 // and normal; [SURFACE_STAT_COMPONENTS][n] float64 sums. The set does not own its level.
 struct LudwigSurfaceStats {
-    LudwigLevel *level = nullptr;
+    LudwigLevel *level = nullptr;               // borrowed
     int device = 0, n_tri = 0;
     float tau = 0.0f, pressure_scale = 0.0f, stress_scale = 0.0f;
-    int32_t *cell = nullptr;
-    float *rec = nullptr;
-    double *sums = nullptr;
+    Dev<int32_t> cell;
+    Dev<float> rec;
+    Dev<double> sums;
     int64_t n_samples = 0;
 };
 
@@ -2098,13 +2138,13 @@ static int surface_stats_launch(LudwigSurfaceStats *S, int64_t t_sub)
 // wall distance, normal, area and moment arm; a slab of per-chunk records for the stages of the tree and one device ring [capacity] of
 // finished records. The host keeps the coarse step of every used slot; _download empties it. The set does not own its level.
 struct LudwigForceSeries {
-    LudwigLevel *level = nullptr;
+    LudwigLevel *level = nullptr;               // borrowed
     int device = 0, n_tri = 0, capacity = 0;
     float tau = 0.0f, pressure_scale = 0.0f, stress_scale = 0.0f;
-    int32_t *cell = nullptr;
-    float *rec = nullptr;
-    ForceRecord *slab = nullptr;                // n_chunks records, then ceil(n / 512) until two or more are left (none for one chunk)
-    ForceRecord *ring = nullptr;
+    Dev<int32_t> cell;
+    Dev<float> rec;
+    Dev<ForceRecord> slab;                      // n_chunks records, then ceil(n / 512) until two or more are left (none for one chunk)
+    Dev<ForceRecord> ring;
     std::vector<int64_t> slot_step;             // coarse step of each used slot, oldest first
 };
 
@@ -2140,18 +2180,18 @@ static int force_series_launch(LudwigForceSeries *F, int64_t t_sub, int64_t t_co
 struct LudwigFluxPlanes {
     int device = 0;
     int n_levels = 0, n_planes = 0, capacity = 0;
-    std::vector<LudwigLevel *> levels;          // as given; an entry without points may be null
+    std::vector<LudwigLevel *> levels;          // borrowed, as given; an entry without points may be null
     struct PerLevel {
         int n = 0;                              // points
-        int32_t *cell = nullptr;                // [n][8] internal block * 512 + cell
-        float *w = nullptr;                     // [n][3]
-        FluxChunk *table = nullptr;             // every stage's workgroups, stage after stage
+        Dev<int32_t> cell;                      // [n][8] internal block * 512 + cell
+        Dev<float> w;                           // [n][3]
+        Dev<FluxChunk> table;                   // every stage's workgroups, stage after stage
         std::vector<int> stage_groups;          // workgroups of each stage (the first: k_flux_chunks)
-        FluxRecord *slab = nullptr;
+        Dev<FluxRecord> slab;
     };
     std::vector<PerLevel> per;
     std::vector<uint8_t> has_list;              // [n_planes][n_levels]
-    FluxRecord *ring = nullptr;
+    Dev<FluxRecord> ring;
     std::vector<int64_t> slot_step;             // coarse step of each used slot, oldest first
 };
 
@@ -2191,9 +2231,9 @@ static int flux_planes_launch(LudwigFluxPlanes *P, int li, int slot, int64_t t_s
 struct LudwigModes {
     int device = 0;
     int n_levels = 0, n_columns = 0, n_rows = 0;
-    std::vector<LudwigLevel *> levels;          // as given
-    double *table = nullptr;
-    std::vector<double *> sums;                 // per level; null: no owned blocks
+    std::vector<LudwigLevel *> levels;          // borrowed, as given
+    Dev<double> table;
+    std::vector<Dev<double>> sums;              // per level; null: no owned blocks
     std::vector<size_t> sums_count;             // doubles in each
     std::vector<int64_t> count;                 // samples of each level since the last reset
 };
@@ -2225,6 +2265,7 @@ struct ObserverSchedule {
     bool due(int64_t t) const { return step_sampled(t, start_step, interval); }
 };
 struct BatchObservers {
+    // every `set` is borrowed: the caller made it and destroys it
     struct : ObserverSchedule { LudwigProbes *set = nullptr; } probes;
     struct : ObserverSchedule { LudwigSurfaceStats *set = nullptr; } surface;
     struct : ObserverSchedule { LudwigForceSeries *set = nullptr; } forces;
@@ -2336,33 +2377,28 @@ int ludwig_map_surface_stresses(const LudwigLevel *L, int vel_field, int32_t n_t
     LW_ENSURE_RHO(L);
     // scratch: [block_pointer | centers | normals | 4 outputs]; a diagnostics call every few hundred steps, so allocated per call
     const size_t nptr = L->h_block_pointer.size(), n = (size_t)n_tri;
-    char *buf = nullptr;
-    const size_t bytes = nptr * 4 + n * 10 * 4;
-    LW_HIP(hipMalloc((void **)&buf, bytes));
-    int32_t *d_ptr = (int32_t *)buf;
-    float *d_c = (float *)(buf + nptr * 4), *d_n = d_c + 3 * n, *d_out = d_n + 3 * n;
-    hipError_t e = hipMemcpyAsync(d_ptr, L->h_block_pointer.data(), nptr * 4, hipMemcpyHostToDevice, L->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_c, centers, n * 12, hipMemcpyHostToDevice, L->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_n, normals, n * 12, hipMemcpyHostToDevice, L->stream);
-    if (e == hipSuccess) {
-        SurfaceParams s{};
-        s.rho = L->rho;
-        s.vel = L->vel[vel_field == LUDWIG_VEL ? 0 : 1];
-        s.obstacle = L->obstacle;
-        s.block_pointer = d_ptr;
-        s.gdx = L->gdx; s.gdy = L->gdy; s.gdz = L->gdz; s.n_tri = n_tri; s.radius = sp->search_radius;
-        s.dx = sp->dx; s.tau = sp->tau; s.off_x = sp->offset_x; s.off_y = sp->offset_y; s.off_z = sp->offset_z;
-        s.pressure_scale = sp->pressure_scale; s.stress_scale = sp->stress_scale;
-        s.centers = d_c; s.normals = d_n;
-        s.p = d_out; s.tx = d_out + n; s.ty = d_out + 2 * n; s.tz = d_out + 3 * n;
-        hipLaunchKernelGGL(k_map_stresses, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, L->stream, s);
-        e = hipGetLastError();
-    }
+    Dev<float> buf;                                   // 4-byte elements throughout: nptr indices, then 10 n floats
+    LW_HIP((hipError_t)buf.alloc(nptr + n * 10));
+    int32_t *d_ptr = (int32_t *)buf.get();
+    float *d_c = buf + nptr, *d_n = d_c + 3 * n, *d_out = d_n + 3 * n;
+    LW_HIP(hipMemcpyAsync(d_ptr, L->h_block_pointer.data(), nptr * 4, hipMemcpyHostToDevice, L->stream));
+    LW_HIP(hipMemcpyAsync(d_c, centers, n * 12, hipMemcpyHostToDevice, L->stream));
+    LW_HIP(hipMemcpyAsync(d_n, normals, n * 12, hipMemcpyHostToDevice, L->stream));
+    SurfaceParams s{};
+    s.rho = L->rho;
+    s.vel = L->vel[vel_field == LUDWIG_VEL ? 0 : 1];
+    s.obstacle = L->obstacle;
+    s.block_pointer = d_ptr;
+    s.gdx = L->gdx; s.gdy = L->gdy; s.gdz = L->gdz; s.n_tri = n_tri; s.radius = sp->search_radius;
+    s.dx = sp->dx; s.tau = sp->tau; s.off_x = sp->offset_x; s.off_y = sp->offset_y; s.off_z = sp->offset_z;
+    s.pressure_scale = sp->pressure_scale; s.stress_scale = sp->stress_scale;
+    s.centers = d_c; s.normals = d_n;
+    s.p = d_out; s.tx = d_out + n; s.ty = d_out + 2 * n; s.tz = d_out + 3 * n;
+    hipLaunchKernelGGL(k_map_stresses, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, L->stream, s);
+    LW_HIP(hipGetLastError());
     float *outs[4] = {pressure, shear_x, shear_y, shear_z};
-    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipMemcpyAsync(outs[i], d_out + (size_t)i * n, n * 4, hipMemcpyDeviceToHost, L->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
-    (void)hipFree(buf);
-    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "surface stresses: %s", hipGetErrorString(e));
+    for (int i = 0; i < 4; ++i) LW_HIP(hipMemcpyAsync(outs[i], d_out + (size_t)i * n, n * 4, hipMemcpyDeviceToHost, L->stream));
+    LW_HIP(hipStreamSynchronize(L->stream));
     return LUDWIG_OK;
 }
 
@@ -2373,20 +2409,16 @@ int ludwig_level_rho_min(const LudwigLevel *L, float *rho_min)
     if (L->n_owned == 0) return LUDWIG_OK;
     LW_HIP(hipSetDevice(L->device));
     LW_ENSURE_RHO(L);
-    int *d = nullptr;
-    LW_HIP(hipMalloc((void **)&d, 2 * sizeof(int)));
+    Dev<int> d;
+    LW_HIP((hipError_t)d.alloc(2));
     const int init[2] = {0x7f800000, 0};                  // +inf, "no NaN seen"
-    hipError_t e = hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, L->stream);
+    LW_HIP(hipMemcpyAsync(d, init, sizeof init, hipMemcpyHostToDevice, L->stream));
     const int64_t n = (int64_t)L->n_owned * CELLS;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_rho_min, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, L->stream, L->rho, L->obstacle, n, d);
-        e = hipGetLastError();
-    }
+    hipLaunchKernelGGL(k_rho_min, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048)), dim3(256), 0, L->stream, L->rho, L->obstacle, n, d);
+    LW_HIP(hipGetLastError());
     int res[2] = {init[0], 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(res, d, sizeof res, hipMemcpyDeviceToHost, L->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(L->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "rho_min: %s", hipGetErrorString(e));
+    LW_HIP(hipMemcpyAsync(res, d, sizeof res, hipMemcpyDeviceToHost, L->stream));
+    LW_HIP(hipStreamSynchronize(L->stream));
     memcpy(rho_min, &res[0], sizeof(float));
     if (res[1]) *rho_min = __builtin_nanf("");            // minimum() of the reference propagates NaN (src/diagnostics.jl:71)
     return LUDWIG_OK;
@@ -2401,7 +2433,7 @@ int ludwig_level_stats_reset(LudwigLevel *L)
     LW_HIP(hipSetDevice(L->device));
     const size_t n = (size_t)L->n_blocks * STAT_COMPONENTS * CELLS;
     if (!L->stats) {
-        const int r = dev_alloc(L, &L->stats, n);
+        const int r = dev_alloc(L, L->stats, n);
         if (r) { L->stats_ready = false; return r; }
     }
     LW_HIP(hipMemsetAsync(L->stats, 0, n * sizeof(double), L->stream));
@@ -2445,7 +2477,7 @@ int ludwig_level_monitor(LudwigLevel *L, int64_t t_sub, int64_t *counts, int64_t
             if (row[NBR_BX] < 0 || row[NBR_BX] >= limit || row[NBR_BY] < 0 || row[NBR_BY] >= limit || row[NBR_BZ] < 0 || row[NBR_BZ] >= limit)
                 return fail(LUDWIG_ERR_INVALID, "monitor: block coordinates (%d, %d, %d) not in 0..%d", row[NBR_BX], row[NBR_BY], row[NBR_BZ], limit - 1);
         }
-        const int r = dev_alloc(L, &L->monitor_slab, total);
+        const int r = dev_alloc(L, L->monitor_slab, total);
         if (r) return r;
     }
     LW_ENSURE_RHO(L);
@@ -2491,7 +2523,7 @@ int ludwig_level_wall_census(LudwigLevel *L, int64_t t_sub, LudwigWallCensus *ou
     if (L->n_owned == 0) return LUDWIG_OK;            // no owned blocks: the empty record, nothing allocated
     LW_HIP(hipSetDevice(L->device));
     if (!L->wall_census) {
-        const int r = dev_alloc(L, &L->wall_census, 1);
+        const int r = dev_alloc(L, L->wall_census, 1);
         if (r) return r;
     }
     LW_ENSURE_RHO(L);
@@ -2507,63 +2539,43 @@ int ludwig_level_wall_census(LudwigLevel *L, int64_t t_sub, LudwigWallCensus *ou
 // Per triangle, in the caller's order: the nearest fluid cell in the internal block order (-1: none) and [3][n] floats of normal;
 // [WALL_SURFACE_ROWS][n] float32 results. The set does not own its level.
 struct LudwigWallSurface {
-    LudwigLevel *level = nullptr;
+    LudwigLevel *level = nullptr;               // borrowed
     int device = 0, n_tri = 0;
     float pressure_scale = 0.0f, stress_scale = 0.0f;
-    int32_t *cell = nullptr;
-    float *nrm = nullptr, *out = nullptr;
+    Dev<int32_t> cell;
+    Dev<float> nrm, out;
     bool computed = false;
 };
 
-void ludwig_wall_surface_destroy(LudwigWallSurface *S)
-{
-    if (!S) return;
-    (void)hipSetDevice(S->device);
-    if (S->cell) (void)hipFree(S->cell);
-    if (S->nrm) (void)hipFree(S->nrm);
-    if (S->out) (void)hipFree(S->out);
-    delete S;
-}
+void ludwig_wall_surface_destroy(LudwigWallSurface *S) { destroy_set(S); }
 
 int ludwig_wall_surface_create(LudwigLevel *L, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *normals,
                                const LudwigSurfaceParams *sp, LudwigWallSurface **out)
 {
     if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (!L || !sp || n_tri < 0 || (n_tri > 0 && (!blocks || !cells || !normals))) return fail(LUDWIG_ERR_INVALID, "null argument");
-    // the kernel indexes cells as internal block * 512 + cell in 32 bits
-    if (n_tri > 0 && (int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
-        return fail(LUDWIG_ERR_INVALID, "wall surface: level has %d blocks, more than 32-bit cell indices reach", L->n_blocks);
-    // everything is checked before anything is allocated
-    std::vector<int32_t> hc((size_t)n_tri);
+    if (n_tri > 0 && !normals) return fail(LUDWIG_ERR_INVALID, "null argument");
+    std::vector<int32_t> hc;
+    if (const int r = triangle_cells("wall surface", L, sp, n_tri, blocks, cells, hc)) return r;
     std::vector<float> hn((size_t)n_tri * 3);
-    for (int32_t i = 0; i < n_tri; ++i) {
-        const int32_t b = blocks[i], x = cells[i];
-        if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "wall surface: triangle %d: block %d not in -1..%d", i, b, L->n_blocks - 1);
-        if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "wall surface: triangle %d: cell %d not in 0..511", i, x);
-        hc[i] = b < 0 ? -1 : internal_cell(L, b, x);
+    for (int32_t i = 0; i < n_tri; ++i)
         for (int a = 0; a < 3; ++a) hn[(size_t)a * n_tri + i] = normals[3 * i + a];
-    }
-    LudwigWallSurface *S = new (std::nothrow) LudwigWallSurface;
+    std::unique_ptr<LudwigWallSurface> S(new (std::nothrow) LudwigWallSurface);
     if (!S) return fail(LUDWIG_ERR_ALLOC, "wall surface: out of host memory");
     S->level = L;
     S->device = L->device;
     S->n_tri = n_tri;
     S->pressure_scale = sp->pressure_scale;
     S->stress_scale = sp->stress_scale;
-    int r = set_device(S->device);
-    if (r == LUDWIG_OK && n_tri > 0) {
+    if (const int r = set_device(S->device)) return r;
+    if (n_tri > 0) {
         hipError_t e = hipSuccess;
         upload_table(e, hc, S->cell);
         upload_table(e, hn, S->nrm);
-        if (e == hipSuccess) e = hipMalloc((void **)&S->out, (size_t)n_tri * WALL_SURFACE_ROWS * sizeof(float));
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "wall surface: %d triangles: %s", n_tri, hipGetErrorString(e));
+        if (e == hipSuccess) e = (hipError_t)S->out.alloc((size_t)n_tri * WALL_SURFACE_ROWS);
+        if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "wall surface: %d triangles: %s", n_tri, hipGetErrorString(e));
     }
-    if (r != LUDWIG_OK) {
-        ludwig_wall_surface_destroy(S);
-        return r;
-    }
-    *out = S;
+    *out = S.release();
     return LUDWIG_OK;
 }
 
@@ -2611,7 +2623,7 @@ int ludwig_level_stats_download(const LudwigLevel *L, int stat, double *host, si
         memset(host, 0, bytes);
         return LUDWIG_OK;
     }
-    return download_components(L, (const double *)L->stats, STAT_COMPONENTS, first, K, host, "statistics download");
+    return download_components(L, (const double *)L->stats, STAT_COMPONENTS, first, K, host);
 }
 
 int ludwig_level_gradient_fields_compute(LudwigLevel *L, int vel_field, float scale)
@@ -2627,7 +2639,7 @@ int ludwig_level_gradient_fields_compute(LudwigLevel *L, int vel_field, float sc
     LW_ENSURE_POPULATIONS(L);
     if (!L->grad) {
         const size_t n = (size_t)L->n_blocks * GRAD_COMPONENTS * CELLS;
-        const int r = dev_alloc(L, &L->grad, n);
+        const int r = dev_alloc(L, L->grad, n);
         if (r) return r;
         LW_HIP(hipMemsetAsync(L->grad, 0, n * sizeof(float), L->stream));   // the ghost blocks are never written
     }
@@ -2651,7 +2663,7 @@ int ludwig_level_gradient_fields_download(const LudwigLevel *L, int which, float
         memset(host, 0, bytes);
         return LUDWIG_OK;
     }
-    return download_components(L, (const float *)L->grad, GRAD_COMPONENTS, first, K, host, "gradient fields download");
+    return download_components(L, (const float *)L->grad, GRAD_COMPONENTS, first, K, host);
 }
 
 // ---- iso-surfaces (ludwig_level_isosurface_*; no reference counterpart) ----
@@ -2684,18 +2696,18 @@ int ludwig_level_isosurface_extract(LudwigLevel *L, int which, int vel_field, fl
     }
     const float *vel = L->vel[vel_field == LUDWIG_VEL ? 0 : 1];
     const size_t no = (size_t)L->n_owned;
-    if (!L->iso_counts) LW_ISO_TRY(dev_alloc(L, &L->iso_counts, no));
-    if (!L->iso_offsets) LW_ISO_TRY(dev_alloc(L, &L->iso_offsets, no));
-    if (!L->iso_skip) LW_ISO_TRY(dev_alloc(L, &L->iso_skip, no));
+    if (!L->iso_counts) LW_ISO_TRY(dev_alloc(L, L->iso_counts, no));
+    if (!L->iso_offsets) LW_ISO_TRY(dev_alloc(L, L->iso_offsets, no));
+    if (!L->iso_skip) LW_ISO_TRY(dev_alloc(L, L->iso_skip, no));
     if (!L->ref2int.empty() && !L->d_int2ref) {
-        LW_ISO_TRY(dev_alloc(L, &L->d_int2ref, (size_t)L->n_blocks));
+        LW_ISO_TRY(dev_alloc(L, L->d_int2ref, (size_t)L->n_blocks));
         LW_HIP(hipMemcpyAsync(L->d_int2ref, L->int2ref.data(), (size_t)L->n_blocks * sizeof(int32_t), hipMemcpyHostToDevice, L->stream));
     }
     IsoArgs a;
     if (which == LUDWIG_ISO_DENSITY) { a.s = L->rho; a.s_stride = CELLS; }
     else if (which == LUDWIG_ISO_Q_CRITERION) { a.s = L->grad + 3 * CELLS; a.s_stride = GRAD_COMPONENTS * CELLS; }
     else {
-        if (!L->iso_scalar) LW_ISO_TRY(dev_alloc(L, &L->iso_scalar, (size_t)L->sk));
+        if (!L->iso_scalar) LW_ISO_TRY(dev_alloc(L, L->iso_scalar, (size_t)L->sk));
         if (which == LUDWIG_ISO_VELOCITY_MAGNITUDE)
             hipLaunchKernelGGL(k_iso_scalar<ISO_VELOCITY_MAGNITUDE>, dim3((unsigned)L->n_blocks), dim3(CELLS / 2), 0, L->stream, L->iso_scalar, vel);
         else
@@ -2730,14 +2742,11 @@ int ludwig_level_isosurface_extract(LudwigLevel *L, int which, int vel_field, fl
     if (total > max_triangles) return LUDWIG_ISO_REFUSED;     // the caller reports it; nothing is allocated for a surface nobody can hold
     if (total == 0) return LUDWIG_OK;
     if (total > L->iso_capacity) {
-        float **fb[] = {&L->iso_pos, &L->iso_att};
-        for (float **q : fb)
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
-        if (L->iso_keys) { (void)hipFree(L->iso_keys); L->iso_keys = nullptr; }
-        L->iso_capacity = 0;
-        LW_ISO_TRY(dev_alloc(L, &L->iso_pos, (size_t)total * ISO_POS_FLOATS));
-        LW_ISO_TRY(dev_alloc(L, &L->iso_att, (size_t)total * ISO_ATT_FLOATS));
-        LW_ISO_TRY(dev_alloc(L, &L->iso_keys, (size_t)total * ISO_KEY_INTS));
+        L->iso_capacity = 0;                      // sized with the result: released first, so the peak does not grow
+        L->iso_pos.reset(); L->iso_att.reset(); L->iso_keys.reset();
+        LW_ISO_TRY(dev_alloc(L, L->iso_pos, (size_t)total * ISO_POS_FLOATS));
+        LW_ISO_TRY(dev_alloc(L, L->iso_att, (size_t)total * ISO_ATT_FLOATS));
+        LW_ISO_TRY(dev_alloc(L, L->iso_keys, (size_t)total * ISO_KEY_INTS));
         L->iso_capacity = total;
     }
     LW_HIP(hipMemcpyAsync(L->iso_offsets, offsets.data(), no * sizeof(int64_t), hipMemcpyHostToDevice, L->stream));
@@ -2799,7 +2808,7 @@ int ludwig_level_subgrid_fields_compute(LudwigLevel *L, int vel_field)
     LW_ENSURE_POPULATIONS(L);
     if (!L->subgrid_fields) {
         const size_t n = (size_t)L->n_blocks * SUBGRID_FIELD_COMPONENTS * CELLS;
-        const int r = dev_alloc(L, &L->subgrid_fields, n);
+        const int r = dev_alloc(L, L->subgrid_fields, n);
         if (r) return r;
         LW_HIP(hipMemsetAsync(L->subgrid_fields, 0, n * sizeof(float), L->stream));   // the ghost blocks are never written
     }
@@ -2823,7 +2832,7 @@ int ludwig_level_subgrid_fields_download(const LudwigLevel *L, int which, float 
         memset(host, 0, bytes);
         return LUDWIG_OK;
     }
-    return download_components(L, (const float *)L->subgrid_fields, SUBGRID_FIELD_COMPONENTS, which, 1, host, "subgrid fields download");
+    return download_components(L, (const float *)L->subgrid_fields, SUBGRID_FIELD_COMPONENTS, which, 1, host);
 }
 
 int ludwig_level_subgrid_stats_reset(LudwigLevel *L)
@@ -2835,7 +2844,7 @@ int ludwig_level_subgrid_stats_reset(LudwigLevel *L)
     LW_HIP(hipSetDevice(L->device));
     const size_t n = (size_t)L->n_blocks * SUBGRID_SUM_COMPONENTS * CELLS;
     if (!L->subgrid_sums) {
-        const int r = dev_alloc(L, &L->subgrid_sums, n);
+        const int r = dev_alloc(L, L->subgrid_sums, n);
         if (r) { L->subgrid_stats_ready = false; return r; }
     }
     LW_HIP(hipMemsetAsync(L->subgrid_sums, 0, n * sizeof(double), L->stream));
@@ -2871,21 +2880,10 @@ int ludwig_level_subgrid_stats_download(const LudwigLevel *L, int which, double 
         memset(host, 0, bytes);
         return LUDWIG_OK;
     }
-    return download_components(L, (const double *)L->subgrid_sums, SUBGRID_SUM_COMPONENTS, which, 1, host, "subgrid statistics download");
+    return download_components(L, (const double *)L->subgrid_sums, SUBGRID_SUM_COMPONENTS, which, 1, host);
 }
 
-void ludwig_probes_destroy(LudwigProbes *P)
-{
-    if (!P) return;
-    (void)hipSetDevice(P->device);
-    for (LudwigProbes::PerLevel &q : P->per) {
-        if (q.cell) (void)hipFree(q.cell);
-        if (q.w) (void)hipFree(q.w);
-        if (q.col) (void)hipFree(q.col);
-    }
-    if (P->ring) (void)hipFree(P->ring);
-    delete P;
-}
+void ludwig_probes_destroy(LudwigProbes *P) { destroy_set(P); }
 
 int ludwig_probes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_probes, const int32_t *level_index,
                          const int32_t *blocks, const int32_t *cells, const float *weights, int32_t capacity, LudwigProbes **out)
@@ -2904,7 +2902,7 @@ int ludwig_probes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
         if (r) return r;
     }
     if (const int r = check_one_device("probes", levels, n_levels, first)) return r;
-    LudwigProbes *P = new (std::nothrow) LudwigProbes;
+    std::unique_ptr<LudwigProbes> P(new (std::nothrow) LudwigProbes);
     if (!P) return fail(LUDWIG_ERR_ALLOC, "probes: out of host memory");
     P->device = first->device;
     P->n_levels = n_levels;
@@ -2912,38 +2910,29 @@ int ludwig_probes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
     P->capacity = capacity;
     P->levels.assign(levels, levels + n_levels);
     P->per.resize(n_levels);
-    int r = set_device(P->device);
-    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
-        std::vector<int32_t> hc, hcol;
-        std::vector<float> hw;
-        const LudwigLevel *L = levels[li];
+    if (const int r = set_device(P->device)) return r;
+    for (int li = 0; li < n_levels; ++li) {
+        StencilTables st;
+        std::vector<int32_t> hcol;
         for (int32_t p = 0; p < n_probes; ++p) {
             if (level_index[p] != li) continue;
-            for (int c = 0; c < 8; ++c) hc.push_back(internal_cell(L, blocks[8 * p + c], cells[8 * p + c]));
-            for (int a = 0; a < 3; ++a) hw.push_back(weights[3 * p + a]);
+            st.add(levels[li], p, blocks, cells, weights);
             hcol.push_back(p);
         }
         LudwigProbes::PerLevel &q = P->per[li];
-        q.n = (int)hcol.size();
+        q.n = st.points();
         if (q.n == 0) continue;
         hipError_t e = hipSuccess;
-        upload_table(e, hc, q.cell);
-        upload_table(e, hw, q.w);
+        st.upload(e, q.cell, q.w);
         upload_table(e, hcol, q.col);
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "probes: level %d tables: %s", li, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "probes: level %d tables: %s", li, hipGetErrorString(e));
         // a probe reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now
         // on (+4 of 216 B per cell where the store was elided), so a batch never replays it
-        if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(levels[li], 1);
+        if (const int r = ludwig_level_set_rho_store(levels[li], 1)) return r;
     }
-    if (r == LUDWIG_OK) {
-        const hipError_t e = hipMalloc((void **)&P->ring, (size_t)capacity * n_probes * 4 * sizeof(float));
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "probes: ring of %d samples: %s", capacity, hipGetErrorString(e));
-    }
-    if (r != LUDWIG_OK) {
-        ludwig_probes_destroy(P);
-        return r;
-    }
-    *out = P;
+    if (const int e = P->ring.alloc((size_t)capacity * n_probes * 4))
+        return fail(LUDWIG_ERR_ALLOC, "probes: ring of %d samples: %s", capacity, hipGetErrorString((hipError_t)e));
+    *out = P.release();
     return LUDWIG_OK;
 }
 
@@ -2995,37 +2984,22 @@ int ludwig_probes_download(LudwigProbes *P, float *values, int64_t *steps, int32
     return LUDWIG_OK;
 }
 
-void ludwig_surface_stats_destroy(LudwigSurfaceStats *S)
-{
-    if (!S) return;
-    (void)hipSetDevice(S->device);
-    if (S->cell) (void)hipFree(S->cell);
-    if (S->rec) (void)hipFree(S->rec);
-    if (S->sums) (void)hipFree(S->sums);
-    delete S;
-}
+void ludwig_surface_stats_destroy(LudwigSurfaceStats *S) { destroy_set(S); }
 
 int ludwig_surface_stats_create(LudwigLevel *L, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *wall_dist,
                                 const float *normals, const LudwigSurfaceParams *sp, LudwigSurfaceStats **out)
 {
     if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (!L || !sp || n_tri < 0 || (n_tri > 0 && (!blocks || !cells || !wall_dist || !normals))) return fail(LUDWIG_ERR_INVALID, "null argument");
-    // the kernel indexes cells as internal block * 512 + cell in 32 bits
-    if (n_tri > 0 && (int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
-        return fail(LUDWIG_ERR_INVALID, "surface statistics: level has %d blocks, more than 32-bit cell indices reach", L->n_blocks);
-    // everything is checked before anything is allocated
-    std::vector<int32_t> hc((size_t)n_tri);
+    if (n_tri > 0 && (!wall_dist || !normals)) return fail(LUDWIG_ERR_INVALID, "null argument");
+    std::vector<int32_t> hc;
+    if (const int r = triangle_cells("surface statistics", L, sp, n_tri, blocks, cells, hc)) return r;
     std::vector<float> hr((size_t)n_tri * 4);
     for (int32_t i = 0; i < n_tri; ++i) {
-        const int32_t b = blocks[i], x = cells[i];
-        if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "surface statistics: triangle %d: block %d not in -1..%d", i, b, L->n_blocks - 1);
-        if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "surface statistics: triangle %d: cell %d not in 0..511", i, x);
-        hc[i] = b < 0 ? -1 : internal_cell(L, b, x);
         hr[i] = wall_dist[i];
         for (int a = 0; a < 3; ++a) hr[(size_t)(a + 1) * n_tri + i] = normals[3 * i + a];
     }
-    LudwigSurfaceStats *S = new (std::nothrow) LudwigSurfaceStats;
+    std::unique_ptr<LudwigSurfaceStats> S(new (std::nothrow) LudwigSurfaceStats);
     if (!S) return fail(LUDWIG_ERR_ALLOC, "surface statistics: out of host memory");
     S->level = L;
     S->device = L->device;
@@ -3033,25 +3007,21 @@ int ludwig_surface_stats_create(LudwigLevel *L, int32_t n_tri, const int32_t *bl
     S->tau = sp->tau;
     S->pressure_scale = sp->pressure_scale;
     S->stress_scale = sp->stress_scale;
-    int r = set_device(S->device);
-    if (r == LUDWIG_OK && n_tri > 0) {
+    if (const int r = set_device(S->device)) return r;
+    if (n_tri > 0) {
         const size_t n = (size_t)n_tri;
         hipError_t e = hipSuccess;
         upload_table(e, hc, S->cell);
         upload_table(e, hr, S->rec);
-        if (e == hipSuccess) e = hipMalloc((void **)&S->sums, n * SURFACE_STAT_COMPONENTS * sizeof(double));
+        if (e == hipSuccess) e = (hipError_t)S->sums.alloc(n * SURFACE_STAT_COMPONENTS);
         // zeroed on the level's stream: ahead of every sample, which is queued there (or on a batch's level stream, which starts behind it)
         if (e == hipSuccess) e = hipMemsetAsync(S->sums, 0, n * SURFACE_STAT_COMPONENTS * sizeof(double), L->stream);
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "surface statistics: %d triangles: %s", n_tri, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "surface statistics: %d triangles: %s", n_tri, hipGetErrorString(e));
     }
     // a sample reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now on
     // (+4 of 216 B per cell where the store was elided), so a batch never replays it
-    if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(L, 1);
-    if (r != LUDWIG_OK) {
-        ludwig_surface_stats_destroy(S);
-        return r;
-    }
-    *out = S;
+    if (const int r = ludwig_level_set_rho_store(L, 1)) return r;
+    *out = S.release();
     return LUDWIG_OK;
 }
 
@@ -3087,16 +3057,7 @@ int ludwig_surface_stats_download(LudwigSurfaceStats *S, double *sums, size_t by
 }
 
 // ---- force series (ludwig_force_series_*) ----
-void ludwig_force_series_destroy(LudwigForceSeries *F)
-{
-    if (!F) return;
-    (void)hipSetDevice(F->device);
-    if (F->cell) (void)hipFree(F->cell);
-    if (F->rec) (void)hipFree(F->rec);
-    if (F->slab) (void)hipFree(F->slab);
-    if (F->ring) (void)hipFree(F->ring);
-    delete F;
-}
+void ludwig_force_series_destroy(LudwigForceSeries *F) { destroy_set(F); }
 
 int ludwig_force_series_create(LudwigLevel *L, int32_t n_tri, const int32_t *blocks, const int32_t *cells, const float *wall_dist,
                                const float *normals, const float *area, const float *arm, const LudwigSurfaceParams *sp, int32_t capacity,
@@ -3107,24 +3068,17 @@ int ludwig_force_series_create(LudwigLevel *L, int32_t n_tri, const int32_t *blo
     if (!L || !sp || n_tri < 0 || (n_tri > 0 && (!blocks || !cells || !wall_dist || !normals || !area || !arm)))
         return fail(LUDWIG_ERR_INVALID, "null argument");
     if (capacity < 1) return fail(LUDWIG_ERR_INVALID, "force series: capacity %d < 1", capacity);
-    // the kernel indexes cells as internal block * 512 + cell in 32 bits
-    if (n_tri > 0 && (int64_t)L->n_blocks * CELLS > (int64_t)INT32_MAX)
-        return fail(LUDWIG_ERR_INVALID, "force series: level has %d blocks, more than 32-bit cell indices reach", L->n_blocks);
-    // everything is checked before anything is allocated
+    std::vector<int32_t> hc;
+    if (const int r = triangle_cells("force series", L, sp, n_tri, blocks, cells, hc)) return r;
     const size_t n = (size_t)n_tri;
-    std::vector<int32_t> hc(n);
     std::vector<float> hr(n * FORCE_REC_ROWS);
     for (int32_t i = 0; i < n_tri; ++i) {
-        const int32_t b = blocks[i], x = cells[i];
-        if (b < -1 || b >= L->n_blocks) return fail(LUDWIG_ERR_INVALID, "force series: triangle %d: block %d not in -1..%d", i, b, L->n_blocks - 1);
-        if (b >= 0 && (x < 0 || x >= CELLS)) return fail(LUDWIG_ERR_INVALID, "force series: triangle %d: cell %d not in 0..511", i, x);
-        hc[i] = b < 0 ? -1 : internal_cell(L, b, x);
         hr[i] = wall_dist[i];
         for (int a = 0; a < 3; ++a) hr[(size_t)(a + 1) * n + i] = normals[3 * (size_t)i + a];
         hr[4 * n + i] = area[i];
         for (int a = 0; a < 3; ++a) hr[(size_t)(a + 5) * n + i] = arm[(size_t)a * n + i];
     }
-    LudwigForceSeries *F = new (std::nothrow) LudwigForceSeries;
+    std::unique_ptr<LudwigForceSeries> F(new (std::nothrow) LudwigForceSeries);
     if (!F) return fail(LUDWIG_ERR_ALLOC, "force series: out of host memory");
     F->level = L;
     F->device = L->device;
@@ -3133,24 +3087,20 @@ int ludwig_force_series_create(LudwigLevel *L, int32_t n_tri, const int32_t *blo
     F->tau = sp->tau;
     F->pressure_scale = sp->pressure_scale;
     F->stress_scale = sp->stress_scale;
-    int r = set_device(F->device);
-    if (r == LUDWIG_OK && n_tri > 0) {
+    if (const int r = set_device(F->device)) return r;
+    if (n_tri > 0) {
         size_t slab = 0;                                   // records of every stage but the last, which goes into the ring
         for (size_t m = (n + CELLS - 1) / CELLS; m > 1; m = (m + CELLS - 1) / CELLS) slab += m;
         hipError_t e = hipSuccess;
         upload_table(e, hc, F->cell);
         upload_table(e, hr, F->rec);
-        if (e == hipSuccess && slab > 0) e = hipMalloc((void **)&F->slab, slab * sizeof(ForceRecord));
-        if (e == hipSuccess) e = hipMalloc((void **)&F->ring, (size_t)capacity * sizeof(ForceRecord));
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "force series: %d triangles, %d records: %s", n_tri, capacity, hipGetErrorString(e));
+        if (e == hipSuccess) e = (hipError_t)F->slab.alloc(slab);
+        if (e == hipSuccess) e = (hipError_t)F->ring.alloc((size_t)capacity);
+        if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "force series: %d triangles, %d records: %s", n_tri, capacity, hipGetErrorString(e));
     }
     // a sample reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now on
-    if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(L, 1);
-    if (r != LUDWIG_OK) {
-        ludwig_force_series_destroy(F);
-        return r;
-    }
-    *out = F;
+    if (const int r = ludwig_level_set_rho_store(L, 1)) return r;
+    *out = F.release();
     return LUDWIG_OK;
 }
 
@@ -3187,19 +3137,7 @@ int ludwig_force_series_download(LudwigForceSeries *F, double *sums, int64_t *co
 }
 
 // ---- flux planes (ludwig_flux_planes_*) ----
-void ludwig_flux_planes_destroy(LudwigFluxPlanes *P)
-{
-    if (!P) return;
-    (void)hipSetDevice(P->device);
-    for (LudwigFluxPlanes::PerLevel &q : P->per) {
-        if (q.cell) (void)hipFree(q.cell);
-        if (q.w) (void)hipFree(q.w);
-        if (q.table) (void)hipFree(q.table);
-        if (q.slab) (void)hipFree(q.slab);
-    }
-    if (P->ring) (void)hipFree(P->ring);
-    delete P;
-}
+void ludwig_flux_planes_destroy(LudwigFluxPlanes *P) { destroy_set(P); }
 
 int ludwig_flux_planes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_planes, const int32_t *plane_start,
                               const int32_t *plane_axis, const int32_t *level_index, const int32_t *blocks, const int32_t *cells,
@@ -3228,7 +3166,7 @@ int ludwig_flux_planes_create(LudwigLevel *const *levels, int32_t n_levels, int3
     }
     if (first)
         if (const int r = check_one_device("flux planes", levels, n_levels, first)) return r;
-    LudwigFluxPlanes *P = new (std::nothrow) LudwigFluxPlanes;
+    std::unique_ptr<LudwigFluxPlanes> P(new (std::nothrow) LudwigFluxPlanes);
     if (!P) return fail(LUDWIG_ERR_ALLOC, "flux planes: out of host memory");
     P->n_levels = n_levels;
     P->n_planes = n_planes;
@@ -3237,25 +3175,20 @@ int ludwig_flux_planes_create(LudwigLevel *const *levels, int32_t n_levels, int3
     P->per.resize(n_levels);
     P->has_list.assign((size_t)n_planes * n_levels, 0);
     if (!first) {                                          // no valid point: nothing on the device, records of zeros
-        *out = P;
+        *out = P.release();
         return LUDWIG_OK;
     }
     P->device = first->device;
-    int r = set_device(P->device);
-    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
-        std::vector<int32_t> hc;
-        std::vector<float> hw;
+    if (const int r = set_device(P->device)) return r;
+    for (int li = 0; li < n_levels; ++li) {
+        StencilTables pts;
         std::vector<std::vector<FluxChunk>> stages(1);
-        const LudwigLevel *L = levels[li];
         int32_t slab = 0;                                  // records so far in the level's slab
         for (int32_t k = 0; k < n_planes; ++k) {
-            const int32_t start = (int32_t)(hc.size() / 8);
-            for (int64_t p = plane_start[k]; p < plane_start[k + 1]; ++p) {
-                if (!valid[p] || level_index[p] != li) continue;
-                for (int c = 0; c < 8; ++c) hc.push_back(internal_cell(L, blocks[8 * p + c], cells[8 * p + c]));
-                for (int a = 0; a < 3; ++a) hw.push_back(weights[3 * p + a]);
-            }
-            int32_t n = (int32_t)(hc.size() / 8) - start;
+            const int32_t start = pts.points();
+            for (int64_t p = plane_start[k]; p < plane_start[k + 1]; ++p)
+                if (valid[p] && level_index[p] == li) pts.add(levels[li], p, blocks, cells, weights);
+            int32_t n = pts.points() - start;
             if (n == 0) continue;
             P->has_list[(size_t)k * n_levels + li] = 1;
             const int32_t final_dst = ~(k * n_levels + li);
@@ -3272,7 +3205,7 @@ int ludwig_flux_planes_create(LudwigLevel *const *levels, int32_t n_levels, int3
             }
         }
         LudwigFluxPlanes::PerLevel &q = P->per[li];
-        q.n = (int)(hc.size() / 8);
+        q.n = pts.points();
         if (q.n == 0) continue;
         std::vector<FluxChunk> table;
         for (const std::vector<FluxChunk> &st : stages) {
@@ -3280,23 +3213,16 @@ int ludwig_flux_planes_create(LudwigLevel *const *levels, int32_t n_levels, int3
             table.insert(table.end(), st.begin(), st.end());
         }
         hipError_t e = hipSuccess;
-        upload_table(e, hc, q.cell);
-        upload_table(e, hw, q.w);
+        pts.upload(e, q.cell, q.w);
         upload_table(e, table, q.table);
-        if (e == hipSuccess && slab > 0) e = hipMalloc((void **)&q.slab, (size_t)slab * sizeof(FluxRecord));
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "flux planes: level %d tables: %s", li, hipGetErrorString(e));
+        if (e == hipSuccess) e = (hipError_t)q.slab.alloc((size_t)slab);
+        if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "flux planes: level %d tables: %s", li, hipGetErrorString(e));
         // a sample reads rho after the level's last sub-step of every sampled coarse step: the level stores it every step from now on
-        if (r == LUDWIG_OK) r = ludwig_level_set_rho_store(levels[li], 1);
+        if (const int r = ludwig_level_set_rho_store(levels[li], 1)) return r;
     }
-    if (r == LUDWIG_OK) {
-        const hipError_t e = hipMalloc((void **)&P->ring, (size_t)capacity * n_planes * n_levels * sizeof(FluxRecord));
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "flux planes: ring of %d records: %s", capacity, hipGetErrorString(e));
-    }
-    if (r != LUDWIG_OK) {
-        ludwig_flux_planes_destroy(P);
-        return r;
-    }
-    *out = P;
+    if (const int e = P->ring.alloc((size_t)capacity * n_planes * n_levels))
+        return fail(LUDWIG_ERR_ALLOC, "flux planes: ring of %d records: %s", capacity, hipGetErrorString((hipError_t)e));
+    *out = P.release();
     return LUDWIG_OK;
 }
 
@@ -3355,15 +3281,7 @@ int ludwig_flux_planes_download(LudwigFluxPlanes *P, double *sums, int64_t *coun
 }
 
 // ---- Fourier modes (ludwig_modes_*) ----
-void ludwig_modes_destroy(LudwigModes *S)
-{
-    if (!S) return;
-    (void)hipSetDevice(S->device);
-    if (S->table) (void)hipFree(S->table);
-    for (double *p : S->sums)
-        if (p) (void)hipFree(p);
-    delete S;
-}
+void ludwig_modes_destroy(LudwigModes *S) { destroy_set(S); }
 
 int ludwig_modes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_columns, int32_t n_rows, const double *weights,
                         LudwigModes **out)
@@ -3380,30 +3298,29 @@ int ludwig_modes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_
         if (!levels[li]) return fail(LUDWIG_ERR_INVALID, "modes: level %d is null", li + 1);
         if (levels[li]->device != levels[0]->device) return fail(LUDWIG_ERR_INVALID, "modes: levels on different devices");
     }
-    LudwigModes *S = new (std::nothrow) LudwigModes;
+    std::unique_ptr<LudwigModes> S(new (std::nothrow) LudwigModes);
     if (!S) return fail(LUDWIG_ERR_ALLOC, "modes: out of host memory");
     S->device = levels[0]->device;
     S->n_levels = n_levels;
     S->n_columns = n_columns;
     S->n_rows = n_rows;
     S->levels.assign(levels, levels + n_levels);
-    S->sums.assign((size_t)n_levels, nullptr);
+    S->sums.resize((size_t)n_levels);
     S->sums_count.assign((size_t)n_levels, 0);
     S->count.assign((size_t)n_levels, 0);
     int r = set_device(S->device);
-    if (r == LUDWIG_OK) {
-        const size_t bytes = (size_t)n_rows * n_columns * sizeof(double);
-        hipError_t e = hipMalloc((void **)&S->table, bytes);
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "modes: hipMalloc(%zu bytes) for the weight table failed: %s", bytes, hipGetErrorString(e));
-        else if ((e = hipMemcpy(S->table, weights, bytes, hipMemcpyHostToDevice)) != hipSuccess)
-            r = fail(LUDWIG_ERR_HIP, "modes: weight table: %s", hipGetErrorString(e));
-    }
+    if (r) return r;
+    const size_t bytes = (size_t)n_rows * n_columns * sizeof(double);
+    if (const int e = S->table.alloc((size_t)n_rows * n_columns))
+        return fail(LUDWIG_ERR_ALLOC, "modes: hipMalloc(%zu bytes) for the weight table failed: %s", bytes, hipGetErrorString((hipError_t)e));
+    if (const hipError_t e = hipMemcpy(S->table, weights, bytes, hipMemcpyHostToDevice))
+        return fail(LUDWIG_ERR_HIP, "modes: weight table: %s", hipGetErrorString(e));
     // all or nothing across levels: a level that fails takes the sums of the levels before it along
     for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
         LudwigLevel *L = levels[li];
         if (L->n_owned == 0) continue;                    // no owned blocks: accepted, does nothing
         const size_t n = (size_t)L->n_blocks * n_columns * MODE_FIELDS * CELLS;
-        r = dev_alloc(L, &S->sums[li], n);
+        r = dev_alloc(L, S->sums[li], n);
         if (r != LUDWIG_OK) break;
         S->sums_count[li] = n;
         // zeroed on the level's stream: ahead of every sample, which is queued there (or on a batch's level stream, which starts behind it)
@@ -3414,14 +3331,11 @@ int ludwig_modes_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_
     // (+4 of 216 B per cell where the store was elided), so a batch never replays it
     for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) r = ludwig_level_set_rho_store(levels[li], 1);
     if (r != LUDWIG_OK) {
-        const std::string msg = g_err;                    // (freeing must not replace the message)
         for (int li = 0; li < n_levels; ++li)
             if (S->sums[li]) levels[li]->device_bytes -= (int64_t)(S->sums_count[li] * sizeof(double));
-        ludwig_modes_destroy(S);
-        g_err = msg;
         return r;
     }
-    *out = S;
+    *out = S.release();
     return LUDWIG_OK;
 }
 
@@ -3465,8 +3379,7 @@ int ludwig_modes_download(LudwigModes *S, int32_t level_index, int32_t column, d
         memset(host, 0, bytes);
         return LUDWIG_OK;
     }
-    return download_components(L, (const double *)S->sums[level_index], S->n_columns * MODE_FIELDS, column * MODE_FIELDS, MODE_FIELDS, host,
-                               "modes download");
+    return download_components(L, (const double *)S->sums[level_index], S->n_columns * MODE_FIELDS, column * MODE_FIELDS, MODE_FIELDS, host);
 }
 
 // ---- slices (ludwig_slices_*; no reference counterpart) ----
@@ -3477,32 +3390,20 @@ struct LudwigSlices {
     int device = 0;
     int n_levels = 0, n_points = 0, n_rows = 0;
     bool grad = false;
-    std::vector<LudwigLevel *> levels;
+    std::vector<LudwigLevel *> levels;          // borrowed
     std::vector<float> scales;
     struct PerLevel {
         int n = 0;
-        int32_t *base = nullptr;                // [n]
-        float *w = nullptr;                     // [n][3]
-        uint8_t *rep = nullptr;                 // [n] bit c: corner c replaced by the base cell
-        int32_t *col = nullptr;                 // [n] place in the set
+        Dev<int32_t> base;                      // [n]
+        Dev<float> w;                           // [n][3]
+        Dev<uint8_t> rep;                       // [n] bit c: corner c replaced by the base cell
+        Dev<int32_t> col;                       // [n] place in the set
     };
     std::vector<PerLevel> per;
-    float *out = nullptr;
+    Dev<float> out;
 };
 
-void ludwig_slices_destroy(LudwigSlices *S)
-{
-    if (!S) return;
-    (void)hipSetDevice(S->device);
-    for (LudwigSlices::PerLevel &q : S->per) {
-        if (q.base) (void)hipFree(q.base);
-        if (q.w) (void)hipFree(q.w);
-        if (q.rep) (void)hipFree(q.rep);
-        if (q.col) (void)hipFree(q.col);
-    }
-    if (S->out) (void)hipFree(S->out);
-    delete S;
-}
+void ludwig_slices_destroy(LudwigSlices *S) { destroy_set(S); }
 
 int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_points, const int32_t *level_index,
                          const int32_t *blocks, const int32_t *cells, const float *weights, const uint8_t *valid,
@@ -3556,7 +3457,7 @@ int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
     }
     if (!first) return fail(LUDWIG_ERR_INVALID, "slices: no valid point");
     if (const int r = check_one_device("slices", levels, n_levels, first)) return r;
-    LudwigSlices *S = new (std::nothrow) LudwigSlices;
+    std::unique_ptr<LudwigSlices> S(new (std::nothrow) LudwigSlices);
     if (!S) return fail(LUDWIG_ERR_ALLOC, "slices: out of host memory");
     S->device = first->device;
     S->n_levels = n_levels;
@@ -3566,8 +3467,8 @@ int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
     S->levels.assign(levels, levels + n_levels);
     S->scales.assign(scales, scales + n_levels);
     S->per.resize(n_levels);
-    int r = set_device(S->device);
-    for (int li = 0; li < n_levels && r == LUDWIG_OK; ++li) {
+    if (const int r = set_device(S->device)) return r;
+    for (int li = 0; li < n_levels; ++li) {
         const size_t n = hcol[li].size();
         LudwigSlices::PerLevel &q = S->per[li];
         q.n = (int)n;
@@ -3591,19 +3492,12 @@ int ludwig_slices_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n
         upload_table(e, sw, q.w);
         upload_table(e, sr, q.rep);
         upload_table(e, sc, q.col);
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_HIP, "slices: level %d tables: %s", li, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "slices: level %d tables: %s", li, hipGetErrorString(e));
     }
-    if (r == LUDWIG_OK) {
-        const size_t bytes = (size_t)n_rows * n_points * sizeof(float);
-        hipError_t e = hipMalloc((void **)&S->out, bytes);
-        if (e == hipSuccess) e = hipMemset(S->out, 0, bytes);           // invalid points stay 0
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "slices: result of %d points: %s", n_points, hipGetErrorString(e));
-    }
-    if (r != LUDWIG_OK) {
-        ludwig_slices_destroy(S);
-        return r;
-    }
-    *out = S;
+    hipError_t e = (hipError_t)S->out.alloc((size_t)n_rows * n_points);
+    if (e == hipSuccess) e = hipMemset(S->out, 0, (size_t)n_rows * n_points * sizeof(float));           // invalid points stay 0
+    if (e != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "slices: result of %d points: %s", n_points, hipGetErrorString(e));
+    *out = S.release();
     return LUDWIG_OK;
 }
 
@@ -3666,8 +3560,8 @@ static int check_locator_levels(const char *set, const char *what, LudwigLevel *
 
 // every level's block_pointer (bp[li], in the library's block order) and the table of StreamLevel entries on the device; with_rho =
 // false leaves the rho pointers null (the tracers never read rho)
-static void upload_locator_table(hipError_t &e, LudwigLevel *const *levels, int32_t n_levels, bool with_rho, std::vector<int32_t *> &bp,
-                                 StreamLevel *&table_dev)
+static void upload_locator_table(hipError_t &e, LudwigLevel *const *levels, int32_t n_levels, bool with_rho, std::vector<Dev<int32_t>> &bp,
+                                 Dev<StreamLevel> &table_dev)
 {
     std::vector<StreamLevel> table(n_levels);
     for (int li = 0; li < n_levels && e == hipSuccess; ++li) {
@@ -3676,7 +3570,7 @@ static void upload_locator_table(hipError_t &e, LudwigLevel *const *levels, int3
         StreamLevel &t = table[li];
         t.bp = bp[li];
         t.obstacle = L->obstacle;
-        t.rho = with_rho ? L->rho : nullptr;
+        t.rho = with_rho ? L->rho.get() : nullptr;
         t.vel[0] = L->vel[0];
         t.vel[1] = L->vel[1];
         t.gx = L->gdx; t.gy = L->gdy; t.gz = L->gdz;
@@ -3692,28 +3586,17 @@ struct LudwigStreamlines {
     int device = 0;
     int n_levels = 0, n_lines = 0, max_steps = 0;
     float step = 0.0f, min_speed = 0.0f;
-    std::vector<LudwigLevel *> levels;
-    std::vector<int32_t *> bp;                  // per level, device
-    StreamLevel *table = nullptr;               // [n_levels], device
-    float *seeds = nullptr, *sign = nullptr;
-    float *rec = nullptr;
-    int32_t *counts = nullptr, *codes = nullptr;
-    hipEvent_t ev = nullptr;
+    std::vector<LudwigLevel *> levels;          // borrowed
+    std::vector<Dev<int32_t>> bp;               // per level
+    Dev<StreamLevel> table;                     // [n_levels]
+    Dev<float> seeds, sign;
+    Dev<float> rec;
+    Dev<int32_t> counts, codes;
+    HipEvent ev;
     bool traced = false;
 };
 
-void ludwig_streamlines_destroy(LudwigStreamlines *S)
-{
-    if (!S) return;
-    (void)hipSetDevice(S->device);
-    for (int32_t *q : S->bp)
-        if (q) (void)hipFree(q);
-    void *bufs[] = {S->table, S->seeds, S->sign, S->rec, S->counts, S->codes};
-    for (void *q : bufs)
-        if (q) (void)hipFree(q);
-    if (S->ev) (void)hipEventDestroy(S->ev);
-    delete S;
-}
+void ludwig_streamlines_destroy(LudwigStreamlines *S) { destroy_set(S); }
 
 int ludwig_streamlines_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_lines, const float *seeds, const float *sign,
                               float step, float min_speed, int32_t max_steps, LudwigStreamlines **out)
@@ -3730,7 +3613,7 @@ int ludwig_streamlines_create(LudwigLevel *const *levels, int32_t n_levels, int3
     for (int32_t i = 0; i < n_lines; ++i)
         if (sign[i] != 1.0f && sign[i] != -1.0f) return fail(LUDWIG_ERR_INVALID, "streamlines: sign[%d] = %g is neither 1 nor -1", i, (double)sign[i]);
     if (int rl = check_locator_levels("streamlines", "a line", levels, n_levels)) return rl;
-    LudwigStreamlines *S = new (std::nothrow) LudwigStreamlines;
+    std::unique_ptr<LudwigStreamlines> S(new (std::nothrow) LudwigStreamlines);
     if (!S) return fail(LUDWIG_ERR_ALLOC, "streamlines: out of host memory");
     S->device = levels[0]->device;
     S->n_levels = n_levels;
@@ -3739,28 +3622,22 @@ int ludwig_streamlines_create(LudwigLevel *const *levels, int32_t n_levels, int3
     S->step = step;
     S->min_speed = min_speed;
     S->levels.assign(levels, levels + n_levels);
-    S->bp.assign(n_levels, nullptr);
-    int r = set_device(S->device);
+    S->bp.resize(n_levels);
+    if (const int r = set_device(S->device)) return r;
     hipError_t e = hipSuccess;
-    if (r == LUDWIG_OK) {
-        upload_locator_table(e, levels, n_levels, true, S->bp, S->table);
-        if (n_lines > 0) {
-            const size_t n = (size_t)n_lines;
-            const std::vector<float> hs(seeds, seeds + 3 * n), hg(sign, sign + n);
-            upload_table(e, hs, S->seeds);
-            upload_table(e, hg, S->sign);
-            if (e == hipSuccess) e = hipMalloc((void **)&S->rec, n * ((size_t)max_steps + 1) * STREAM_REC_FLOATS * sizeof(float));
-            if (e == hipSuccess) e = hipMalloc((void **)&S->counts, n * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMalloc((void **)&S->codes, n * sizeof(int32_t));
-        }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev, hipEventDisableTiming);
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "streamlines: %d lines of %d steps: %s", n_lines, max_steps, hipGetErrorString(e));
+    upload_locator_table(e, levels, n_levels, true, S->bp, S->table);
+    if (n_lines > 0) {
+        const size_t n = (size_t)n_lines;
+        const std::vector<float> hs(seeds, seeds + 3 * n), hg(sign, sign + n);
+        upload_table(e, hs, S->seeds);
+        upload_table(e, hg, S->sign);
+        if (e == hipSuccess) e = (hipError_t)S->rec.alloc(n * ((size_t)max_steps + 1) * STREAM_REC_FLOATS);
+        if (e == hipSuccess) e = (hipError_t)S->counts.alloc(n);
+        if (e == hipSuccess) e = (hipError_t)S->codes.alloc(n);
     }
-    if (r != LUDWIG_OK) {
-        ludwig_streamlines_destroy(S);
-        return r;
-    }
-    *out = S;
+    if (e == hipSuccess) e = (hipError_t)S->ev.create();
+    if (e != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "streamlines: %d lines of %d steps: %s", n_lines, max_steps, hipGetErrorString(e));
+    *out = S.release();
     return LUDWIG_OK;
 }
 
@@ -3834,27 +3711,16 @@ struct LudwigTracers {
     int n_levels = 0, n_seeds = 0, generations = 0, release_every = 0;
     int64_t n_slots = 0, n_advances = 0;
     float dt = 0.0f;
-    std::vector<LudwigLevel *> levels;
-    std::vector<int32_t *> bp;                  // per level, device
-    StreamLevel *table = nullptr;               // [n_levels], device
-    float *seeds = nullptr, *pos = nullptr, *rec = nullptr;
-    int32_t *state = nullptr;
-    hipEvent_t ev = nullptr;
+    std::vector<LudwigLevel *> levels;          // borrowed
+    std::vector<Dev<int32_t>> bp;               // per level
+    Dev<StreamLevel> table;                     // [n_levels]
+    Dev<float> seeds, pos, rec;
+    Dev<int32_t> state;
+    HipEvent ev;
     bool snapshot = false;
 };
 
-void ludwig_tracers_destroy(LudwigTracers *S)
-{
-    if (!S) return;
-    (void)hipSetDevice(S->device);
-    for (int32_t *q : S->bp)
-        if (q) (void)hipFree(q);
-    void *bufs[] = {S->table, S->seeds, S->pos, S->rec, S->state};
-    for (void *q : bufs)
-        if (q) (void)hipFree(q);
-    if (S->ev) (void)hipEventDestroy(S->ev);
-    delete S;
-}
+void ludwig_tracers_destroy(LudwigTracers *S) { destroy_set(S); }
 
 int ludwig_tracers_create(LudwigLevel *const *levels, int32_t n_levels, int32_t n_seeds, const float *seeds, int32_t generations,
                           int32_t release_every, float dt, LudwigTracers **out)
@@ -3871,7 +3737,7 @@ int ludwig_tracers_create(LudwigLevel *const *levels, int32_t n_levels, int32_t 
     if ((int64_t)n_seeds * (int64_t)generations > (int64_t)INT32_MAX / 8)
         return fail(LUDWIG_ERR_INVALID, "tracers: %d seeds of %d generations are more than 2^28 - 1 slots", n_seeds, generations);
     if (int rl = check_locator_levels("tracers", "a particle", levels, n_levels)) return rl;
-    LudwigTracers *S = new (std::nothrow) LudwigTracers;
+    std::unique_ptr<LudwigTracers> S(new (std::nothrow) LudwigTracers);
     if (!S) return fail(LUDWIG_ERR_ALLOC, "tracers: out of host memory");
     S->device = levels[0]->device;
     S->n_levels = n_levels;
@@ -3881,29 +3747,23 @@ int ludwig_tracers_create(LudwigLevel *const *levels, int32_t n_levels, int32_t 
     S->n_slots = (int64_t)n_seeds * generations;
     S->dt = dt;
     S->levels.assign(levels, levels + n_levels);
-    S->bp.assign(n_levels, nullptr);
-    int r = set_device(S->device);
+    S->bp.resize(n_levels);
+    if (const int r = set_device(S->device)) return r;
     hipError_t e = hipSuccess;
-    if (r == LUDWIG_OK) {
-        upload_locator_table(e, levels, n_levels, false, S->bp, S->table);      // a tracer carries no rho
-        if (S->n_slots > 0) {
-            const size_t n = (size_t)S->n_slots;
-            const std::vector<float> hs(seeds, seeds + 3 * (size_t)n_seeds);
-            const std::vector<int32_t> empty(n, TRACER_EMPTY);
-            const std::vector<float> zero(3 * n, 0.0f);
-            upload_table(e, hs, S->seeds);
-            upload_table(e, zero, S->pos);
-            upload_table(e, empty, S->state);
-            if (e == hipSuccess) e = hipMalloc((void **)&S->rec, n * STREAM_REC_FLOATS * sizeof(float));
-        }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&S->ev, hipEventDisableTiming);
-        if (e != hipSuccess) r = fail(LUDWIG_ERR_ALLOC, "tracers: %d seeds of %d generations: %s", n_seeds, generations, hipGetErrorString(e));
+    upload_locator_table(e, levels, n_levels, false, S->bp, S->table);      // a tracer carries no rho
+    if (S->n_slots > 0) {
+        const size_t n = (size_t)S->n_slots;
+        const std::vector<float> hs(seeds, seeds + 3 * (size_t)n_seeds);
+        const std::vector<int32_t> empty(n, TRACER_EMPTY);
+        const std::vector<float> zero(3 * n, 0.0f);
+        upload_table(e, hs, S->seeds);
+        upload_table(e, zero, S->pos);
+        upload_table(e, empty, S->state);
+        if (e == hipSuccess) e = (hipError_t)S->rec.alloc(n * STREAM_REC_FLOATS);
     }
-    if (r != LUDWIG_OK) {
-        ludwig_tracers_destroy(S);
-        return r;
-    }
-    *out = S;
+    if (e == hipSuccess) e = (hipError_t)S->ev.create();
+    if (e != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "tracers: %d seeds of %d generations: %s", n_seeds, generations, hipGetErrorString(e));
+    *out = S.release();
     return LUDWIG_OK;
 }
 
@@ -4162,35 +4022,32 @@ static int batch_impl(LudwigLevel *const *levels, int32_t n_levels, int64_t t_st
     if (concurrent) {
         LW_HIP(hipSetDevice(levels[0]->device));
         LW_HIP(hipStreamSynchronize(user_stream));             // everything queued before the batch is done
-        // 1. every level gets its stream and its two events - or none does: a half-made set is destroyed again, so that a later
-        //    batch never finds a level with a stream but no events. The levels keep the caller's stream until all of it exists.
+        // 1. every level gets its stream and its two events - or none does: they are made beside the levels and moved in once all
+        //    exist, so that a later batch never finds a level with a stream but no events. The levels keep the caller's stream until then.
         int pr_least = 0, pr_greatest = 0;
         LW_HIP(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest));
         const int pr_mode = env::level_stream_priority();
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < n_levels && e == hipSuccess; ++i) {
-            LudwigLevel *L = levels[i];
-            if (L->own_stream && L->ev_stepped && L->ev_consumed) continue;
+        struct Made { HipStream st; HipEvent stepped, consumed; };
+        std::vector<Made> made((size_t)n_levels);
+        int e = 0;
+        for (int i = 0; i < n_levels && !e; ++i) {
+            if (levels[i]->own_stream) continue;                              // complete from an earlier batch: keep
             // the finest level is the critical chain (2^(n-1) sub-steps per coarse step): its stream gets the highest priority, the
             // coarser levels fill what it leaves free (graded priorities: no better)
             // LUDWIG_LEVEL_STREAM_PRIORITY=2: graded - the finest level highest, its parent (whose stream carries the finest level's interface
             // pass since round 3) one below, the rest lowest
             int pr = pr_mode == 0 ? pr_least : (i == n_levels - 1 ? pr_greatest : pr_least);
             if (pr_mode == 2) pr = std::min(pr_least, pr_greatest + (n_levels - 1 - i));
-            if (!L->own_stream) e = hipStreamCreateWithPriority(&L->own_stream, hipStreamNonBlocking, pr);
-            if (e == hipSuccess && !L->ev_stepped) e = hipEventCreateWithFlags(&L->ev_stepped, hipEventDisableTiming);
-            if (e == hipSuccess && !L->ev_consumed) e = hipEventCreateWithFlags(&L->ev_consumed, hipEventDisableTiming);
+            e = made[i].st.create(hipStreamNonBlocking, pr);
+            if (!e) e = made[i].stepped.create();
+            if (!e) e = made[i].consumed.create();
         }
-        if (e != hipSuccess) {
-            for (int i = 0; i < n_levels; ++i) {
-                LudwigLevel *L = levels[i];
-                if (L->own_stream && L->ev_stepped && L->ev_consumed) continue;      // complete from an earlier batch: keep
-                hipEvent_t *evs[] = {&L->ev_stepped, &L->ev_consumed};
-                for (hipEvent_t *ev : evs)
-                    if (*ev) { (void)hipEventDestroy(*ev); *ev = nullptr; }
-                if (L->own_stream) { (void)hipStreamDestroy(L->own_stream); L->own_stream = nullptr; }
-            }
-            return fail(LUDWIG_ERR_HIP, "batch: level streams: %s", hipGetErrorString(e));
+        if (e) return fail(LUDWIG_ERR_HIP, "batch: level streams: %s", hipGetErrorString((hipError_t)e));
+        for (int i = 0; i < n_levels; ++i) {
+            if (!made[i].st) continue;
+            levels[i]->own_stream = std::move(made[i].st);
+            levels[i]->ev_stepped = std::move(made[i].stepped);
+            levels[i]->ev_consumed = std::move(made[i].consumed);
         }
         // 2. switch over; one way back for every early return
         auto restore = [&]() { for (int j = 0; j < n_levels; ++j) levels[j]->stream = user_stream; };
@@ -4458,28 +4315,28 @@ constexpr int TIMING_RING = 256;
 struct LudwigComm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1, device = 0;
-    hipStream_t stream = nullptr;       // small collectives (diagnostics)
-    float *scratch = nullptr;           // device, 2 x 256 floats
+    HipStream stream;                   // small collectives (diagnostics)
+    Dev<float> scratch;                 // 2 x 256 floats
 };
 
 struct LudwigHaloPlan {
-    LudwigLevel *L = nullptr;
-    LudwigComm *comm = nullptr;
+    LudwigLevel *L = nullptr;           // borrowed
+    LudwigComm *comm = nullptr;         // borrowed
     std::vector<int32_t> peers;
     struct Group {
         int64_t n_send = 0, n_recv = 0, n_send_oct = 0, n_recv_oct = 0, n_send_single = 0, n_recv_single = 0;
-        float *send_buf = nullptr, *recv_buf = nullptr;
-        uint4 *send_desc = nullptr, *recv_desc = nullptr;
-        uint2 *send_single = nullptr, *recv_single = nullptr;
+        Dev<float> send_buf, recv_buf;
+        Dev<uint4> send_desc, recv_desc;
+        Dev<uint2> send_single, recv_single;
         std::vector<int64_t> send_off, recv_off;       // [n_peers + 1] prefix sums
     } g[LUDWIG_HALO_GROUPS];
-    hipStream_t s_comm = nullptr;                      // high priority: a queue of its own beside the stepping stream
-    hipEvent_t ev_ready = nullptr, ev_done = nullptr;
+    HipStream s_comm;                                  // high priority: a queue of its own beside the stepping stream
+    HipEvent ev_ready, ev_done;
     bool pending = false;                              // an exchange has been queued since the last wait
     bool self_via_rccl = false;                        // LUDWIG_HALO_SELF_VIA_RCCL: messages to this rank itself go through ncclSend / ncclRecv
     bool timing = false;
     bool in_stream = false;                            // ludwig_halo_plan_in_stream: the exchange runs ON the level's stream (no event hand-over)
-    hipEvent_t t0[TIMING_RING] = {}, t1[TIMING_RING] = {};
+    HipEvent t0[TIMING_RING], t1[TIMING_RING];
     int64_t n_timed = 0, n_read = 0;
 };
 
@@ -4592,9 +4449,9 @@ int ludwig_comm_create(const void *unique_id, int rank, int world, int device, L
     memcpy(&id, unique_id, sizeof id);
     ncclResult_t r = api->CommInitRank(&c->comm, world, id, rank);
     if (r != ncclSuccess) { delete c; return fail(LUDWIG_ERR_HIP, "ncclCommInitRank: %s", api->GetErrorString(r)); }
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->scratch, 512 * sizeof(float));
-    if (e != hipSuccess) { ludwig_comm_destroy(c); return fail(LUDWIG_ERR_HIP, "communicator set-up: %s", hipGetErrorString(e)); }
+    int e = c->stream.create(hipStreamNonBlocking);
+    if (!e) e = c->scratch.alloc(512);
+    if (e) { ludwig_comm_destroy(c); return fail(LUDWIG_ERR_HIP, "communicator set-up: %s", hipGetErrorString((hipError_t)e)); }
     *out = c;
     return LUDWIG_OK;
 }
@@ -4606,8 +4463,6 @@ void ludwig_comm_destroy(LudwigComm *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     RcclApi *api = rccl();
     if (c->comm && api) (void)api->CommDestroy(c->comm);
-    if (c->scratch) (void)hipFree(c->scratch);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -4640,18 +4495,6 @@ void ludwig_halo_plan_destroy(LudwigHaloPlan *P)
     if (!P) return;
     if (P->L) (void)hipSetDevice(P->L->device);
     if (P->s_comm) (void)hipStreamSynchronize(P->s_comm);
-    for (auto &G : P->g) {
-        void *ptrs[] = {G.send_buf, G.recv_buf, G.send_desc, G.recv_desc, G.send_single, G.recv_single};
-        for (void *q : ptrs)
-            if (q) (void)hipFree(q);
-    }
-    for (int i = 0; i < TIMING_RING; ++i) {
-        if (P->t0[i]) (void)hipEventDestroy(P->t0[i]);
-        if (P->t1[i]) (void)hipEventDestroy(P->t1[i]);
-    }
-    if (P->ev_ready) (void)hipEventDestroy(P->ev_ready);
-    if (P->ev_done) (void)hipEventDestroy(P->ev_done);
-    if (P->s_comm) (void)hipStreamDestroy(P->s_comm);
     delete P;
 }
 
@@ -4666,19 +4509,12 @@ int ludwig_halo_plan_create(LudwigLevel *L, LudwigComm *comm, const LudwigHaloPl
         if (comm ? (r < 0 || r >= comm->world) : r != 0) return fail(LUDWIG_ERR_INVALID, "peer %d: rank %d not in the communicator", p, r);
     }
     LW_HIP(hipSetDevice(L->device));
-    LudwigHaloPlan *P = new (std::nothrow) LudwigHaloPlan();
+    std::unique_ptr<LudwigHaloPlan> P(new (std::nothrow) LudwigHaloPlan());
     if (!P) return fail(LUDWIG_ERR_ALLOC, "host allocation failed");
     P->L = L; P->comm = comm;
     P->peers.assign(desc->peer_ranks, desc->peer_ranks + desc->n_peers);
     P->self_via_rccl = comm && env::halo_self_via_rccl();
     int rc = LUDWIG_OK;
-    auto upload = [&](const auto &v, auto **dst) -> int {
-        *dst = nullptr;
-        if (v.empty()) return LUDWIG_OK;
-        LW_HIP(hipMalloc((void **)dst, v.size() * sizeof(v[0])));
-        LW_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
-        return LUDWIG_OK;
-    };
     for (int g = 0; g < LUDWIG_HALO_GROUPS && rc == LUDWIG_OK; ++g) {
         LudwigHaloPlan::Group &G = P->g[g];
         G.send_off.assign((size_t)desc->n_peers + 1, 0);
@@ -4699,22 +4535,24 @@ int ludwig_halo_plan_create(LudwigLevel *L, LudwigComm *comm, const LudwigHaloPl
         if ((rc = build_octets(L, HALO_GROUP_COMPS[g], desc->recv_index[g], G.n_recv, rd, rs))) break;
         G.n_send_oct = (int64_t)sd.size(); G.n_recv_oct = (int64_t)rd.size();
         G.n_send_single = (int64_t)ss.size(); G.n_recv_single = (int64_t)rs.size();
-        if ((rc = upload(sd, &G.send_desc)) || (rc = upload(rd, &G.recv_desc)) || (rc = upload(ss, &G.send_single)) || (rc = upload(rs, &G.recv_single))) break;
         hipError_t e = hipSuccess;
-        if (G.n_send) e = hipMalloc((void **)&G.send_buf, (size_t)G.n_send * 4);
-        if (e == hipSuccess && G.n_recv) e = hipMalloc((void **)&G.recv_buf, (size_t)G.n_recv * 4);
+        upload_table(e, sd, G.send_desc);
+        upload_table(e, rd, G.recv_desc);
+        upload_table(e, ss, G.send_single);
+        upload_table(e, rs, G.recv_single);
+        if (e != hipSuccess) { rc = fail(LUDWIG_ERR_HIP, "halo descriptors: %s", hipGetErrorString(e)); break; }
+        e = (hipError_t)G.send_buf.alloc((size_t)G.n_send);
+        if (e == hipSuccess) e = (hipError_t)G.recv_buf.alloc((size_t)G.n_recv);
         if (e != hipSuccess) rc = fail(LUDWIG_ERR_ALLOC, "halo buffers: %s", hipGetErrorString(e));
     }
-    if (rc == LUDWIG_OK) {
-        int pr_least = 0, pr_greatest = 0;
-        hipError_t e = hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&P->s_comm, hipStreamNonBlocking, pr_greatest);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&P->ev_ready, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&P->ev_done, hipEventDisableTiming);
-        if (e != hipSuccess) rc = fail(LUDWIG_ERR_HIP, "halo plan streams: %s", hipGetErrorString(e));
-    }
-    if (rc) { ludwig_halo_plan_destroy(P); return rc; }
-    *out = P;
+    if (rc) return rc;
+    int pr_least = 0, pr_greatest = 0;
+    hipError_t e = hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
+    if (e == hipSuccess) e = (hipError_t)P->s_comm.create(hipStreamNonBlocking, pr_greatest);
+    if (e == hipSuccess) e = (hipError_t)P->ev_ready.create();
+    if (e == hipSuccess) e = (hipError_t)P->ev_done.create();
+    if (e != hipSuccess) return fail(LUDWIG_ERR_HIP, "halo plan streams: %s", hipGetErrorString(e));
+    *out = P.release();
     return LUDWIG_OK;
 }
 
@@ -4722,8 +4560,11 @@ int ludwig_halo_plan_timing(LudwigHaloPlan *P, int enable)
 {
     if (!P) return fail(LUDWIG_ERR_INVALID, "null plan");
     LW_HIP(hipSetDevice(P->L->device));
-    if (enable && !P->t0[0])
-        for (int i = 0; i < TIMING_RING; ++i) { LW_HIP(hipEventCreate(&P->t0[i])); LW_HIP(hipEventCreate(&P->t1[i])); }
+    if (enable && !P->t0[0]) {               // all 2 x TIMING_RING events, or none: made beside the plan, then moved in
+        std::vector<HipEvent> made(2 * TIMING_RING);
+        for (HipEvent &ev : made) LW_HIP((hipError_t)ev.create(hipEventDefault));
+        for (int i = 0; i < TIMING_RING; ++i) { P->t0[i] = std::move(made[2 * i]); P->t1[i] = std::move(made[2 * i + 1]); }
+    }
     P->timing = enable != 0;
     P->n_read = P->n_timed;
     return LUDWIG_OK;

@@ -198,16 +198,18 @@ def test_observed_batch_rejects_bad_arguments_without_a_device():
 
 
 def test_side_buffer_set_is_made_completely_or_not_at_all(tmp_path):
-    """The second set of a level's interface side buffers (four buffers, two events) goes through csrc/all_or_nothing.hpp; the
-    stand-alone program fails the allocator at each of the six positions in turn and finds every slot null and nothing live after each.
-    Built with the address and undefined-behaviour sanitizers (runtime linked statically, so the program needs nothing around it): a
-    double free or a use of a released pointer ends the program with an error too."""
-    exe = str(tmp_path / "all_or_nothing_check")
+    """The second set of a level's interface side buffers (four buffers, two events) is made from the owning types of
+    csrc/device_memory.hpp, as locals that are moved into the level once all exist; the stand-alone program fails the allocator at each
+    of the six positions in turn and finds every slot null and nothing live after each, then checks the types themselves (release once,
+    move, reset, a failed replacement leaves the previous array). Built with the address and undefined-behaviour sanitizers (runtime
+    linked statically, so the program needs nothing around it): a double free or a use of a released pointer ends the program with an
+    error too."""
+    exe = str(tmp_path / "device_memory_check")
     subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-static-libasan", "-static-libubsan", "-I" + build.CSRC, os.path.join(ROOT, "tests", "all_or_nothing_check.cpp"),
+                    "-static-libasan", "-static-libubsan", "-I" + build.CSRC, os.path.join(ROOT, "tests", "device_memory_check.cpp"),
                     "-o", exe], check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
-    assert out.returncode == 0 and "all-or-nothing OK" in out.stdout, out.stdout + out.stderr
+    assert out.returncode == 0 and "device memory OK" in out.stdout, out.stdout + out.stderr
 
 
 def test_switch_table_lists_the_switches_the_library_reads():
