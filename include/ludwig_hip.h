@@ -655,6 +655,53 @@ int  ludwig_streamlines_trace(LudwigStreamlines *set, int64_t t_coarse);
  * Synchronizes. LUDWIG_ERR_STATE before the first trace. */
 int  ludwig_streamlines_download(LudwigStreamlines *set, int32_t *counts, int32_t *codes, float *vertices, size_t bytes);
 
+/* ---- volume images: rays marched through the level hierarchy on the device and composited (no reference counterpart) ----
+ * A render set is made over a level array, all of it, under the streamline sets' conditions (block_pointer, no ghost blocks, one device).
+ * Float32, no contraction, every product, sum, quotient and sqrtf rounded on its own; only + - x / sqrtf floorf, ldexpf (a scaling by
+ * a power of two, exact), comparisons and int <-> float conversions; open_ludwig_amd/render.py (render_host) restates every bit. Positions are the streamlines' P.
+ * Camera: eye, corner (the centre of pixel (0, 0), the top-left one), du, dv (the steps per pixel column and row), dir (a unit vector),
+ * perspective (0 or 1), built by the host in float64 and cast once. Pixel (i, j), column i, row j: T_a = (corner_a + (float)i du_a) +
+ * (float)j dv_a. Orthographic: O = T, D = dir. Perspective: O = eye, d = T - O, m = sqrtf((dx dx + dy dy) + dz dz), D = d / m; m not > 0
+ * or not finite: code MISS.
+ * Box: lo_a = 0, hi_a = (float)(8 grid_dim_a of level index 0) + 0.5f. t0 = 0, t1 = +inf; per axis x, y, z: D_a == 0: MISS unless
+ * lo_a <= O_a <= hi_a; else a = (lo_a - O_a) / D_a, b = (hi_a - O_a) / D_a, t0 = fmaxf(t0, fminf(a, b)), t1 = fminf(t1, fmaxf(a, b)).
+ * !(t0 < t1): MISS.
+ * s(P) is the streamlines' sample(P) applied to one per-cell scalar of the chosen level: the finest level whose active blocks hold the
+ * base cell (none: OUTSIDE), an obstacle base cell: OBSTACLE, weights g - floorf(g), a corner outside the grid, in an absent block or
+ * in an obstacle cell takes the base cell's value, trilinear x, then y, then z, each lerp (1 - w) a + w b. The scalars are those of
+ * LUDWIG_ISO_* from the same sources: rho; sqrtf((ux ux + uy uy) + uz uz) per cell, then interpolated; Q and sqrtf((wx wx + wy wy) +
+ * wz wz) of ludwig_level_gradient_fields_compute on the level's newest velocity buffer with scales[level index].
+ * March: t = t0, T = 1, (R, G, B) = 0, n = 0. Loop: !(t < t1): code EXIT; n == max_samples: code SAMPLES; P_a = O_a + t D_a;
+ * (kind, s, li) = sample(P), n += 1, li = 0 when OUTSIDE; delta = step 2^-li; OBSTACLE: shade the body, code BODY; found and s == s:
+ * x = fminf(fmaxf((s - lo) inv, 0), 1) with inv = 1.0f / (hi - lo) (fmaxf gives 0 for a NaN), e = table[(int)(x 255.0f + 0.5f)] =
+ * (r, g, b, kappa), alpha = fminf(kappa delta, 1.0f), w = T alpha, R = R + w r (G, B alike), T = T - w, T < t_min: code OPAQUE;
+ * t = t + delta. After the loop, unless BODY: R = R + T bg_r (G, B alike). A = 1 - T.
+ * Body: o(e) = 1 if the base cell's face neighbour at e on its own level is an obstacle cell of an active block, else 0 (outside the
+ * grid, absent block: 0); n_a = o(-e_a) - o(+e_a), nn = n.n; nn == 0: shade = 1, else c = -((n_x D_x + n_y D_y) + n_z D_z) /
+ * sqrtf((float)nn), shade = 0.3f + 0.7f fmaxf(c, 0.0f). R = R + T (body_r shade) (G, B alike), then T = 0.
+ * Per pixel: RGBA floats, an int32 end code and the int32 sample count n. A pixel is written by one lane: no atomics. */
+typedef struct LudwigRender LudwigRender;   /* opaque */
+enum { LUDWIG_RENDER_EXIT = 0, LUDWIG_RENDER_MISS = 1, LUDWIG_RENDER_BODY = 2, LUDWIG_RENDER_OPAQUE = 3, LUDWIG_RENDER_SAMPLES = 4 };
+/* uploads every level's block_pointer (in the library's block order) and allocates the buffers of max_pixels pixels (24 bytes each).
+ * Errors as ludwig_streamlines_create; max_pixels not in 1..2^31 - 1: LUDWIG_ERR_INVALID. */
+int  ludwig_render_create(LudwigLevel *const *levels, int32_t n_levels, int64_t max_pixels, LudwigRender **out);
+/* frees the set, not the levels */
+void ludwig_render_destroy(LudwigRender *set);
+/* one image of scalar `which` (enum LudwigIsoScalar) of every level's newest state after coarse step t_coarse (the buffers
+ * ludwig_streamlines_trace reads). scales: n_levels floats, the gradient fields' scale per level (read for every scalar). camera: 16
+ * floats - eye, corner, du, dv, dir, one unused. params: 10 floats - step, lo, hi, t_min, background r g b, body r g b. table: 256
+ * entries r, g, b, kappa (extinction per coarse cell length). For Q and |omega| every level's gradient fields are computed first, on its
+ * stream, into the level's own gradient buffers (as ludwig_level_isosurface_extract does); |u| and |omega| go into buffers of the set.
+ * Then one launch on the first level's stream, ordered against the other levels' streams as ludwig_streamlines_trace is. Apart from
+ * the gradient buffers only the set's own buffers are written. Refused before anything is launched, LUDWIG_ERR_INVALID: a null array,
+ * t_coarse < 0, an unknown `which`, perspective not 0 or 1, width or height < 1 or width height > max_pixels, step, t_min or a scale
+ * not finite or <= 0, hi not > lo, max_samples < 1. */
+int  ludwig_render_image(LudwigRender *set, int64_t t_coarse, int which, const float *scales, const float *camera, int perspective,
+                         int32_t width, int32_t height, const float *params, int32_t max_samples, const float *table);
+/* the last image: rgba [height][width][4] floats, codes and samples [height][width] int32; bytes = the size of rgba. Synchronizes.
+ * LUDWIG_ERR_STATE before the first image. */
+int  ludwig_render_download(LudwigRender *set, float *rgba, int32_t *codes, int32_t *samples, size_t bytes);
+
 /* ---- tracers: particles advected through the level hierarchy on the device, inside a batch (no reference counterpart) ----
  * A tracer set is made over a level array, all of it, under the streamline sets' conditions (block_pointer, no ghost blocks, one device).
  * Float32, no contraction; open_ludwig_amd/tracers.py (advance_host, snapshot_host) restates every bit. Positions are the streamlines' P.

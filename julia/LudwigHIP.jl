@@ -274,6 +274,35 @@ streamlines_download!(counts::Vector{Int32}, codes::Vector{Int32}, vertices::Arr
     GC.@preserve counts codes vertices check(ccall((:ludwig_streamlines_download, LIB), Cint,
         (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Float32}, Csize_t), s, counts, codes, vertices, sizeof(vertices)))
 
+# volume images (no reference counterpart): rays marched through ALL levels on the device and composited, one lane per ray
+const RENDER_EXIT = Int32(0)
+const RENDER_MISS = Int32(1)
+const RENDER_BODY = Int32(2)
+const RENDER_OPAQUE = Int32(3)
+const RENDER_SAMPLES = Int32(4)
+"""a render set over every level of `grids` (each created with block_pointer, without ghost blocks) with room for `max_pixels` pixels.
+Free it with `render_destroy`."""
+function render_create(grids::Vector{DeviceLevel}, max_pixels::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles check(ccall((:ludwig_render_create, LIB), Cint, (Ptr{Ptr{Cvoid}}, Int32, Int64, Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int64(max_pixels), out))
+    return out[]
+end
+render_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_render_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""queue one image of scalar `which` (0 density, 1 |u|, 2 Q, 3 |omega|) of the newest state after coarse step `t_coarse`: scales one
+Float32 per level, camera 16 Float32 (eye, corner, du, dv, dir, 0), params 10 Float32 (step, lo, hi, t_min, background, body colour),
+table 4 x 256 Float32 (r, g, b, kappa)"""
+render_image!(s::Ptr{Cvoid}, t_coarse::Integer, which::Integer, scales::Vector{Float32}, camera::Vector{Float32}, perspective::Bool,
+              width::Integer, height::Integer, params::Vector{Float32}, max_samples::Integer, table::Matrix{Float32}) =
+    GC.@preserve scales camera params table check(ccall((:ludwig_render_image, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Cint, Ptr{Float32}, Ptr{Float32}, Cint, Int32, Int32, Ptr{Float32}, Int32, Ptr{Float32}),
+        s, Int64(t_coarse), Cint(which), scales, camera, Cint(perspective), Int32(width), Int32(height), params, Int32(max_samples), table))
+"""the last image into rgba (4 x width x height Float32), codes and samples (width x height Int32)"""
+render_download!(rgba::Array{Float32,3}, codes::Matrix{Int32}, samples::Matrix{Int32}, s::Ptr{Cvoid}) =
+    GC.@preserve rgba codes samples check(ccall((:ludwig_render_download, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Csize_t), s, rgba, codes, samples, sizeof(rgba)))
+
 # tracers (no reference counterpart): particles advected through ALL levels on the device, inside a batch
 const TRACER_EMPTY = Int32(-1)
 const TRACER_ALIVE = Int32(0)

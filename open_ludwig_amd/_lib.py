@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_surface_stats_download", "ludwig_execute_timestep_batch_sampled",
     "ludwig_slices_create", "ludwig_slices_destroy", "ludwig_slices_sample", "ludwig_slices_download",
     "ludwig_streamlines_create", "ludwig_streamlines_destroy", "ludwig_streamlines_trace", "ludwig_streamlines_download",
+    "ludwig_render_create", "ludwig_render_destroy", "ludwig_render_image", "ludwig_render_download",
     "ludwig_tracers_create", "ludwig_tracers_destroy", "ludwig_tracers_advance", "ludwig_tracers_snapshot", "ludwig_tracers_download",
     "ludwig_execute_timestep_batch_tracers",
     "ludwig_level_monitor",
@@ -244,6 +245,10 @@ def load() -> C.CDLL:
         "ludwig_streamlines_destroy": (None, [vp]),
         "ludwig_streamlines_trace": (C.c_int, [vp, i64]),
         "ludwig_streamlines_download": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),
+        "ludwig_render_create": (C.c_int, [vp, i32, i64, C.POINTER(vp)]),
+        "ludwig_render_destroy": (None, [vp]),
+        "ludwig_render_image": (C.c_int, [vp, i64, i32, vp, vp, i32, i32, i32, vp, i32, vp]),
+        "ludwig_render_download": (C.c_int, [vp, vp, vp, vp, C.c_size_t]),
         "ludwig_tracers_create": (C.c_int, [vp, i32, i32, vp, i32, i32, f32, C.POINTER(vp)]),
         "ludwig_tracers_destroy": (None, [vp]),
         "ludwig_tracers_advance": (C.c_int, [vp, i64]),

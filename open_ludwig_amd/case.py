@@ -24,6 +24,7 @@ from . import modes as modes_mod
 from . import monitor as monitor_mod
 from . import probes as probes_mod
 from . import slices as slices_mod
+from . import render as render_mod
 from . import streamlines as stream_mod
 from . import tracers as tracer_mod
 from . import statistics as stats_mod
@@ -48,9 +49,9 @@ class DiagRow:
 
 
 def _close_observers(st) -> None:
-    """close a stepper's probe, surface, slice, wall-surface, force-series, streamline, tracer, flux-plane and mode sets (each may be
-    None or absent)"""
-    for name in ("probes", "surface", "slices", "wall_surface", "forces", "stream_set", "tracer_set", "fluxes", "modes"):
+    """close a stepper's probe, surface, slice, wall-surface, force-series, streamline, tracer, flux-plane, mode and render sets (each
+    may be None or absent)"""
+    for name in ("probes", "surface", "slices", "wall_surface", "forces", "stream_set", "tracer_set", "fluxes", "modes", "render_set"):
         obs = getattr(st, name, None)
         if obs is not None:
             obs.close()
@@ -80,6 +81,7 @@ class HipStepper:
         self.fluxes = None                     # flux_planes_setup
         self._flux_series = None
         self.modes = None                      # modes_setup
+        self.render_set = None                 # render_setup
 
     def batch(self, t_start: int, n: int, u_curr, params) -> None:
         if self.probes is None and self.forces is None and self.fluxes is None:
@@ -302,6 +304,21 @@ class HipStepper:
         (counts [n], codes [n], records [n, max_steps + 1, 8])"""
         self.stream_set.trace(t_coarse)
         return self.stream_set.download()
+
+    # -- volume images (render.py; no reference counterpart) --
+    def render_setup(self, max_pixels: int, start_step: int = 1, interval: int = 1) -> None:
+        """one device set over every level with room for max_pixels pixels; the caller renders after the coarse steps start_step + k
+        interval (run_case cuts its batches there)"""
+        render_mod.check_schedule(start_step, interval)
+        if self.render_set is not None:
+            self.render_set.close()
+        self.render_set = render_mod.DeviceRender(self.dev, max_pixels)
+
+    def render(self, plan, t_coarse: int):
+        """one image of a view (render.ViewPlan) of the newest state of all levels after coarse step t_coarse (the last batch must have
+        ended there), derivatives per unit length as in the flow file: (rgba [h, w, 4], codes [h, w], samples [h, w])"""
+        self.render_set.image(t_coarse, plan.field, render_mod.level_scales(self.host), **plan.arguments())
+        return self.render_set.download()
 
     # -- tracers (tracers.py; no reference counterpart) --
     def tracers_setup(self, seeds, generations: int = 1, release_every: int = 1, start_step: int = 1, interval: int = 1) -> None:
@@ -949,6 +966,11 @@ class DistributedStepper:
         raise RuntimeError("advanced.streamlines is enabled, but a distributed run cannot trace streamlines yet: a line crosses the "
                            "ranks' blocks, and each rank holds only its own (DESIGN section 8, Next)")
 
+    # -- volume images: not over ranks, for the streamlines' reason: a ray crosses every level of every rank --
+    def render_setup(self, *args, **kwargs) -> None:
+        raise RuntimeError("advanced.render is enabled, but a distributed run cannot render images yet: a ray crosses the ranks' "
+                           "blocks, and each rank holds only its own (DESIGN section 8, Next)")
+
     # -- flux planes: not over ranks - a record is one tree over a plane's points in point order, not a sum of per-rank parts --
     def flux_planes_setup(self, *args, **kwargs) -> None:
         raise RuntimeError("advanced.flux_planes is enabled, but a distributed run cannot integrate flux planes yet: a record is one "
@@ -1048,6 +1070,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     downloaded fields (streamlines.trace_host). Each group is written to stream_<name>_%06d.vtp, listed in stream_<name>.pvd; lines of
     fewer than two vertices are left out of the file and counted in the log (streamlines.py). A stepper whose streamlines_setup raises
     (the distributed one) ends the run before the first step.
+    With cfg.render_enabled, every view is rendered after the coarse steps start_step + k interval - batches are cut there as for
+    slices - from the newest state of all levels: on the device where the stepper offers render, else from downloaded fields
+    (render.host_image). Each image is written to render_<name>_%06d.png and logs its rays per end code and its samples (render.py). A
+    stepper whose render_setup raises (the distributed one) ends the run before the first step.
     With cfg.tracers_enabled, the seed groups' particles are advanced behind the coarse steps start_step + k interval INSIDE the batches
     where the stepper offers tracers_setup - no batch is cut for an advance - and batches are cut only after the snapshot steps
     start_step + k output_interval, as for slices; a stepper without tracers_setup goes through tracers.HostTracers on downloaded
@@ -1121,6 +1147,17 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             try:
                 st.streamlines_setup(stream_plan.seeds, stream_plan.sign, cfg.streamlines_step, cfg.streamlines_min_speed,
                                      cfg.streamlines_max_steps, stream_start, stream_interval)
+            except Exception:
+                if hasattr(st, "close"):
+                    st.close()
+                raise
+    render_on = bool(cfg.render_enabled)
+    rd_start, rd_interval = cfg.render_start_step, cfg.render_interval
+    if render_on:
+        render_plans = [render_mod.ViewPlan(v, cfg.render_width, cfg.render_height, params.mesh_offset, grids[0].dx) for v in cfg.render_views]
+        if hasattr(st, "render_setup"):
+            try:
+                st.render_setup(cfg.render_max_pixels, rd_start, rd_interval)
             except Exception:
                 if hasattr(st, "close"):
                     st.close()
@@ -1317,6 +1354,15 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             for gi, name in enumerate(stream_plan.names):
                 log(f"streamlines {name!r}: step {step}: {stream_mod.summary(stream_plan, gi, counts, codes)}")
 
+    def take_render(step):
+        """every view of the state after coarse step `step`; files out, one log line per image"""
+        for plan in render_plans:
+            rgba, codes, samples = st.render(plan, step) if hasattr(st, "render") else render_mod.host_image(st, grids, plan, step)
+            if writing:
+                render_mod.write_png(os.path.join(out_dir, render_mod.render_file_name(plan.name, step)), render_mod.quantise(rgba))
+            if log:
+                log(f"render {plan.name!r}: step {step}: {render_mod.summary(codes, samples)}")
+
     def take_tracers(step):
         """the advance of the host fallback behind coarse step `step`, and at a snapshot step the snapshot: files out, one log line
         per group"""
@@ -1446,8 +1492,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             batch_end = min(t + batch - 1, total_steps)
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if (stats_on or surf_host is not None or slices_on or iso_on or stream_on or tracers_on or (flux_on and not dev_fluxes)
-                    or modes_live[0]):
+            if (stats_on or surf_host is not None or slices_on or iso_on or stream_on or render_on or tracers_on
+                    or (flux_on and not dev_fluxes) or modes_live[0]):
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
@@ -1460,6 +1506,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     cuts.update(stats_mod.sample_steps(t, batch_end, iso_start, iso_interval))
                 if stream_on:
                     cuts.update(stats_mod.sample_steps(t, batch_end, stream_start, stream_interval))
+                if render_on:
+                    cuts.update(stats_mod.sample_steps(t, batch_end, rd_start, rd_interval))
                 if tracers_on:           # on the device an advance cuts nothing: only the snapshot steps do
                     tr_cuts = set(stats_mod.sample_steps(t, batch_end, tr_start, tr_interval if tr_host is not None else tr_out))
                     cuts.update(tr_cuts)
@@ -1495,6 +1543,8 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         take_isosurfaces(s_step)
                     if stream_on and stats_mod.is_sample_step(s_step, stream_start, stream_interval):
                         take_streamlines(s_step)
+                    if render_on and stats_mod.is_sample_step(s_step, rd_start, rd_interval):
+                        take_render(s_step)
                     if tracers_on and s_step in tr_cuts:
                         take_tracers(s_step)
                     if flux_on and not dev_fluxes and stats_mod.is_sample_step(s_step, fx_start, fx_interval):

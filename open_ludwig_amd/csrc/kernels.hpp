@@ -2069,6 +2069,200 @@ __global__ __launch_bounds__(64) void k_tracers_snapshot(const TracerArgs a)
     if (c == 1) rec[1] = make_float4(q[2], q[3], (float)li, (float)code);
 }
 
+// ---- volume images (ludwig_render_*; no reference counterpart; include/ludwig_hip.h states the definition and
+// open_ludwig_amd/render.py restates it in numpy bit for bit) ----
+// One lane per ray, one wavefront per 8 x 8 pixel tile: the rays of a wave stay within a few cells of each other, so their block_pointer
+// entries, obstacle bytes and scalar values share cache lines, and a frame has millions of independent rays to hide the chain of dependent
+// loads of one sample (block_pointer, then obstacle, then values) - unlike a streamline set, where eight lanes share a point because the
+// points are few. Within a lane the eight corners are eight independent loads at each link of the chain.
+// The locate loop runs over the levels with a wave-uniform counter, so a level's table entry is read with scalar loads; a lane that
+// finds its level keeps what it needs of the entry in registers. Guards are the streamlines' (stream_cell, stream_block): a coordinate
+// becomes an integer only after the float range test, a block index is used only when the block_pointer entry is positive. The colour
+// table index comes from a value clamped to [0, 1]. A pixel is written by its own lane and by nothing else: no atomics.
+struct RenderScalar {
+    const float *s;              // the scalar of cell c of internal block b: s[b * stride + c]
+    int64_t stride;
+};
+
+struct RenderArgs {
+    const StreamLevel *lv;       // [n_levels]: bp, obstacle and the grid's extent are read, rho and vel are not
+    const RenderScalar *sc;      // [n_levels]
+    int32_t n_levels;
+    int32_t width, height, perspective;
+    float eye[3], corner[3], du[3], dv[3], dir[3];
+    float hi[3];                 // the box's upper corner
+    float step, lo, inv, t_min;
+    int32_t max_samples;
+    float bg[3], body[3];
+    const float4 *table;         // [256] r, g, b, kappa
+    float4 *rgba;                // [height][width]
+    int32_t *codes, *samples;    // [height][width]
+};
+
+constexpr int RENDER_EXIT = 0, RENDER_MISS = 1, RENDER_BODY = 2, RENDER_OPAQUE = 3, RENDER_SAMPLES = 4;
+constexpr int RENDER_FOUND = 0, RENDER_OUTSIDE = 1, RENDER_OBSTACLE = 2;
+
+// what a lane keeps of the level it found: the part of the table entry stream_block reads, and the scalar
+struct RenderHit {
+    StreamLevel L;               // bp, obstacle, gx, gy, gz
+    const float *s;
+    int64_t stride;
+    int i0[3];                   // base cell
+    int b0;                      // its internal block
+};
+
+// sample(P) of one lane: RENDER_FOUND with the value in s, RENDER_OBSTACLE or RENDER_OUTSIDE; li = the level index (0 when outside);
+// h describes the base cell unless outside
+__device__ __forceinline__ int render_sample(const RenderArgs &a, float px, float py, float pz, float &s, int &li, RenderHit &h)
+{
+    int found = -1;
+    float g[3] = {0.0f, 0.0f, 0.0f};
+    for (int l = a.n_levels - 1; l >= 0; --l) {                      // l is the same in every lane
+        if (found < 0) {
+            const StreamLevel &L = a.lv[l];
+            float gl[3];
+            int il[3];
+            if (stream_cell(L, l, px, py, pz, gl, il)) {
+                const int b = stream_block(L, il[0], il[1], il[2]);
+                if (b >= 0) {
+                    found = l;
+                    h.L.bp = L.bp; h.L.obstacle = L.obstacle;
+                    h.L.gx = L.gx; h.L.gy = L.gy; h.L.gz = L.gz;
+                    h.s = a.sc[l].s; h.stride = a.sc[l].stride;
+                    h.b0 = b;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) { g[k] = gl[k]; h.i0[k] = il[k]; }
+                }
+            }
+        }
+        if (__ballot(found < 0) == 0) break;
+    }
+    li = max(found, 0);
+    if (found < 0) return RENDER_OUTSIDE;
+    // the eight corners: eight block_pointer entries, then eight obstacle bytes, then eight values, each set independent loads
+    int bc[8], cell[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int x = h.i0[0] + (c & 1), y = h.i0[1] + ((c >> 1) & 1), z = h.i0[2] + (c >> 2);
+        bc[c] = c == 0 ? h.b0 : stream_block(h.L, x, y, z);
+        cell[c] = (x & 7) + 8 * (y & 7) + 64 * (z & 7);
+    }
+    bool fluid[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) fluid[c] = bc[c] >= 0 && h.L.obstacle[(int64_t)bc[c] * CELLS + cell[c]] == 0;
+    if (!fluid[0]) return RENDER_OBSTACLE;
+    float v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {                                    // a corner that is no fluid cell of the level takes the base cell's value
+        const int b = fluid[c] ? bc[c] : h.b0, ce = fluid[c] ? cell[c] : cell[0];
+        v[c] = h.s[(int64_t)b * h.stride + ce];
+    }
+    const float wx = g[0] - floorf(g[0]), wy = g[1] - floorf(g[1]), wz = g[2] - floorf(g[2]);
+    const float x0 = probe_lerp(v[0], v[1], wx), x1 = probe_lerp(v[2], v[3], wx), x2 = probe_lerp(v[4], v[5], wx), x3 = probe_lerp(v[6], v[7], wx);
+    s = probe_lerp(probe_lerp(x0, x1, wy), probe_lerp(x2, x3, wy), wz);
+    return RENDER_FOUND;
+}
+
+// 1 if the cell (x, y, z) of the hit's level is an obstacle cell of an active block, else 0
+__device__ __forceinline__ int render_solid(const RenderHit &h, int x, int y, int z)
+{
+    const int b = stream_block(h.L, x, y, z);
+    if (b < 0) return 0;
+    return h.L.obstacle[(int64_t)b * CELLS + (x & 7) + 8 * (y & 7) + 64 * (z & 7)] != 0 ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void k_render(const RenderArgs a)
+{
+    const int tiles_x = (a.width + 7) >> 3;
+    const int tile = (int)blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int i = 8 * tx + ((int)threadIdx.x & 7), j = 8 * ty + ((int)threadIdx.x >> 3);
+    if (i >= a.width || j >= a.height) return;
+    const int64_t pixel = (int64_t)j * a.width + i;
+    float o[3], d[3];
+    bool miss = false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) o[k] = (a.corner[k] + (float)i * a.du[k]) + (float)j * a.dv[k];
+    if (a.perspective) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            d[k] = o[k] - a.eye[k];
+            o[k] = a.eye[k];
+        }
+        const float m = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        miss = !(m > 0.0f && m < __int_as_float(0x7f800000));       // zero, infinite or NaN
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = d[k] / m;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = a.dir[k];
+    }
+    float t0 = 0.0f, t1 = __int_as_float(0x7f800000);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (d[k] == 0.0f) {
+            if (!(0.0f <= o[k] && o[k] <= a.hi[k])) miss = true;
+        } else {
+            const float p = (0.0f - o[k]) / d[k], q = (a.hi[k] - o[k]) / d[k];
+            t0 = fmaxf(t0, fminf(p, q));
+            t1 = fminf(t1, fmaxf(p, q));
+        }
+    }
+    if (!(t0 < t1)) miss = true;
+    float T = 1.0f, R = 0.0f, G = 0.0f, B = 0.0f;
+    int n = 0, code = RENDER_MISS;
+    if (!miss) {
+        float t = t0;
+        for (;;) {
+            if (!(t < t1)) { code = RENDER_EXIT; break; }
+            if (n == a.max_samples) { code = RENDER_SAMPLES; break; }
+            const float px = o[0] + t * d[0], py = o[1] + t * d[1], pz = o[2] + t * d[2];
+            float s = 0.0f;
+            int li = 0;
+            RenderHit h{};
+            const int kind = render_sample(a, px, py, pz, s, li, h);
+            ++n;
+            const float delta = ldexpf(a.step, -li);                 // exact
+            if (kind == RENDER_OBSTACLE) {
+                const int x = h.i0[0], y = h.i0[1], z = h.i0[2];
+                const int nx = render_solid(h, x - 1, y, z) - render_solid(h, x + 1, y, z);
+                const int ny = render_solid(h, x, y - 1, z) - render_solid(h, x, y + 1, z);
+                const int nz = render_solid(h, x, y, z - 1) - render_solid(h, x, y, z + 1);
+                const int nn = nx * nx + ny * ny + nz * nz;
+                float shade = 1.0f;
+                if (nn != 0) {
+                    const float c = -(((float)nx * d[0] + (float)ny * d[1]) + (float)nz * d[2]) / sqrtf((float)nn);
+                    shade = 0.3f + 0.7f * fmaxf(c, 0.0f);
+                }
+                R = R + T * (a.body[0] * shade);
+                G = G + T * (a.body[1] * shade);
+                B = B + T * (a.body[2] * shade);
+                T = 0.0f;
+                code = RENDER_BODY;
+                break;
+            }
+            if (kind == RENDER_FOUND && s == s) {
+                const float x = fminf(fmaxf((s - a.lo) * a.inv, 0.0f), 1.0f);    // fmaxf returns 0 for a NaN product
+                const float4 e = a.table[(int)(x * 255.0f + 0.5f)];
+                const float w = T * fminf(e.w * delta, 1.0f);
+                R = R + w * e.x;
+                G = G + w * e.y;
+                B = B + w * e.z;
+                T = T - w;
+                if (T < a.t_min) { code = RENDER_OPAQUE; break; }
+            }
+            t = t + delta;
+        }
+    }
+    if (code != RENDER_BODY) {
+        R = R + T * a.bg[0];
+        G = G + T * a.bg[1];
+        B = B + T * a.bg[2];
+    }
+    a.rgba[pixel] = make_float4(R, G, B, 1.0f - T);
+    a.codes[pixel] = code;
+    a.samples[pixel] = n;
+}
+
 // ---- iso-surfaces (ludwig_level_isosurface_*; no reference counterpart; open_ludwig_amd/isosurface.py states the definition and
 // restates it in numpy bit for bit) ----
 // Workgroup r = reference block r of the owned ones (the output order), 256 lanes, two x-consecutive anchor cells per lane. The block's

@@ -3536,8 +3536,8 @@ int ludwig_slices_download(LudwigSlices *S, float *values, size_t bytes)
     return LUDWIG_OK;
 }
 
-// ---- what the sets that locate points on the hierarchy themselves share (streamlines, tracers) ----
-// the creators' checks of the level array (`set` = "streamlines", "tracers"; `what` = "a line", "a particle")
+// ---- what the sets that locate points on the hierarchy themselves share (streamlines, tracers, render) ----
+// the creators' checks of the level array (`set` = "streamlines", "tracers", "render"; `what` = "a line", "a particle", "a ray")
 static int check_locator_levels(const char *set, const char *what, LudwigLevel *const *levels, int32_t n_levels)
 {
     for (int li = 0; li < n_levels; ++li) {
@@ -3700,6 +3700,186 @@ int ludwig_streamlines_download(LudwigStreamlines *S, int32_t *counts, int32_t *
     for (size_t i = 0; i < n; ++i) longest = std::max(longest, counts[i]);
     if (longest > 0)                                              // the used head of every line's row
         LW_HIP(hipMemcpy2D(vertices, row, S->rec, row, (size_t)longest * STREAM_REC_FLOATS * sizeof(float), n, hipMemcpyDeviceToHost));
+    return LUDWIG_OK;
+}
+
+// ---- volume images (ludwig_render_*; no reference counterpart) ----
+// The streamlines' level table plus what an image needs: per level the scalar's address (uploaded with every image, it depends on the
+// field and on t_coarse) and, for the scalars that are stored nowhere (|u|, |omega|), a buffer of the set, allocated by the first image
+// that asks for it; the colour table; the pixel buffers [max_pixels]. The host copies of the two uploaded tables belong to the set, so
+// an upload's source outlives the call that queued it.
+struct LudwigRender {
+    int device = 0;
+    int n_levels = 0;
+    int64_t max_pixels = 0;
+    int32_t width = 0, height = 0;              // of the last image; 0: none yet
+    std::vector<LudwigLevel *> levels;          // borrowed
+    std::vector<Dev<int32_t>> bp;               // per level
+    Dev<StreamLevel> table;                     // [n_levels]
+    std::vector<Dev<float>> scalar;             // per level [n_blocks][512], null until |u| or |omega| is first asked for
+    Dev<RenderScalar> sc;                       // [n_levels]
+    Dev<float4> colours;                        // [256]
+    Dev<float4> rgba;
+    Dev<int32_t> codes, samples;
+    std::vector<RenderScalar> h_sc;
+    std::vector<float4> h_colours;
+    HipEvent ev;
+    HipEvent uploaded;                          // behind the last upload of h_sc and h_colours
+    bool upload_queued = false;
+};
+
+void ludwig_render_destroy(LudwigRender *S) { destroy_set(S); }
+
+int ludwig_render_create(LudwigLevel *const *levels, int32_t n_levels, int64_t max_pixels, LudwigRender **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > 30) return fail(LUDWIG_ERR_INVALID, "render: n_levels %d not in 1..30", n_levels);
+    if (max_pixels < 1 || max_pixels > (int64_t)INT32_MAX)
+        return fail(LUDWIG_ERR_INVALID, "render: max_pixels %lld not in 1..2^31 - 1", (long long)max_pixels);
+    if (int rl = check_locator_levels("render", "a ray", levels, n_levels)) return rl;
+    std::unique_ptr<LudwigRender> S(new (std::nothrow) LudwigRender);
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "render: out of host memory");
+    S->device = levels[0]->device;
+    S->n_levels = n_levels;
+    S->max_pixels = max_pixels;
+    S->levels.assign(levels, levels + n_levels);
+    S->bp.resize(n_levels);
+    S->scalar.resize(n_levels);
+    S->h_sc.resize(n_levels);
+    S->h_colours.resize(256);
+    if (const int r = set_device(S->device)) return r;
+    hipError_t e = hipSuccess;
+    upload_locator_table(e, levels, n_levels, true, S->bp, S->table);
+    if (e == hipSuccess) e = (hipError_t)S->sc.alloc((size_t)n_levels);
+    if (e == hipSuccess) e = (hipError_t)S->colours.alloc(256);
+    if (e == hipSuccess) e = (hipError_t)S->rgba.alloc((size_t)max_pixels);
+    if (e == hipSuccess) e = (hipError_t)S->codes.alloc((size_t)max_pixels);
+    if (e == hipSuccess) e = (hipError_t)S->samples.alloc((size_t)max_pixels);
+    if (e == hipSuccess) e = (hipError_t)S->ev.create();
+    if (e == hipSuccess) e = (hipError_t)S->uploaded.create();
+    if (e != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "render: %lld pixels: %s", (long long)max_pixels, hipGetErrorString(e));
+    *out = S.release();
+    return LUDWIG_OK;
+}
+
+int ludwig_render_image(LudwigRender *S, int64_t t_coarse, int which, const float *scales, const float *camera, int perspective,
+                        int32_t width, int32_t height, const float *params, int32_t max_samples, const float *table)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null render set");
+    if (!scales || !camera || !params || !table) return fail(LUDWIG_ERR_INVALID, "render: null argument");
+    if (t_coarse < 0) return fail(LUDWIG_ERR_INVALID, "render: t_coarse %lld < 0", (long long)t_coarse);
+    if (which < LUDWIG_ISO_DENSITY || which > LUDWIG_ISO_VORTICITY_MAGNITUDE) return fail(LUDWIG_ERR_INVALID, "render: unknown scalar %d", which);
+    if (perspective != 0 && perspective != 1) return fail(LUDWIG_ERR_INVALID, "render: perspective %d is neither 0 nor 1", perspective);
+    if (width < 1 || height < 1 || (int64_t)width * height > S->max_pixels)
+        return fail(LUDWIG_ERR_INVALID, "render: %d x %d pixels, the set holds 1..%lld", width, height, (long long)S->max_pixels);
+    const float step = params[0], lo = params[1], hi = params[2], t_min = params[3];
+    if (!(step > 0.0f) || !std::isfinite(step)) return fail(LUDWIG_ERR_INVALID, "render: step %g must be positive and finite", (double)step);
+    if (!(t_min > 0.0f) || !std::isfinite(t_min)) return fail(LUDWIG_ERR_INVALID, "render: t_min %g must be positive and finite", (double)t_min);
+    if (!(hi > lo)) return fail(LUDWIG_ERR_INVALID, "render: range [%g, %g] is empty", (double)lo, (double)hi);
+    if (max_samples < 1) return fail(LUDWIG_ERR_INVALID, "render: max_samples %d < 1", max_samples);
+    for (int li = 0; li < S->n_levels; ++li)
+        if (!(scales[li] > 0.0f) || !std::isfinite(scales[li]))
+            return fail(LUDWIG_ERR_INVALID, "render: scales[%d] = %g must be positive and finite", li, (double)scales[li]);
+    LW_HIP(hipSetDevice(S->device));
+    hipStream_t st = S->levels[0]->stream;
+    if (S->upload_queued) LW_HIP(hipEventSynchronize(S->uploaded));   // the host tables are free to be rewritten
+    const bool gradient = which == LUDWIG_ISO_Q_CRITERION || which == LUDWIG_ISO_VORTICITY_MAGNITUDE;
+    for (int li = 0; li < S->n_levels; ++li) {
+        LudwigLevel *L = S->levels[li];
+        LW_ENSURE_RHO(L);
+        const int vf = vel_out(L, (t_coarse + 1) * ((int64_t)1 << li) - 1) == L->vel[1] ? LUDWIG_VEL_TEMP : LUDWIG_VEL;
+        RenderScalar &q = S->h_sc[li];
+        q.s = nullptr;
+        q.stride = CELLS;
+        if (L->n_blocks > 0) {                                    // a level without blocks is found by no ray
+            if (gradient) {
+                const int r = ludwig_level_gradient_fields_compute(L, vf, scales[li]);
+                if (r) return r;
+            }
+            if (which == LUDWIG_ISO_DENSITY) q.s = L->rho;
+            else if (which == LUDWIG_ISO_Q_CRITERION) { q.s = L->grad + 3 * CELLS; q.stride = GRAD_COMPONENTS * CELLS; }
+            else {
+                if (!S->scalar[li]) {
+                    const hipError_t ea = (hipError_t)S->scalar[li].alloc((size_t)L->n_blocks * CELLS);
+                    if (ea != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "render: scalar of level %d: %s", li, hipGetErrorString(ea));
+                }
+                if (which == LUDWIG_ISO_VELOCITY_MAGNITUDE)
+                    hipLaunchKernelGGL(k_iso_scalar<ISO_VELOCITY_MAGNITUDE>, dim3((unsigned)L->n_blocks), dim3(CELLS / 2), 0, L->stream,
+                                       S->scalar[li], (const float *)L->vel[vf == LUDWIG_VEL ? 0 : 1]);
+                else
+                    hipLaunchKernelGGL(k_iso_scalar<ISO_VORTICITY_MAGNITUDE>, dim3((unsigned)L->n_blocks), dim3(CELLS / 2), 0, L->stream,
+                                       S->scalar[li], (const float *)L->grad);
+                LW_HIP(hipGetLastError());
+                q.s = S->scalar[li];
+            }
+        }
+        if (L->stream != st) {                                    // the image reads what this level's stream has queued
+            LW_HIP(hipEventRecord(S->ev, L->stream));
+            LW_HIP(hipStreamWaitEvent(st, S->ev, 0));
+        }
+    }
+    for (int i = 0; i < 256; ++i) S->h_colours[i] = make_float4(table[4 * i], table[4 * i + 1], table[4 * i + 2], table[4 * i + 3]);
+    LW_HIP(hipMemcpyAsync(S->sc, S->h_sc.data(), (size_t)S->n_levels * sizeof(RenderScalar), hipMemcpyHostToDevice, st));
+    LW_HIP(hipMemcpyAsync(S->colours, S->h_colours.data(), 256 * sizeof(float4), hipMemcpyHostToDevice, st));
+    LW_HIP(hipEventRecord(S->uploaded, st));
+    S->upload_queued = true;
+    RenderArgs a;
+    a.lv = S->table;
+    a.sc = S->sc;
+    a.n_levels = S->n_levels;
+    a.width = width;
+    a.height = height;
+    a.perspective = perspective;
+    for (int k = 0; k < 3; ++k) {
+        a.eye[k] = camera[k];
+        a.corner[k] = camera[3 + k];
+        a.du[k] = camera[6 + k];
+        a.dv[k] = camera[9 + k];
+        a.dir[k] = camera[12 + k];
+        a.bg[k] = params[4 + k];
+        a.body[k] = params[7 + k];
+    }
+    a.hi[0] = (float)(8 * S->levels[0]->gdx) + 0.5f;
+    a.hi[1] = (float)(8 * S->levels[0]->gdy) + 0.5f;
+    a.hi[2] = (float)(8 * S->levels[0]->gdz) + 0.5f;
+    a.step = step;
+    a.lo = lo;
+    a.inv = 1.0f / (hi - lo);
+    a.t_min = t_min;
+    a.max_samples = max_samples;
+    a.table = S->colours;
+    a.rgba = S->rgba;
+    a.codes = S->codes;
+    a.samples = S->samples;
+    const int64_t tiles = (int64_t)((width + 7) / 8) * ((height + 7) / 8);
+    hipLaunchKernelGGL(k_render, dim3((unsigned)tiles), dim3(64), 0, st, a);
+    LW_HIP(hipGetLastError());
+    S->width = width;
+    S->height = height;
+    bool others = false;
+    for (int li = 1; li < S->n_levels; ++li) others = others || S->levels[li]->stream != st;
+    if (others) {                                                 // and nothing queued there later overtakes the image's reads
+        LW_HIP(hipEventRecord(S->ev, st));
+        for (int li = 1; li < S->n_levels; ++li)
+            if (S->levels[li]->stream != st) LW_HIP(hipStreamWaitEvent(S->levels[li]->stream, S->ev, 0));
+    }
+    return LUDWIG_OK;
+}
+
+int ludwig_render_download(LudwigRender *S, float *rgba, int32_t *codes, int32_t *samples, size_t bytes)
+{
+    if (!S) return fail(LUDWIG_ERR_INVALID, "null render set");
+    if (S->width == 0) return fail(LUDWIG_ERR_STATE, "render: download before ludwig_render_image");
+    const size_t n = (size_t)S->width * S->height;
+    if (bytes != n * sizeof(float4)) return fail(LUDWIG_ERR_INVALID, "render: got %zu bytes, expected %zu", bytes, n * sizeof(float4));
+    if (!rgba || !codes || !samples) return fail(LUDWIG_ERR_INVALID, "null argument");
+    LW_HIP(hipSetDevice(S->device));
+    LW_HIP(hipStreamSynchronize(S->levels[0]->stream));
+    LW_HIP(hipMemcpy(rgba, S->rgba, n * sizeof(float4), hipMemcpyDeviceToHost));
+    LW_HIP(hipMemcpy(codes, S->codes, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    LW_HIP(hipMemcpy(samples, S->samples, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return LUDWIG_OK;
 }
 

@@ -143,6 +143,15 @@ class CaseConfig:
     streamlines_direction: str = "both"
     streamlines_max_vertices: int = 20_000_000
     streamlines_seeds: Tuple["StreamlineSeeds", ...] = ()
+    # volume images, advanced.render (no reference counterpart): every view ray-marched on the device through every level every
+    # `interval` coarse steps from `start_step`, written to render_<name>_%06d.png (render.py)
+    render_enabled: bool = False
+    render_start_step: int = 1
+    render_interval: int = 100
+    render_width: int = 1280
+    render_height: int = 720
+    render_max_pixels: int = 8_294_400
+    render_views: Tuple["RenderView", ...] = ()
     # tracers, advanced.tracers (no reference counterpart): particles advected on the device inside every batch, one advance every
     # `interval` coarse steps from `start_step`, one release per seed every `release_every` advances into a ring of `generations`; every
     # `output_interval` coarse steps a snapshot goes to tracers_<name>_%06d.vtp and tracers_<name>.pvd (tracers.py)
@@ -228,6 +237,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     slices = _slices_config(g("advanced", "slices", default=None))
     isosurfaces = _isosurfaces_config(g("advanced", "isosurfaces", default=None))
     streamlines = _streamlines_config(g("advanced", "streamlines", default=None))
+    render = _render_config(g("advanced", "render", default=None))
     tracers = _tracers_config(g("advanced", "tracers", default=None), int(g("basic", "simulation", "steps", required=True)))
     flux_planes = _flux_planes_config(g("advanced", "flux_planes", default=None))
     fourier_modes = _fourier_modes_config(g("advanced", "fourier_modes", default=None))
@@ -289,6 +299,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **slices,
         **isosurfaces,
         **streamlines,
+        **render,
         **tracers,
         **flux_planes,
         **fourier_modes,
@@ -758,6 +769,98 @@ def _streamlines_config(sc) -> dict:
     return dict(streamlines_enabled=True, streamlines_start_step=start, streamlines_interval=interval, streamlines_step=step,
                 streamlines_max_steps=max_steps, streamlines_min_speed=min_speed, streamlines_direction=direction,
                 streamlines_max_vertices=cap, streamlines_seeds=tuple(groups))
+
+
+@dataclass(frozen=True)
+class RenderView:
+    """one entry of advanced.render.views (semantics: render.py); camera points in the STL frame after stl_scale"""
+    name: str
+    field: str                                              # isosurface.FIELDS
+    lo: float
+    hi: float
+    colormap: Tuple[Tuple[float, float, float, float, float], ...]   # control points [x, r, g, b, opacity]
+    opacity: float                                          # times the control points' opacity: extinction per coarse cell length
+    camera: Tuple[Tuple[str, object], ...]                  # the camera mapping's items, validated
+    step: float
+    max_samples: int
+    background: Tuple[float, float, float]
+    body_color: Tuple[float, float, float]
+
+
+def _render_config(rc) -> dict:
+    """advanced.render: {enabled: false, start_step: 1, interval: 100, width: 1280, height: 720, max_pixels: 8294400, views: [{name, field,
+    range: [lo, hi], colormap: gray | heat | coolwarm | [[x, r, g, b, opacity], ...], opacity: 1.0, camera: {type, position, look_at, up,
+    fov | extent}, step: 0.5, max_samples: 4096, background: [0, 0, 0], body_color: [0.7, 0.7, 0.7]}]} -> CaseConfig fields. Absent or
+    disabled: the defaults."""
+    if rc is None:
+        return {}
+    if not isinstance(rc, dict):
+        raise ValueError("advanced.render must be a mapping")
+    if not bool(rc.get("enabled", False)):
+        return {}
+    from .isosurface import FIELDS
+    from .render import Camera, control_points
+    try:
+        start, interval = int(rc.get("start_step", 1)), int(rc.get("interval", 100))
+        width, height, cap = int(rc.get("width", 1280)), int(rc.get("height", 720)), int(rc.get("max_pixels", 8_294_400))
+    except (TypeError, ValueError):
+        raise ValueError("advanced.render: start_step, interval, width, height and max_pixels must be integers") from None
+    for key, v in (("interval", interval), ("start_step", start), ("width", width), ("height", height), ("max_pixels", cap)):
+        if v < 1:
+            raise ValueError(f"advanced.render.{key} must be >= 1, got {v}")
+    if width * height > cap:
+        raise ValueError(f"advanced.render: width x height = {width * height} pixels are more than advanced.render.max_pixels = {cap}")
+    raw = rc.get("views") or []
+    if not isinstance(raw, (list, tuple)) or not raw:
+        raise ValueError("advanced.render.enabled needs at least one entry in advanced.render.views")
+
+    def colour(vc, key, default, where):
+        try:
+            c = tuple(float(v) for v in vc.get(key, default))
+        except (TypeError, ValueError):
+            raise ValueError(f"{where}.{key} must be [r, g, b]") from None
+        if len(c) != 3 or not all(math.isfinite(v) and 0.0 <= v <= 1.0 for v in c):
+            raise ValueError(f"{where}.{key} must be three numbers in 0..1, got {list(c)}")
+        return c
+    views, seen = [], set()
+    for i, vc in enumerate(raw):
+        where = f"advanced.render.views[{i}]"
+        if not isinstance(vc, dict):
+            raise ValueError(f"{where} must be a mapping")
+        name = str(vc.get("name", ""))
+        if not name or not all(ch.isalnum() or ch in "_-." for ch in name) or name.startswith("."):
+            raise ValueError(f"{where}.name {name!r} is not a plain file-name stem")
+        if name in seen:
+            raise ValueError(f"{where}.name {name!r} is not unique")
+        seen.add(name)
+        field = str(vc.get("field", ""))
+        if field not in FIELDS:
+            raise ValueError(f"{where}.field {vc.get('field')!r} is unknown (one of {', '.join(FIELDS)})")
+        try:
+            lo, hi = (float(v) for v in vc["range"])
+        except (KeyError, TypeError, ValueError):
+            raise ValueError(f"{where}.range must be [lo, hi]") from None
+        if not (math.isfinite(lo) and math.isfinite(hi) and float(np.float32(hi)) > float(np.float32(lo))):
+            raise ValueError(f"{where}.range must be finite with hi > lo in float32, got [{lo}, {hi}]")
+        points = control_points(vc.get("colormap", "gray"), f"{where}.colormap")
+        try:
+            opacity, step = float(vc.get("opacity", 1.0)), float(vc.get("step", 0.5))
+            max_samples = int(vc.get("max_samples", 4096))
+        except (TypeError, ValueError):
+            raise ValueError(f"{where}.opacity, {where}.step and {where}.max_samples must be numbers") from None
+        if not (math.isfinite(opacity) and opacity >= 0.0):
+            raise ValueError(f"{where}.opacity must be finite and >= 0, got {opacity}")
+        if not (math.isfinite(step) and step > 0.0):
+            raise ValueError(f"{where}.step must be positive and finite, got {step}")
+        if max_samples < 1:
+            raise ValueError(f"{where}.max_samples must be >= 1, got {max_samples}")
+        cam = vc.get("camera")
+        Camera.build(cam, width, height, where=f"{where}.camera")          # refuses what it cannot build
+        cam_items = tuple((str(k), tuple(float(x) for x in v) if isinstance(v, (list, tuple)) else v) for k, v in sorted(cam.items()))
+        views.append(RenderView(name, field, lo, hi, tuple(tuple(float(v) for v in p) for p in points), opacity, cam_items, step,
+                                max_samples, colour(vc, "background", (0.0, 0.0, 0.0), where), colour(vc, "body_color", (0.7, 0.7, 0.7), where)))
+    return dict(render_enabled=True, render_start_step=start, render_interval=interval, render_width=width, render_height=height,
+                render_max_pixels=cap, render_views=tuple(views))
 
 
 def _tracers_config(tc, steps: int) -> dict:
