@@ -741,6 +741,49 @@ int  ludwig_execute_timestep_batch_tracers(LudwigLevel *const *levels, int32_t n
                                            int64_t force_start_step, int32_t force_interval, LudwigTracers *tracers, int64_t start_step,
                                            int32_t interval);
 
+/* ---- warm start: a level filled from another hierarchy's flow, resampled on the device (no reference counterpart: the reference starts
+ * every run from rest, init_eq! src/main.jl:109-134) ----
+ * What is carried over is the macroscopic state, rho and u; the populations restart at their equilibrium, so the non-equilibrium part
+ * (the viscous stress) is rebuilt by the first steps. A level initialised this way is NOT what a continued run would hold, not even on
+ * an identical grid. A cell that a finer source level covers takes the finer level's interpolated value (sample(P) chooses the finest).
+ *
+ * A flow source is a level hierarchy reduced to what the streamlines' sample(P) reads: per level the grid dimensions, the dense 1-based
+ * block_pointer, obstacle, rho and ONE velocity array, in device memory of its own (17 B per cell; no populations; no LudwigLevel).
+ * Float32, no contraction; open_ludwig_amd/warm_start.py (init_host) restates every bit.
+ *
+ * ludwig_level_init_from_source: for every cell (x, y, z) of every block the level holds (ghost blocks included), with the global cell
+ * coordinates gc_a = 8 (map_a - 1) + x_a of its block row: P_a = a_a ((float)gc_a + 0.5f) + b_a - the sum in brackets is exact (a level
+ * with more than 2^23 cells per axis is refused), the product and the sum are rounded once each; map = a_x, a_y, a_z, b_x, b_y, b_z, so P
+ * is a position in cell units of the source's level index 0. (code, q, li) = the streamlines' sample(P) on the source, with rho. If code
+ * is 0 and all four q are finite, with s = vel_scale: rho' = 1.0f + (q_rho - 1.0f) (s s), u'_k = q_k s; otherwise rho', u' = fallback
+ * (rho, ux, uy, uz). An obstacle cell of the level gets rho' = 1, u' = 0. Stored: rho = rho', vel = vel_temp = u', f = f_temp =
+ * calculate_equilibrium(rho', u', w_k, c_k) (src/physics_utils.jl:34-39) for the 27 k; on a level with temporal storage f_old, rho_old and
+ * vel_old get the same values. counts (may be NULL), over the non-obstacle cells of the level: [0] found, [1] outside the source, [2] in
+ * a source obstacle cell, [3] found but not finite, then [4 + li] the found cells per source level - integer sums, whatever the order.
+ * Afterwards the level is in the state ludwig_level_upload of these arrays would leave it in: nothing older survives in a record, an
+ * elided rho store or an aliased saved state. Queued on the level's stream; with counts one small download and one synchronisation. A
+ * level created with n_owned < 0 accepts the call and does nothing (counts zero). */
+typedef struct LudwigFlowSource LudwigFlowSource;   /* opaque */
+/* Host arrays per level, level index 0 first, in the reference layout and block order: grid_dims[3 li + a] blocks per axis,
+ * block_pointer[li] [dim_x,dim_y,dim_z] 1-based with 0 = absent, obstacle[li] [8,8,8,nb] u8, rho[li] [8,8,8,nb] f32, vel[li] [8,8,8,nb,3]
+ * f32 with nb = n_blocks[li]. LUDWIG_ERR_INVALID: a null array, n_levels not in 1..30, a block_pointer entry outside 0..nb, more than
+ * 2^24 cells per axis. */
+int  ludwig_flow_source_create(int device, int32_t n_levels, const int32_t *grid_dims, const int32_t *n_blocks,
+                               const int32_t *const *block_pointer, const uint8_t *const *obstacle, const float *const *rho,
+                               const float *const *vel, LudwigFlowSource **out);
+/* A device-to-device copy of every level's newest state after coarse step t_coarse (level index li: sub-step 2^li (t_coarse + 1) - 1,
+ * vel_temp if that is even, vel if odd; rho as a download would return it), under the streamline sets' conditions (block_pointer, no
+ * ghost blocks, one device; errors as ludwig_streamlines_create). The copies are queued on the levels' streams behind their steps and
+ * waited for; the source shares no memory with the levels, which may step on or be destroyed. */
+int  ludwig_flow_source_from_levels(LudwigLevel *const *levels, int32_t n_levels, int64_t t_coarse, LudwigFlowSource **out);
+/* frees the source; levels initialised from it keep what they got */
+void ludwig_flow_source_destroy(LudwigFlowSource *src);
+/* map: 6 floats, fallback: 4 floats, counts: 4 + (levels of the source) int64 or NULL. Refused before anything is launched or written,
+ * LUDWIG_ERR_INVALID: a null level, source, map or fallback; a map or fallback entry that is not finite; a_a <= 0; vel_scale not finite
+ * or <= 0; more than 2^23 cells per axis. LUDWIG_ERR_STATE: the source is on another device than the level. */
+int  ludwig_level_init_from_source(LudwigLevel *level, const LudwigFlowSource *src, const float *map, float vel_scale,
+                                   const float *fallback, int64_t *counts);
+
 /* ---- subgrid model: the WALE eddy viscosity the step collides with, and its time-averaged measures (no reference counterpart for the
  * output; the model is perform_timestep_v2!'s, src/physics_kernels.jl:251-300) ----
  * Per cell of the blocks this device owns, from one velocity buffer u: the gradient in lattice units g_ij = 0.5f (u_i(+e_j) - u_i(-e_j))

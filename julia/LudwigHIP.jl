@@ -333,6 +333,44 @@ function tracers_download!(records::Matrix{Float32}, s::Ptr{Cvoid})
     return Int(n[])
 end
 
+# warm start (no reference counterpart): a level filled from another hierarchy's rho and u, the populations at their equilibrium
+"""a flow source from host arrays, one entry per level (first level first): block_pointer (Array{Int32,3}, 1-based, 0 = absent), obstacle
+(8 x 8 x 8 x nb UInt8), rho (8 x 8 x 8 x nb Float32), vel (8 x 8 x 8 x nb x 3 Float32). Free it with `flow_source_destroy`."""
+function flow_source_create(device::Integer, block_pointer::Vector{Array{Int32,3}}, obstacle::Vector{Array{UInt8,4}},
+                            rho::Vector{Array{Float32,4}}, vel::Vector{Array{Float32,5}})
+    n = length(block_pointer)
+    dims = Int32[size(block_pointer[li], a) for a in 1:3, li in 1:n]
+    nb = Int32[size(rho[li], 4) for li in 1:n]
+    pb = Ptr{Int32}[pointer(a) for a in block_pointer]
+    po = Ptr{UInt8}[pointer(a) for a in obstacle]
+    pr = Ptr{Float32}[pointer(a) for a in rho]
+    pv = Ptr{Float32}[pointer(a) for a in vel]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve block_pointer obstacle rho vel dims nb pb po pr pv check(ccall((:ludwig_flow_source_create, LIB), Cint,
+        (Cint, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Ptr{Int32}}, Ptr{Ptr{UInt8}}, Ptr{Ptr{Float32}}, Ptr{Ptr{Float32}}, Ref{Ptr{Cvoid}}),
+        Cint(device), Int32(n), dims, nb, pb, po, pr, pv, out))
+    return out[]
+end
+"""a flow source copied on the device from the newest state of `grids` after coarse step `t_coarse` (the streamline sets' conditions)"""
+function flow_source_from_levels(grids::Vector{DeviceLevel}, t_coarse::Integer)
+    handles = Ptr{Cvoid}[g.handle for g in grids]
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve handles check(ccall((:ludwig_flow_source_from_levels, LIB), Cint, (Ptr{Ptr{Cvoid}}, Int32, Int64, Ref{Ptr{Cvoid}}),
+        handles, Int32(length(grids)), Int64(t_coarse), out))
+    return out[]
+end
+flow_source_destroy(s::Ptr{Cvoid}) = ccall((:ludwig_flow_source_destroy, LIB), Cvoid, (Ptr{Cvoid},), s)
+"""fill `grid` from the source: map = (a_x, a_y, a_z, b_x, b_y, b_z), P = a (cell centre) + b in cells of the source's first level;
+rho' = 1 + (rho - 1) vel_scale^2, u' = u vel_scale, fallback (rho, ux, uy, uz) where the source has no finite value; f = f_temp =
+equilibrium. Returns the counts: found, outside, source obstacle, non-finite, then found per source level (`n_src_levels` of them)."""
+function init_from_source!(grid::DeviceLevel, src::Ptr{Cvoid}, map::Vector{Float32}, vel_scale::Real, fallback::Vector{Float32},
+                           n_src_levels::Integer)
+    counts = zeros(Int64, 4 + n_src_levels)
+    GC.@preserve map fallback counts check(ccall((:ludwig_level_init_from_source, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Cfloat, Ptr{Float32}, Ptr{Int64}), grid.handle, src, map, Float32(vel_scale), fallback, counts))
+    return counts
+end
+
 # surface statistics (no reference counterpart): 7 float64 sums per triangle of p, p^2, tau, |tau|, |tau|^2 at its nearest fluid cell
 """a surface set on `grid`: per triangle its nearest fluid cell (0-based reference block index, -1 = none; cell x + 8y + 64z), wall
 distance in lattice units and normal (3 x n); tau and the two scales from `sp`. Free it with `surface_stats_destroy`."""

@@ -74,6 +74,7 @@ EXPORTED_SYMBOLS = [
     "ludwig_flux_planes_create", "ludwig_flux_planes_destroy", "ludwig_flux_planes_sample", "ludwig_flux_planes_download",
     "ludwig_modes_create", "ludwig_modes_destroy", "ludwig_modes_reset", "ludwig_modes_accumulate", "ludwig_modes_download",
     "ludwig_record_step_rule", "ludwig_level_record_steps",
+    "ludwig_flow_source_create", "ludwig_flow_source_from_levels", "ludwig_flow_source_destroy", "ludwig_level_init_from_source",
 ]
 UNIQUE_ID_BYTES = 128
 HALO_GROUPS = ("f", "vel", "f_post", "rho")      # group index of partition.FIELD_GROUPS in a LudwigHaloPlanDesc
@@ -278,6 +279,10 @@ def load() -> C.CDLL:
         "ludwig_modes_download": (C.c_int, [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_int32)]),
         "ludwig_execute_timestep_batch_tracers": (C.c_int, [C.POINTER(vp), i32, i64, i32, f32, C.POINTER(StepFlags), C.POINTER(BatchSamplers),
                                                             vp, i64, i32, vp, i64, i32]),
+        "ludwig_flow_source_create": (C.c_int, [i32, i32, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+        "ludwig_flow_source_from_levels": (C.c_int, [C.POINTER(vp), i32, i64, C.POINTER(vp)]),
+        "ludwig_flow_source_destroy": (None, [vp]),
+        "ludwig_level_init_from_source": (C.c_int, [vp, vp, vp, f32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError if the .so does not export what the header declares

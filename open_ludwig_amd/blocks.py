@@ -468,6 +468,19 @@ class DeviceLevel(_lib.Handle):
         """init_eq! (src/main.jl:109-134)"""
         _lib.check(self._lib.ludwig_init_equilibrium(self.handle))
 
+    # -- warm start (warm_start.py; no reference counterpart) --
+    def init_from_source(self, source, map6, vel_scale=1.0, fallback=(1.0, 0.0, 0.0, 0.0), counts: bool = True):
+        """fill every state array of the level from a warm_start.DeviceFlowSource: rho and u resampled at P = a (cell centre) + b
+        (map6 = a_x, a_y, a_z, b_x, b_y, b_z, float32), rho' = 1 + (rho - 1) vel_scale^2, u' = u vel_scale, `fallback` (rho, ux, uy, uz)
+        where the source holds no finite value; f = f_temp = equilibrium (warm_start.py states the definition).
+        -> counts int64 [4 + source levels]: found, outside, source obstacle, non-finite, found per source level (None with counts=False)"""
+        m = np.ascontiguousarray(map6, dtype=np.float32).reshape(6)
+        fb = np.ascontiguousarray(fallback, dtype=np.float32).reshape(4)
+        c = np.zeros(4 + source.n_levels, np.int64) if counts else None
+        _lib.check(self._lib.ludwig_level_init_from_source(self.handle, source.handle, m.ctypes.data, float(np.float32(vel_scale)),
+                                                           fb.ctypes.data, c.ctypes.data if counts else None))
+        return c
+
     def copy_to_old(self, t_sub: int) -> None:
         """copy_to_old!(level, f_in, vel_in) for the step t_sub about to run (src/blocks.jl:199-205)."""
         _lib.check(self._lib.ludwig_save_old(self.handle, int(t_sub)))

@@ -31,6 +31,7 @@ from . import statistics as stats_mod
 from . import subgrid as subgrid_mod
 from . import surface_stats as surface_mod
 from . import wall_diagnostics as wall_mod
+from . import warm_start as warm_mod
 from . import _lib
 from .blocks import adapt
 from .preprocess import CaseConfig, DomainParameters, setup_multilevel_domain, solver_params
@@ -104,6 +105,25 @@ class HipStepper:
             if X is not None:
                 self._flux_series.append(*X.download())
             t = seg_end + 1
+
+    # -- warm start (warm_start.py; no reference counterpart) --
+    def flow_source(self, t_coarse: int):
+        """a warm_start.DeviceFlowSource of every level's newest state after coarse step t_coarse, copied on the device"""
+        return warm_mod.DeviceFlowSource.from_levels(self.dev, t_coarse)
+
+    def init_from(self, state_or_source, first_step: int, maps, vel_scale=1.0, fallback=(1.0, 0.0, 0.0, 0.0)):
+        """fill every level from a warm_start.FlowState (uploaded for the call) or a DeviceFlowSource; maps: one map [6] per level
+        (warm_start.affine_map). The run then continues at coarse step first_step: f = f_temp, so the A/B parity of that step finds the
+        same state either way. -> the counts of every level (DeviceLevel.init_from_source)"""
+        if int(first_step) < 1:
+            raise ValueError(f"initial condition: first_step {first_step} < 1")
+        own = isinstance(state_or_source, warm_mod.FlowState)
+        src = warm_mod.DeviceFlowSource(state_or_source, self.dev[0].device) if own else state_or_source
+        try:
+            return [d.init_from_source(src, maps[li], vel_scale, fallback) for li, d in enumerate(self.dev)]
+        finally:
+            if own:
+                src.close()
 
     # -- probes (no reference counterpart) --
     def probes_setup(self, plan, start_step: int = 1, interval: int = 1, capacity: int = 64) -> None:
@@ -961,6 +981,19 @@ class DistributedStepper:
         raise RuntimeError("advanced.isosurfaces is enabled, but a distributed run cannot extract iso-surfaces yet: ghost blocks hold no "
                            "gradient fields and only part of rho / vel (DESIGN section 8, Next)")
 
+    # -- warm start: not over ranks (a state holds whole levels; each rank holds only its own blocks) --
+    def state_files_setup(self, *args, **kwargs) -> None:
+        raise RuntimeError("advanced.state_files is enabled, but a distributed run cannot write state files yet: each rank holds only "
+                           "its own blocks of a level")
+
+    def init_from(self, *args, **kwargs):
+        raise RuntimeError("advanced.initial_condition is set, but a distributed run cannot start from a state file yet: the source "
+                           "hierarchy would have to be held by every rank")
+
+    def flow_source(self, *args, **kwargs):
+        raise RuntimeError("a distributed run cannot make a flow source (advanced.initial_condition, advanced.state_files): each rank "
+                           "holds only its own blocks of a level")
+
     # -- streamlines: not over ranks. A line wanders through every level and every block, and a rank holds only its own --
     def streamlines_setup(self, *args, **kwargs) -> None:
         raise RuntimeError("advanced.streamlines is enabled, but a distributed run cannot trace streamlines yet: a line crosses the "
@@ -1106,7 +1139,14 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     interval, n < N = samples. Batches are cut at a window's last step only - one cut per window, none for the samples. There the sums
     are downloaded, flow_modes_%06d.vtu (output.export_modes_mesh) and one flow_modes.csv row per mode and level are written, and with
     `repeat` the sums are reset for the next window (without it the set is closed). A window unfinished at the end of the run writes
-    nothing and says so in `log`. Device only: a stepper without modes_setup raises."""
+    nothing and says so in `log`. Device only: a stepper without modes_setup raises.
+    With cfg.state_files_enabled (advanced.state_files) and an out_dir, state_%06d.npz (warm_start.FlowState: rho and the newest velocity
+    of every level, from downloaded fields) is written after the coarse steps that are multiples of `interval` and after the last step
+    (interval 0: the last step only); batches are cut there as for slices.
+    With cfg.initial_condition_state (advanced.initial_condition), after set-up and the rest state every level is filled from that state
+    file on the device (warm_start.py: rho and u resampled, the populations at their equilibrium - NOT what a continued run would hold),
+    `log` gets one line of counts per level, and the loop starts at coarse step first_step and runs `steps` steps from there: step
+    numbers in every file count from first_step. Device only: a stepper without init_from raises."""
     import time as _time
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
@@ -1124,6 +1164,32 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     # a frequency the sampling cannot resolve is refused before anything is allocated on a device
     mplan = modes_mod.plan_modes(cfg, params, log) if modes_on else None
     st = stepper_factory(grids)
+    ic_on = bool(cfg.initial_condition_state)
+    first_step = int(cfg.initial_condition_first_step) if ic_on else 1
+    state_on = bool(cfg.state_files_enabled) and out_dir is not None and write_files
+    try:
+        if cfg.state_files_enabled and hasattr(st, "state_files_setup"):
+            st.state_files_setup()               # the distributed stepper refuses
+        if ic_on:
+            if not hasattr(st, "init_from"):
+                raise RuntimeError(f"advanced.initial_condition is set, but {type(st).__name__} offers no init_from: a level is filled "
+                                   "from a state file on the device only")
+            ic_state = warm_mod.load_state(warm_mod.resolve_state_path(cfg.initial_condition_state, cfg.case_dir))
+            ic_scale = cfg.initial_condition_velocity_scale
+            if ic_scale is None:                 # auto: both runs' flows at their own lattice speed
+                ic_scale = float(cfg.u_lattice) / ic_state.u_lattice
+            ic_counts = st.init_from(ic_state, first_step, [warm_mod.affine_map(ic_state, g.dx, params.mesh_offset) for g in grids], ic_scale,
+                                     (1.0, float(ramp_velocity(first_step, cfg.ramp_steps, cfg.u_lattice)), 0.0, 0.0))
+            if log:
+                log(f"initial condition: {cfg.initial_condition_state} (case {ic_state.case!r}, step {ic_state.step}, "
+                    f"{ic_state.n_levels} levels), velocity scale {ic_scale:.6g}, first step {first_step}; the populations restart at "
+                    "equilibrium")
+                for g, c in zip(grids, ic_counts):
+                    log(warm_mod.counts_line(g.level_id, c))
+    except Exception:
+        if hasattr(st, "close"):
+            st.close()
+        raise
     if modes_on and not hasattr(st, "modes_setup"):
         if hasattr(st, "close"):
             st.close()
@@ -1212,10 +1278,10 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             st.close()
         raise RuntimeError(f"advanced.forces.series is enabled, but {type(st).__name__} offers no force_series_setup: the force series "
                            "is reduced on the device only")
-    total_steps = steps if steps is not None else cfg.steps
+    total_steps = first_step - 1 + (steps if steps is not None else cfg.steps)
     rows: List[DiagRow] = []
     batch = cfg.async_depth
-    t = 1
+    t = first_step
     writing = out_dir is not None and write_files
     if probes_on:
         st.probes_setup(pplan, cfg.probes_start_step, cfg.probes_interval, max(batch, 1))
@@ -1493,7 +1559,7 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
             actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
             if (stats_on or surf_host is not None or slices_on or iso_on or stream_on or render_on or tracers_on
-                    or (flux_on and not dev_fluxes) or modes_live[0]):
+                    or (flux_on and not dev_fluxes) or modes_live[0] or state_on):
                 # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
                 cuts = set()
                 if stats_on:
@@ -1518,6 +1584,13 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     ends = modes_mod.window_end_steps(t, batch_end, mplan.start_step, mplan.interval, mplan.samples)
                     mode_cuts = set(ends if mplan.repeat else ends[:1])
                     cuts.update(mode_cuts)
+                state_cuts = set()
+                if state_on:             # the multiples of the interval, and the last step
+                    if cfg.state_files_interval > 0:
+                        state_cuts.update(stats_mod.sample_steps(t, batch_end, cfg.state_files_interval, cfg.state_files_interval))
+                    if batch_end == total_steps:
+                        state_cuts.add(total_steps)
+                    cuts.update(state_cuts)
                 seg = t
                 for s_step in sorted(cuts):
                     st.batch(seg, s_step - seg + 1, u_curr, sp)
@@ -1551,6 +1624,12 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                         flux_host.append((s_step, *flux_mod.host_sample(st, fplans, s_step)))
                     if s_step in mode_cuts:
                         take_modes(s_step)
+                    if s_step in state_cuts:
+                        warm_mod.save_state(os.path.join(out_dir, warm_mod.state_file_name(s_step)),
+                                            warm_mod.state_from_stepper(st, grids, s_step, params.mesh_offset, float(cfg.u_lattice),
+                                                                        os.path.basename(cfg.case_dir)))
+                        if log:
+                            log(f"state file {warm_mod.state_file_name(s_step)} written")
                     seg = s_step + 1
                 if seg <= batch_end:
                     st.batch(seg, batch_end - seg + 1, u_curr, sp)

@@ -3157,4 +3157,120 @@ __global__ __launch_bounds__(256) void k_wall_surface(float *__restrict__ out, c
     o[4 * N] = s.u_tau; o[5 * N] = s.y_plus; o[6 * N] = (float)s.code;
 }
 
+// ---- warm start (ludwig_level_init_from_source; no reference counterpart; include/ludwig_hip.h states the definition and
+// open_ludwig_amd/warm_start.py restates it in numpy bit for bit) ----
+// A level filled from another hierarchy's rho and u, the populations at their equilibrium. One workgroup of 256 lanes per destination
+// block, two phases:
+//   sample: the block's 512 cells in 16 rounds of 32, one group of eight lanes per cell - stream_sample's mapping, unchanged: the lanes
+//           of a group form the same P from the same words, so they run the same control flow and a shuffle meets its partners; every
+//           group of every round samples (512 = 16 x 32: no lane leaves early). Lane 0 of the group classifies the cell, scales or
+//           replaces the values and leaves rho', u' in LDS (8 KiB); the outcome counters are integer adds in LDS, then one integer
+//           atomic per non-zero counter and block - sums of integers, so the counts depend on no scheduling.
+//   store:  the pass is write-bound - 244 B per cell (27 + 27 populations, 3 + 3 velocities, rho), 368 B with the saved state - so
+//           every store is the widest there is: a lane holds four x-consecutive cells and writes 16 B, 128 lanes cover one component
+//           of the block (2 KiB contiguous, 1 KiB per wave instruction). The two halves of the workgroup share the components: half h
+//           evaluates and stores the populations k with k % 2 == h into every population array; half 0 stores vel, rho and rho_old,
+//           half 1 vel_temp and vel_old. The halves are whole waves: the choice is wave-uniform.
+// Writes: this block's 512 cells of the level's own arrays (block = blockIdx.x < n_blocks, the grid's size) and counts[0 .. 4 +
+// n_levels - 1]. The source is only read, through stream_sample's checked indices.
+constexpr int WARM_OUTCOMES = 4;                 // found, outside, source obstacle, non-finite
+constexpr int WARM_MAX_LEVELS = 30;
+struct WarmArgs {
+    StreamArgs s;                // lv, n_levels of the source, temp_mask 0; the rest unused
+    const int32_t *meta;         // destination: [n_blocks][NBR_STRIDE]
+    const uint8_t *obstacle;     // destination: [block][512]
+    float *f[3];                 // f, f_temp, f_old (null without temporal storage)
+    float *vel[3];               // vel, vel_temp, vel_old (null without)
+    float *rho[2];               // rho, rho_old (null without)
+    float map[6];                // a_x, a_y, a_z, b_x, b_y, b_z
+    float scale;
+    float fallback[4];
+    unsigned long long *counts;  // [4 + n_levels], null: not wanted
+};
+
+__global__ __launch_bounds__(256) void k_init_from_source(const WarmArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float s_q[4][CELLS];
+    __shared__ unsigned s_n[WARM_OUTCOMES + WARM_MAX_LEVELS];
+    const int t = (int)threadIdx.x;
+    const int64_t blk = blockIdx.x;
+    if (t < WARM_OUTCOMES + WARM_MAX_LEVELS) s_n[t] = 0u;
+    __syncthreads();
+    const int32_t *row = a.meta + blk * NBR_STRIDE;
+    const int ox = 8 * (row[NBR_BX] - 1), oy = 8 * (row[NBR_BY] - 1), oz = 8 * (row[NBR_BZ] - 1);
+    {
+        const int c = t & 7, grp = t >> 3;
+        const StreamLevel mine = a.s.lv[max(a.s.n_levels - 1 - c, 0)];
+        const float s2 = a.scale * a.scale;
+        for (int r = 0; r < CELLS / 32; ++r) {
+            const int cell = r * 32 + grp;
+            const int x = cell & 7, y = (cell >> 3) & 7, z = cell >> 6;
+            const float px = a.map[0] * ((float)(ox + x) + 0.5f) + a.map[3];
+            const float py = a.map[1] * ((float)(oy + y) + 0.5f) + a.map[4];
+            const float pz = a.map[2] * ((float)(oz + z) + 0.5f) + a.map[5];
+            float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            int li = 0;
+            const int code = stream_sample(a.s, mine, c, px, py, pz, q, li);
+            if (c == 0) {
+                float o[4] = {a.fallback[0], a.fallback[1], a.fallback[2], a.fallback[3]};
+                int slot = code;                                     // 1 outside, 2 source obstacle
+                if (code == 0) {
+                    const bool finite = __builtin_isfinite(q[0]) && __builtin_isfinite(q[1]) && __builtin_isfinite(q[2]) &&
+                                        __builtin_isfinite(q[3]);
+                    slot = finite ? 0 : 3;
+                    if (finite) {
+                        o[0] = 1.0f + (q[0] - 1.0f) * s2;
+                        o[1] = q[1] * a.scale;
+                        o[2] = q[2] * a.scale;
+                        o[3] = q[3] * a.scale;
+                    }
+                }
+                if (a.obstacle[blk * CELLS + cell]) {
+                    o[0] = 1.0f; o[1] = 0.0f; o[2] = 0.0f; o[3] = 0.0f;
+                } else if (a.counts) {
+                    atomicAdd(&s_n[slot], 1u);
+                    if (slot == 0) atomicAdd(&s_n[WARM_OUTCOMES + li], 1u);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s_q[k][cell] = o[k];
+            }
+        }
+    }
+    __syncthreads();
+    if (a.counts && t < WARM_OUTCOMES + a.s.n_levels && s_n[t] != 0u) atomicAdd(a.counts + t, (unsigned long long)s_n[t]);
+    const int h = t >> 7, c4 = (t & 127) * 4;
+    const float4 r4 = *(const float4 *)&s_q[0][c4], x4 = *(const float4 *)&s_q[1][c4], y4 = *(const float4 *)&s_q[2][c4],
+                 z4 = *(const float4 *)&s_q[3][c4];
+    static_for<0, Q>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        if ((k & 1) == h) {
+            constexpr float w = WEIGHT(k), cx = (float)CX(k), cy = (float)CY(k), cz = (float)CZ(k);
+            float4 e;
+            e.x = calculate_equilibrium(r4.x, x4.x, y4.x, z4.x, w, cx, cy, cz);
+            e.y = calculate_equilibrium(r4.y, x4.y, y4.y, z4.y, w, cx, cy, cz);
+            e.z = calculate_equilibrium(r4.z, x4.z, y4.z, z4.z, w, cx, cy, cz);
+            e.w = calculate_equilibrium(r4.w, x4.w, y4.w, z4.w, w, cx, cy, cz);
+            const int64_t at = (blk * Q + k) * CELLS + c4;
+#pragma unroll
+            for (int m = 0; m < 3; ++m)
+                if (a.f[m]) *(float4 *)(a.f[m] + at) = e;
+        }
+    });
+    const int64_t vat = blk * 3 * CELLS + c4, sat = blk * CELLS + c4;
+    auto store_vel = [&](float *v) {
+        if (!v) return;
+        *(float4 *)(v + vat) = x4;
+        *(float4 *)(v + vat + CELLS) = y4;
+        *(float4 *)(v + vat + 2 * CELLS) = z4;
+    };
+    if (h == 0) {
+        store_vel(a.vel[0]);
+        *(float4 *)(a.rho[0] + sat) = r4;
+        if (a.rho[1]) *(float4 *)(a.rho[1] + sat) = r4;
+    } else {
+        store_vel(a.vel[1]);
+        store_vel(a.vel[2]);
+    }
+}
+
 }  // namespace lw

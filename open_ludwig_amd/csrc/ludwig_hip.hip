@@ -4047,6 +4047,196 @@ int ludwig_tracers_download(LudwigTracers *S, float *records, size_t bytes, int6
     return LUDWIG_OK;
 }
 
+// ---- warm start (ludwig_flow_source_*, ludwig_level_init_from_source; no reference counterpart) ----
+// A flow source is a hierarchy reduced to what stream_sample reads - per level block_pointer, obstacle, rho and ONE velocity array, in
+// memory of its own - behind a StreamLevel table whose two vel entries both point at that array (temp_mask 0). It is no LudwigLevel
+// and holds no populations: 17 B per cell. Block order: a host-made source keeps the caller's (reference) order, one made from live
+// levels keeps theirs (the internal one); block_pointer names the blocks in the same order either way.
+struct LudwigFlowSource {
+    int device = 0;
+    int n_levels = 0;
+    std::vector<Dev<int32_t>> bp;
+    std::vector<Dev<uint8_t>> obstacle;
+    std::vector<Dev<float>> rho, vel;
+    Dev<StreamLevel> table;                     // [n_levels]
+};
+
+void ludwig_flow_source_destroy(LudwigFlowSource *S) { destroy_set(S); }
+
+static int flow_source_new(int device, int32_t n_levels, std::unique_ptr<LudwigFlowSource> &S)
+{
+    S.reset(new (std::nothrow) LudwigFlowSource);
+    if (!S) return fail(LUDWIG_ERR_ALLOC, "flow source: out of host memory");
+    S->device = device;
+    S->n_levels = n_levels;
+    S->bp.resize(n_levels);
+    S->obstacle.resize(n_levels);
+    S->rho.resize(n_levels);
+    S->vel.resize(n_levels);
+    return LUDWIG_OK;
+}
+
+// the table entry of level li once its four arrays are allocated
+static StreamLevel flow_source_entry(const LudwigFlowSource *S, int li, int gx, int gy, int gz, int n_blocks)
+{
+    StreamLevel t;
+    t.bp = S->bp[li];
+    t.obstacle = S->obstacle[li];
+    t.rho = S->rho[li];
+    t.vel[0] = t.vel[1] = S->vel[li];
+    t.gx = gx; t.gy = gy; t.gz = gz;
+    t.n_blocks = n_blocks;
+    return t;
+}
+
+int ludwig_flow_source_create(int device, int32_t n_levels, const int32_t *grid_dims, const int32_t *n_blocks, const int32_t *const *block_pointer,
+                              const uint8_t *const *obstacle, const float *const *rho, const float *const *vel, LudwigFlowSource **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!grid_dims || !n_blocks || !block_pointer || !obstacle || !rho || !vel) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > WARM_MAX_LEVELS) return fail(LUDWIG_ERR_INVALID, "flow source: n_levels %d not in 1..30", n_levels);
+    for (int li = 0; li < n_levels; ++li) {
+        const int32_t *gd = grid_dims + 3 * li;
+        const int32_t nb = n_blocks[li];
+        if (nb < 0 || gd[0] < 0 || gd[1] < 0 || gd[2] < 0) return fail(LUDWIG_ERR_INVALID, "flow source: level %d has a negative size", li);
+        if ((int64_t)nb * CELLS * 4 >= (int64_t)1 << 32) return fail(LUDWIG_ERR_INVALID, "flow source: level %d has too many blocks", li);
+        for (int a = 0; a < 3; ++a)
+            if ((int64_t)gd[a] * 8 > (1 << 24))
+                return fail(LUDWIG_ERR_INVALID, "flow source: level %d has more cells per axis than float32 counts exactly", li);
+        const size_t nptr = (size_t)gd[0] * gd[1] * gd[2];
+        if ((nptr > 0 && !block_pointer[li]) || (nb > 0 && (!obstacle[li] || !rho[li] || !vel[li] || nptr == 0)))
+            return fail(LUDWIG_ERR_INVALID, "flow source: level %d: null array", li);
+        for (size_t i = 0; i < nptr; ++i)                      // the kernel trusts a positive entry as a block index
+            if (block_pointer[li][i] < 0 || block_pointer[li][i] > nb)
+                return fail(LUDWIG_ERR_INVALID, "flow source: level %d: block_pointer entry %d out of range", li, block_pointer[li][i]);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(LUDWIG_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(LUDWIG_ERR_INVALID, "device %d out of range (have %d)", device, ndev);
+    if (const int r = set_device(device)) return r;
+    std::unique_ptr<LudwigFlowSource> S;
+    if (const int r = flow_source_new(device, n_levels, S)) return r;
+    std::vector<StreamLevel> table(n_levels);
+    hipError_t e = hipSuccess;
+    for (int li = 0; li < n_levels && e == hipSuccess; ++li) {
+        const int32_t *gd = grid_dims + 3 * li;
+        const size_t nb = (size_t)n_blocks[li], nptr = (size_t)gd[0] * gd[1] * gd[2];
+        upload_table(e, std::vector<int32_t>(block_pointer[li], block_pointer[li] + nptr), S->bp[li]);
+        if (nb > 0) {
+            upload_table(e, std::vector<uint8_t>(obstacle[li], obstacle[li] + nb * CELLS), S->obstacle[li]);
+            upload_table(e, std::vector<float>(rho[li], rho[li] + nb * CELLS), S->rho[li]);
+            std::vector<float> v(nb * 3 * CELLS);              // [8,8,8,nb,3] -> block-major [nb][3][512]
+            for (size_t k = 0; k < 3; ++k)
+                for (size_t b = 0; b < nb; ++b) memcpy(&v[(b * 3 + k) * CELLS], &vel[li][(k * nb + b) * CELLS], CELLS * sizeof(float));
+            upload_table(e, v, S->vel[li]);
+        }
+        table[li] = flow_source_entry(S.get(), li, gd[0], gd[1], gd[2], (int)nb);
+    }
+    upload_table(e, table, S->table);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "flow source: %s", hipGetErrorString(e));
+    *out = S.release();
+    return LUDWIG_OK;
+}
+
+int ludwig_flow_source_from_levels(LudwigLevel *const *levels, int32_t n_levels, int64_t t_coarse, LudwigFlowSource **out)
+{
+    if (!out) return fail(LUDWIG_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!levels) return fail(LUDWIG_ERR_INVALID, "null argument");
+    if (n_levels < 1 || n_levels > WARM_MAX_LEVELS) return fail(LUDWIG_ERR_INVALID, "flow source: n_levels %d not in 1..30", n_levels);
+    if (t_coarse < 0) return fail(LUDWIG_ERR_INVALID, "flow source: t_coarse %lld < 0", (long long)t_coarse);
+    if (int rl = check_locator_levels("flow source", "a sample", levels, n_levels)) return rl;
+    const int device = levels[0]->device;
+    if (const int r = set_device(device)) return r;
+    std::unique_ptr<LudwigFlowSource> S;
+    if (const int r = flow_source_new(device, n_levels, S)) return r;
+    std::vector<StreamLevel> table(n_levels);
+    hipError_t e = hipSuccess;
+    for (int li = 0; li < n_levels; ++li) {
+        LudwigLevel *L = levels[li];
+        LW_ENSURE_RHO(L);                                      // rho as a download would return it, and f / vel out of any record
+        const size_t c = (size_t)L->sk;
+        upload_table(e, L->h_block_pointer, S->bp[li]);
+        if (e == hipSuccess) e = (hipError_t)S->obstacle[li].alloc(c);
+        if (e == hipSuccess) e = (hipError_t)S->rho[li].alloc(c);
+        if (e == hipSuccess) e = (hipError_t)S->vel[li].alloc(c * 3);
+        if (e != hipSuccess) break;
+        if (c > 0) {                                           // ordered behind the steps queued on the level's stream
+            const float *v = vel_out(L, (t_coarse + 1) * ((int64_t)1 << li) - 1);
+            LW_HIP(hipMemcpyAsync(S->obstacle[li], L->obstacle, c, hipMemcpyDeviceToDevice, L->stream));
+            LW_HIP(hipMemcpyAsync(S->rho[li], L->rho, c * 4, hipMemcpyDeviceToDevice, L->stream));
+            LW_HIP(hipMemcpyAsync(S->vel[li], v, c * 3 * 4, hipMemcpyDeviceToDevice, L->stream));
+        }
+        table[li] = flow_source_entry(S.get(), li, L->gdx, L->gdy, L->gdz, L->n_blocks);
+    }
+    upload_table(e, table, S->table);
+    if (e != hipSuccess) return fail(LUDWIG_ERR_ALLOC, "flow source: %s", hipGetErrorString(e));
+    for (int li = 0; li < n_levels; ++li) LW_HIP(hipStreamSynchronize(levels[li]->stream));     // whoever reads the source finds it complete
+    *out = S.release();
+    return LUDWIG_OK;
+}
+
+int ludwig_level_init_from_source(LudwigLevel *L, const LudwigFlowSource *S, const float *map, float vel_scale, const float *fallback,
+                                  int64_t *counts)
+{
+    if (!L || !S || !map || !fallback) return fail(LUDWIG_ERR_INVALID, "null argument");
+    for (int a = 0; a < 6; ++a)
+        if (!std::isfinite(map[a])) return fail(LUDWIG_ERR_INVALID, "init from source: map[%d] = %g is not finite", a, (double)map[a]);
+    for (int a = 0; a < 3; ++a)
+        if (!(map[a] > 0.0f)) return fail(LUDWIG_ERR_INVALID, "init from source: map[%d] = %g must be positive", a, (double)map[a]);
+    if (!std::isfinite(vel_scale) || !(vel_scale > 0.0f))
+        return fail(LUDWIG_ERR_INVALID, "init from source: vel_scale %g must be positive and finite", (double)vel_scale);
+    for (int a = 0; a < 4; ++a)
+        if (!std::isfinite(fallback[a])) return fail(LUDWIG_ERR_INVALID, "init from source: fallback[%d] = %g is not finite", a, (double)fallback[a]);
+    if (S->device != L->device) return fail(LUDWIG_ERR_STATE, "init from source: the source is on device %d, the level on %d", S->device, L->device);
+    // (float)gc + 0.5f must be exact
+    for (int b = 0; b < L->n_blocks; ++b)
+        for (int a = 0; a < 3; ++a) {
+            const int32_t m = L->h_meta[(size_t)b * NBR_STRIDE + NBR_BX + a];
+            if (m < 1 || (int64_t)m * 8 > (1 << 23))
+                return fail(LUDWIG_ERR_INVALID, "init from source: block coordinate %d: more than 2^23 cells per axis (or < 1)", m);
+        }
+    const int n_counts = WARM_OUTCOMES + S->n_levels;
+    if (counts) std::fill(counts, counts + n_counts, (int64_t)0);
+    if (L->n_owned == 0 || L->n_blocks == 0) return LUDWIG_OK;   // a level that only holds ghost copies: accepted, nothing to do
+    LW_HIP(hipSetDevice(L->device));
+    // The level ends up as if f, f_temp, vel, vel_temp, rho (and the saved state) had been uploaded: the same helper, field by field -
+    // whatever only a record, an elided rho store or an aliased saved state holds is settled before the arrays are overwritten.
+    ++L->version;
+    static const int written[] = {LUDWIG_F, LUDWIG_F_TEMP, LUDWIG_VEL, LUDWIG_VEL_TEMP, LUDWIG_RHO, LUDWIG_F_OLD, LUDWIG_VEL_OLD, LUDWIG_RHO_OLD};
+    for (int i = 0; i < (L->has_temporal ? 8 : 5); ++i)
+        if (const int r = before_external_write(L, written[i])) return r;
+    L->rho_old_pending = false;                                // rho_old is written here: no save is owed any more
+    Dev<unsigned long long> d_counts;
+    if (counts) {
+        LW_HIP((hipError_t)d_counts.alloc((size_t)n_counts));
+        LW_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_counts * sizeof(unsigned long long), L->stream));
+    }
+    WarmArgs a{};
+    a.s.lv = S->table;
+    a.s.n_levels = S->n_levels;
+    a.s.temp_mask = 0u;
+    a.meta = L->meta;
+    a.obstacle = L->obstacle;
+    a.f[0] = L->f[0]; a.f[1] = L->f[1]; a.f[2] = L->has_temporal ? L->f_old.get() : nullptr;
+    a.vel[0] = L->vel[0]; a.vel[1] = L->vel[1]; a.vel[2] = L->has_temporal ? L->vel_old.get() : nullptr;
+    a.rho[0] = L->rho; a.rho[1] = L->has_temporal ? L->rho_old.get() : nullptr;
+    for (int i = 0; i < 6; ++i) a.map[i] = map[i];
+    a.scale = vel_scale;
+    for (int i = 0; i < 4; ++i) a.fallback[i] = fallback[i];
+    a.counts = counts ? d_counts.get() : nullptr;
+    hipLaunchKernelGGL(k_init_from_source, dim3((unsigned)L->n_blocks), dim3(256), 0, L->stream, a);
+    LW_HIP(hipGetLastError());
+    if (counts) {
+        std::vector<unsigned long long> h((size_t)n_counts);
+        LW_HIP(hipMemcpyAsync(h.data(), d_counts, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, L->stream));
+        LW_HIP(hipStreamSynchronize(L->stream));
+        for (int i = 0; i < n_counts; ++i) counts[i] = (int64_t)h[i];
+    }
+    return LUDWIG_OK;
+}
+
 // ---- the batch (ludwig_execute_timestep_batch*): what it refuses, how it runs, its entry points ----
 static int check_batch_levels(LudwigLevel *const *levels, int32_t n_levels, int32_t batch_size, const LudwigStepFlags *flags)
 {

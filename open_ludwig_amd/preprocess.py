@@ -192,6 +192,15 @@ class CaseConfig:
     wall_diagnostics_enabled: bool = False
     wall_diagnostics_band: Tuple[float, float] = (30.0, 300.0)      # the y+ range ShareInBand counts, 0 < lo < hi
     y_plus_target: float = 100.0                        # advanced.high_re.wall_model.y_plus_target, echoed in wall_model.csv
+    # warm start (no reference counterpart; warm_start.py). advanced.state_files: state_%06d.npz - rho and the newest velocity of every
+    # level - after the coarse steps that are multiples of `interval` and after the last step (interval 0: the last step only).
+    # advanced.initial_condition: every level is filled from such a file after set-up, the populations at their equilibrium, and the
+    # step loop starts at first_step; velocity_scale None = auto: this case's u_lattice over the state's
+    state_files_enabled: bool = False
+    state_files_interval: int = 0
+    initial_condition_state: str = ""                   # path, relative to the case folder; empty: start from rest
+    initial_condition_first_step: int = 1
+    initial_condition_velocity_scale: Optional[float] = None
 
     @property
     def reference_area_config(self) -> float:
@@ -243,6 +252,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
     fourier_modes = _fourier_modes_config(g("advanced", "fourier_modes", default=None))
     flow_monitor = _flow_monitor_config(g("advanced", "flow_monitor", default=None))
     wall_diag = _wall_diagnostics_config(g("advanced", "wall_diagnostics", default=None))
+    warm = _warm_start_config(g("advanced", "state_files", default=None), g("advanced", "initial_condition", default=None))
     return CaseConfig(
         stl_file=g("basic", "stl_file", required=True), stl_scale=float(g("basic", "stl_scale", required=True)),
         surface_resolution=int(g("basic", "surface_resolution", required=True)), num_levels=int(g("basic", "num_levels", required=True)),
@@ -305,6 +315,7 @@ def load_case_configuration(config_path: str, overrides: Optional[dict] = None) 
         **fourier_modes,
         **flow_monitor,
         **wall_diag,
+        **warm,
         y_plus_target=float(g("advanced", "high_re", "wall_model", "y_plus_target", default=100.0)),
     )
 
@@ -363,6 +374,41 @@ def _probes_config(pc) -> dict:
         raise ValueError("advanced.probes.names must be unique")
     return dict(probes_enabled=True, probes_start_step=start, probes_interval=interval, probes_points=tuple(pts),
                 probes_names=tuple(names))
+
+
+def _warm_start_config(sc, ic) -> dict:
+    """advanced.state_files: {enabled: false, interval: 0} and advanced.initial_condition: {state: <path>, first_step: 1, velocity_scale:
+    auto} -> CaseConfig fields. Absent (or state_files disabled): the defaults - nothing is allocated, launched or written."""
+    out = {}
+    if sc is not None:
+        if not isinstance(sc, dict):
+            raise ValueError("advanced.state_files must be a mapping")
+        if bool(sc.get("enabled", False)):
+            interval = int(sc.get("interval", 0))
+            if interval < 0:
+                raise ValueError(f"advanced.state_files.interval must be >= 0, got {interval}")
+            out.update(state_files_enabled=True, state_files_interval=interval)
+    if ic is not None:
+        if not isinstance(ic, dict):
+            raise ValueError("advanced.initial_condition must be a mapping")
+        state = ic.get("state")
+        if not isinstance(state, str) or not state:
+            raise ValueError("advanced.initial_condition.state must be the path of a state file")
+        first = int(ic.get("first_step", 1))
+        if first < 1:
+            raise ValueError(f"advanced.initial_condition.first_step must be >= 1, got {first}")
+        scale = ic.get("velocity_scale", "auto")
+        if scale == "auto" or scale is None:
+            scale = None
+        else:
+            try:
+                scale = float(scale)
+            except (TypeError, ValueError):
+                raise ValueError(f"advanced.initial_condition.velocity_scale must be a number or auto, got {scale!r}") from None
+            if not (math.isfinite(scale) and scale > 0.0):
+                raise ValueError(f"advanced.initial_condition.velocity_scale must be positive and finite, got {scale}")
+        out.update(initial_condition_state=state, initial_condition_first_step=first, initial_condition_velocity_scale=scale)
+    return out
 
 
 def _flow_monitor_config(mc) -> dict:
