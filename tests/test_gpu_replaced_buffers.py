@@ -6,10 +6,8 @@ import numpy as np
 import pytest
 
 import _edge_states as es
-import _surface_common as sc
-from open_ludwig_amd import _lib, adapt, cases, execute_timestep_batch, flux_planes as fp, force_series as fs, order as order_mod
-from open_ludwig_amd import preprocess as pp, probes as pm, slices as sl, streamlines as st, surface_stats as ss, tracers as tr
-from open_ludwig_amd import wall_diagnostics as wd
+from _observer_sets import KINDS, POINTS, SEEDS, T, makers, surface_plan  # noqa: F401
+from open_ludwig_amd import adapt, cases, execute_timestep_batch, order as order_mod
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -73,57 +71,7 @@ def test_triangle_buffers_grow_and_are_reused(gpu):
         dev.close()
 
 
-# ---- observer sets: one maker and one sampler per kind ----
-def surface_plan(n_blocks, n=600, seed=3):
-    """a hand-made plan: more triangles than one chunk of 512 (the force series reduces in two stages), some without a cell"""
-    rng = np.random.default_rng(seed)
-    found = rng.random(n) > 0.1
-    blocks = np.where(found, rng.integers(0, n_blocks, n), -1).astype(np.int32)
-    cells = np.where(found, rng.integers(0, 512, n), 0).astype(np.int32)
-    normals = rng.standard_normal((n, 3))
-    normals /= np.linalg.norm(normals, axis=1, keepdims=True)
-    plan = ss.SurfacePlan(found, blocks, cells, rng.uniform(0.1, 0.9, n).astype(F32), normals.astype(F32))
-    return plan, rng.uniform(0.5, 1.5, n).astype(F32), rng.uniform(-4.0, 4.0, (3, n)).astype(F32)
-
-
-POINTS = [[3.3, 4.2, 5.1], [30.5, 9.25, 17.75], [20.0, 8.0, 8.0], [15.9, 16.1, 24.0]]
-SEEDS = np.array([[5.2, 7.3, 11.6], [3.25, 20.125, 2.9], [16.0, 16.0, 16.0]], dtype=F32)
-T = 2                                                       # the state the samples read: after coarse step 2
-
-
-def makers(grids, dev):
-    g = grids[0]
-    plan, area, arm = surface_plan(g.n_blocks)
-    sparams = sc.tunnel_params((16.0, 16.0, 16.0), 5.0)
-    pplan = pm.plan_probes(POINTS, grids)
-    fplans = [fp.plan_flux_plane(pp.FluxPlane("x", 0, 12.0, None, 1.0), grids),
-              fp.plan_flux_plane(pp.FluxPlane("z", 2, 20.0, ((4.0, 27.0), (4.0, 27.0)), 1.0), grids)]
-    splans = [sl.plan_slice(pp.SlicePlane("z", 2, 16.05, ((0.2, 30.8), (0.3, 30.7)), 0.37, pp.SLICE_FIELDS), grids)]
-    W = np.array([[1.0, 0.5], [0.25, -1.0]])
-
-    def sampled(S, *calls):
-        for name, args in calls:
-            getattr(S, name)(*args)
-        out = S.download(0, 1) if isinstance(S, _lib.ModeSet) else S.download()
-        return [np.asarray(x) for x in (out if isinstance(out, (tuple, list)) else (out,))]
-
-    return {
-        "probes": (lambda: pm.DeviceProbes(pplan, [dev], 8, 1, 1), lambda S: sampled(S, ("sample", (0, T)))),
-        "surface_stats": (lambda: ss.DeviceSurfaceStats(plan, dev, 0, g.tau, sparams), lambda S: sampled(S, ("accumulate", (T,)))),
-        "force_series": (lambda: fs.DeviceForceSeries(plan, area, arm, dev, 0, g.tau, sparams), lambda S: sampled(S, ("sample", (T, T)))),
-        "flux_planes": (lambda: fp.DeviceFluxPlanes(fplans, [dev], 4), lambda S: sampled(S, ("sample", (T,)))),
-        "modes": (lambda: _lib.ModeSet([dev], W), lambda S: sampled(S, ("accumulate", (0, T, 0)))),
-        "wall_surface": (lambda: wd.DeviceWallSurface(plan, dev, sparams), lambda S: sampled(S, ("compute", (T,)))),
-        "slices": (lambda: sl.DeviceSlices(splans, [dev], grids), lambda S: sampled(S, ("sample", (T,)))),
-        "streamlines": (lambda: st.DeviceStreamlines([dev], SEEDS, np.ones(len(SEEDS), F32), 0.5, 1.0e-6, 40),
-                        lambda S: sampled(S, ("trace", (T,)))),
-        "tracers": (lambda: tr.DeviceTracers([dev], SEEDS, 2, 1, 1, 1), lambda S: sampled(S, ("advance", (T,)), ("advance", (T,)), ("snapshot", (T,)))),
-    }
-
-
-KINDS = ("probes", "surface_stats", "force_series", "flux_planes", "modes", "wall_surface", "slices", "streamlines", "tracers")
-
-
+# ---- observer sets: one maker and one sampler per kind (tests/_observer_sets.py) ----
 @pytest.fixture(scope="module")
 def stepped(gpu):
     """one level two steps on, shared by every kind: a set reads the level and writes only its own buffers"""
