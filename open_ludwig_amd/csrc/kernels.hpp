@@ -956,11 +956,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_MIN_
 // x directions of each; the x shift then is the usual lane shift plus face column. The previous step's velocity of the y and z
 // neighbours is in those same records (the centre one, cy = +-1 and cz = +-1), so no velocity is loaded and nothing is shuffled
 // in y. At the outer faces of a run the wave loads the x neighbour's 9 records of its face column, spread over all 64 lanes, and
-// evaluates the one population of each that crosses the face. Every block is all-neighbour, carries no obstacle / sponge / near-wall flag, and the level has no
+// evaluates the one population of each that crosses the face.
+// Order: pull, publish (the face columns the neighbouring waves need, into LDS), the outer faces' loads, workgroup barrier, the
+// outer faces' evaluation, x shift, finish_cell. Only the first and last wave of a run have outer faces (~150 instructions); what
+// they make is written and read by that one wave, so it needs no workgroup barrier - in front of the barrier it kept the waves in
+// between waiting, behind it the four waves reach the barrier together, and the loads, issued in front of it once the pull's
+// registers are free, are in flight while the wave waits (profiles/paired_pull_vs_parent.txt).
+// Every block is all-neighbour, carries no obstacle / sponge / near-wall flag, and the level has no
 // wall model (the host's eligibility rule), so this is finish_cell<false, false> with flags = 0 - the f path's arithmetic, operation
 // by operation - and the result is stored as a record again.
 #ifndef LW_REC_WAVES
-#define LW_REC_WAVES 4      // waves per SIMD the register allocator must leave room for: 128 VGPRs, 107 used (at 96 the allocator spills)
+#define LW_REC_WAVES 4      // waves per SIMD the register allocator must leave room for: 128 VGPRs, 125 used (at 96 the allocator spills)
 #endif
 #ifndef LW_REC_AHEAD
 #define LW_REC_AHEAD 3      // records whose loads are in flight while one is evaluated (11 registers each)
@@ -988,45 +994,67 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_REC_
     __shared__ float xedge[NW][2][12][8];
     float fs[Q];
     float uc[3], uT[3], uB[3], uN[3], uS[3];
-    if (active) {
     // ---- the run's outer faces: the first wave needs column 7 of the -x neighbour, the last wave column 0 of the +x neighbour (a
     // lone block both): per face 9 records x 8 rows, of each the one population that crosses the face ----
     // Spread over the whole wave: lane (x', y) takes row y of record j = x', j = (cy+1) + 3 (cz+1) = 0..7, so (cy, cz), the source
     // plane and the block - the x neighbour, or for the row that leaves it in y the y neighbour of the x neighbour - are per-lane
     // selections among wave-uniform values, and the population is collide_value in its per-lane form (DirLaneFace). 11 loads and one
-    // evaluation with 64 lanes active, where eight lanes used to walk through nine records.
-    auto face_rows = [&](auto sc) {
-        constexpr int side = decltype(sc)::value;                     // 0: from -x, 1: from +x
-        constexpr int jx = side == 0 ? 4 - 1 : 4 + 1;
+    // evaluation with 64 lanes active, where eight lanes used to walk through nine records. Loads (face_load, ninth_load: in front of
+    // the workgroup barrier) and evaluation (face_eval, ninth_eval: behind it) are separate steps; rf and r9 carry the records across.
+    auto face_dir = [&](int &cy, int &cz) {
         const int j = l.x;
         const int jz = (j >= 3 ? 1 : 0) + (j >= 6 ? 1 : 0);         // j / 3
-        const int cy = j - 3 * jz - 1, cz = jz - 1, g = 2 - jz;      // g = 1 - cz
+        cy = j - 3 * jz - 1;
+        cz = jz - 1;
+    };
+    float rf[2][R_COMP], r9[R_COMP];
+    auto face_load = [&](auto sc) {
+        constexpr int side = decltype(sc)::value;                     // 0: from -x, 1: from +x
+        constexpr int jx = side == 0 ? 4 - 1 : 4 + 1;
+        int cy, cz;
+        face_dir(cy, cz);
+        const int g = 1 - cz;
         auto by_g = [&](int v0, int v1, int v2) { return g == 0 ? v0 : (g == 1 ? v1 : v2); };      // values, not lvalues (see source_block)
         const int bX = by_g(nbr.id[0][jx], nbr.id[1][jx], nbr.id[2][jx]);
         const int bXlo = by_g(nbr.id[0][jx - 3], nbr.id[1][jx - 3], nbr.id[2][jx - 3]);            // its -y neighbour: cy = +1 rows of y = 0
         const int bXhi = by_g(nbr.id[0][jx + 3], nbr.id[1][jx + 3], nbr.id[2][jx + 3]);            // its +y neighbour: cy = -1 rows of y = 7
         const int blk = (cy == 1 && l.y0) ? bXlo : ((cy == -1 && l.y7) ? bXhi : bX);
         const int zsrc = by_g(nbr.zs[0], nbr.zs[1], nbr.zs[2]);
-        float r[R_COMP];
-        load_record_at(r, p.rec_in, record_offset<WIDE>(blk, zsrc) + (uint32_t)(((side == 0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
+        load_record_at(rf[side], p.rec_in, record_offset<WIDE>(blk, zsrc) + (uint32_t)(((side == 0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
+    };
+    auto face_eval = [&](auto sc) {
+        constexpr int side = decltype(sc)::value;
+        int cy, cz;
+        face_dir(cy, cz);
+        const int j = l.x;
+        const float(&r)[R_COMP] = rf[side];
         float(&mine)[12][8] = xedge[wave][side];
         mine[j][l.y] = record_face(DirLaneFace{cy, cz}, r, side == 0);
         if (j == 4) { mine[9][l.y] = r[R_UX]; mine[10][l.y] = r[R_UY]; mine[11][l.y] = r[R_UZ]; }      // cy = cz = 0: the face neighbour itself
     };
-    if (first) face_rows(std::integral_constant<int, 0>{});
-    if (last) face_rows(std::integral_constant<int, 1>{});
-    // the ninth record (cy = cz = +1), in the lanes of the face column: four wave-uniform offsets, one chosen per lane
-    if ((first && l.x0) || (last && l.x7)) {
-        constexpr int j = 8, cy = 1, g = 0;
+    // the ninth record (cy = cz = +1), in the lanes of the face column: four wave-uniform offsets, one chosen per lane; both sides of
+    // a lone block in one masked evaluation
+    const bool ninth = (first && l.x0) || (last && l.x7);
+    auto ninth_load = [&]() {
+        constexpr int cy = 1, g = 0;
         const int wX = nbr.id[g][4 - 1], wXY = nbr.id[g][4 - 1 - 3 * cy], eX = nbr.id[g][4 + 1], eXY = nbr.id[g][4 + 1 - 3 * cy];
         const auto oW = record_offset<WIDE>(wX, nbr.zs[g]), oWY = record_offset<WIDE>(wXY, nbr.zs[g]);
         const auto oE = record_offset<WIDE>(eX, nbr.zs[g]), oEY = record_offset<WIDE>(eXY, nbr.zs[g]);
         const auto off = l.x0 ? (l.y0 ? oWY : oW) : (l.y0 ? oEY : oE);
-        float r[R_COMP];
-        load_record_at(r, p.rec_in, off + (uint32_t)(((l.x0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
-        xedge[wave][l.x0 ? 0 : 1][j][l.y] = record_face(DirConst<DIR(1, 1, 1)>{}, r, l.x0);
-    }
-    __builtin_amdgcn_sched_barrier(0);      // the faces are done before the pull's loads start: their registers are free again
+        load_record_at(r9, p.rec_in, off + (uint32_t)(((l.x0 ? 7 : 0) + 8 * ((l.y - cy) & 7)) * 4));
+    };
+    auto ninth_eval = [&]() { xedge[wave][l.x0 ? 0 : 1][8][l.y] = record_face(DirConst<DIR(1, 1, 1)>{}, r9, l.x0); };
+    auto outer_face_loads = [&]() {
+        if (first) face_load(std::integral_constant<int, 0>{});
+        if (last) face_load(std::integral_constant<int, 1>{});
+        if (ninth) ninth_load();
+    };
+    auto outer_face_evals = [&]() {
+        if (first) face_eval(std::integral_constant<int, 0>{});
+        if (last) face_eval(std::integral_constant<int, 1>{});
+        if (ninth) ninth_eval();
+    };
+    if (active) {
     // ---- the 9 records at (x, y - cy, z - cz) ----
     {
         float r[9][R_COMP];
@@ -1070,9 +1098,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(LW_REC_
         if (l.x7) xch[wave][18 + c][l.y] = uc[c];
         if (l.x0) xch[wave][21 + c][l.y] = uc[c];
     }
+    outer_face_loads();      // 11 registers a side and 11 for the ninth record, live only after the pull's records are dead
     }   // if (active)
     __syncthreads();
     if (!active) return;
+    outer_face_evals();
+    // xedge is written and read by different lanes of this one wave: the LDS serves a wave's accesses in order, so wavefront-scope
+    // release / acquire (no instruction) and a barrier the compiler moves nothing across are all the reads below need - no second
+    // workgroup barrier
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     const int wlo = first ? 0 : wave - 1, whi = last ? NW - 1 : wave + 1;
     static_for<0, Q>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
