@@ -120,17 +120,10 @@ __device__ __forceinline__ float gradient_noise(int32_t gx, int32_t gy, int32_t 
     return ((float)(h & 0xFFFFu) / 32768.0f) - 1.0f;
 }
 
-// reference src/physics_utils.jl:34-39
-__device__ __forceinline__ float calculate_equilibrium(float rho, float ux, float uy, float uz, float w_k,
-                                                       float cx, float cy, float cz)
-{
-    const float cu = cx * ux + cy * uy + cz * uz;
-    const float usq = ux * ux + uy * uy + uz * uz;
-    return rho * w_k * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * usq);
-}
-
 // ---- coarse -> fine interface value, reference src/physics_interpolation.jl:16-138: the trilinear kernel; the corner
 // fetch, the blend in time and the rescaling live in k_interface_sources / k_interface_links below ----
+// Not probe_trilinear below: the reference's interface pass weights as a (1 - w) + b w and its probes as (1 - w) a + w b; the products
+// are the same, the operands of each multiply are swapped, and the step's machine code is kept as it is.
 __device__ __forceinline__ float trilin(float v000, float v100, float v010, float v110, float v001, float v101,
                                         float v011, float v111, float wx, float wy, float wz)
 {
@@ -262,10 +255,8 @@ __device__ __forceinline__ int source_block(const NeighbourIds &n, const LanePos
     else if constexpr (cy != 0) sel = yo ? cY : c00;
     return sel;
 }
-// ---- the WALE model as a function (k_subgrid; no reference counterpart as a function) ----
-// finish_cell's "WALE eddy viscosity" block below, restated operation by operation from gsq11 to the background floor: the same operand
-// order, the same 1.0e-12f guards, the same sqrtf(sqrtf(jl_max(OP1, 1.0e-12f))), under the same -ffp-contract=off, so on the gradient
-// the step forms it gives the step's nu_eddy bit for bit. The step keeps its own block; this one serves the observers.
+// ---- the WALE model, reference src/physics_kernels.jl:251-300: ONE source for the step (finish_cell takes nu_eddy and the compiler
+// drops s2 and code) and for the observers (k_subgrid), so both get the same bits from the same gradient ----
 // nu_eddy: the effective value after the floor, what the step turns into tau_turb. s2 = 2 OP2 = |S|^2 = 2 S_ij S_ij (the doubling is
 // exact). code: SUBGRID_NO_OP1 - OP1 <= 1e-12 (or NaN), SUBGRID_NO_DENOM - denom <= 1e-12 (or NaN), SUBGRID_FLOOR - the model is
 // evaluated and is not above nu_bg, so the floor wins (a NaN model value, which jl_max propagates, is here too), SUBGRID_MODEL - the
@@ -328,6 +319,21 @@ template <class T>
 __device__ __forceinline__ T equilibrium_value(float rho, float w_k, T cu, float usq_eq)
 {
     return rho * w_k * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * usq_eq);
+}
+// reference src/physics_utils.jl:34-39: the same with c . u and u . u formed from run-time c (sponge target, interface pass, warm start)
+__device__ __forceinline__ float calculate_equilibrium(float rho, float ux, float uy, float uz, float w_k,
+                                                       float cx, float cy, float cz)
+{
+    return equilibrium_value<float>(rho, w_k, cx * ux + cy * uy + cz * uz, ux * ux + uy * uy + uz * uz);
+}
+// The equilibrium at rho = 1 of the flow (u, 0, 0): what patch_missing_sources pulls across the inlet and the outlet, reference
+// src/physics_kernels.jl:99-113. Not a call of equilibrium_value: the reference writes the last term as 1.5 * u * u here, which is
+// (1.5 u) u, and 1.5 * usq there - other bits.
+template <int K>
+__device__ __forceinline__ float edge_equilibrium(float u)
+{
+    const float cu = (float)CX(K) * u;
+    return WEIGHT(K) * (1.0f + 3.0f * cu + 4.5f * cu * cu - 1.5f * u * u);
 }
 
 // Two running sums that finish_cell advances side by side. PACKED: one register pair - a term for both is one packed add, a term
@@ -617,37 +623,12 @@ __device__ __forceinline__ void finish_cell(const SCParams &p, const int flags, 
         if (p.store_rho) st_f32(p.rho, own.b, S_BLOCK_BYTES, own.cell4, rho);
     }
 
-    // ---- WALE eddy viscosity from the previous step's velocity, reference :251-300 ----
+    // ---- WALE eddy viscosity (wale_state) from the previous step's velocity, reference :251-300 ----
     const float g11 = 0.5f * (ux_E - ux_W), g12 = 0.5f * (ux_N - ux_S), g13 = 0.5f * (ux_T - ux_B);
     const float g21 = 0.5f * (uy_E - uy_W), g22 = 0.5f * (uy_N - uy_S), g23 = 0.5f * (uy_T - uy_B);
     const float g31 = 0.5f * (uz_E - uz_W), g32 = 0.5f * (uz_N - uz_S), g33 = 0.5f * (uz_T - uz_B);
 
-    const float gsq11 = g11 * g11 + g12 * g21 + g13 * g31;
-    const float gsq12 = g11 * g12 + g12 * g22 + g13 * g32;
-    const float gsq13 = g11 * g13 + g12 * g23 + g13 * g33;
-    const float gsq21 = g21 * g11 + g22 * g21 + g23 * g31;
-    const float gsq22 = g21 * g12 + g22 * g22 + g23 * g32;
-    const float gsq23 = g21 * g13 + g22 * g23 + g23 * g33;
-    const float gsq31 = g31 * g11 + g32 * g21 + g33 * g31;
-    const float gsq32 = g31 * g12 + g32 * g22 + g33 * g32;
-    const float gsq33 = g31 * g13 + g32 * g23 + g33 * g33;
-
-    const float tr_gsq = gsq11 + gsq22 + gsq33;
-    const float tr_term = tr_gsq / 3.0f;
-    const float Sd11 = gsq11 - tr_term, Sd22 = gsq22 - tr_term, Sd33 = gsq33 - tr_term;
-    const float Sd12 = 0.5f * (gsq12 + gsq21), Sd13 = 0.5f * (gsq13 + gsq31), Sd23 = 0.5f * (gsq23 + gsq32);
-    const float S12 = 0.5f * (g12 + g21), S13 = 0.5f * (g13 + g31), S23 = 0.5f * (g23 + g32);
-    const float OP1 = Sd11 * Sd11 + Sd22 * Sd22 + Sd33 * Sd33 + 2.0f * (Sd12 * Sd12 + Sd13 * Sd13 + Sd23 * Sd23);
-    const float OP2 = g11 * g11 + g22 * g22 + g33 * g33 + 2.0f * (S12 * S12 + S13 * S13 + S23 * S23);
-
-    float nu_eddy = 0.0f;
-    if (OP1 > 1.0e-12f) {
-        const float OP1_32 = OP1 * sqrtf(OP1);
-        const float OP2_52 = OP2 * OP2 * sqrtf(jl_max(OP2, 1.0e-12f));
-        const float denom = OP2_52 + OP1 * sqrtf(sqrtf(jl_max(OP1, 1.0e-12f)));
-        if (denom > 1.0e-12f) nu_eddy = (p.c_wale * p.c_wale) * OP1_32 / denom;
-    }
-    nu_eddy = jl_max(nu_eddy, p.nu_bg);
+    const float nu_eddy = wale_state(g11, g12, g13, g21, g22, g23, g31, g32, g33, p.c_wale, p.nu_bg).nu_eddy;
     const float tau_turb = p.tau + nu_eddy * 3.0f;
     const float omega = 1.0f / jl_max(tau_turb, 0.500001f);
 
@@ -746,11 +727,9 @@ __device__ __forceinline__ void patch_missing_sources(const SCParams &p, const i
                                             ? gradient_noise(gy, gz, p.seed, 1234) * p.inlet_turbulence * p.u_inlet
                                             : 0.0f;
                     const float u_inst = p.u_inlet + noise;
-                    const float cu_in = (float)cx * u_inst;
-                    val = WEIGHT(k) * (1.0f + 3.0f * cu_in + 4.5f * cu_in * cu_in - 1.5f * u_inst * u_inst);
+                    val = edge_equilibrium<k>(u_inst);
                 } else if (is_outlet) {
-                    const float cu_out = (float)cx * p.u_inlet;
-                    val = WEIGHT(k) * (1.0f + 3.0f * cu_out + 4.5f * cu_out * cu_out - 1.5f * p.u_inlet * p.u_inlet);
+                    val = edge_equilibrium<k>(p.u_inlet);
                 } else if (is_y_min && p.is_symmetric == 1) {
                     val = ld_own(p.f_in, own.b, F_BLOCK_BYTES, MIRROR_Y(k) * COMP_BYTES + own.cell4);
                 } else if (is_y_min || is_y_max) {
@@ -1632,6 +1611,16 @@ __device__ __forceinline__ void stage_velocity_tile(float *u, const float *__res
         if (hat[r] >= 0) u[hat[r]] = h[r];
 }
 
+// vorticity and Q of g[i][j] = du_i/dx_j in the order stated above: ONE source for k_velocity_gradient_fields and k_slice_sample<true>
+__device__ __forceinline__ void vorticity_q(float (&q)[GRAD_COMPONENTS], const float (&g)[3][3])
+{
+    q[0] = g[2][1] - g[1][2];
+    q[1] = g[0][2] - g[2][0];
+    q[2] = g[1][0] - g[0][1];
+    q[3] = -0.5f * (((g[0][0] * g[0][0] + g[1][1] * g[1][1]) + g[2][2] * g[2][2]) +
+                    2.0f * ((g[0][1] * g[1][0] + g[0][2] * g[2][0]) + g[1][2] * g[2][1]));
+}
+
 __global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restrict__ out, const float *__restrict__ vel,
                                                                   const uint8_t *__restrict__ obstacle,
                                                                   const int32_t *__restrict__ meta, float scale)
@@ -1649,18 +1638,16 @@ __global__ __launch_bounds__(256) void k_velocity_gradient_fields(float *__restr
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const int a = at + s;
-        const float *ux = u, *uy = u + T3, *uz = u + 2 * T3;
-        const float g11 = (0.5f * (ux[a + 1] - ux[a - 1])) * scale, g12 = (0.5f * (ux[a + T] - ux[a - T])) * scale;
-        const float g13 = (0.5f * (ux[a + T2] - ux[a - T2])) * scale;
-        const float g21 = (0.5f * (uy[a + 1] - uy[a - 1])) * scale, g22 = (0.5f * (uy[a + T] - uy[a - T])) * scale;
-        const float g23 = (0.5f * (uy[a + T2] - uy[a - T2])) * scale;
-        const float g31 = (0.5f * (uz[a + 1] - uz[a - 1])) * scale, g32 = (0.5f * (uz[a + T] - uz[a - T])) * scale;
-        const float g33 = (0.5f * (uz[a + T2] - uz[a - T2])) * scale;
+        constexpr int step[3] = {1, T, T2};
+        float g[3][3], q[GRAD_COMPONENTS];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) g[i][j] = (0.5f * (u[i * T3 + a + step[j]] - u[i * T3 + a - step[j]])) * scale;
+        vorticity_q(q, g);
         const bool solid = (s == 0 ? ob0 : ob1) != 0;
-        res[0][s] = solid ? 0.0f : g32 - g23;
-        res[1][s] = solid ? 0.0f : g13 - g31;
-        res[2][s] = solid ? 0.0f : g21 - g12;
-        res[3][s] = solid ? 0.0f : -0.5f * (((g11 * g11 + g22 * g22) + g33 * g33) + 2.0f * ((g12 * g21 + g13 * g31) + g23 * g32));
+#pragma unroll
+        for (int m = 0; m < GRAD_COMPONENTS; ++m) res[m][s] = solid ? 0.0f : q[m];
     }
     float *o = out + b * GRAD_COMPONENTS * CELLS + c;
 #pragma unroll
@@ -1729,18 +1716,22 @@ __global__ __launch_bounds__(256) void k_subgrid(std::conditional_t<MODE == SUBG
 // (1 - w) a + w b - with -ffp-contract=off, so open_ludwig_amd/probes.py (trilinear) restates it bit for bit. out = the slot,
 // [n_set][4]: rho, ux, uy, uz. Bounded by a launch latency, not by bandwidth: 128 B gathered per probe.
 __device__ __forceinline__ float probe_lerp(float a, float b, float w) { return (1.0f - w) * a + w * b; }
-
-__global__ __launch_bounds__(64) void k_probe_sample(float *__restrict__ out, const int32_t *__restrict__ cell, const float *__restrict__ w,
-                                                     const int32_t *__restrict__ col, int n, const float *__restrict__ rho,
-                                                     const float *__restrict__ vel)
+// corner c = dx + 2 dy + 4 dz: x, then y, then z. ONE source for the probes, slices, flux planes and the renderer.
+__device__ __forceinline__ float probe_trilinear(const float (&v)[8], float wx, float wy, float wz)
 {
-    const int p = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (p >= n) return;
+    const float x00 = probe_lerp(v[0], v[1], wx), x10 = probe_lerp(v[2], v[3], wx);
+    const float x01 = probe_lerp(v[4], v[5], wx), x11 = probe_lerp(v[6], v[7], wx);
+    const float y0 = probe_lerp(x00, x10, wy), y1 = probe_lerp(x01, x11, wy);
+    return probe_lerp(y0, y1, wz);
+}
+// res = rho, ux, uy, uz at point p of a planned set: the eight corners cell[8 p ..] gathered, then probe_trilinear with w[3 p ..]
+__device__ __forceinline__ void stencil_sample(float (&res)[4], int64_t p, const int32_t *__restrict__ cell, const float *__restrict__ w,
+                                               const float *__restrict__ rho, const float *__restrict__ vel)
+{
     int64_t e[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) e[c] = cell[8 * p + c];
     const float wx = w[3 * p], wy = w[3 * p + 1], wz = w[3 * p + 2];
-    float res[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float v[8];
@@ -1749,11 +1740,18 @@ __global__ __launch_bounds__(64) void k_probe_sample(float *__restrict__ out, co
             const int64_t b = e[c] >> 9, cc = e[c] & 511;
             v[c] = k == 0 ? rho[e[c]] : vel[(b * 3 + (k - 1)) * CELLS + cc];
         }
-        const float x00 = probe_lerp(v[0], v[1], wx), x10 = probe_lerp(v[2], v[3], wx);
-        const float x01 = probe_lerp(v[4], v[5], wx), x11 = probe_lerp(v[6], v[7], wx);
-        const float y0 = probe_lerp(x00, x10, wy), y1 = probe_lerp(x01, x11, wy);
-        res[k] = probe_lerp(y0, y1, wz);
+        res[k] = probe_trilinear(v, wx, wy, wz);
     }
+}
+
+__global__ __launch_bounds__(64) void k_probe_sample(float *__restrict__ out, const int32_t *__restrict__ cell, const float *__restrict__ w,
+                                                     const int32_t *__restrict__ col, int n, const float *__restrict__ rho,
+                                                     const float *__restrict__ vel)
+{
+    const int p = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (p >= n) return;
+    float res[4];
+    stencil_sample(res, p, cell, w, rho, vel);
     *(float4 *)(out + 4 * (int64_t)col[p]) = make_float4(res[0], res[1], res[2], res[3]);
 }
 
@@ -1820,21 +1818,15 @@ __global__ __launch_bounds__(64) void k_slice_sample(float *__restrict__ out, in
 #pragma unroll
                 for (int i = 0; i < 3; ++i) g[i][j] = (0.5f * (slice_vel(vel, hi, i) - slice_vel(vel, lo, i))) * scale;
             }
-            v[4][c] = g[2][1] - g[1][2];
-            v[5][c] = g[0][2] - g[2][0];
-            v[6][c] = g[1][0] - g[0][1];
-            v[7][c] = -0.5f * (((g[0][0] * g[0][0] + g[1][1] * g[1][1]) + g[2][2] * g[2][2]) +
-                               2.0f * ((g[0][1] * g[1][0] + g[0][2] * g[2][0]) + g[1][2] * g[2][1]));
+            float q[GRAD_COMPONENTS];
+            vorticity_q(q, g);
+#pragma unroll
+            for (int m = 0; m < GRAD_COMPONENTS; ++m) v[4 + m][c] = q[m];
         }
     }
     float res[NQ];
 #pragma unroll
-    for (int k = 0; k < NQ; ++k) {
-        const float x00 = probe_lerp(v[k][0], v[k][1], wx), x10 = probe_lerp(v[k][2], v[k][3], wx);
-        const float x01 = probe_lerp(v[k][4], v[k][5], wx), x11 = probe_lerp(v[k][6], v[k][7], wx);
-        const float y0 = probe_lerp(x00, x10, wy), y1 = probe_lerp(x01, x11, wy);
-        res[k] = probe_lerp(y0, y1, wz);
-    }
+    for (int k = 0; k < NQ; ++k) res[k] = probe_trilinear(v[k], wx, wy, wz);
     const int64_t o = col[p];
     out[o] = res[0];
     out[n_set + o] = res[1];
@@ -2194,8 +2186,7 @@ __device__ __forceinline__ int render_sample(const RenderArgs &a, float px, floa
         v[c] = h.s[(int64_t)b * h.stride + ce];
     }
     const float wx = g[0] - floorf(g[0]), wy = g[1] - floorf(g[1]), wz = g[2] - floorf(g[2]);
-    const float x0 = probe_lerp(v[0], v[1], wx), x1 = probe_lerp(v[2], v[3], wx), x2 = probe_lerp(v[4], v[5], wx), x3 = probe_lerp(v[6], v[7], wx);
-    s = probe_lerp(probe_lerp(x0, x1, wy), probe_lerp(x2, x3, wy), wz);
+    s = probe_trilinear(v, wx, wy, wz);
     return RENDER_FOUND;
 }
 
@@ -2637,6 +2628,16 @@ struct MonitorRecord {
     float rho_min, rho_max, v2_max, pad;
 };
 constexpr unsigned long long MONITOR_NO_KEY = ~0ull;
+// the neutral record: what a level without fluid cells reports and what a missing record counts as
+__device__ __forceinline__ MonitorRecord monitor_empty()
+{
+    MonitorRecord r;
+    r.sum_rho = r.sum_rho_v2 = 0.0;
+    r.n_fluid = r.n_bad = 0;
+    r.key_rho_min = r.key_rho_max = r.key_v2_max = r.key_bad = MONITOR_NO_KEY;
+    r.rho_min = __int_as_float(0x7f800000); r.rho_max = r.v2_max = __int_as_float(0xff800000); r.pad = 0.0f;
+    return r;
+}
 constexpr int MONITOR_COORD_BITS = 18;                         // block coordinates 1 .. 2^18 - 1 per axis, 9 bits of cell
 __device__ __forceinline__ unsigned long long monitor_block_key(int bx, int by, int bz)
 {
@@ -2716,11 +2717,9 @@ __global__ __launch_bounds__(256) void k_monitor_blocks(MonitorRecord *__restric
     if (t != 0) return;
     const int32_t *row = meta + b * NBR_STRIDE;
     const unsigned long long base = monitor_block_key(row[NBR_BX], row[NBR_BY], row[NBR_BZ]);
-    MonitorRecord o;
+    MonitorRecord o = monitor_empty();
     o.sum_rho = (part[0].s0 + part[1].s0) + (part[2].s0 + part[3].s0);
     o.sum_rho_v2 = (part[0].s1 + part[1].s1) + (part[2].s1 + part[3].s1);
-    o.n_fluid = o.n_bad = 0;
-    o.rho_min = __int_as_float(0x7f800000); o.rho_max = o.v2_max = __int_as_float(0xff800000); o.pad = 0.0f;
     int c0 = -1, c1 = -1, c2 = -1, cb = -1;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {                                    // waves in cell order: a strict comparison keeps the lowest cell
@@ -2774,12 +2773,7 @@ __global__ __launch_bounds__(256) void k_monitor_combine(MonitorRecord *__restri
     __shared__ MonitorRecord part[4];
     const int t = (int)threadIdx.x;
     const int64_t i = (int64_t)blockIdx.x * CELLS + 2 * t;
-    MonitorRecord a;
-    a.sum_rho = a.sum_rho_v2 = 0.0;
-    a.n_fluid = a.n_bad = 0;
-    a.key_rho_min = a.key_rho_max = a.key_v2_max = a.key_bad = MONITOR_NO_KEY;
-    a.rho_min = __int_as_float(0x7f800000); a.rho_max = a.v2_max = __int_as_float(0xff800000); a.pad = 0.0f;
-    MonitorRecord b = a;
+    MonitorRecord a = monitor_empty(), b = a;
     if (i < n) a = in[i];
     if (i + 1 < n) b = in[i + 1];
     a.sum_rho = monitor_wave_sum(a.sum_rho + b.sum_rho);
@@ -2871,38 +2865,24 @@ __device__ __forceinline__ bool force_contributions(float c[9], int64_t i, int64
     return fabsf(p) > 1.0e-10f;
 }
 
-__global__ __launch_bounds__(256) void k_force_chunks(ForceRecord *__restrict__ slab, const int32_t *__restrict__ cell,
-                                                      const float *__restrict__ rec, int n, const float *__restrict__ rho,
-                                                      const float *__restrict__ vel, float tau, float pressure_scale, float stress_scale)
+// The four waves of a workgroup through LDS: a.s = every wave's node, count = its integer count -> the caller's lane 0 (true) holds
+// the workgroup's node in `a`. part / pc: LDS.
+template <typename Rec, int ROWS, long long Rec::*CNT, typename PC>
+__device__ __forceinline__ bool tree_join_waves(Rec &a, PC count, int64_t n, double (*part)[ROWS], PC *pc)
 {
-    __shared__ double part[4][9];
-    __shared__ int cov[4];
     const int t = (int)threadIdx.x;
-    const int64_t N = n, i = (int64_t)blockIdx.x * CELLS + 2 * t;
-    float c0[9], c1[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) c0[k] = c1[k] = 0.0f;
-    bool k0 = false, k1 = false;
-    if (i < N) k0 = force_contributions(c0, i, N, cell, rec, rho, vel, tau, pressure_scale, stress_scale);
-    if (i + 1 < N) k1 = force_contributions(c1, i + 1, N, cell, rec, rho, vel, tau, pressure_scale, stress_scale);
-    const int n_cov = __popcll(__ballot(k0)) + __popcll(__ballot(k1));
-    double s[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) s[k] = force_wave_sum(N > 1 ? (double)c0[k] + (double)c1[k] : (double)c0[k], N);
     if ((t & 63) == 0) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) part[t >> 6][k] = s[k];
-        cov[t >> 6] = n_cov;
+        for (int k = 0; k < ROWS; ++k) part[t >> 6][k] = a.s[k];
+        pc[t >> 6] = count;
     }
     __syncthreads();
-    if (t != 0) return;
-    ForceRecord o;
+    if (t != 0) return false;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) o.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], N);
-    o.covered = (long long)((cov[0] + cov[1]) + (cov[2] + cov[3]));
-    slab[blockIdx.x] = o;
+    for (int k = 0; k < ROWS; ++k) a.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], n);
+    a.*CNT = (long long)((pc[0] + pc[1]) + (pc[2] + pc[3]));
+    return true;
 }
-
 // One workgroup's node of a tree of records {double s[ROWS]; long long <CNT>;} (the force series' and the flux planes'): records
 // in[chunk * 512 ..] of n -> the caller's lane 0 (true) holds their node in `a`; missing records are +0.0. part / pc: LDS.
 template <typename Rec, int ROWS, long long Rec::*CNT>
@@ -2921,17 +2901,36 @@ __device__ __forceinline__ bool tree_combine(Rec &a, const Rec *__restrict__ in,
     for (int o = 1; o < 64; o <<= 1) a.*CNT += __shfl_xor(a.*CNT, o, 64);
 #pragma unroll
     for (int k = 0; k < ROWS; ++k) a.s[k] = force_wave_sum(n > 1 ? a.s[k] + b.s[k] : a.s[k], n);
-    if ((t & 63) == 0) {
+    return tree_join_waves<Rec, ROWS, CNT>(a, a.*CNT, n, part, pc);
+}
+// The leaf level of the same tree: elements chunk * 512 .. of n, two per lane (tree level 1). fill(c, i) forms the ROWS float values
+// of element i and says whether it counts; they are widened to double here. A missing element is +0.0 and does not count.
+template <typename Rec, int ROWS, long long Rec::*CNT, class FILL>
+__device__ __forceinline__ bool tree_leaf(Rec &a, int64_t n, int64_t chunk, double (*part)[ROWS], int *pc, FILL fill)
+{
+    const int64_t i = chunk * CELLS + 2 * (int)threadIdx.x;
+    float c0[ROWS], c1[ROWS];
 #pragma unroll
-        for (int k = 0; k < ROWS; ++k) part[t >> 6][k] = a.s[k];
-        pc[t >> 6] = a.*CNT;
-    }
-    __syncthreads();
-    if (t != 0) return false;
+    for (int k = 0; k < ROWS; ++k) c0[k] = c1[k] = 0.0f;
+    bool k0 = false, k1 = false;
+    if (i < n) k0 = fill(c0, i);
+    if (i + 1 < n) k1 = fill(c1, i + 1);
+    const int counted = __popcll(__ballot(k0)) + __popcll(__ballot(k1));
 #pragma unroll
-    for (int k = 0; k < ROWS; ++k) a.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], n);
-    a.*CNT = (pc[0] + pc[1]) + (pc[2] + pc[3]);
-    return true;
+    for (int k = 0; k < ROWS; ++k) a.s[k] = force_wave_sum(n > 1 ? (double)c0[k] + (double)c1[k] : (double)c0[k], n);
+    return tree_join_waves<Rec, ROWS, CNT>(a, counted, n, part, pc);
+}
+
+__global__ __launch_bounds__(256) void k_force_chunks(ForceRecord *__restrict__ slab, const int32_t *__restrict__ cell,
+                                                      const float *__restrict__ rec, int n, const float *__restrict__ rho,
+                                                      const float *__restrict__ vel, float tau, float pressure_scale, float stress_scale)
+{
+    __shared__ double part[4][9];
+    __shared__ int cov[4];
+    const int64_t N = n;
+    ForceRecord o;
+    const auto fill = [&](float (&c)[9], int64_t i) { return force_contributions(c, i, N, cell, rec, rho, vel, tau, pressure_scale, stress_scale); };
+    if (tree_leaf<ForceRecord, 9, &ForceRecord::covered>(o, N, (int64_t)blockIdx.x, part, cov, fill)) slab[blockIdx.x] = o;
 }
 
 __global__ __launch_bounds__(256) void k_force_combine(ForceRecord *__restrict__ out, const ForceRecord *__restrict__ in, int64_t n)
@@ -2965,21 +2964,8 @@ __device__ __forceinline__ void flux_contributions(float c[FLUX_ROWS], int64_t p
                                                    const float *__restrict__ w, const float *__restrict__ rho,
                                                    const float *__restrict__ vel)
 {
-    int64_t e[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) e[k] = cell[8 * p + k];
-    const float wx = w[3 * p], wy = w[3 * p + 1], wz = w[3 * p + 2];
     float res[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = k == 0 ? rho[e[j]] : vel[((e[j] >> 9) * 3 + (k - 1)) * CELLS + (e[j] & 511)];
-        const float x00 = probe_lerp(v[0], v[1], wx), x10 = probe_lerp(v[2], v[3], wx);
-        const float x01 = probe_lerp(v[4], v[5], wx), x11 = probe_lerp(v[6], v[7], wx);
-        const float y0 = probe_lerp(x00, x10, wy), y1 = probe_lerp(x01, x11, wy);
-        res[k] = probe_lerp(y0, y1, wz);
-    }
+    stencil_sample(res, p, cell, w, rho, vel);
     const float r = res[0], ux = res[1], uy = res[2], uz = res[3];
     const float un = axis == 0 ? ux : (axis == 1 ? uy : uz);
     const float m = r * un;
@@ -3001,30 +2987,9 @@ __global__ __launch_bounds__(256) void k_flux_chunks(FluxRecord *__restrict__ sl
     __shared__ double part[4][FLUX_ROWS];
     __shared__ int cnt[4];
     const FluxChunk d = chunks[blockIdx.x];
-    const int t = (int)threadIdx.x;
-    const int64_t N = d.n, i = (int64_t)d.chunk * CELLS + 2 * t;
-    float c0[FLUX_ROWS], c1[FLUX_ROWS];
-#pragma unroll
-    for (int k = 0; k < FLUX_ROWS; ++k) c0[k] = c1[k] = 0.0f;
-    const bool k0 = i < N, k1 = i + 1 < N;
-    if (k0) flux_contributions(c0, d.start + i, d.axis, cell, w, rho, vel);
-    if (k1) flux_contributions(c1, d.start + i + 1, d.axis, cell, w, rho, vel);
-    const int n_in = __popcll(__ballot(k0)) + __popcll(__ballot(k1));
-    double s[FLUX_ROWS];
-#pragma unroll
-    for (int k = 0; k < FLUX_ROWS; ++k) s[k] = force_wave_sum(N > 1 ? (double)c0[k] + (double)c1[k] : (double)c0[k], N);
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < FLUX_ROWS; ++k) part[t >> 6][k] = s[k];
-        cnt[t >> 6] = n_in;
-    }
-    __syncthreads();
-    if (t != 0) return;
     FluxRecord o;
-#pragma unroll
-    for (int k = 0; k < FLUX_ROWS; ++k) o.s[k] = force_join_waves(part[0][k], part[1][k], part[2][k], part[3][k], N);
-    o.count = (long long)((cnt[0] + cnt[1]) + (cnt[2] + cnt[3]));
-    flux_store(slab, slot, d.dst, o);
+    const auto fill = [&](float (&c)[FLUX_ROWS], int64_t i) { flux_contributions(c, d.start + i, d.axis, cell, w, rho, vel); return true; };
+    if (tree_leaf<FluxRecord, FLUX_ROWS, &FluxRecord::count>(o, d.n, d.chunk, part, cnt, fill)) flux_store(slab, slot, d.dst, o);
 }
 
 __global__ __launch_bounds__(256) void k_flux_combine(FluxRecord *__restrict__ slab, FluxRecord *__restrict__ slot,
@@ -3039,11 +3004,14 @@ __global__ __launch_bounds__(256) void k_flux_combine(FluxRecord *__restrict__ s
 
 // ---- wall diagnostics (ludwig_level_wall_census, ludwig_wall_surface_*; no reference counterpart: the reference reads y_plus_target
 // and never computes a y+) ----
-// The state wall_model_force_mag passes through on its way to the force, restated operation by operation (same operand order, jl_pow /
-// jl_log, -ffp-contract=off) beside it; that function is left alone. code: WALL_FAR not near the wall (!(0 < d < 10)), WALL_SKIPPED near
-// the wall but the model is skipped (u_mag <= 1e-6 or nu_visc <= 1e-10), WALL_POWER the power law's u_tau is kept (y_p <= 11.81 or
-// u_plus_law <= 0.1), WALL_LOG the log law replaced it; WALL_FORCED is or-ed in where the step applies a force (tau_wall > tau_res).
-// y_plus is the FINAL u_tau * dist_wall / nu_visc, not the provisional y_p that picks the branch. Codes below WALL_POWER give zeros.
+// The state wall_model_force_mag passes through on its way to the force: a second copy of its chain (same operand order, jl_pow / jl_log,
+// -ffp-contract=off), and the one formula this file still holds twice. Every form with one body for both - a template on "wants the
+// state", a core the two call - cost the step's function two instructions and the order of two compares ("Single
+// source"), and the step's machine code is not traded for source. A change to one goes into the other.
+// code: WALL_FAR not near the wall (!(0 < d < 10)), WALL_SKIPPED near the wall but the model is skipped (u_mag <= 1e-6 or
+// nu_visc <= 1e-10), WALL_POWER the power law's u_tau is kept (y_p <= 11.81 or u_plus_law <= 0.1), WALL_LOG the log law replaced it;
+// WALL_FORCED is or-ed in where the step applies a force (tau_wall > tau_res). y_plus is the FINAL u_tau * dist_wall / nu_visc, not the
+// provisional y_p that picks the branch. Codes below WALL_POWER give zeros.
 constexpr int WALL_FAR = 0, WALL_SKIPPED = 1, WALL_POWER = 2, WALL_LOG = 3, WALL_FORCED = 4;
 struct WallState {
     float u_tau, y_plus;

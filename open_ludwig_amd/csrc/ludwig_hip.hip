@@ -1059,25 +1059,55 @@ int record_step_wanted(LudwigLevel *L, const LudwigLevel *parent, const LudwigSt
     return LUDWIG_OK;
 }
 
+// Several launches (parts, the two paths) may belong to one sub-step: it counts once.
+void count_step(LudwigLevel *L, int64_t t_sub)
+{
+    if (t_sub != L->last_step_t) { ++L->step_count; L->last_step_t = t_sub; }
+}
+
+// ---- from the runtime flags of a launch to the instantiation of its kernel: ONE place each for the f path and the record path ----
+using StepKernel = void (*)(SCParams);
+// from_records: rec[in] holds the state (wide = 64-bit per-lane record addresses); else it is read from f[in] / vel[in] (wide = the level's)
+StepKernel record_step_kernel(bool from_records, bool wide)
+{
+    if (from_records) return wide ? k_step_records<XRUN, true> : k_step_records<XRUN, false>;
+    return wide ? k_records_from_populations<XRUN, true> : k_records_from_populations<XRUN, false>;
+}
+template <bool GENERAL, bool POST, bool WALL, bool RHO_ONLY>
+StepKernel xrun_kernel(bool wide)
+{
+    return wide ? k_stream_collide_xrun<XRUN, GENERAL, POST, WALL, RHO_ONLY, true> : k_stream_collide_xrun<XRUN, GENERAL, POST, WALL, RHO_ONLY, false>;
+}
+// (The order in which the instantiations are named here and above is the order of the kernels in the code object. tools/device_code_diff.py
+// compares bytes, and the wall-model kernels hold their distance to wall_model_force_mag: keep the order when nothing else changes.)
+StepKernel stream_collide_kernel(bool general, bool post, bool wall, bool rho_only, bool wide)
+{
+    if (!rho_only) {
+        // WALL without POST goes through the <POST, WALL> instantiation (no block is flagged for the f_post store, so the null
+        // pointer is never used): the register allocator gets <POST = false, WALL = true> down to 96 VGPRs only by spilling
+        // 208 B per lane, while the POST variant sits at 88-90 without - same arithmetic, same bits
+        // GENERAL without POST needs a 104-byte spill to stay at 96 VGPRs: the POST variant serves it too
+        if (general) return wall ? xrun_kernel<true, true, true, false>(wide) : xrun_kernel<true, true, false, false>(wide);
+        if (wall) return xrun_kernel<false, true, true, false>(wide);
+        return post ? xrun_kernel<false, true, false, false>(wide) : xrun_kernel<false, false, false, false>(wide);
+    }
+    return general ? xrun_kernel<true, false, false, true>(wide) : xrun_kernel<false, false, false, true>(wide);   // ensure_rho's replay
+}
+
 // One whole-level step in -> out that writes records: from rec[in] where that holds the state, else from f[in] / vel[in].
 int launch_record_step(LudwigLevel *L, SCParams p, int in, int out, int64_t t_sub)
 {
-    if (t_sub != L->last_step_t) { ++L->step_count; L->last_step_t = t_sub; }
+    count_step(L, t_sub);
     L->rho_replay[LUDWIG_PART_ALL].stale = false;     // superseded, as by any whole-level step
     p.items = L->rec_items;
     p.rec_out = L->rec[out];
     p.store_rho = 0;
     const dim3 grid((unsigned)(L->n_items[LUDWIG_PART_ALL][2] / XRUN)), block(64 * XRUN);
-    if (L->rec_valid[in]) {
-        p.rec_in = L->rec[in];
-        // 64-bit per-lane record addresses from 4 GiB of records on (190 650 blocks)
-        if ((uint64_t)L->n_blocks * R_BLOCK_BYTES >= (1ull << 32)) hipLaunchKernelGGL((k_step_records<XRUN, true>), grid, block, 0, L->stream, p);
-        else hipLaunchKernelGGL((k_step_records<XRUN, false>), grid, block, 0, L->stream, p);
-    } else if (L->wide) {
-        hipLaunchKernelGGL((k_records_from_populations<XRUN, true>), grid, block, 0, L->stream, p);
-    } else {
-        hipLaunchKernelGGL((k_records_from_populations<XRUN, false>), grid, block, 0, L->stream, p);
-    }
+    const bool from_records = L->rec_valid[in];
+    if (from_records) p.rec_in = L->rec[in];
+    // 64-bit per-lane record addresses from 4 GiB of records on (190 650 blocks)
+    const bool wide = from_records ? (uint64_t)L->n_blocks * R_BLOCK_BYTES >= (1ull << 32) : L->wide;
+    hipLaunchKernelGGL(record_step_kernel(from_records, wide), grid, block, 0, L->stream, p);
     LW_HIP(hipGetLastError());
     L->rec_valid[out] = true;
     L->f_valid[out] = false;
@@ -1152,7 +1182,7 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
         if (r) return r;
     }
     {
-        if (t_sub != L->last_step_t) { ++L->step_count; L->last_step_t = t_sub; }
+        count_step(L, t_sub);
         const bool store = env::eager_rho() || L->rho_eager || part != LUDWIG_PART_ALL;
         // This launch reuses the previous step's INPUT buffer as its output. A whole-level launch supersedes the elided rho of
         // the previous one (the reference would be overwriting it right now, unread); a part launch covers only some of the
@@ -1178,20 +1208,7 @@ int launch_stream_collide(LudwigLevel *L, const LudwigLevel *parent, int64_t t_s
         if (n_items == 0) return LUDWIG_OK;
         p.items = items;
         const dim3 grid((unsigned)(n_items / XRUN)), block(64 * XRUN);
-#define LW_LAUNCH_X(G, P, W) do { if (L->wide) hipLaunchKernelGGL((k_stream_collide_xrun<XRUN, G, P, W, false, true>), grid, block, 0, cs, p); \
-            else hipLaunchKernelGGL((k_stream_collide_xrun<XRUN, G, P, W, false, false>), grid, block, 0, cs, p); } while (0)
-        // WALL without POST goes through the <POST, WALL> instantiation (no block is flagged for the f_post store, so the null
-        // pointer is never used): the register allocator gets <POST = false, WALL = true> down to 96 VGPRs only by spilling
-        // 208 B per lane, while the POST variant sits at 88-90 without - same arithmetic, same bits
-        if (general) {       // GENERAL without POST needs a 104-byte spill to stay at 96 VGPRs: the POST variant serves it too
-            if (wall) LW_LAUNCH_X(true, true, true);
-            else LW_LAUNCH_X(true, true, false);
-        } else {
-            if (wall) LW_LAUNCH_X(false, true, true);
-            else if (post) LW_LAUNCH_X(false, true, false);
-            else LW_LAUNCH_X(false, false, false);
-        }
-#undef LW_LAUNCH_X
+        hipLaunchKernelGGL(stream_collide_kernel(general, post, wall, false, L->wide), grid, block, 0, cs, p);
         LW_HIP(hipGetLastError());
         return LUDWIG_OK;
     };
@@ -1245,15 +1262,8 @@ int ensure_rho(LudwigLevel *L)
         for (int c = 1; c < N_CLASSES; ++c) {
             if (L->n_items[part][c] == 0) continue;
             p.items = L->items[part][c];
-            const bool general = c == 1;
             const dim3 grid((unsigned)(L->n_items[part][c] / XRUN)), block(64 * XRUN);
-            if (L->wide) {
-                if (general) hipLaunchKernelGGL((k_stream_collide_xrun<XRUN, true, false, false, true, true>), grid, block, 0, L->stream, p);
-                else hipLaunchKernelGGL((k_stream_collide_xrun<XRUN, false, false, false, true, true>), grid, block, 0, L->stream, p);
-            } else {
-                if (general) hipLaunchKernelGGL((k_stream_collide_xrun<XRUN, true, false, false, true, false>), grid, block, 0, L->stream, p);
-                else hipLaunchKernelGGL((k_stream_collide_xrun<XRUN, false, false, false, true, false>), grid, block, 0, L->stream, p);
-            }
+            hipLaunchKernelGGL(stream_collide_kernel(c == 1, false, false, true, L->wide), grid, block, 0, L->stream, p);
             LW_HIP(hipGetLastError());
         }
         rr.stale = false;
@@ -1295,6 +1305,14 @@ int launch_bouzidi(LudwigLevel *L, int64_t t_sub, float q_min)
 // and the device array (block-major, internal block order). One component and the same block order: one copy; otherwise one
 // component at a time through `scratch` and a kernel that places every block. K = components, es = element size (1: obstacle,
 // 2: q map, else 4). Synchronous on the level's stream.
+template <class T>
+void place_component(const LudwigLevel *L, void *dev, void *scratch, int K, int k, bool to_device)
+{
+    const int64_t n = L->sk;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (to_device) hipLaunchKernelGGL(k_component_to_internal<T>, grid, block, 0, L->stream, (T *)dev, (const T *)scratch, L->d_ref2int, n, K, k);
+    else hipLaunchKernelGGL(k_component_to_reference<T>, grid, block, 0, L->stream, (T *)scratch, (const T *)dev, L->d_ref2int, n, K, k);
+}
 int copy_field(LudwigLevel *L, void *dev, void *host, int K, size_t es, bool to_device)
 {
     const size_t plane = (size_t)L->sk * es;                   // one component in bytes
@@ -1307,19 +1325,14 @@ int copy_field(LudwigLevel *L, void *dev, void *host, int K, size_t es, bool to_
     }
     if (!L->scratch) LW_HIP((hipError_t)L->scratch.alloc((size_t)L->sk));
     void *const scratch = L->scratch;
-    const int64_t n = L->sk;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const auto place = es == 1 ? place_component<uint8_t> : (es == 2 ? place_component<uint16_t> : place_component<float>);
     for (int k = 0; k < K; ++k) {
         char *h = (char *)host + (size_t)k * plane;
         if (to_device) {
             LW_HIP(hipMemcpyAsync(scratch, h, plane, hipMemcpyHostToDevice, L->stream));
-            if (es == 1) hipLaunchKernelGGL(k_component_to_internal<uint8_t>, grid, block, 0, L->stream, (uint8_t *)dev, (const uint8_t *)scratch, L->d_ref2int, n, K, k);
-            else if (es == 2) hipLaunchKernelGGL(k_component_to_internal<uint16_t>, grid, block, 0, L->stream, (uint16_t *)dev, (const uint16_t *)scratch, L->d_ref2int, n, K, k);
-            else hipLaunchKernelGGL(k_component_to_internal<float>, grid, block, 0, L->stream, (float *)dev, (const float *)scratch, L->d_ref2int, n, K, k);
+            place(L, dev, scratch, K, k, true);
         } else {
-            if (es == 1) hipLaunchKernelGGL(k_component_to_reference<uint8_t>, grid, block, 0, L->stream, (uint8_t *)scratch, (const uint8_t *)dev, L->d_ref2int, n, K, k);
-            else if (es == 2) hipLaunchKernelGGL(k_component_to_reference<uint16_t>, grid, block, 0, L->stream, (uint16_t *)scratch, (const uint16_t *)dev, L->d_ref2int, n, K, k);
-            else hipLaunchKernelGGL(k_component_to_reference<float>, grid, block, 0, L->stream, (float *)scratch, (const float *)dev, L->d_ref2int, n, K, k);
+            place(L, dev, scratch, K, k, false);
             LW_HIP(hipMemcpyAsync(h, scratch, plane, hipMemcpyDeviceToHost, L->stream));
             LW_HIP(hipStreamSynchronize(L->stream));          // pageable destination: the copy must be over before scratch is reused
         }

@@ -108,7 +108,8 @@ def plan_flux_plane(spec: FluxPlane, grids: Sequence, offset=(0.0, 0.0, 0.0)) ->
     return FluxPlan(spec, axes, h, dims, pts, dom, valid, level, blocks, cells, weights, replaced)
 
 
-# ---- the numpy restatement of k_flux_chunks / k_flux_combine and of the download's sum over levels ----
+# ---- the numpy restatement of k_flux_chunks / k_flux_combine (kernels.hpp stencil_sample, flux_contributions, tree_leaf, tree_combine)
+# and of the download's sum over levels ----
 def contributions(plan: FluxPlan, idx: np.ndarray, rho: np.ndarray, vel: np.ndarray) -> np.ndarray:
     """[len(idx), 8] float32: the rows of points idx of one level from its fields in the reference layout"""
     s = trilinear(gather(plan, idx, rho, vel), plan.weights[idx][:, None, :])      # [m, 4]: rho, ux, uy, uz

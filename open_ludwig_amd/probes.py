@@ -10,8 +10,8 @@ Semantics ("Probes"):
     LEVEL is replaced by the base cell: one rule for the domain edge, the edge of a refinement level and the body surface (no parent
     interpolation).
   * Values: rho, ux, uy, uz in lattice units (the flow file's Density / Velocity), trilinear in float32 in one fixed order - x first,
-    then y, then z, each lerp (1 - w) a + w b (`trilinear` below; the device kernel k_probe_sample evaluates the same expressions with
-    -ffp-contract=off, bit for bit) - from the level's NEWEST state after the coarse step (statistics.t_sub_after; vel_temp if that
+    then y, then z, each lerp (1 - w) a + w b (`trilinear` below; on the device kernels.hpp probe_trilinear, gathered by stencil_sample for
+    k_probe_sample, evaluates the same expressions with -ffp-contract=off, bit for bit) - from the level's NEWEST state after the coarse step (statistics.t_sub_after; vel_temp if that
     sub-step is even, vel if odd).
   * Sampled coarse steps: start_step + k interval.
 Physical units: u_phys = u * (U_phys / u_lattice) = u * params.velocity_scale.

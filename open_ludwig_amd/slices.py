@@ -22,7 +22,8 @@ Semantics ("Slices"):
   * Sampled coarse steps: start_step + k interval. Files: slice_<name>_%06d.vti (VTK XML ImageData: Origin and Spacing in the domain
     frame, float32 point arrays named as in the flow file plus a UInt8 Valid array) and slice_<name>.pvd (time = step * time_scale),
     rewritten after every file.
-The device kernel is k_slice_sample (ludwig_slices_*); sample_slice below restates it bit for bit.
+The device kernel is k_slice_sample (ludwig_slices_*; vorticity and Q by kernels.hpp vorticity_q, the interpolation by probe_trilinear);
+sample_slice below restates it bit for bit.
 """
 from __future__ import annotations
 

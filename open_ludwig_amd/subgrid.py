@@ -1,6 +1,6 @@
 """The subgrid model made visible (no reference counterpart: the reference folds its WALE eddy viscosity into tau_turb and drops it).
 
-The device (libludwig_hip.so, ludwig_level_subgrid_*) restates the step's WALE block beside it, operation by operation in float32, on
+The device (libludwig_hip.so, ludwig_level_subgrid_*) evaluates the step's own WALE function (kernels.hpp wale_state), in float32, on
 the gradient the step forms: g_ij = 0.5 (u_i(+e_j) - u_i(-e_j)) in lattice units, the cell's own value where no block lies across a
 face. Evaluated on the velocity sub-step t wrote, nu_t is bit for bit the value sub-step t + 1 collides with. nu_t is the EFFECTIVE
 viscosity: it includes the `nu_sgs_background` floor, max(nu_model, nu_bg), because that is what the step uses; the code field says

@@ -1,7 +1,7 @@
 """Float32 restatement of the subgrid observer (kernels.hpp wale_state, k_subgrid), for the tests.
 
-Written from the model's formula in the step's operand order (reference src/physics_kernels.jl:251-300; kernels.hpp finish_cell, "WALE
-eddy viscosity"), on tests/_gradient_ref.gradient_tensor(vel, neighbor_table, scale = 1): the gradient in lattice units with the
+Written from the model's formula in the step's operand order (reference src/physics_kernels.jl:251-300; kernels.hpp wale_state, which
+finish_cell calls), on tests/_gradient_ref.gradient_tensor(vel, neighbor_table, scale = 1): the gradient in lattice units with the
 cell's own value where no block lies across a face. Every operation is one float32 numpy ufunc, so the result is what the device
 computes with -ffp-contract=off, bit for bit. It does not call tests/_step_ref.py: test_subgrid_host.py ties the two together.
 The Float64 sums are restated as the sequential additions the device makes."""
