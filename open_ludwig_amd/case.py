@@ -467,6 +467,19 @@ class DistributedStepper:
                 for o, a in zip(outs, part[1]):
                     o[:, :, :, part[0]] = a
 
+    @staticmethod
+    def _scatter_columns(parts, outs) -> None:
+        """the same along the LAST axis: the ranks' gathered (columns, one [..., n_columns] array per output, ...) into `outs`"""
+        for part in parts:
+            if part is not None:
+                for o, a in zip(outs, part[1:]):
+                    o[..., part[0]] = a
+
+    @staticmethod
+    def _samples(parts) -> int:
+        """the sample count the gathered parts end with (every rank that sent one counted the same samples); 0 when nobody did"""
+        return ([0] + [part[-1] for part in parts if part is not None])[-1]
+
     def _start(self, params) -> None:
         probe_cells, mine = None, None
         if self._probe_cfg is not None:
@@ -522,21 +535,21 @@ class DistributedStepper:
             if M is not None and stats_mod.is_sample_step(t, M.start_step, M.interval):
                 self._modes_accumulate(t)      # owned blocks only: no ghost is read, nothing to join
             if S is not None and S.is_sample_step(t):
-                self.runner._join(fin)
+                self.runner.join(fin)
                 S.accumulate(stats_mod.t_sub_after(fin, t))
             if P is not None and probes_mod.is_sample_step(t, P.start_step, P.interval):
                 if self._probe_pending == P.capacity:
                     self._series.append(*P.download())
                     self._probe_pending = 0
                 for lvl in P.levels_with_probes:
-                    self.runner._join(lvl)     # the level's ghosts (peer corners) are in place
+                    self.runner.join(lvl)     # the level's ghosts (peer corners) are in place
                     P.sample(lvl, stats_mod.t_sub_after(lvl, t))
                 self._probe_pending += 1
             if F is not None and F.is_sample_step(t):
                 if self._force_pending == F.capacity:
                     self._fseries.append(*F.download())
                     self._force_pending = 0
-                self.runner._join(fin)
+                self.runner.join(fin)
                 F.sample(stats_mod.t_sub_after(fin, t), t)
                 self._force_pending += 1
         self.runner.synchronize()
@@ -633,9 +646,8 @@ class DistributedStepper:
             return None
         rows = slices_mod.ROWS_GRAD if any(p.gradient for p in self._slice_plans) else slices_mod.ROWS_BASIC
         out = [np.zeros((rows, p.n), dtype=np.float32) for p in self._slice_plans]
-        for part in parts:
-            for k, (cols, v) in enumerate(part or ()):
-                out[k][:, cols] = v
+        for k, o in enumerate(out):
+            self._scatter_columns([part and part[k] for part in parts], [o])
         return out
 
     # -- surface statistics: each rank accumulates the triangles whose cell it owns (the rule of _triangle_map); per-triangle sums do
@@ -654,19 +666,26 @@ class DistributedStepper:
             self._surface_create()
         return plan
 
+    def _surface_share(self, plan):
+        """(sel, local): the triangles of a SurfacePlan whose cell this rank owns (the rule of _triangle_map), and the plan of those
+        alone with the finest level's blocks renumbered to this rank's owned ones; local is None where the rank holds no copy of that
+        level (a level held without an owned block still gets its empty set: it counts the samples)"""
+        fin = len(self.host) - 1
+        sel = np.flatnonzero(plan.found & (self._level_owner(fin)[np.maximum(plan.blocks, 0)] == self.rank))
+        if self.runner.levels[fin] is None:
+            assert sel.size == 0
+            return sel, None
+        local = plan.subset(sel)
+        local.blocks = self._owned_g2l(fin)[local.blocks].astype(np.int32)
+        assert (local.blocks >= 0).all()
+        return sel, local
+
     def _surface_create(self) -> None:
         plan, params, start, interval = self._surface_cfg
         fin = len(self.host) - 1
-        owner = self._level_owner(fin)
-        self._surface_sel = np.flatnonzero(plan.found & (owner[np.maximum(plan.blocks, 0)] == self.rank))
-        lv = self.runner.levels[fin]
-        if lv is None:                         # (a level held without an owned block still gets its empty set: it counts the samples)
-            assert self._surface_sel.size == 0
-            return
-        local = plan.subset(self._surface_sel)
-        local.blocks = self._owned_g2l(fin)[local.blocks].astype(np.int32)
-        assert (local.blocks >= 0).all()
-        self.surface = surface_mod.DeviceSurfaceStats(local, lv, fin, self.host[fin].tau, params, start, interval)
+        self._surface_sel, local = self._surface_share(plan)
+        if local is not None:
+            self.surface = surface_mod.DeviceSurfaceStats(local, self.runner.levels[fin], fin, self.host[fin].tau, params, start, interval)
 
     def surface_stats_sums(self):
         """(sums [7, n_tri] Float64 in triangle order, samples) on rank 0 (None elsewhere); collective"""
@@ -679,12 +698,8 @@ class DistributedStepper:
         if parts is None:
             return None
         out = np.zeros((len(surface_mod.COMPONENTS), plan.n), dtype=np.float64)
-        n = 0
-        for part in parts:
-            if part is not None:
-                sel, sums, n = part
-                out[:, sel] = sums
-        return out, n
+        self._scatter_columns(parts, [out])
+        return out, self._samples(parts)
 
     # -- force series: each rank reduces the triangles whose cell it owns (the rule of _triangle_map) in global triangle order; a
     # triangle without a cell adds signed zeros only and belongs to nobody. The ranks' records are added in rank order in Float64 on
@@ -708,16 +723,10 @@ class DistributedStepper:
     def _forces_create(self) -> None:
         mesh, plan, params, start, interval, capacity = self._forces_cfg
         fin = len(self.host) - 1
-        owner = self._level_owner(fin)
-        self._forces_sel = np.flatnonzero(plan.found & (owner[np.maximum(plan.blocks, 0)] == self.rank))
-        lv = self.runner.levels[fin]
-        if lv is None:
-            assert self._forces_sel.size == 0
+        self._forces_sel, local = self._surface_share(plan)
+        if local is None:
             return
-        local = plan.subset(self._forces_sel)
-        local.blocks = self._owned_g2l(fin)[local.blocks].astype(np.int32)
-        assert (local.blocks >= 0).all()
-        self.forces = fseries_mod.from_mesh(mesh, local, lv, fin, self.host[fin].tau, params, start, interval, capacity,
+        self.forces = fseries_mod.from_mesh(mesh, local, self.runner.levels[fin], fin, self.host[fin].tau, params, start, interval, capacity,
                                             select=self._forces_sel)
         self._fseries = fseries_mod.Series()
         self._force_pending = 0
@@ -762,17 +771,9 @@ class DistributedStepper:
 
     def _wall_surface_create(self) -> None:
         plan, params = self._wall_cfg
-        fin = len(self.host) - 1
-        owner = self._level_owner(fin)
-        self._wall_sel = np.flatnonzero(plan.found & (owner[np.maximum(plan.blocks, 0)] == self.rank))
-        lv = self.runner.levels[fin]
-        if lv is None:
-            assert self._wall_sel.size == 0
-            return
-        local = plan.subset(self._wall_sel)
-        local.blocks = self._owned_g2l(fin)[local.blocks].astype(np.int32)
-        assert (local.blocks >= 0).all()
-        self.wall_surface = wall_mod.DeviceWallSurface(local, lv, params)
+        self._wall_sel, local = self._surface_share(plan)
+        if local is not None:
+            self.wall_surface = wall_mod.DeviceWallSurface(local, self.runner.levels[len(self.host) - 1], params)
 
     def wall_census(self, level: int, t_coarse: int):
         """the wall_diagnostics.Census of the GLOBAL level after coarse step t_coarse on rank 0 (None elsewhere): the ranks' records
@@ -793,9 +794,7 @@ class DistributedStepper:
         if parts is None:
             return None
         out = np.zeros((len(wall_mod.ROWS), plan.n), dtype=np.float32)
-        for part in parts:
-            if part is not None:
-                out[:, part[0]] = part[1]
+        self._scatter_columns(parts, [out])
         return out
 
     # -- collectives of a few scalars --
@@ -866,9 +865,7 @@ class DistributedStepper:
             if parts is not None:
                 n = mesh.centers.shape[0]
                 maps = [np.zeros(n, dtype=np.float32) for _ in range(4)]
-                for s2, *arrs in parts:
-                    for m, a in zip(maps, arrs):
-                        m[s2] = a
+                self._scatter_columns(parts, maps)
                 fr.maps = tuple(maps)
         return fr
 
@@ -907,7 +904,7 @@ class DistributedStepper:
         nb = self.host[level].n_blocks
         out = [np.zeros((8, 8, 8, nb) + ((k,) if k > 1 else ()), dtype=np.float64, order="F") for k in (1, 3, 6)]
         self._scatter_blocks(parts, out)
-        n = ([0] + [part[2] for part in parts if part is not None])[-1]
+        n = self._samples(parts)
         return out[0], out[1], out[2], n
 
     def statistics(self, level: int):
@@ -958,7 +955,7 @@ class DistributedStepper:
             return None
         out = [np.zeros((8, 8, 8, self.host[level].n_blocks, 4), dtype=np.float64, order="F") for _ in range(self._modes_cfg[0].shape[1])]
         self._scatter_blocks(parts, out)
-        n = ([0] + [part[2] for part in parts if part is not None])[-1]
+        n = self._samples(parts)
         return out, n
 
     # -- velocity-gradient fields: every rank computes on its owned blocks after batch() (its 'vel' halo ghosts are current for
@@ -1045,7 +1042,7 @@ class DistributedStepper:
             return None
         out = [np.zeros((8, 8, 8, self.host[level].n_blocks), dtype=np.float64, order="F") for _ in range(3)]
         self._scatter_blocks(parts, out)
-        n = ([0] + [part[2] for part in parts if part is not None])[-1]
+        n = self._samples(parts)
         return out[0], out[1], out[2], n
 
     def close(self):

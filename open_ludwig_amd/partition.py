@@ -33,6 +33,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import PART_ALL, PART_BOUNDARY, PART_INTERIOR
 from .blocks import BLOCK_SIZE, BlockLevel, build_lattice_arrays, build_neighbor_table
 
 _CX, _CY, _CZ, _W, _OPP, _MY, _MZ = build_lattice_arrays()
@@ -580,6 +581,189 @@ def exchange_requests(my_requests: Dict[int, Dict[str, np.ndarray]], world: int,
     return to_me
 
 
+def plan_with_peers(view: LocalView, n_global: int, needs: Optional[Dict[str, np.ndarray]], world: int, rank: int,
+                    requests_to_me: Optional[Callable] = None, self_requests: bool = False) -> HaloPlan:
+    """The set-up hand-shake of one level: this rank's requests, what the peers ask of it, the plan. The peers' requests come from
+    `requests_to_me(own requests)` where the caller plays the peers (loop-back tests), else over the default process group. A world
+    of one exchanges nothing - unless `self_requests` hands it its own requests (periodic_box_plan alone: a box that wraps onto itself)."""
+    mine = make_requests(view, n_global, needs)
+    if requests_to_me is not None:
+        to_me = requests_to_me(mine)
+    elif world > 1:
+        to_me = exchange_requests(mine, world, rank)
+    else:
+        to_me = {rank: mine[rank]} if self_requests and rank in mine else {}
+    return build_plan(view, n_global, mine, to_me)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# what DistributedLevelRunner and MultiLevelRunner share: transport bring-up, the level schedule, teardown
+# ----------------------------------------------------------------------------------------------------------------
+def resolve_transport(transport: Optional[str], stage_through_host: bool) -> str:
+    """"native" (RCCL called from the library) unless the caller, host staging or LUDWIG_HALO_TRANSPORT says "torch" """
+    transport = transport or ("torch" if stage_through_host else os.environ.get("LUDWIG_HALO_TRANSPORT", "native"))
+    assert transport in ("native", "torch") and not (stage_through_host and transport == "native")
+    return transport
+
+
+def open_communicator(transport: str, comm, device: int):
+    """(transport, comm, own_comm): the native transport's communicator - the caller's, or one opened here (own_comm: the runner
+    destroys it; None with a single process) - and the transport that really runs."""
+    if transport != "native" or comm is not None:
+        return transport, comm, False
+    from . import _lib
+    try:
+        comm = native_comm(device)
+        return transport, comm, comm is not None
+    except _lib.LudwigError as e:
+        # the library could not bring up its own RCCL communicator (no librccl to resolve, ncclCommInitRank refused):
+        # the same exchange over the RCCL communicator torch.distributed already holds - said loudly, never silently
+        import sys
+        print(f"[ludwig] native RCCL communicator unavailable ({e}); halo exchange falls back to torch.distributed", file=sys.stderr, flush=True)
+        return "torch", None, False
+
+
+def exchange_stream(transport: str, dev, overlap: bool, s_comp):
+    """the stream TorchHalo exchanges on: a high-priority one under overlap (see init_rccl), else the compute stream; the native
+    transport needs none (every plan has its own)"""
+    if transport == "native":
+        return None
+    import torch
+    return torch.cuda.Stream(dev, priority=-1) if overlap else s_comp
+
+
+def make_halo(transport: str, plan: HaloPlan, level, rank: int, dev, comm, wire_rank: Optional[Dict[int, int]], stage_through_host: bool,
+              s_comp, s_comm):
+    """One level's exchanger: a NativeHalo, or a TorchHalo whose HaloExchanger packs and unpacks with the library's kernels on the
+    current stream (`level`: the DeviceLevel; None where the rank holds no block of it and the lists are empty)."""
+    if transport == "native":
+        return NativeHalo(plan, level, comm, wire_rank)
+    import ctypes as C
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    handle = level.handle if level is not None else None
+
+    def pack(name, idx, out):
+        _lib.check(lib.ludwig_halo_pack(handle, _lib.FIELD_NAMES[name], C.c_void_p(idx.data_ptr()), idx.numel(),
+                                        C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def unpack(name, idx, src):
+        _lib.check(lib.ludwig_halo_unpack(handle, _lib.FIELD_NAMES[name], C.c_void_p(idx.data_ptr()), idx.numel(),
+                                          C.c_void_p(src.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    hx = HaloExchanger(plan, rank, dev, pack, unpack, stage_through_host)
+    if wire_rank:
+        hx.wire_rank = dict(wire_rank)
+    return TorchHalo(hx, s_comp, s_comm)
+
+
+def _post_and_join_now(ex, fields: Dict[str, str], on_plan_stream: bool) -> None:
+    """an exchange whose result is needed at once (the f_post halo before the Bouzidi correction): nothing can run under it, so the
+    native transport queues it on the level's own stream - no hand-over to the plan's stream and back - unless `on_plan_stream`"""
+    if isinstance(ex, NativeHalo) and not ex.in_stream and not on_plan_stream:
+        ex.set_in_stream(True)           # (joins an exchange still in flight first)
+        try:
+            ex.post(fields)
+        finally:
+            ex.set_in_stream(False)
+        return
+    ex.post(fields)
+    ex.join()
+
+
+def step_level(L, ex, params, t_sub: int, parent, parent_tau, tw, u, stepping: bool, overlap: bool, has_children: bool,
+               lone_level_f_post: bool = False) -> None:
+    """One level step + its halo exchange (same-level ghosts and the parent-data ghosts of peers' finer blocks): the one Python
+    statement of the schedule (ludwig_step_distributed is the overlap order of a level without children, in C). `ex`: the level's
+    exchanger or None; `stepping`: the rank owns blocks of the level (else only ghost copies, refreshed by the exchange).
+    No overlap: whole-level launch, [f_post halo, Bouzidi correction], the exchange, waited for.
+    Overlap (the exchange runs on its own stream):
+      * a level WITH children: boundary part (every block a ghost or a peer depends on) first, then the exchange under the
+        interior part; the children start when both are done.
+      * a level nobody below reads, or one with Bouzidi cells: interior part first - its blocks have no ghost neighbour, so they
+        may run while the exchange of the PREVIOUS (sub-)step is still arriving - then the boundary part, which waits for it. The
+        correction rewrites f_out from the post-collision values of neighbour cells, so its small f_post halo (only the links
+        that reach across a cut) is exchanged in between and waited for. The f / u halo goes last; without children it is left
+        in flight under whatever comes next (the next step's interior part, or a coarser level's step).
+    lone_level_f_post: the one place where the two callers differ. MultiLevelRunner passes False: the f_post halo moves whenever
+    the plan has one, in the level's own stream (_post_and_join_now). DistributedLevelRunner passes True: it moves only where this
+    rank's level has post-collision storage, through post + join on the plan's stream."""
+    from .physics import apply_bouzidi_correction, stream_collide
+    fields = {"f": "f_temp", "vel": "vel_temp"} if t_sub % 2 == 0 else {"f": "f", "vel": "vel"}
+    has_post_halo = False
+    if ex is not None:
+        if ex.plan.has("rho"):
+            fields["rho"] = "rho"
+        has_post_halo = ex.plan.has("f_post")
+    bouzidi = stepping and L.has_post_collision
+    if lone_level_f_post:
+        has_post_halo = has_post_halo and bouzidi
+    if overlap and has_children and not bouzidi:
+        if ex is not None:
+            ex.join()
+        if stepping:
+            stream_collide(L, parent, parent_tau, u, params, t_sub, tw, part=PART_BOUNDARY)
+        if ex is not None:
+            ex.post(fields)                                  # waits for the boundary part only: the interior part runs under it
+        if stepping:
+            stream_collide(L, parent, parent_tau, u, params, t_sub, tw, part=PART_INTERIOR)
+        if ex is not None:
+            ex.join()                                        # children interpolate from this level's ghosts next
+        return
+    if not overlap:
+        if stepping:
+            stream_collide(L, parent, parent_tau, u, params, t_sub, tw, part=PART_ALL)
+    else:
+        if stepping:
+            stream_collide(L, parent, parent_tau, u, params, t_sub, tw, part=PART_INTERIOR)
+        if ex is not None:
+            ex.join()                                        # ghosts of this step's input are in place
+        if stepping:
+            stream_collide(L, parent, parent_tau, u, params, t_sub, tw, part=PART_BOUNDARY)
+    if has_post_halo:
+        _post_and_join_now(ex, {"f_post": "f_post_collision"}, lone_level_f_post)
+    if bouzidi:
+        apply_bouzidi_correction(L, t_sub, params.q_min_threshold)
+    if ex is not None:
+        ex.post(fields)
+        if has_children or not overlap:                      # under overlap a level nobody below reads leaves its exchange in flight
+            ex.join()
+
+
+def close_runner(runner, levels, dist=None, detach_streams: Optional[Callable] = None, final_sync: bool = False) -> None:
+    """Teardown of either runner in a fixed order: (1) everything queued has run, (2) the halo plans and the library's communicator
+    are destroyed, torch's wrappers of our streams and the events recorded on them dropped (`detach_streams`: what the runner does
+    to let go of streams of its own), (3) the process group is destroyed (pass torch.distributed as `dist` when this runner is the
+    last user of the default group), (4) [final_sync: the device is idle again,] the levels' device memory is freed; a stream the
+    runner created itself goes after that, in its own close(). Round 2 destroyed the stream first, under live ExternalStream
+    wrappers and a live communicator, and left the rest to interpreter shutdown: one profiled run ended in a SIGSEGV inside
+    __cxa_finalize (profiles/README.md)."""
+    import gc
+    runner.synchronize()
+    halos = runner.ex if isinstance(runner.ex, list) else [runner.ex]
+    for ex in halos:
+        if ex is not None:
+            ex.close()
+    runner.ex = [] if halos is runner.ex else None
+    halos = ex = None                    # the last references: the exchangers' buffers and stream wrappers go now, not at return
+    if runner._own_comm:
+        native_comm_destroy(runner.comm)
+    runner.comm = None
+    if detach_streams is not None:
+        detach_streams()
+    runner.s_comm = runner.s_comp = None
+    gc.collect()
+    if dist is not None and dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+    if final_sync:
+        runner.synchronize()
+    for lv in levels:
+        if lv is not None:
+            lv.close()
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # global topologies used by bench.py and the tests
 # ----------------------------------------------------------------------------------------------------------------
@@ -640,8 +824,7 @@ class DistributedLevelRunner:
         from . import order as order_mod
         self.torch, self._lib, self.C = torch, _lib, C
         self.view, self.params, self.overlap = view, params, overlap
-        self.transport = transport or ("torch" if stage_through_host else os.environ.get("LUDWIG_HALO_TRANSPORT", "native"))
-        assert self.transport in ("native", "torch") and not (stage_through_host and self.transport == "native")
+        self.transport = resolve_transport(transport, stage_through_host)
         torch.cuda.set_device(device)
         name_post_collision_readers(view.level, plan)
         self.level = adapt(view.level, device)
@@ -671,74 +854,24 @@ class DistributedLevelRunner:
                     items = order_mod.build(order, coords[ids])
                     items = np.where(items >= 0, (ids[np.maximum(items, 0) >> 3] << 3) | (items & 7), -1).astype(np.int32)
                     self.level.set_order(items, part)
-        lib = _lib.load()
-        handle = self.level.handle
-        self.comm, self._own_comm = comm, False
-        if self.transport == "native":
-            if self.comm is None:
-                try:
-                    self.comm = native_comm(device)
-                    self._own_comm = self.comm is not None
-                except _lib.LudwigError as e:
-                    # the library could not bring up its own RCCL communicator (no librccl to resolve, ncclCommInitRank refused):
-                    # the same exchange over the RCCL communicator torch.distributed already holds - said loudly, never silently
-                    import sys
-                    print(f"[ludwig] native RCCL communicator unavailable ({e}); halo exchange falls back to torch.distributed", file=sys.stderr, flush=True)
-                    self.transport = "torch"
-        if self.transport == "native":
-            self.ex = NativeHalo(plan, self.level, self.comm, wire_rank)
-            self.s_comm = None
-        else:
-            def pack(name, idx, out):
-                _lib.check(lib.ludwig_halo_pack(handle, _lib.FIELD_NAMES[name], C.c_void_p(idx.data_ptr()), idx.numel(),
-                                                C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
-
-            def unpack(name, idx, src):
-                _lib.check(lib.ludwig_halo_unpack(handle, _lib.FIELD_NAMES[name], C.c_void_p(idx.data_ptr()), idx.numel(),
-                                                  C.c_void_p(src.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
-
-            hx = HaloExchanger(plan, view.rank, self.dev, pack, unpack, stage_through_host)
-            if wire_rank:
-                hx.wire_rank = dict(wire_rank)
-            self.s_comm = torch.cuda.Stream(self.dev, priority=-1) if overlap else self.s_comp      # see init_rccl
-            self.ex = TorchHalo(hx, self.s_comp, self.s_comm)
+        self.transport, self.comm, self._own_comm = open_communicator(self.transport, comm, device)
+        self.s_comm = exchange_stream(self.transport, self.dev, overlap, self.s_comp)
+        self.ex = make_halo(self.transport, plan, self.level, view.rank, self.dev, self.comm, wire_rank, stage_through_host,
+                            self.s_comp, self.s_comm)
 
     def step(self, t: int, u_curr=0.0) -> None:
         """One step with the halo exchange hidden behind the NEXT step's interior blocks:
              compute stream : interior(t) | wait exchange(t-1) | boundary(t) | [f_post halo, Bouzidi correction(t)] |
              comm stream    :   exchange(t-1): pack, send/recv, unpack        |                                      exchange(t) ...
-        Interior blocks (no ghost neighbour) read and write owned cells only, so they may run while the ghosts of their input are
-        still arriving; the boundary blocks wait for them. Levels with Bouzidi cells follow the same schedule: the correction
-        rewrites f_out after the collision from the post-collision values of neighbour cells, so its small f_post halo (only the
-        links that reach across a cut) is exchanged in between and waited for, and the f / u halo goes last.
-        Native transport: all of it is ONE call into the library (ludwig_step_distributed)."""
-        from .physics import apply_bouzidi_correction, stream_collide
-        _lib = self._lib
-        out_f, out_v = ("f_temp", "vel_temp") if t % 2 == 0 else ("f", "vel")
-        if not self.overlap:
-            stream_collide(self.level, None, np.float32(0.5), u_curr, self.params, t, part=_lib.PART_ALL)
-            if self.level.has_post_collision:
-                if self.ex.plan.has("f_post"):
-                    self.ex.post({"f_post": "f_post_collision"})
-                    self.ex.join()
-                apply_bouzidi_correction(self.level, t, self.params.q_min_threshold)
-            self.ex.post({"f": out_f, "vel": out_v})
-            self.ex.join()
-            return
-        if self.transport == "native":
+        which is step_level's order for a level nobody below reads. Native transport: all of it is ONE call into the library
+        (ludwig_step_distributed); every other case is step_level itself."""
+        if self.overlap and self.transport == "native":
             fl = self.params.to_c()
-            _lib.check(_lib.load().ludwig_step_distributed(self.level.handle, self.ex.handle, None, int(t), float(np.float32(u_curr)), 0.5, 0.0,
-                                                           self.C.byref(fl)))
+            self._lib.check(self._lib.load().ludwig_step_distributed(self.level.handle, self.ex.handle, None, int(t), float(np.float32(u_curr)),
+                                                                     0.5, 0.0, self.C.byref(fl)))
             return
-        stream_collide(self.level, None, np.float32(0.5), u_curr, self.params, t, part=_lib.PART_INTERIOR)
-        self.ex.join()                                      # ghosts of this step's input are in place
-        stream_collide(self.level, None, np.float32(0.5), u_curr, self.params, t, part=_lib.PART_BOUNDARY)
-        if self.level.has_post_collision:
-            if self.ex.plan.has("f_post"):
-                self.ex.post({"f_post": "f_post_collision"})
-                self.ex.join()
-            apply_bouzidi_correction(self.level, t, self.params.q_min_threshold)
-        self.ex.post({"f": out_f, "vel": out_v})
+        step_level(self.level, self.ex, self.params, t, None, np.float32(0.5), 0.0, u_curr, stepping=True, overlap=self.overlap,
+                   has_children=False, lone_level_f_post=True)
 
     def exchange_now(self, f_name: str, vel_name: str) -> None:
         """refresh the ghosts of the two named fields and wait (set-up: ghosts of a start state)"""
@@ -753,28 +886,9 @@ class DistributedLevelRunner:
         self.torch.cuda.synchronize(self.dev)
 
     def close(self, dist=None) -> None:
-        """Teardown in a fixed order: (1) everything queued has run, (2) the halo plan and the library's communicator are destroyed,
-        torch's wrappers of our streams and the events recorded on them dropped, (3) the process group is destroyed (pass
-        torch.distributed as `dist` when this runner is the last user of the default group), (4) the level's device memory is
-        freed, (5) the CU-masked stream underneath is destroyed. Round 2 destroyed the stream first, under live ExternalStream
-        wrappers and a live communicator, and left the rest to interpreter shutdown: one profiled run ended in a SIGSEGV inside
-        __cxa_finalize (profiles/README.md)."""
-        import gc
-        self.synchronize()
-        self.ex.close()
-        self.ex = None
-        if self._own_comm:
-            native_comm_destroy(self.comm)
-        self.comm = None
-        self.level.set_stream(None)
-        self.s_comm = None
-        self.s_comp = None
-        gc.collect()
-        if dist is not None and dist.is_initialized():
-            dist.barrier()
-            dist.destroy_process_group()
-        self.torch.cuda.synchronize(self.dev)
-        self.level.close()
+        """close_runner's order; this runner's own are the level's stream (detached before its wrapper is dropped), a last synchronise
+        before the level is freed, and (5) the CU-masked stream underneath, destroyed last"""
+        close_runner(self, [self.level], dist, detach_streams=lambda: self.level.set_stream(None), final_sync=True)
         for ptr in self._own_streams:
             self._lib.check(self._lib.load().ludwig_stream_destroy(self.dev.index, self.C.c_void_p(ptr)))
         self._own_streams = []
@@ -786,10 +900,7 @@ def distributed_level(global_level: BlockLevel, owner: np.ndarray, params, rank:
     view = build_local_level(global_level.level_id, global_level.active_block_coords, global_level.neighbor_table, owner, rank,
                              float(global_level.tau), temporal=global_level.f_old.size > 27)
     slice_level_fields(view, global_level)
-    n_global = global_level.n_blocks
-    mine = make_requests(view, n_global)
-    to_me = exchange_requests(mine, world, rank) if world > 1 else {}
-    plan = build_plan(view, n_global, mine, to_me)
+    plan = plan_with_peers(view, global_level.n_blocks, None, world, rank)
     return DistributedLevelRunner(view, plan, params, device, overlap=overlap, stage_through_host=stage_through_host, transport=transport)
 
 
@@ -952,10 +1063,67 @@ def probe_needs(view: LocalView, n_global: int, cells: np.ndarray) -> Dict[str, 
     return {"rho": loc, "vel": np.concatenate([loc + k * sk for k in range(3)])}
 
 
+def plan_levels(grids: Sequence[BlockLevel], owners, params, rank: int, world: int, upload_state: bool = True,
+                probe_cells: Optional[Sequence[np.ndarray]] = None, requests_to_me: Optional[Callable] = None):
+    """Host side of MultiLevelRunner, no GPU needed: rank `rank`'s (views, plans) of nested levels, one of each per level, with the
+    levels' comm_boundary marks and post-collision readers set. `owners`, `upload_state`, `probe_cells`: as MultiLevelRunner takes
+    them. requests_to_me(level index, own requests): what the peers would ask, where the caller plays them (loop-back tests); else
+    the ranks shake hands over the default process group, level by level."""
+    dims = (params.domain_nx, params.domain_ny, params.domain_nz)
+    if isinstance(owners, np.ndarray):
+        owner1 = owners
+        owners = [owner1] + [ancestor_owner(g.level_id, g.active_block_coords, grids[0].active_block_coords, owner1) for g in grids[1:]]
+    assert len(owners) == len(grids)
+    # finest first: a level's ghost set includes the parent blocks this rank's finer blocks interpolate from
+    views: List[Optional[LocalView]] = [None] * len(grids)
+    for i in range(len(grids) - 1, -1, -1):
+        g = grids[i]
+        extra = None
+        if i + 1 < len(grids):
+            child_owned = np.flatnonzero(np.asarray(owners[i + 1]) == rank)
+            extra = required_parent_blocks(grids[i + 1], child_owned, g)
+        v = build_local_level(g.level_id, g.active_block_coords, g.neighbor_table, owners[i], rank, float(g.tau),
+                              temporal=g.f_old.size > 27, extra_ghosts=extra)
+        slice_level_fields(v, g, state=upload_state)
+        views[i] = v
+    # plans before any device level: which blocks of a level send anything is part of the level's description (comm_boundary)
+    plans: List[HaloPlan] = []
+    for i, (v, g) in enumerate(zip(views, grids)):
+        needs = compute_needs(v) if v.n_owned > 0 else {"f": np.zeros(0, np.int64), "vel": np.zeros(0, np.int64)}
+        needs.setdefault("f_post", np.zeros(0, np.int64))
+        needs.setdefault("rho", np.zeros(0, np.int64))
+        if i + 1 < len(grids) and views[i + 1].n_owned > 0:
+            extra = interpolation_needs(views[i + 1], v, dims)
+            for name in ("f", "rho", "vel"):
+                needs[name] = np.unique(np.concatenate([needs[name], extra[name]]))
+        if probe_cells is not None and len(probe_cells[i]):
+            extra = probe_needs(v, g.n_blocks, probe_cells[i])
+            for name in ("rho", "vel"):
+                needs[name] = np.unique(np.concatenate([needs[name], extra[name]]))
+        plan = plan_with_peers(v, g.n_blocks, needs, world, rank,
+                               None if requests_to_me is None else (lambda mine, i=i: requests_to_me(i, mine)))
+        plans.append(plan)
+        # "boundary" part = owned blocks next to a ghost block (they read ghosts) AND owned blocks any peer reads from (same-level
+        # halo, or parent data of a peer's finer blocks - those may lie anywhere): stepped first, so that the exchange can run
+        # under the remaining, interior blocks
+        if v.n_owned > 0:
+            sk = 512 * v.level.n_blocks
+            for pr in plan.peers:
+                for name in FIELD_GROUPS:
+                    off = plan.send[pr][name]
+                    if len(off):
+                        blk = (np.asarray(off, dtype=np.int64) % sk) // 512
+                        v.level.comm_boundary[blk[blk < v.n_owned]] = 1
+    for v, plan in zip(views, plans):
+        name_post_collision_readers(v.level, plan)
+    return views, plans
+
+
 class MultiLevelRunner:
     """Distributed recursive_step! (src/solver_control.jl:21-143) for nested levels: same call order and A/B parity as
     the single-device driver, plus after every level step the halo exchange of that level (same-level ghosts AND the
-    parent-data ghosts its children interpolate from), overlapped with compute on a second HIP stream (_step_level).
+    parent-data ghosts its children interpolate from), overlapped with compute on a second HIP stream (step_level).
+    The constructor is plan_levels (host only) plus the device bring-up.
 
     owners: one owner array per level (`level_owners`: every level cut on its own, the default of DistributedStepper), or a
     single level-1 array (whole hierarchies per rank: `balanced_owner` + `ancestor_owner`)."""
@@ -968,89 +1136,23 @@ class MultiLevelRunner:
         on the device right away (DistributedStepper: init_eq!); on the shipped Wing_5_deg that is 25 GB of zeros per rank otherwise.
         probe_cells: per level, the cells (global block id * 512 + cell) the probes and slice points this rank owns read; those in ghost
         blocks join the level's 'rho' and 'vel' halo (None: every plan as without probes and slices)"""
-        import ctypes as C
         import torch
-        from . import _lib
         from .blocks import adapt
         self.params, self.rank, self.world = params, rank, world
-        self.torch, self._lib = torch, _lib
-        dims = (params.domain_nx, params.domain_ny, params.domain_nz)
-        if isinstance(owners, np.ndarray):
-            owner1 = owners
-            owners = [owner1] + [ancestor_owner(g.level_id, g.active_block_coords, grids[0].active_block_coords, owner1) for g in grids[1:]]
-        assert len(owners) == len(grids)
-        # finest first: a level's ghost set includes the parent blocks this rank's finer blocks interpolate from
-        views: List[Optional[LocalView]] = [None] * len(grids)
-        for i in range(len(grids) - 1, -1, -1):
-            g = grids[i]
-            extra = None
-            if i + 1 < len(grids):
-                child_owned = np.flatnonzero(np.asarray(owners[i + 1]) == rank)
-                extra = required_parent_blocks(grids[i + 1], child_owned, g)
-            v = build_local_level(g.level_id, g.active_block_coords, g.neighbor_table, owners[i], rank, float(g.tau),
-                                  temporal=g.f_old.size > 27, extra_ghosts=extra)
-            slice_level_fields(v, g, state=upload_state)
-            views[i] = v
-        self.views = views
-        torch.cuda.set_device(device)
+        self.torch = torch
+        torch.cuda.set_device(device)            # (before the hand-shake: an object collective over nccl goes through the current device)
         self.dev = torch.device("cuda", device)
-        lib = _lib.load()
-        # plans first: which blocks of a level send anything is part of the level's description (comm_boundary)
-        plans: List[HaloPlan] = []
-        for i, (v, g) in enumerate(zip(self.views, grids)):
-            needs = compute_needs(v) if v.n_owned > 0 else {"f": np.zeros(0, np.int64), "vel": np.zeros(0, np.int64)}
-            needs.setdefault("f_post", np.zeros(0, np.int64))
-            needs.setdefault("rho", np.zeros(0, np.int64))
-            if i + 1 < len(grids) and self.views[i + 1].n_owned > 0:
-                extra = interpolation_needs(self.views[i + 1], v, dims)
-                for name in ("f", "rho", "vel"):
-                    needs[name] = np.unique(np.concatenate([needs[name], extra[name]]))
-            if probe_cells is not None and len(probe_cells[i]):
-                extra = probe_needs(v, g.n_blocks, probe_cells[i])
-                for name in ("rho", "vel"):
-                    needs[name] = np.unique(np.concatenate([needs[name], extra[name]]))
-            mine = make_requests(v, g.n_blocks, needs)
-            if requests_to_me is not None:          # loop-back tests: what the peers would ask, supplied by the caller (level index, own requests)
-                to_me = requests_to_me(i, mine)
-            else:
-                to_me = exchange_requests(mine, world, rank) if world > 1 else {}
-            plan = build_plan(v, g.n_blocks, mine, to_me)
-            plans.append(plan)
-            # "boundary" part = owned blocks next to a ghost block (they read ghosts) AND owned blocks any peer reads from (same-level
-            # halo, or parent data of a peer's finer blocks - those may lie anywhere): stepped first, so that the exchange can run
-            # under the remaining, interior blocks
-            if v.n_owned > 0:
-                sk = 512 * v.level.n_blocks
-                for pr in plan.peers:
-                    for name in FIELD_GROUPS:
-                        off = plan.send[pr][name]
-                        if len(off):
-                            blk = (np.asarray(off, dtype=np.int64) % sk) // 512
-                            v.level.comm_boundary[blk[blk < v.n_owned]] = 1
+        self.views, self.plans = plan_levels(grids, owners, params, rank, world, upload_state, probe_cells, requests_to_me)
         # no local copy at all of a level: None (skipped); only ghost copies (parent data for finer blocks): kept, never stepped
-        for v, plan in zip(self.views, plans):
-            name_post_collision_readers(v.level, plan)
         self.levels = [adapt(v.level, device, upload_state) if v.level.n_blocks > 0 else None for v in self.views]
-        self.plans = plans
         self.overlap = overlap
-        self.transport = transport or ("torch" if stage_through_host else os.environ.get("LUDWIG_HALO_TRANSPORT", "native"))
-        assert self.transport in ("native", "torch") and not (stage_through_host and self.transport == "native")
         self.s_comp = torch.cuda.current_stream(self.dev)
         for L in self.levels:
             if L is not None:
                 L.set_stream(self.s_comp.cuda_stream)
-        self.comm, self._own_comm = comm, False
-        self.ex: List = []
-        if self.transport == "native":
-            # RCCL called from the library (NativeHalo): every level's plan has its own high-priority stream; one communicator
-            if self.comm is None:
-                try:
-                    self.comm = native_comm(device)
-                    self._own_comm = self.comm is not None
-                except _lib.LudwigError as e:
-                    import sys
-                    print(f"[ludwig] native RCCL communicator unavailable ({e}); halo exchange falls back to torch.distributed", file=sys.stderr, flush=True)
-                    self.transport = "torch"
+        # native: RCCL called from the library (NativeHalo): every level's plan has its own high-priority stream; one communicator
+        self.transport, self.comm, self._own_comm = open_communicator(resolve_transport(transport, stage_through_host), comm, device)
+        self.s_comm = exchange_stream(self.transport, self.dev, overlap, self.s_comp)
         # per level: is hiding the exchange behind part of the level's own step worth two cross-stream hand-overs and two launches
         # instead of one? Only where a level step is long against them - nested levels take 2^(l-1) steps per coarse step, most of them
         # on levels of a few thousand blocks whose whole exchange is shorter than one hand-over (tools/multilevel_runner_host_cost.py).
@@ -1059,115 +1161,32 @@ class MultiLevelRunner:
         # one launch; a level this rank shares with nobody likewise. RCCL loop-back, two nested levels (profiles/
         # r03_nested_loopback_in_stream_ab.txt): 64 + 256 owned blocks 0.25 -> 0.17 ms per coarse step, 1 728 + 2 304 a wash.
         below = int(os.environ.get("LUDWIG_HALO_IN_STREAM_BELOW", "8192"))
-        self.level_overlap = [bool(overlap)] * len(plans)
-        if self.transport == "native":
-            for i, plan in enumerate(plans):
-                if self.levels[i] is None:
-                    assert not plan.peers, "a level without a local copy exchanges nothing"
-                    self.ex.append(None)
-                else:
-                    hx = NativeHalo(plan, self.levels[i], self.comm, wire_ranks[i] if wire_ranks else None)
-                    if overlap and (not plan.peers or self.views[i].n_owned < below):
-                        hx.set_in_stream(True)
-                        self.level_overlap[i] = False
-                    self.ex.append(hx)
-            self.s_comm = None
-        else:
-            self.s_comm = torch.cuda.Stream(self.dev, priority=-1) if overlap else self.s_comp      # see init_rccl
-            for i, plan in enumerate(plans):
-                handle = self.levels[i].handle if self.levels[i] is not None else None
+        self.level_overlap = [bool(overlap)] * len(self.plans)
+        self.ex: List = []
+        for i, plan in enumerate(self.plans):
+            if self.transport == "native" and self.levels[i] is None:
+                assert not plan.peers, "a level without a local copy exchanges nothing"
+                self.ex.append(None)
+                continue
+            hx = make_halo(self.transport, plan, self.levels[i], rank, self.dev, self.comm, wire_ranks[i] if wire_ranks else None,
+                           stage_through_host, self.s_comp, self.s_comm)
+            if self.transport == "native" and overlap and (not plan.peers or self.views[i].n_owned < below):
+                hx.set_in_stream(True)
+                self.level_overlap[i] = False
+            self.ex.append(hx)
 
-                def pack(name, idx, out, handle=handle):
-                    _lib.check(lib.ludwig_halo_pack(handle, _lib.FIELD_NAMES[name], C.c_void_p(idx.data_ptr()), idx.numel(),
-                                                    C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
-
-                def unpack(name, idx, src, handle=handle):
-                    _lib.check(lib.ludwig_halo_unpack(handle, _lib.FIELD_NAMES[name], C.c_void_p(idx.data_ptr()), idx.numel(),
-                                                      C.c_void_p(src.data_ptr()), C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
-
-                hx = HaloExchanger(plan, rank, self.dev, pack, unpack, stage_through_host)
-                if wire_ranks:
-                    hx.wire_rank = dict(wire_ranks[i])
-                self.ex.append(TorchHalo(hx, self.s_comp, self.s_comm))
-
-    def _join(self, i: int) -> None:
+    def join(self, i: int) -> None:
         """the compute stream waits for level i's exchange in flight (its ghosts are about to be read)"""
         if self.ex[i] is not None:
             self.ex[i].join()
 
-    def _post(self, i: int, fields: Dict[str, str]) -> None:
-        """level i's exchange, queued behind what the compute stream holds so far; what is launched afterwards runs under it"""
-        if self.ex[i] is not None:
-            self.ex[i].post(fields)
-
-    def _post_and_join_now(self, i: int, fields: Dict[str, str]) -> None:
-        """an exchange whose result is needed at once (the f_post halo before the Bouzidi correction): nothing can run under it, so the
-        native transport queues it on the level's own stream - no hand-over to the plan's stream and back"""
-        ex = self.ex[i]
-        if ex is None:
-            return
-        if isinstance(ex, NativeHalo) and not ex.in_stream:
-            ex.set_in_stream(True)           # (joins an exchange still in flight first)
-            try:
-                ex.post(fields)
-            finally:
-                ex.set_in_stream(False)
-            return
-        ex.post(fields)
-        ex.join()
-
     def _step_level(self, i: int, t_sub: int, parent, parent_tau, tw, u, has_children: bool) -> None:
-        """One level step + its halo exchange (same-level ghosts and the parent-data ghosts of peers' finer blocks).
-        Overlap (the exchange runs on its own stream):
-          * a level WITH children: boundary part (every block a ghost or a peer depends on) first, then the exchange under the
-            interior part; the children start when both are done.
-          * the finest level (nobody below reads its ghosts): interior part first - it reads no ghost - while the exchange of
-            its PREVIOUS sub-step is still arriving, then the boundary part, [f_post halo, Bouzidi correction], and its own
-            exchange is left in flight under whatever comes next (the next sub-step's interior part, or a coarser level's step)."""
-        from .physics import apply_bouzidi_correction, stream_collide
-        _lib = self._lib
-        L, ex = self.levels[i], self.ex[i]
-        stepping = self.views[i].n_owned > 0                 # else: only ghost copies here, refreshed by the exchange below
-        out_f, out_v = ("f_temp", "vel_temp") if t_sub % 2 == 0 else ("f", "vel")
-        fields = {"f": out_f, "vel": out_v}
-        plan = ex.plan if ex is not None else None
-        if plan is not None and plan.has("rho"):
-            fields["rho"] = "rho"
-        has_post_halo = plan is not None and plan.has("f_post")
+        """step_level for level i, once the parent's ghosts (interpolation stencils) are in place; the rank steps the level where it
+        owns blocks of it, else it holds only ghost copies, refreshed by the exchange"""
         if i > 0:
-            self._join(i - 1)                                # the parent's ghosts (interpolation stencils) must be in place
-        if not self.level_overlap[i]:
-            if stepping:
-                stream_collide(L, parent, parent_tau, u, self.params, t_sub, tw, part=_lib.PART_ALL)
-            if has_post_halo:
-                self._post_and_join_now(i, {"f_post": "f_post_collision"})
-            if stepping and L.has_post_collision:
-                apply_bouzidi_correction(L, t_sub, self.params.q_min_threshold)
-            self._post(i, fields)
-            self._join(i)
-            return
-        bouzidi = stepping and L.has_post_collision
-        if has_children and not bouzidi:
-            self._join(i)
-            if stepping:
-                stream_collide(L, parent, parent_tau, u, self.params, t_sub, tw, part=_lib.PART_BOUNDARY)
-            self._post(i, fields)                            # waits for the boundary part only: the interior part runs under it
-            if stepping:
-                stream_collide(L, parent, parent_tau, u, self.params, t_sub, tw, part=_lib.PART_INTERIOR)
-            self._join(i)                                    # children interpolate from this level's ghosts next
-            return
-        if stepping:
-            stream_collide(L, parent, parent_tau, u, self.params, t_sub, tw, part=_lib.PART_INTERIOR)
-        self._join(i)
-        if stepping:
-            stream_collide(L, parent, parent_tau, u, self.params, t_sub, tw, part=_lib.PART_BOUNDARY)
-        if has_post_halo:
-            self._post_and_join_now(i, {"f_post": "f_post_collision"})
-        if bouzidi:
-            apply_bouzidi_correction(L, t_sub, self.params.q_min_threshold)
-        self._post(i, fields)
-        if has_children:
-            self._join(i)
+            self.join(i - 1)
+        step_level(self.levels[i], self.ex[i], self.params, t_sub, parent, parent_tau, tw, u, self.views[i].n_owned > 0,
+                   self.level_overlap[i], has_children)
 
     def _rec(self, lvl: int, t_sub: int, parent, parent_tau, tw, u) -> None:
         if lvl > len(self.levels):
@@ -1176,7 +1195,7 @@ class MultiLevelRunner:
         has_children = lvl < len(self.levels)
         if L is not None:
             if has_children and self.params.use_temporal_interp and L.has_temporal_storage:
-                self._join(lvl - 1)
+                self.join(lvl - 1)
                 L.copy_to_old(t_sub)
             self._step_level(lvl - 1, t_sub, parent, parent_tau, tw, u, has_children)
         if has_children:
@@ -1193,26 +1212,10 @@ class MultiLevelRunner:
         self.torch.cuda.synchronize(self.dev)
 
     def close(self, dist=None) -> None:
-        """same order as DistributedLevelRunner.close: device idle, plans and communicator gone, process group gone, levels freed"""
-        import gc
+        """close_runner's order; a second call does nothing"""
         if not self.levels and not self.ex:
             return
-        self.synchronize()
-        for ex in self.ex:
-            if ex is not None:
-                ex.close()
-        self.ex = []
-        if self._own_comm:
-            native_comm_destroy(self.comm)
-        self.comm = None
-        self.s_comm = None
-        gc.collect()
-        if dist is not None and dist.is_initialized():
-            dist.barrier()
-            dist.destroy_process_group()
-        for lv in self.levels:
-            if lv is not None:
-                lv.close()
+        close_runner(self, self.levels, dist)
         self.levels = []
 
 
@@ -1262,9 +1265,7 @@ def periodic_box_plan(rank: int, world: int, nb_per_rank: Tuple[int, int, int], 
     params = SolverParams(domain_nx=8 * nbg[0], domain_ny=8 * nbg[1], domain_nz=8 * nbg[2], wall_model_active=False, c_wale=0.5,
                           nu_sgs_bg=0.0005, inlet_turbulence=0.0, use_temporal_interp=False, sponge_blend_dist=False)
     n_global = len(coords)
-    mine = make_requests(view, n_global)
-    to_me = exchange_requests(mine, world, rank) if world > 1 else ({rank: mine[rank]} if rank in mine else {})
-    plan = build_plan(view, n_global, mine, to_me)
+    plan = plan_with_peers(view, n_global, None, world, rank, self_requests=True)
     return view, plan, params, n_global
 
 

@@ -9,6 +9,11 @@ from open_ludwig_amd.physics import SolverParams
 from oracle import oracle
 
 
+def _asked_of(reqs, r):
+    """the in-process hand-shake: what every rank's requests (reqs[q]: peer -> lists) ask of rank r"""
+    return {q: reqs[q][r] for q in range(len(reqs)) if r in reqs[q]}
+
+
 def _run_partitioned(nbg, world, steps, grid=None):
     grid = grid or partition.rank_grid(world)
     coords, table, owner = partition.periodic_box_topology(nbg, grid)
@@ -20,8 +25,7 @@ def _run_partitioned(nbg, world, steps, grid=None):
     reqs = [partition.make_requests(v, n_global) for v in views]
     plans = []
     for r, v in enumerate(views):
-        to_me = {q: reqs[q][r] for q in range(world) if r in reqs[q]}
-        plans.append(partition.build_plan(v, n_global, reqs[r], to_me))
+        plans.append(partition.build_plan(v, n_global, reqs[r], _asked_of(reqs, r)))
     for t in range(1, steps + 1):
         for v in views:
             oracle.execute_timestep_batch([v.level], t, 1, np.float32(0.0), params)
@@ -299,3 +303,57 @@ def test_post_collision_readers_are_the_f_post_send_lists():
             assert len(p.send[q]["f_post"]) == len(plans[q].recv[r]["f_post"])
         total += readers.size
     assert total > 0, "no link reaches across the cut: the case does not exercise the readers"
+
+
+def test_plan_levels_plans_every_rank_of_a_nest_without_a_device():
+    """partition.plan_levels, the host half of MultiLevelRunner, for every rank of a two-level tunnel with each level cut on its own.
+    The hand-shake is played in-process through requests_to_me: a first pass collects every rank's requests, the second answers
+    them. For every level and pair of ranks, what r sends to q has the length q expects from r; and each plan's bytes_per_step() is
+    what a walk that uses neither the runner nor plan_levels gives: 4 bytes for every element of r's blocks another rank needs -
+    its same-level needs (compute_needs) and the parent data of its finer blocks (interpolation_needs), owner by owner."""
+    world = 2
+    grids, params = cases.tunnel_with_sphere((6, 4, 4), levels=2, wall_model=False, temporal=True)
+    dims = (params.domain_nx, params.domain_ny, params.domain_nz)
+    owners = partition.level_owners(grids, world)
+    asked = [[None] * world for _ in grids]                # asked[i][q]: rank q's requests on level i
+
+    def collect(q):
+        def requests_to_me(i, mine):
+            asked[i][q] = mine
+            return {}
+        return requests_to_me
+
+    for q in range(world):
+        partition.plan_levels(grids, owners, params, q, world, requests_to_me=collect(q))
+    got = [partition.plan_levels(grids, owners, params, r, world, requests_to_me=lambda i, mine, r=r: _asked_of(asked[i], r))
+           for r in range(world)]
+    # the independent walk: sent[i][r] = elements of level i other ranks need from rank r
+    sent = np.zeros((len(grids), world), dtype=np.int64)
+    for q in range(world):
+        views = [None] * len(grids)
+        for i in (1, 0):
+            g = grids[i]
+            extra = partition.required_parent_blocks(grids[1], np.flatnonzero(owners[1] == q), g) if i == 0 else None
+            views[i] = partition.build_local_level(g.level_id, g.active_block_coords, g.neighbor_table, owners[i], q, float(g.tau),
+                                                   temporal=True, extra_ghosts=extra)
+            partition.slice_level_fields(views[i], g, state=False)      # (the f_post needs follow the sphere's links)
+        for i, v in enumerate(views):
+            needs = [partition.compute_needs(v)] if v.n_owned > 0 else []
+            if i == 0 and views[1].n_owned > 0:
+                needs.append(partition.interpolation_needs(views[1], v, dims))
+            for name in partition.FIELD_GROUPS:
+                off = np.unique(np.concatenate([n.get(name, np.zeros(0, np.int64)) for n in needs] + [np.zeros(0, np.int64)]))
+                blk = (off % (v.level.n_blocks * 512)) // 512
+                assert (blk >= v.n_owned).all(), "a need inside an owned block"
+                sent[i] += np.bincount(v.ghost_owner[blk - v.n_owned], minlength=world)
+    total = 0
+    for i in range(len(grids)):
+        for r in range(world):
+            views_r, plans_r = got[r]
+            assert views_r[i].rank == r and plans_r[i].bytes_per_step() == 4 * sent[i][r], (i, r)
+            for q in plans_r[i].peers:
+                for name in partition.FIELD_GROUPS:
+                    assert len(plans_r[i].send[q][name]) == len(got[q][1][i].recv[r][name]), (i, r, q, name)
+            total += plans_r[i].bytes_per_step()
+        assert sent[i].sum() > 0, f"level {i + 1} is not cut: nothing to plan"
+    assert total > 0
