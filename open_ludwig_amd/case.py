@@ -857,7 +857,7 @@ class DistributedStepper:
                                                       mesh.normals[sel], g.tau, params)
         part = np.zeros(10, dtype=np.float32)
         part[:9] = forces_mod.partial_force_sums(mesh, p, tx, ty, tz, params, select=sel)
-        part[9] = np.count_nonzero(np.abs(p) > 1e-10)
+        part[9] = forces_mod.coverage_count(p)
         total, cov = forces_mod.combine_partial_sums(part, self._comm_device())      # fixed order: rank 0, 1, ...
         fr = forces_mod.finish_forces(total, cov, params, symmetric)
         if want_maps:                          # output steps only: per-triangle loads to rank 0 for the surface VTU

@@ -2815,7 +2815,8 @@ __global__ __launch_bounds__(256) void k_monitor_combine(MonitorRecord *__restri
 // sampled coarse step) ----
 // Triangle i reads cell[i] (internal block * 512 + cell, -1: none) and rec = [8][n] floats: wall distance, normal x, y, z, area, arm x,
 // y, z. Per triangle, float32 with -ffp-contract=off: p, tau from wall_stress (zeros without a cell), dFp_j = ((-p) n_j) A,
-// dFv_j = tau_j A, dF = dFp + dFv, dM = arm x dF in the operand order of forces.partial_force_sums; covered = |p| > 1e-10f. The nine
+// dFv_j = tau_j A, dF = dFp + dFv, dM = arm x dF in the operand order of forces.partial_force_sums; covered = (double)|p| > 1e-10,
+// the reference's Float64 comparison (src/forces/surface.jl:430: float32(1e-10) itself counts). The nine
 // values are widened to double and summed in ONE balanced tree over the triangles in the caller's order: adjacent pairs halved, +0.0
 // where a length is odd, and no addition once one value is left - the tree over the triangles padded with +0.0 to the next power of
 // two (forces.tree_sum_f64). A level of the tree that joins nodes of `half` elements adds iff count > half: below that the right-hand
@@ -2862,7 +2863,7 @@ __device__ __forceinline__ bool force_contributions(float c[9], int64_t i, int64
     c[3] = sx * A; c[4] = sy * A; c[5] = sz * A;
     const float fx = c[0] + c[3], fy = c[1] + c[4], fz = c[2] + c[5];
     c[6] = ry * fz - rz * fy; c[7] = rz * fx - rx * fz; c[8] = rx * fy - ry * fx;
-    return fabsf(p) > 1.0e-10f;
+    return (double)fabsf(p) > 1.0e-10;
 }
 
 // The four waves of a workgroup through LDS: a.s = every wave's node, count = its integer count -> the caller's lane 0 (true) holds

@@ -9,7 +9,8 @@ Semantics ("Force series"):
     forces.csv's always-`vel` buffer; on a nested case the finest level ends on an odd sub-step and the two coincide - and from them
     the nine Float32 contributions of forces.force_series_contributions, in the operand order of forces.partial_force_sums.
   * The contributions are widened to Float64 and added in one fixed balanced tree over the triangles in the caller's order
-    (forces.tree_sum_f64, the monitor's tree); the coverage count |p| > 1e-10 is an integer sum. One record = 9 Float64 + 1 Int64:
+    (forces.tree_sum_f64, the monitor's tree); the coverage count, |p| widened to Float64 > 1e-10
+    (forces.coverage_count), is an integer sum. One record = 9 Float64 + 1 Int64:
     forces.record_of(force_series_contributions(...)) restates the device kernels bit for bit.
   * Sampled coarse steps: start_step + k interval. Records wait in a device ring of `capacity` until they are downloaded.
   * Symmetry doubling and the coefficients stay on the host: forces.finish_forces on the Float64 sums.

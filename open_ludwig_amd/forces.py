@@ -202,7 +202,7 @@ def moment_arms(mesh, params, select=None) -> np.ndarray:
 
 def force_series_contributions(mesh, p, tau_x, tau_y, tau_z, params, select=None) -> Tuple[np.ndarray, int]:
     """What every triangle adds to the nine sums of partial_force_sums, with its expressions and operand order: Float32 [n, 9] =
-    dFp(3), dFv(3), dM(3), and the coverage count |p| > 1e-10 of integrate_surface_forces. One record of the device force series
+    dFp(3), dFv(3), dM(3), and the coverage count (coverage_count) of integrate_surface_forces. One record of the device force series
     (k_force_chunks / k_force_combine) is tree_sum_f64 of every column widened to Float64, bit for bit."""
     nrm = mesh.normals.astype(np.float32)
     A = mesh.areas.astype(np.float32)
@@ -215,7 +215,14 @@ def force_series_contributions(mesh, p, tau_x, tau_y, tau_z, params, select=None
     dF = dFp + dFv
     dM = np.stack([ry * dF[:, 2] - rz * dF[:, 1], rz * dF[:, 0] - rx * dF[:, 2], rx * dF[:, 1] - ry * dF[:, 0]], axis=1)
     out = np.concatenate([dFp, dFv, dM], axis=1).astype(np.float32)
-    return out, int(np.count_nonzero(np.abs(p) > f32(1e-10)))
+    return out, coverage_count(p)
+
+
+def coverage_count(p) -> int:
+    """count(x -> abs(x) > 1e-10, p) of src/forces/surface.jl:430: the Float32 pressure is widened and compared with the Float64
+    literal, as Julia promotes it. float32(1e-10) is 1.00000001335e-10, so a comparison in Float32 (which numpy makes when a Float32
+    array meets a Python float) leaves out the one value |p| == float32(1e-10) that the reference counts."""
+    return int(np.count_nonzero(np.abs(np.asarray(p, dtype=np.float32)).astype(np.float64) > 1e-10))
 
 
 def record_of(contributions: np.ndarray) -> np.ndarray:
@@ -266,7 +273,7 @@ def combine_partial_sums(part: np.ndarray, comm_device=None):
 
 def integrate_surface_forces(mesh, p, tau_x, tau_y, tau_z, params, symmetric: bool = False) -> ForceResult:
     sums = partial_force_sums(mesh, p, tau_x, tau_y, tau_z, params)
-    return finish_forces(sums, int(np.count_nonzero(np.abs(p) > 1e-10)), params, symmetric)
+    return finish_forces(sums, coverage_count(p), params, symmetric)
 
 
 def compute_aerodynamics(mesh, level_host, rho, vel, params, symmetric: bool = False, search_radius: int = 5) -> ForceResult:
