@@ -255,6 +255,43 @@ def _interface_parent_cells(geom, k, cells, dims, ptr):
     return out
 
 
+def bouzidi_arm(T, level, geom, params, post, f_out, br=None):
+    """apply_bouzidi_correction! (src/bouzidi_kernel.jl:29-91) in the working type T: corrects f_out in place from the post-collision
+    state `post`, ORs the branch bits into br (if given) and returns the cells whose post-collision state was read. The one statement of
+    the arm: _level_step calls it, and so does the device test of the correction alone (tests/test_gpu_setup_reference.py)."""
+    shape = post.shape[:4]
+    if br is None:
+        br = np.zeros(shape, dtype=np.uint16)
+    cb = np.asarray(level.bouzidi_cell_block).astype(np.int64) - 1
+    x, y, z = (np.asarray(a).astype(np.int64) - 1 for a in (level.bouzidi_cell_x, level.bouzidi_cell_y, level.bouzidi_cell_z))
+    q_min = np.float32(params.q_min_threshold)
+    q_all = np.asarray(level.bouzidi_q_map)[x, y, z, cb, :].astype(np.float32)
+    read = np.zeros(shape, dtype=bool)
+    for k in range(27):
+        q32 = q_all[:, k]
+        ok = (q32 > q_min) & (q32 <= np.float32(1))
+        br[x, y, z, cb] |= np.where(ok, np.uint16(BZ_IN_RANGE), np.uint16(0))
+        br[x, y, z, cb] |= np.where(~ok & (q32 != 0), np.uint16(BZ_OUT_OF_RANGE), np.uint16(0))
+        if not ok.any():
+            continue
+        xs, ys, zs, bs, q = x[ok], y[ok], z[ok], cb[ok], q32[ok].astype(T)
+        f_k = post[xs, ys, zs, bs, k]
+        read[xs, ys, zs, bs] = True
+        ix, iy, iz, blk, present = geom.neighbour(C_K[OPP[k]])
+        ix, iy, iz = (np.broadcast_to(a, shape)[xs, ys, zs, bs] for a in (ix, iy, iz))
+        blk, present = blk[xs, ys, zs, bs], present[xs, ys, zs, bs]
+        low = q < T(0.5)
+        behind = np.where(present, post[ix, iy, iz, blk, k], f_k)
+        read[ix[low & present], iy[low & present], iz[low & present], blk[low & present]] = True
+        near_wall = T(2) * q * f_k + (T(1) - T(2) * q) * behind
+        inv = T(1) / (T(2) * q)
+        far_wall = inv * f_k + (T(2) * q - T(1)) * inv * post[xs, ys, zs, bs, OPP[k]]
+        f_out[xs, ys, zs, bs, OPP[k]] = np.where(low, near_wall, far_wall)
+        br[xs, ys, zs, bs] |= np.where(low, np.uint16(BZ_LT_HALF), np.uint16(BZ_GE_HALF))
+        br[xs, ys, zs, bs] |= np.where(low & ~present, np.uint16(BZ_NO_BEHIND), np.uint16(0))
+    return read
+
+
 def _level_step(T, level, geom, st, f_in_name, f_out_name, vel_in_name, vel_out_name, parent: Optional[_Parent], t_sub, weight, u_curr, params):
     """perform_timestep_v2! for one level: stream-collide, then Bouzidi. Returns the branch record [8,8,8,nb] uint16."""
     nb = level.n_blocks
@@ -404,36 +441,7 @@ def _level_step(T, level, geom, st, f_in_name, f_out_name, vel_in_name, vel_out_
 
     # ---- Bouzidi ----
     if store_post:
-        post = st["f_post_collision"]
-        f_out = st[f_out_name]
-        cb = np.asarray(level.bouzidi_cell_block).astype(np.int64) - 1
-        x, y, z = (np.asarray(a).astype(np.int64) - 1 for a in (level.bouzidi_cell_x, level.bouzidi_cell_y, level.bouzidi_cell_z))
-        q_min = np.float32(params.q_min_threshold)
-        q_all = np.asarray(level.bouzidi_q_map)[x, y, z, cb, :].astype(np.float32)
-        read = np.zeros(shape, dtype=bool)
-        for k in range(27):
-            q32 = q_all[:, k]
-            ok = (q32 > q_min) & (q32 <= np.float32(1))
-            br[x, y, z, cb] |= np.where(ok, np.uint16(BZ_IN_RANGE), np.uint16(0))
-            br[x, y, z, cb] |= np.where(~ok & (q32 != 0), np.uint16(BZ_OUT_OF_RANGE), np.uint16(0))
-            if not ok.any():
-                continue
-            xs, ys, zs, bs, q = x[ok], y[ok], z[ok], cb[ok], q32[ok].astype(T)
-            f_k = post[xs, ys, zs, bs, k]
-            read[xs, ys, zs, bs] = True
-            ix, iy, iz, blk, present = geom.neighbour(C_K[OPP[k]])
-            ix, iy, iz = (np.broadcast_to(a, shape)[xs, ys, zs, bs] for a in (ix, iy, iz))
-            blk, present = blk[xs, ys, zs, bs], present[xs, ys, zs, bs]
-            low = q < T(0.5)
-            behind = np.where(present, post[ix, iy, iz, blk, k], f_k)
-            read[ix[low & present], iy[low & present], iz[low & present], blk[low & present]] = True
-            near_wall = T(2) * q * f_k + (T(1) - T(2) * q) * behind
-            inv = T(1) / (T(2) * q)
-            far_wall = inv * f_k + (T(2) * q - T(1)) * inv * post[xs, ys, zs, bs, OPP[k]]
-            f_out[xs, ys, zs, bs, OPP[k]] = np.where(low, near_wall, far_wall)
-            br[xs, ys, zs, bs] |= np.where(low, np.uint16(BZ_LT_HALF), np.uint16(BZ_GE_HALF))
-            br[xs, ys, zs, bs] |= np.where(low & ~present, np.uint16(BZ_NO_BEHIND), np.uint16(0))
-        st["post_read"] = read
+        st["post_read"] = bouzidi_arm(T, level, geom, params, st["f_post_collision"], st[f_out_name], br)
     return br
 
 
