@@ -1072,6 +1072,27 @@ def flow_stats(rho: np.ndarray, obstacle: np.ndarray) -> float:
     return float(rho[~obstacle].min())
 
 
+def _refuse_device_only(st, cfg: CaseConfig) -> None:
+    """RuntimeError, naming the key and the missing method, for the first enabled feature that needs a method this stepper lacks"""
+    eddy_on = "EddyViscosityRatio" in cfg.output_fields
+    for on, key, method, what in (
+            (cfg.initial_condition_state, "advanced.initial_condition is set", "init_from", "a level is filled from a state file"),
+            (cfg.fourier_modes_enabled, "advanced.fourier_modes is enabled", "modes_setup", "the Fourier modes are accumulated"),
+            (cfg.wall_diagnostics_enabled, "advanced.wall_diagnostics is enabled", "wall_diagnostics_setup",
+             "the wall diagnostics are evaluated"),
+            (eddy_on or cfg.statistics_subgrid,
+             ("basic.simulation.output_fields.eddy_viscosity" if eddy_on else "advanced.statistics.subgrid") + " is set", "subgrid_fields",
+             "the subgrid model's eddy viscosity is evaluated"),
+            (cfg.forces_series_enabled, "advanced.forces.series is enabled", "force_series_setup", "the force series is reduced")):
+        if on and not hasattr(st, method):
+            raise RuntimeError(f"{key}, but {type(st).__name__} offers no {method}: {what} on the device only")
+
+
+def _every(start_step: int, interval: int):
+    """steps_in(t, batch_end) of a cut schedule: the coarse steps start_step + k interval of a batch"""
+    return lambda t, batch_end: stats_mod.sample_steps(t, batch_end, start_step, interval)
+
+
 def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Optional[int] = None, stl_path: Optional[str] = None,
              log: Optional[Callable[[str], None]] = None, setup=None, out_dir: Optional[str] = None, write_files: bool = True):
     """solve_main (src/main.jl:54-249). Returns (rows, setup_report, params).
@@ -1148,29 +1169,43 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
     from . import output as out_mod
     grids, mesh, params, report = setup if setup is not None else setup_multilevel_domain(cfg, stl_path)
     sp = solver_params(cfg, params)
-    probes_on = bool(cfg.probes_enabled)
-    # points are refused (outside the domain, inside the body) before anything is allocated on a device
+    writing = out_dir is not None and write_files
+    fin = len(grids) - 1
+    probes_on, slices_on, iso_on, stream_on = cfg.probes_enabled, cfg.slices_enabled, cfg.isosurfaces_enabled, cfg.streamlines_enabled
+    render_on, tracers_on, flux_on, modes_on = cfg.render_enabled, cfg.tracers_enabled, cfg.flux_planes_enabled, cfg.fourier_modes_enabled
+    surf_on, wall_on, fseries_on, monitor_on = (cfg.surface_statistics_enabled, cfg.wall_diagnostics_enabled, cfg.forces_series_enabled,
+                                                cfg.flow_monitor_enabled)
+    stats_on, subgrid_on, eddy_on = cfg.statistics_enabled, cfg.statistics_subgrid, "EddyViscosityRatio" in cfg.output_fields
+    # probe points outside the domain or inside the body, a slice or flux plane outside the domain and a frequency the sampling cannot
+    # resolve are refused before anything is allocated on a device
     pplan = probes_mod.plan_probes(cfg.probes_points, grids, params.mesh_offset, cfg.probes_names) if probes_on else None
-    slices_on = bool(cfg.slices_enabled)
-    sl_start, sl_interval = cfg.slices_start_step, cfg.slices_interval
-    # a plane outside the domain is refused before anything is allocated on a device
     splans = [slices_mod.plan_slice(spec, grids, params.mesh_offset) for spec in cfg.slices_planes] if slices_on else []
-    # a flux plane outside the domain is refused before anything is allocated on a device
-    fplans = [flux_mod.plan_flux_plane(spec, grids, params.mesh_offset) for spec in cfg.flux_planes_planes] if cfg.flux_planes_enabled else []
-    modes_on = bool(cfg.fourier_modes_enabled)
-    # a frequency the sampling cannot resolve is refused before anything is allocated on a device
+    fplans = [flux_mod.plan_flux_plane(spec, grids, params.mesh_offset) for spec in cfg.flux_planes_planes] if flux_on else []
     mplan = modes_mod.plan_modes(cfg, params, log) if modes_on else None
     st = stepper_factory(grids)
-    ic_on = bool(cfg.initial_condition_state)
-    first_step = int(cfg.initial_condition_first_step) if ic_on else 1
-    state_on = bool(cfg.state_files_enabled) and out_dir is not None and write_files
-    try:
+    try:                                 # whatever fails from here on, the stepper is closed once
+        _refuse_device_only(st, cfg)     # they depend on cfg and the stepper's type alone: a refused run allocates nothing
+        first_step = int(cfg.initial_condition_first_step) if cfg.initial_condition_state else 1
+        total_steps = first_step - 1 + (steps if steps is not None else cfg.steps)
+        batch = cfg.async_depth
+
+        def begin_csv(name, *header):
+            """start out_dir's file `name` with its header line(s); nothing when this run writes no files"""
+            if writing:
+                with open(os.path.join(out_dir, name), "w") as io:
+                    io.writelines(l + "\n" for l in header)
+
+        def append_csv(name, lines):
+            """append lines to out_dir's file `name`; nothing when this run writes no files (a generator is then not run) or has no lines"""
+            lines = list(lines) if writing else []
+            if lines:
+                with open(os.path.join(out_dir, name), "a") as io:
+                    io.writelines(l + "\n" for l in lines)
+
+        # ---- set-up: the stepper's calls in a fixed order (the surface statistics before the two observers that share their plan) ----
         if cfg.state_files_enabled and hasattr(st, "state_files_setup"):
             st.state_files_setup()               # the distributed stepper refuses
-        if ic_on:
-            if not hasattr(st, "init_from"):
-                raise RuntimeError(f"advanced.initial_condition is set, but {type(st).__name__} offers no init_from: a level is filled "
-                                   "from a state file on the device only")
+        if cfg.initial_condition_state:
             ic_state = warm_mod.load_state(warm_mod.resolve_state_path(cfg.initial_condition_state, cfg.case_dir))
             ic_scale = cfg.initial_condition_velocity_scale
             if ic_scale is None:                 # auto: both runs' flows at their own lattice speed
@@ -1183,557 +1218,484 @@ def run_case(cfg: CaseConfig, stepper_factory: Callable = HipStepper, steps: Opt
                     "equilibrium")
                 for g, c in zip(grids, ic_counts):
                     log(warm_mod.counts_line(g.level_id, c))
-    except Exception:
-        if hasattr(st, "close"):
-            st.close()
-        raise
-    if modes_on and not hasattr(st, "modes_setup"):
-        if hasattr(st, "close"):
-            st.close()
-        raise RuntimeError(f"advanced.fourier_modes is enabled, but {type(st).__name__} offers no modes_setup: the Fourier modes are "
-                           "accumulated on the device only")
-    iso_on = bool(cfg.isosurfaces_enabled)
-    iso_start, iso_interval = cfg.isosurfaces_start_step, cfg.isosurfaces_interval
-    if iso_on and hasattr(st, "isosurfaces_setup"):
-        try:
-            st.isosurfaces_setup(iso_start, iso_interval)
-        except Exception:
-            if hasattr(st, "close"):
-                st.close()
-            raise
-    stream_on = bool(cfg.streamlines_enabled)
-    stream_start, stream_interval = cfg.streamlines_start_step, cfg.streamlines_interval
-    if stream_on:
-        stream_plan = stream_mod.SeedPlan([(s.name, np.asarray(s.points, dtype=np.float64)) for s in cfg.streamlines_seeds],
-                                          cfg.streamlines_direction, params.mesh_offset, grids[0].dx)
-        if hasattr(st, "streamlines_setup"):
-            try:
-                st.streamlines_setup(stream_plan.seeds, stream_plan.sign, cfg.streamlines_step, cfg.streamlines_min_speed,
-                                     cfg.streamlines_max_steps, stream_start, stream_interval)
-            except Exception:
-                if hasattr(st, "close"):
-                    st.close()
-                raise
-    render_on = bool(cfg.render_enabled)
-    rd_start, rd_interval = cfg.render_start_step, cfg.render_interval
-    if render_on:
-        render_plans = [render_mod.ViewPlan(v, cfg.render_width, cfg.render_height, params.mesh_offset, grids[0].dx) for v in cfg.render_views]
-        if hasattr(st, "render_setup"):
-            try:
-                st.render_setup(cfg.render_max_pixels, rd_start, rd_interval)
-            except Exception:
-                if hasattr(st, "close"):
-                    st.close()
-                raise
-    tracers_on = bool(cfg.tracers_enabled)
-    tr_start, tr_interval, tr_out = cfg.tracers_start_step, cfg.tracers_interval, cfg.tracers_output_interval
-    tr_host = None                       # the host fallback (a stepper without tracers_setup)
-    if tracers_on:
-        tr_plan = tracer_mod.TracerPlan([(s.name, np.asarray(s.points, dtype=np.float64)) for s in cfg.tracers_seeds], params.mesh_offset,
-                                        grids[0].dx)
-        if hasattr(st, "tracers_setup"):
-            try:
-                st.tracers_setup(tr_plan.seeds, cfg.tracers_generations, cfg.tracers_release_every, tr_start, tr_interval)
-            except Exception:
-                if hasattr(st, "close"):
-                    st.close()
-                raise
-        else:
-            tr_host = tracer_mod.HostTracers(tr_plan.seeds, cfg.tracers_generations, cfg.tracers_release_every, tr_interval)
-        warn = tracer_mod.jump_warning(tr_interval, float(cfg.u_lattice), len(grids))
-        if warn and log:
-            log(warn)
-    flux_on = bool(cfg.flux_planes_enabled)
-    fx_start, fx_interval = cfg.flux_planes_start_step, cfg.flux_planes_interval
-    dev_fluxes = flux_on and hasattr(st, "flux_planes_setup")      # else the host fallback from downloaded fields
-    if dev_fluxes:
-        try:
-            st.flux_planes_setup(fplans, fx_start, fx_interval, max(cfg.async_depth, 1))
-        except Exception:
-            if hasattr(st, "close"):
-                st.close()
-            raise
-    if flux_on and cfg.flux_planes_boxes and cfg.symmetric_analysis and log:
-        log("flux planes: symmetric_analysis is on; the control-volume force of a box is that of the modelled half, not doubled")
-    wall_on = bool(cfg.wall_diagnostics_enabled)
-    if wall_on and not hasattr(st, "wall_diagnostics_setup"):
-        if hasattr(st, "close"):
-            st.close()
-        raise RuntimeError(f"advanced.wall_diagnostics is enabled, but {type(st).__name__} offers no wall_diagnostics_setup: the wall "
-                           "diagnostics are evaluated on the device only")
-    eddy_on = "EddyViscosityRatio" in cfg.output_fields
-    subgrid_on = bool(cfg.statistics_subgrid)
-    if (eddy_on or subgrid_on) and not hasattr(st, "subgrid_fields"):
-        if hasattr(st, "close"):
-            st.close()
-        key = "basic.simulation.output_fields.eddy_viscosity" if eddy_on else "advanced.statistics.subgrid"
-        raise RuntimeError(f"{key} is set, but {type(st).__name__} offers no subgrid_fields: the subgrid model's eddy viscosity is "
-                           "evaluated on the device only")
-    fseries_on = bool(cfg.forces_series_enabled)
-    if fseries_on and not hasattr(st, "force_series_setup"):
-        if hasattr(st, "close"):
-            st.close()
-        raise RuntimeError(f"advanced.forces.series is enabled, but {type(st).__name__} offers no force_series_setup: the force series "
-                           "is reduced on the device only")
-    total_steps = first_step - 1 + (steps if steps is not None else cfg.steps)
-    rows: List[DiagRow] = []
-    batch = cfg.async_depth
-    t = first_step
-    writing = out_dir is not None and write_files
-    if probes_on:
-        st.probes_setup(pplan, cfg.probes_start_step, cfg.probes_interval, max(batch, 1))
-    dev_slices = slices_on and hasattr(st, "slices_setup")
-    if dev_slices:
-        st.slices_setup(splans, sl_start, sl_interval)
-    surf_on = bool(cfg.surface_statistics_enabled)
-    surf_start, surf_interval = cfg.surface_statistics_start_step, cfg.surface_statistics_interval
-    fin = len(grids) - 1
-    surf_host = None                     # the host fallback (a stepper without surface_stats_setup)
-    if surf_on:
-        if hasattr(st, "surface_stats_setup"):
-            splan = st.surface_stats_setup(mesh, params, surf_start, surf_interval)
-        else:
-            splan = surface_mod.plan_surface(mesh, grids[fin], params)
-            surf_host = surface_mod.HostSurfaceStats(splan, grids[fin].tau, params, surf_start, surf_interval)
-    if wall_on:
-        st.wall_diagnostics_setup(mesh, params, splan if surf_on else None)      # one plan for both surface observers
-    if fseries_on:                       # after the surface statistics: one plan for both
-        st.force_series_setup(mesh, params, cfg.forces_series_start_step, cfg.forces_series_interval, max(batch, 1))
-    if modes_on:
-        st.modes_setup(mplan.W, mplan.start_step, mplan.interval)
-    wall_band = cfg.wall_diagnostics_band
-    wall_taken = [None, None]            # the coarse step of the last wall-surface values, and the values
-    if writing:
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "convergence.csv"), "w") as io:
-            io.write(out_mod.CONVERGENCE_CSV_HEADER + "\n")
-        if cfg.forces_enabled:
-            out_mod.write_force_csv_header(os.path.join(out_dir, "forces.csv"))
-        if surf_on:
-            with open(os.path.join(out_dir, "forces_mean.csv"), "w") as io:
-                io.write(surface_mod.FORCES_MEAN_CSV_HEADER + "\n")
-        if fseries_on:
-            with open(os.path.join(out_dir, "forces_series.csv"), "w") as io:
-                io.write(fseries_mod.csv_header() + "\n")
-        if flux_on:
-            with open(os.path.join(out_dir, "fluxes.csv"), "w") as io:
-                io.write(flux_mod.FLUXES_CSV_HEADER + "\n")
-            if cfg.flux_planes_boxes:
-                with open(os.path.join(out_dir, "flux_boxes.csv"), "w") as io:
-                    io.write(flux_mod.BOXES_CSV_COMMENT + "\n" + flux_mod.BOXES_CSV_HEADER + "\n")
-        if modes_on:
-            with open(os.path.join(out_dir, "flow_modes.csv"), "w") as io:
-                io.write(modes_mod.CSV_HEADER + "\n")
-        if slices_on:
-            slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
+        if iso_on and hasattr(st, "isosurfaces_setup"):
+            st.isosurfaces_setup(cfg.isosurfaces_start_step, cfg.isosurfaces_interval)
         if stream_on:
-            stream_writer = stream_mod.StreamlineWriter(out_dir, stream_plan, params.time_scale)
+            stream_plan = stream_mod.SeedPlan([(s.name, np.asarray(s.points, dtype=np.float64)) for s in cfg.streamlines_seeds],
+                                              cfg.streamlines_direction, params.mesh_offset, grids[0].dx)
+            if hasattr(st, "streamlines_setup"):
+                st.streamlines_setup(stream_plan.seeds, stream_plan.sign, cfg.streamlines_step, cfg.streamlines_min_speed,
+                                     cfg.streamlines_max_steps, cfg.streamlines_start_step, cfg.streamlines_interval)
+        if render_on:
+            render_plans = [render_mod.ViewPlan(v, cfg.render_width, cfg.render_height, params.mesh_offset, grids[0].dx)
+                            for v in cfg.render_views]
+            if hasattr(st, "render_setup"):
+                st.render_setup(cfg.render_max_pixels, cfg.render_start_step, cfg.render_interval)
+        tr_start, tr_interval = cfg.tracers_start_step, cfg.tracers_interval
+        tr_host = None                       # the host fallback (a stepper without tracers_setup)
         if tracers_on:
-            tracer_writer = tracer_mod.TracerWriter(out_dir, tr_plan, params.time_scale, cfg.tracers_generations, cfg.tracers_release_every,
-                                                    tr_start, tr_interval)
-        if iso_on:
-            iso_writer = iso_mod.IsoWriter(out_dir, [s.name for s in cfg.isosurfaces_surfaces], params.time_scale)
-        if probes_on:
-            probes_mod.write_points_csv(os.path.join(out_dir, "probes_points.csv"), pplan, grids)
-            with open(os.path.join(out_dir, "probes.csv"), "w") as io:
-                io.write(probes_mod.series_csv_header(pplan.names) + "\n")
-        if cfg.flow_monitor_enabled:
-            with open(os.path.join(out_dir, "flow_monitor.csv"), "w") as io:
-                io.write(monitor_mod.CSV_HEADER + "\n")
-        if wall_on:
-            with open(os.path.join(out_dir, "wall_model.csv"), "w") as io:
-                io.write(wall_mod.wall_model_csv_header(cfg.y_plus_target, wall_band) + "\n")
-            with open(os.path.join(out_dir, "wall_forces.csv"), "w") as io:
-                io.write(wall_mod.WALL_FORCES_CSV_HEADER + "\n")
-    probes_written = [0]
-
-    def take_monitor(step, state_step):
-        """a record of every level from the state after coarse step state_step; rows and warnings out; the first diverged level's
-        FlowDiverged or None (collective in a distributed run)"""
-        diverged = None
-        for lvl, g in enumerate(grids):
-            if hasattr(st, "monitor"):
-                rec = st.monitor(lvl, state_step)
+            tr_plan = tracer_mod.TracerPlan([(s.name, np.asarray(s.points, dtype=np.float64)) for s in cfg.tracers_seeds],
+                                            params.mesh_offset, grids[0].dx)
+            if hasattr(st, "tracers_setup"):
+                st.tracers_setup(tr_plan.seeds, cfg.tracers_generations, cfg.tracers_release_every, tr_start, tr_interval)
             else:
-                vel_name = "vel_temp" if stats_mod.t_sub_after(lvl, state_step) % 2 == 0 else "vel"
-                rho_l, vel_l = st.field(lvl, "rho"), st.field(lvl, vel_name)
-                rec = monitor_mod.host_monitor(rho_l, vel_l, g.obstacle, g.active_block_coords) if rho_l is not None else None
-            if rec is None:
-                continue
-            if writing:
-                with open(os.path.join(out_dir, "flow_monitor.csv"), "a") as io:
-                    io.write(monitor_mod.csv_row(step, state_step, g.level_id, rec, g.dx, params.mesh_offset) + "\n")
-            if log:
-                for line in monitor_mod.warnings_of(rec, step, g.level_id, g.dx, params.mesh_offset):
-                    log(line)
-            if rec.n_bad > 0 and diverged is None:
-                diverged = monitor_mod.FlowDiverged(step, g.level_id, rec.first_bad,
-                                                    monitor_mod.cell_coordinates(rec.first_bad, g.dx, params.mesh_offset), rec.n_bad)
-        return diverged
-
-    if iso_on:
-        iso_skips = iso_mod.skip_flags(grids)
-        iso_boxes = {s.name: [iso_mod.cell_box(s.bounds, g.dx, params.mesh_offset) for g in grids] for s in cfg.isosurfaces_surfaces}
-
-    def take_isosurfaces(step):
-        """every surface from the state after coarse step `step`, levels merged in ascending order; files out"""
-        cap = int(cfg.isosurfaces_max_triangles)
-        for spec in cfg.isosurfaces_surfaces:
-            boxes = iso_boxes[spec.name]
-            if hasattr(st, "isosurface"):
-                parts, total, refused = [], 0, False
-                for li, g in enumerate(grids):
-                    if iso_skips[li].all():
-                        continue
-                    # once the cap is passed the remaining levels are only counted
-                    n, pos, att, keys = st.isosurface(li, spec.field, spec.value, step, iso_skips[li], boxes[li][0], boxes[li][1],
-                                                      0 if refused else cap - total)
-                    total += n
-                    if pos is None:
-                        refused = True
-                    else:
-                        parts.append((li, g.dx, pos, att, keys))
-            else:
-                parts = iso_mod.host_extract_levels(st, grids, spec.field, spec.value, step, boxes, iso_skips)
-                total = sum(p[2].shape[0] for p in parts)
-                refused = total > cap
-            if refused:
-                if log:
-                    log(f"isosurface {spec.name!r}: step {step}: {total} triangles, more than advanced.isosurfaces.max_triangles = {cap}; "
-                        "no file written")
-            elif writing:
-                iso_writer.write(step, spec.name, iso_mod.merge_levels(parts))
-
-    def take_streamlines(step):
-        """every group's lines through the state after coarse step `step`; files out, one log line per group"""
-        if hasattr(st, "streamlines"):
-            counts, codes, records = st.streamlines(step)
-        else:
-            counts, codes, records = stream_mod.trace_host(stream_mod.stepper_levels(st, grids, step), stream_plan.seeds, stream_plan.sign,
-                                                           cfg.streamlines_step, cfg.streamlines_min_speed, cfg.streamlines_max_steps)
-        if writing:
-            stream_writer.write(step, counts, codes, records)
-        if log:
-            for gi, name in enumerate(stream_plan.names):
-                log(f"streamlines {name!r}: step {step}: {stream_mod.summary(stream_plan, gi, counts, codes)}")
-
-    def take_render(step):
-        """every view of the state after coarse step `step`; files out, one log line per image"""
-        for plan in render_plans:
-            rgba, codes, samples = st.render(plan, step) if hasattr(st, "render") else render_mod.host_image(st, grids, plan, step)
-            if writing:
-                render_mod.write_png(os.path.join(out_dir, render_mod.render_file_name(plan.name, step)), render_mod.quantise(rgba))
-            if log:
-                log(f"render {plan.name!r}: step {step}: {render_mod.summary(codes, samples)}")
-
-    def take_tracers(step):
-        """the advance of the host fallback behind coarse step `step`, and at a snapshot step the snapshot: files out, one log line
-        per group"""
-        levels = tracer_mod.stepper_levels(st, grids, step) if tr_host is not None else None
-        if tr_host is not None:
-            tr_host.advance(levels)
-        if not stats_mod.is_sample_step(step, tr_start, tr_out):
-            return
-        rec, n_adv = (tr_host.snapshot(levels), tr_host.n_advances) if tr_host is not None else st.tracers_snapshot(step)
-        if writing:
-            tracer_writer.write(step, rec, n_adv)
-        if log:
-            for gi, name in enumerate(tr_plan.names):
-                log(f"tracers {name!r}: step {step}: {tracer_mod.summary(tr_plan, gi, rec, cfg.tracers_generations)}")
-
-    def wall_values(state_step):
-        """the wall-surface values of the state after coarse step state_step, evaluated once per step (collective in a distributed run)"""
-        if wall_taken[0] != state_step:
-            wall_taken[:] = [state_step, st.wall_surface_values(state_step)]
-        return wall_taken[1]
-
-    def take_wall(step, state_step):
-        """a census of every level (with the wall model on) and the modelled surface loads from the state after coarse step state_step;
-        rows out (collective in a distributed run)"""
-        if sp.wall_model_active:
-            for lvl, g in enumerate(grids):
-                rec = st.wall_census(lvl, state_step)
-                if writing and rec is not None:
-                    with open(os.path.join(out_dir, "wall_model.csv"), "a") as io:
-                        io.write(wall_mod.wall_model_csv_row(step, g.level_id, rec, wall_band) + "\n")
-        vals = wall_values(state_step)
-        if writing and vals is not None:
-            fr_model = wall_mod.model_forces(mesh, vals, params, cfg.symmetric_analysis)
-            with open(os.path.join(out_dir, "wall_forces.csv"), "a") as io:
-                io.write(wall_mod.wall_forces_csv_row(step, mesh, vals, fr_model) + "\n")
-
-    def flush_probes():
-        """append the samples not yet in probes.csv (collective in a distributed run)"""
-        series = st.probes_series()
-        if writing and series is not None:
-            p_steps, p_vals = series
-            new_rows = probes_mod.series_csv_rows(p_steps[probes_written[0]:], p_vals[probes_written[0]:], params.time_scale)
-            with open(os.path.join(out_dir, "probes.csv"), "a") as io:
-                io.writelines(r + "\n" for r in new_rows)
-            probes_written[0] = p_steps.size
-    fseries_coeffs = []                  # (Cd, Cl, Cmy) of the rows after the ramp
-
-    def flush_force_series(u_batch):
-        """append the records the batch that has just ended drained - only those leave the stepper - to forces_series.csv (collective in a
-        distributed run)"""
-        series = st.force_series_new()
-        if series is None:
-            return
-        f_steps, f_sums, f_cov = series
-        lines = []
-        for i in range(f_steps.size):
-            fr_i = forces_mod.finish_forces(f_sums[i], int(f_cov[i]), params, cfg.symmetric_analysis)
-            lines.append(fseries_mod.csv_row(int(f_steps[i]), float(f_steps[i]) * params.time_scale, fr_i, u_batch))
-            if f_steps[i] > cfg.ramp_steps:
-                fseries_coeffs.append((fr_i.Cd, fr_i.Cl, fr_i.Cmy))
-        if writing and lines:
-            with open(os.path.join(out_dir, "forces_series.csv"), "a") as io:
-                io.writelines(l + "\n" for l in lines)
-    flux_host = []                       # the host fallback's samples of the batch: (step, sums, counts)
-    flux_box_cd = {}                     # box name -> Cd of the rows after the ramp
-
-    def flush_fluxes():
-        """append the samples the batch that has just ended took to fluxes.csv and flux_boxes.csv"""
+                tr_host = tracer_mod.HostTracers(tr_plan.seeds, cfg.tracers_generations, cfg.tracers_release_every, tr_interval)
+            warn = tracer_mod.jump_warning(tr_interval, float(cfg.u_lattice), len(grids))
+            if warn and log:
+                log(warn)
+        dev_fluxes = flux_on and hasattr(st, "flux_planes_setup")      # else the host fallback from downloaded fields
         if dev_fluxes:
-            f_steps, f_sums, f_counts = st.flux_planes_new()
-        else:
-            f_steps = np.array([s for s, _, _ in flux_host], dtype=np.int64)
-            f_sums, f_counts = [a for _, a, _ in flux_host], [c for _, _, c in flux_host]
-            flux_host.clear()
-        plane_rows, box_rows, box_values = flux_mod.csv_rows(fplans, cfg.flux_planes_boxes, f_steps, f_sums, f_counts, params)
-        for step, name, b in box_values:
-            if step > cfg.ramp_steps:
-                flux_box_cd.setdefault(name, []).append(b.Cd)
-        if writing and plane_rows:
-            with open(os.path.join(out_dir, "fluxes.csv"), "a") as io:
-                io.writelines(l + "\n" for l in plane_rows)
-        if writing and box_rows:
-            with open(os.path.join(out_dir, "flux_boxes.csv"), "a") as io:
-                io.writelines(l + "\n" for l in box_rows)
-    modes_live = [modes_on]              # False once a window has ended without `repeat`
+            st.flux_planes_setup(fplans, cfg.flux_planes_start_step, cfg.flux_planes_interval, max(batch, 1))
+        if flux_on and cfg.flux_planes_boxes and cfg.symmetric_analysis and log:
+            log("flux planes: symmetric_analysis is on; the control-volume force of a box is that of the modelled half, not doubled")
+        if probes_on:
+            st.probes_setup(pplan, cfg.probes_start_step, cfg.probes_interval, max(batch, 1))
+        dev_slices = slices_on and hasattr(st, "slices_setup")
+        if dev_slices:
+            st.slices_setup(splans, cfg.slices_start_step, cfg.slices_interval)
+        surf_start, surf_interval = cfg.surface_statistics_start_step, cfg.surface_statistics_interval
+        surf_host = None                     # the host fallback (a stepper without surface_stats_setup)
+        if surf_on:
+            if hasattr(st, "surface_stats_setup"):
+                splan = st.surface_stats_setup(mesh, params, surf_start, surf_interval)
+            else:
+                splan = surface_mod.plan_surface(mesh, grids[fin], params)
+                surf_host = surface_mod.HostSurfaceStats(splan, grids[fin].tau, params, surf_start, surf_interval)
+        if wall_on:
+            st.wall_diagnostics_setup(mesh, params, splan if surf_on else None)      # one plan for both surface observers
+        if fseries_on:                       # after the surface statistics: one plan for both
+            st.force_series_setup(mesh, params, cfg.forces_series_start_step, cfg.forces_series_interval, max(batch, 1))
+        if modes_on:
+            st.modes_setup(mplan.W, mplan.start_step, mplan.interval)
+        state_on = bool(cfg.state_files_enabled) and writing
+        wall_band = cfg.wall_diagnostics_band
 
-    def take_modes(step):
-        """the window that ends with coarse step `step`: sums down, files out, then the reset for the next window (collective in a
-        distributed run)"""
-        first = step - (mplan.samples - 1) * mplan.interval
-        finals = {}
-        for lvl in range(len(grids)):
-            got = st.modes_sums(lvl)                                                                  # collective
-            if got is None:
-                continue
-            if got[1] != mplan.samples:
-                raise RuntimeError(f"fourier modes: level {lvl + 1} holds {got[1]} samples at step {step}, the window has {mplan.samples}")
-            finals[lvl] = modes_mod.finalize(np.stack(got[0]), mplan.W)
-        if writing and finals:
-            out_mod.export_modes_mesh(step, grids, finals.__getitem__, (first, step, mplan.samples, mplan.interval), mplan.frequencies_hz,
-                                      out_dir)
-            with open(os.path.join(out_dir, "flow_modes.csv"), "a") as io:
-                for k in range(mplan.n_modes):
-                    for lvl, g in enumerate(grids):
-                        io.write(modes_mod.csv_row(mplan, first, step, k, g.level_id,
-                                                   *modes_mod.level_energy(finals[lvl][1][k], g.obstacle)) + "\n")
-        if log:
-            log(f"fourier modes: window of steps {first}..{step} ({mplan.samples} samples) written at step {step}")
-        if mplan.repeat:
-            st.modes_reset()
-        else:
-            modes_live[0] = False
-            if st.modes is not None:
-                st.modes.close()
-                st.modes = None
-    t0 = last_diag = _time.time()
-    total_cells = sum(g.n_blocks * 512 for g in grids)
-    fr = None
-    stats_on = bool(cfg.statistics_enabled)
-    stats_window = [0, 0, 0]             # samples, first and last sampled step
-    # derived flow arrays on output steps: (VTU name, index into gradient_fields' result, components)
-    grad_names = [g for g in (("Vorticity", 0, 3), ("QCriterion", 1, 1)) if g[0] in cfg.output_fields]
-    monitor_on = bool(cfg.flow_monitor_enabled)
-    diverged = None
-    try:
+        # ---- the files this run starts ----
+        if writing:
+            os.makedirs(out_dir, exist_ok=True)
+            if cfg.forces_enabled:
+                out_mod.write_force_csv_header(os.path.join(out_dir, "forces.csv"))
+            if slices_on:
+                slice_writer = slices_mod.SliceWriter(out_dir, splans, params.time_scale)
+            if stream_on:
+                stream_writer = stream_mod.StreamlineWriter(out_dir, stream_plan, params.time_scale)
+            if tracers_on:
+                tracer_writer = tracer_mod.TracerWriter(out_dir, tr_plan, params.time_scale, cfg.tracers_generations,
+                                                        cfg.tracers_release_every, tr_start, tr_interval)
+            if iso_on:
+                iso_writer = iso_mod.IsoWriter(out_dir, [s.name for s in cfg.isosurfaces_surfaces], params.time_scale)
+            if probes_on:
+                probes_mod.write_points_csv(os.path.join(out_dir, "probes_points.csv"), pplan, grids)
+                begin_csv("probes.csv", probes_mod.series_csv_header(pplan.names))
+            begin_csv("convergence.csv", out_mod.CONVERGENCE_CSV_HEADER)
+            if surf_on:
+                begin_csv("forces_mean.csv", surface_mod.FORCES_MEAN_CSV_HEADER)
+            if fseries_on:
+                begin_csv("forces_series.csv", fseries_mod.csv_header())
+            if flux_on:
+                begin_csv("fluxes.csv", flux_mod.FLUXES_CSV_HEADER)
+            if flux_on and cfg.flux_planes_boxes:
+                begin_csv("flux_boxes.csv", flux_mod.BOXES_CSV_COMMENT, flux_mod.BOXES_CSV_HEADER)
+            if modes_on:
+                begin_csv("flow_modes.csv", modes_mod.CSV_HEADER)
+            if monitor_on:
+                begin_csv("flow_monitor.csv", monitor_mod.CSV_HEADER)
+            if wall_on:
+                begin_csv("wall_model.csv", wall_mod.wall_model_csv_header(cfg.y_plus_target, wall_band))
+                begin_csv("wall_forces.csv", wall_mod.WALL_FORCES_CSV_HEADER)
+
+        # ---- what is taken at a diagnostics step, from the state at batch end ----
+        def take_monitor(step, state_step):
+            """a record of every level from the state after coarse step state_step; rows and warnings out; the first diverged level's
+            FlowDiverged or None (collective in a distributed run)"""
+            diverged = None
+            for lvl, g in enumerate(grids):
+                if hasattr(st, "monitor"):
+                    rec = st.monitor(lvl, state_step)
+                else:
+                    vel_name = "vel_temp" if stats_mod.t_sub_after(lvl, state_step) % 2 == 0 else "vel"
+                    rho_l, vel_l = st.field(lvl, "rho"), st.field(lvl, vel_name)
+                    rec = monitor_mod.host_monitor(rho_l, vel_l, g.obstacle, g.active_block_coords) if rho_l is not None else None
+                if rec is None:
+                    continue
+                if writing:
+                    append_csv("flow_monitor.csv", [monitor_mod.csv_row(step, state_step, g.level_id, rec, g.dx, params.mesh_offset)])
+                if log:
+                    for line in monitor_mod.warnings_of(rec, step, g.level_id, g.dx, params.mesh_offset):
+                        log(line)
+                if rec.n_bad > 0 and diverged is None:
+                    diverged = monitor_mod.FlowDiverged(step, g.level_id, rec.first_bad,
+                                                        monitor_mod.cell_coordinates(rec.first_bad, g.dx, params.mesh_offset), rec.n_bad)
+            return diverged
+        wall_taken = [None, None]            # the coarse step of the last wall-surface values, and the values
+
+        def wall_values(state_step):
+            """the wall-surface values of the state after coarse step state_step, evaluated once per step (collective in a distributed run)"""
+            if wall_taken[0] != state_step:
+                wall_taken[:] = [state_step, st.wall_surface_values(state_step)]
+            return wall_taken[1]
+
+        def take_wall(step, state_step):
+            """a census of every level (with the wall model on) and the modelled surface loads from the state after coarse step
+            state_step; rows out (collective in a distributed run)"""
+            if sp.wall_model_active:
+                for lvl, g in enumerate(grids):
+                    rec = st.wall_census(lvl, state_step)
+                    if writing and rec is not None:
+                        append_csv("wall_model.csv", [wall_mod.wall_model_csv_row(step, g.level_id, rec, wall_band)])
+            vals = wall_values(state_step)
+            if writing and vals is not None:
+                fr_model = wall_mod.model_forces(mesh, vals, params, cfg.symmetric_analysis)
+                append_csv("wall_forces.csv", [wall_mod.wall_forces_csv_row(step, mesh, vals, fr_model)])
+        probes_written = [0]
+
+        def flush_probes():
+            """append the samples not yet in probes.csv (collective in a distributed run)"""
+            series = st.probes_series()
+            if writing and series is not None:
+                p_steps, p_vals = series
+                append_csv("probes.csv", probes_mod.series_csv_rows(p_steps[probes_written[0]:], p_vals[probes_written[0]:], params.time_scale))
+                probes_written[0] = p_steps.size
+
+        # ---- what is drained after every batch ----
+        fseries_coeffs = []                  # (Cd, Cl, Cmy) of the rows after the ramp
+
+        def flush_force_series(u_batch):
+            """append the records the batch that has just ended drained - only those leave the stepper - to forces_series.csv (collective
+            in a distributed run)"""
+            series = st.force_series_new()
+            if series is None:
+                return
+            f_steps, f_sums, f_cov = series
+            lines = []
+            for i in range(f_steps.size):
+                fr_i = forces_mod.finish_forces(f_sums[i], int(f_cov[i]), params, cfg.symmetric_analysis)
+                lines.append(fseries_mod.csv_row(int(f_steps[i]), float(f_steps[i]) * params.time_scale, fr_i, u_batch))
+                if f_steps[i] > cfg.ramp_steps:
+                    fseries_coeffs.append((fr_i.Cd, fr_i.Cl, fr_i.Cmy))
+            append_csv("forces_series.csv", lines)
+        flux_host = []                       # the host fallback's samples of the batch: (step, sums, counts)
+        flux_box_cd = {}                     # box name -> Cd of the rows after the ramp
+
+        def flush_fluxes():
+            """append the samples the batch that has just ended took to fluxes.csv and flux_boxes.csv"""
+            if dev_fluxes:
+                f_steps, f_sums, f_counts = st.flux_planes_new()
+            else:
+                f_steps = np.array([s for s, _, _ in flux_host], dtype=np.int64)
+                f_sums, f_counts = [a for _, a, _ in flux_host], [c for _, _, c in flux_host]
+                flux_host.clear()
+            plane_rows, box_rows, box_values = flux_mod.csv_rows(fplans, cfg.flux_planes_boxes, f_steps, f_sums, f_counts, params)
+            for step, name, b in box_values:
+                if step > cfg.ramp_steps:
+                    flux_box_cd.setdefault(name, []).append(b.Cd)
+            append_csv("fluxes.csv", plane_rows)
+            append_csv("flux_boxes.csv", box_rows)
+
+        # ---- what is taken at a cut: each take(step) acts on the state after coarse step `step` ----
+        stats_window = [0, 0, 0]             # samples, first and last sampled step
+
+        def take_statistics(step):
+            """a sample of the flow statistics, and of the subgrid model's sums with them; start_step resets both"""
+            if step == cfg.statistics_start_step:
+                st.stats_reset()
+                if subgrid_on:
+                    st.subgrid_stats_reset()
+                stats_window[:] = [0, step, step]
+            st.stats_sample(step)
+            if subgrid_on:
+                st.subgrid_stats_sample(step)
+            stats_window[0] += 1
+            stats_window[2] = step
+
+        def take_surface_host(step):
+            """a sample of the host fallback's surface statistics from downloaded fields"""
+            t_sub = stats_mod.t_sub_after(fin, step)
+            surf_host.accumulate(st.field(fin, "rho"), st.field(fin, "vel_temp" if t_sub % 2 == 0 else "vel"))
+
+        def take_slices(step):
+            """every plane; files out"""
+            got = st.slices_sample(step) if dev_slices else slices_mod.host_sample(st, splans, grids, step)
+            if writing:
+                slice_writer.write(step, got)
+        if iso_on:
+            iso_skips = iso_mod.skip_flags(grids)
+            iso_boxes = {s.name: [iso_mod.cell_box(s.bounds, g.dx, params.mesh_offset) for g in grids] for s in cfg.isosurfaces_surfaces}
+
+        def take_isosurfaces(step):
+            """every surface, levels merged in ascending order; files out"""
+            cap = int(cfg.isosurfaces_max_triangles)
+            for spec in cfg.isosurfaces_surfaces:
+                boxes = iso_boxes[spec.name]
+                if hasattr(st, "isosurface"):
+                    parts, total, refused = [], 0, False
+                    for li, g in enumerate(grids):
+                        if iso_skips[li].all():
+                            continue
+                        # once the cap is passed the remaining levels are only counted
+                        n, pos, att, keys = st.isosurface(li, spec.field, spec.value, step, iso_skips[li], boxes[li][0], boxes[li][1],
+                                                          0 if refused else cap - total)
+                        total += n
+                        if pos is None:
+                            refused = True
+                        else:
+                            parts.append((li, g.dx, pos, att, keys))
+                else:
+                    parts = iso_mod.host_extract_levels(st, grids, spec.field, spec.value, step, boxes, iso_skips)
+                    total = sum(p[2].shape[0] for p in parts)
+                    refused = total > cap
+                if refused:
+                    if log:
+                        log(f"isosurface {spec.name!r}: step {step}: {total} triangles, more than advanced.isosurfaces.max_triangles = "
+                            f"{cap}; no file written")
+                elif writing:
+                    iso_writer.write(step, spec.name, iso_mod.merge_levels(parts))
+
+        def take_streamlines(step):
+            """every group's lines; files out, one log line per group"""
+            if hasattr(st, "streamlines"):
+                counts, codes, records = st.streamlines(step)
+            else:
+                counts, codes, records = stream_mod.trace_host(stream_mod.stepper_levels(st, grids, step), stream_plan.seeds,
+                                                               stream_plan.sign, cfg.streamlines_step, cfg.streamlines_min_speed,
+                                                               cfg.streamlines_max_steps)
+            if writing:
+                stream_writer.write(step, counts, codes, records)
+            if log:
+                for gi, name in enumerate(stream_plan.names):
+                    log(f"streamlines {name!r}: step {step}: {stream_mod.summary(stream_plan, gi, counts, codes)}")
+
+        def take_render(step):
+            """every view; files out, one log line per image"""
+            for plan in render_plans:
+                rgba, codes, samples = st.render(plan, step) if hasattr(st, "render") else render_mod.host_image(st, grids, plan, step)
+                if writing:
+                    render_mod.write_png(os.path.join(out_dir, render_mod.render_file_name(plan.name, step)), render_mod.quantise(rgba))
+                if log:
+                    log(f"render {plan.name!r}: step {step}: {render_mod.summary(codes, samples)}")
+
+        def take_tracers(step):
+            """the advance of the host fallback behind coarse step `step`, and at a snapshot step the snapshot: files out, one log line
+            per group"""
+            levels = tracer_mod.stepper_levels(st, grids, step) if tr_host is not None else None
+            if tr_host is not None:
+                tr_host.advance(levels)
+            if not stats_mod.is_sample_step(step, tr_start, cfg.tracers_output_interval):
+                return
+            rec, n_adv = (tr_host.snapshot(levels), tr_host.n_advances) if tr_host is not None else st.tracers_snapshot(step)
+            if writing:
+                tracer_writer.write(step, rec, n_adv)
+            if log:
+                for gi, name in enumerate(tr_plan.names):
+                    log(f"tracers {name!r}: step {step}: {tracer_mod.summary(tr_plan, gi, rec, cfg.tracers_generations)}")
+
+        def take_flux_host(step):
+            """a sample of the host fallback's flux planes from downloaded fields, kept for flush_fluxes"""
+            flux_host.append((step, *flux_mod.host_sample(st, fplans, step)))
+        modes_live = [modes_on]              # False once a window has ended without `repeat`
+
+        def modes_steps(t, batch_end):
+            """a sample cuts nothing: only a window's last step does (the first one alone without `repeat`)"""
+            if not modes_live[0]:
+                return []
+            ends = modes_mod.window_end_steps(t, batch_end, mplan.start_step, mplan.interval, mplan.samples)
+            return ends if mplan.repeat else ends[:1]
+
+        def take_modes(step):
+            """the window that ends with coarse step `step`: sums down, files out, then the reset for the next window (collective in a
+            distributed run)"""
+            first = step - (mplan.samples - 1) * mplan.interval
+            finals = {}
+            for lvl in range(len(grids)):
+                got = st.modes_sums(lvl)                                                                  # collective
+                if got is None:
+                    continue
+                if got[1] != mplan.samples:
+                    raise RuntimeError(f"fourier modes: level {lvl + 1} holds {got[1]} samples at step {step}, the window has "
+                                       f"{mplan.samples}")
+                finals[lvl] = modes_mod.finalize(np.stack(got[0]), mplan.W)
+            if writing and finals:
+                out_mod.export_modes_mesh(step, grids, finals.__getitem__, (first, step, mplan.samples, mplan.interval), mplan.frequencies_hz,
+                                          out_dir)
+                append_csv("flow_modes.csv", (modes_mod.csv_row(mplan, first, step, k, g.level_id,
+                                                                *modes_mod.level_energy(finals[lvl][1][k], g.obstacle))
+                                              for k in range(mplan.n_modes) for lvl, g in enumerate(grids)))
+            if log:
+                log(f"fourier modes: window of steps {first}..{step} ({mplan.samples} samples) written at step {step}")
+            if mplan.repeat:
+                st.modes_reset()
+            else:
+                modes_live[0] = False
+                if st.modes is not None:
+                    st.modes.close()
+                    st.modes = None
+
+        def state_steps(t, batch_end):
+            """the multiples of the interval, and the last step"""
+            every = cfg.state_files_interval
+            steps = set(stats_mod.sample_steps(t, batch_end, every, every)) if every > 0 else set()
+            return steps | {total_steps} if batch_end == total_steps else steps
+
+        def take_state(step):
+            """state_%06d.npz from downloaded fields"""
+            warm_mod.save_state(os.path.join(out_dir, warm_mod.state_file_name(step)),
+                                warm_mod.state_from_stepper(st, grids, step, params.mesh_offset, float(cfg.u_lattice),
+                                                            os.path.basename(cfg.case_dir)))
+            if log:
+                log(f"state file {warm_mod.state_file_name(step)} written")
+
+        # the cut schedule, in the order of action at a cut: (steps_in(t, batch_end) -> that output's cut steps of a batch, take(step)).
+        # What a stepper samples inside its batches (device tracers' advances, device flux planes, the modes' samples) cuts nothing.
+        cutters = [(steps_in, take) for on, steps_in, take in (
+            (stats_on, _every(cfg.statistics_start_step, cfg.statistics_interval), take_statistics),
+            (surf_host is not None, _every(surf_start, surf_interval), take_surface_host),
+            (slices_on, _every(cfg.slices_start_step, cfg.slices_interval), take_slices),
+            (iso_on, _every(cfg.isosurfaces_start_step, cfg.isosurfaces_interval), take_isosurfaces),
+            (stream_on, _every(cfg.streamlines_start_step, cfg.streamlines_interval), take_streamlines),
+            (render_on, _every(cfg.render_start_step, cfg.render_interval), take_render),
+            # the host fallback cuts at every advance step, the device at the snapshot steps only
+            (tracers_on, _every(tr_start, tr_interval if tr_host is not None else cfg.tracers_output_interval), take_tracers),
+            (flux_on and not dev_fluxes, _every(cfg.flux_planes_start_step, cfg.flux_planes_interval), take_flux_host),
+            (modes_on, modes_steps, take_modes),
+            (state_on, state_steps, take_state)) if on]
+
+        def run_batch(t, batch_end, u_curr):
+            """coarse steps t..batch_end, cut after every step of the schedule - with the batch's own inlet speed: the same steps, the
+            same bits - where the takes of that step act in the schedule's order"""
+            takes = {}
+            for steps_in, take in cutters:
+                for step in steps_in(t, batch_end):
+                    takes.setdefault(step, []).append(take)
+            seg = t
+            for step in sorted(takes):
+                st.batch(seg, step - seg + 1, u_curr, sp)
+                for take in takes[step]:
+                    take(step)
+                seg = step + 1
+            if seg <= batch_end:
+                st.batch(seg, batch_end - seg + 1, u_curr, sp)
+
+        t0 = last_diag = _time.time()
+        total_cells = sum(g.n_blocks * 512 for g in grids)
+        rows: List[DiagRow] = []
+        fr = None                            # the newest loads: the output step reuses those of a diagnostics step at the same step
+
+        def diagnostics_step(t, batch_end, u_curr):
+            """when a multiple of diag_freq lies in t..batch_end: a row, the probes' new samples, the monitor and the wall diagnostics from
+            the state at batch end; after the last step the monitor and the wall diagnostics in any case. -> the monitor's FlowDiverged
+            or None"""
+            nonlocal fr, last_diag
+            diag_step = (batch_end // cfg.diag_freq) * cfg.diag_freq
+            at_diag = t <= diag_step <= batch_end
+            if at_diag:
+                rho1 = None
+                if hasattr(st, "rho_min"):
+                    rho_min = st.rho_min(0)
+                else:
+                    rho1 = st.field(0, "rho")
+                    rho_min = flow_stats(rho1, grids[0].obstacle)
+                cd = cl = cs = cmy = float("nan")
+                if cfg.forces_enabled:
+                    fr = _aerodynamics(st, grids, mesh, params, cfg.symmetric_analysis, rho1 if len(grids) == 1 else None)
+                    cd, cl, cs, cmy = fr.Cd, fr.Cl, fr.Cs, fr.Cmy
+                rows.append(DiagRow(diag_step, float(u_curr), rho_min, cd, cl, cs, cmy))
+                now = _time.time()
+                mlups = (total_cells * cfg.diag_freq) / (max(now - last_diag, 1e-9) * 1e6)     # src/main.jl:189
+                last_diag = now
+                if writing:
+                    time_phys = float(diag_step) * params.time_scale
+                    if cfg.forces_enabled:
+                        out_mod.append_force_csv(os.path.join(out_dir, "forces.csv"), diag_step, time_phys, fr, u_curr)
+                    append_csv("convergence.csv", [out_mod.convergence_csv_row(diag_step, now - t0, time_phys, u_curr, rho_min, mlups,
+                                                                               cd if cfg.forces_enabled else None,
+                                                                               cl if cfg.forces_enabled else None)])
+                if log:
+                    log(f"{diag_step:8d} | {float(u_curr):.4f} | {rho_min:.4f} | {cd:8.4f} | {cl:8.4f}")
+                if probes_on:
+                    flush_probes()
+            elif batch_end != total_steps:
+                return None
+            step = diag_step if at_diag else batch_end       # the last step is no diagnostics step: a record of the end state
+            diverged = take_monitor(step, batch_end) if monitor_on else None
+            if wall_on:
+                take_wall(step, batch_end)
+            return diverged
+        # derived flow arrays on output steps: (VTU name, index into gradient_fields' result, components)
+        grad_names = [g for g in (("Vorticity", 0, 3), ("QCriterion", 1, 1)) if g[0] in cfg.output_fields]
+
+        def output_step(t, batch_end):
+            """when a multiple of output_freq lies in t..batch_end: the flow, surface and mean files of that step (src/main.jl:213-231)"""
+            nonlocal fr
+            out_step = (batch_end // cfg.output_freq) * cfg.output_freq
+            if out_dir is None or not t <= out_step <= batch_end:
+                return
+            fetched = {}
+
+            def fields(lvl, name):
+                if name == "obstacle":
+                    return grids[lvl].obstacle
+                if (lvl, name) not in fetched:
+                    fetched[(lvl, name)] = st.field(lvl, name)          # collective in a distributed run
+                return fetched[(lvl, name)]
+
+            levels = sorted({l for l, _ in out_mod.select_export_blocks([g.active_block_coords for g in grids])})
+            vel_name = "vel_temp" if out_step % 2 == 0 else "vel"
+            for lvl in levels:
+                fields(lvl, "rho"); fields(lvl, vel_name)
+            derived = None
+            if grad_names:
+                # the buffer the file's Velocity comes from, derivatives per unit length of the file's coordinates
+                grad = {lvl: st.gradient_fields(lvl, vel_name, np.float32(1.0 / grids[lvl].dx)) for lvl in levels}      # collective
+                derived = [(name, (lambda lvl, k=k: grad[lvl][k]), ncomp) for name, k, ncomp in grad_names]
+            if eddy_on:
+                # nu_t of the buffer the file's Velocity comes from over the level's nu, both Float32
+                eddy = {}
+                for lvl in levels:
+                    got = st.subgrid_fields(lvl, vel_name)                                               # collective
+                    eddy[lvl] = subgrid_mod.ratio_field(got[0], grids[lvl].tau) if got is not None else None
+                derived = (derived or []) + [("EddyViscosityRatio", eddy.__getitem__, 1)]
+            if cfg.forces_enabled and (fr is None or fr.maps is None or out_step != (out_step // cfg.diag_freq) * cfg.diag_freq):
+                fr = _aerodynamics(st, grids, mesh, params, cfg.symmetric_analysis, want_maps=True)
+            wall_vals = wall_values(batch_end) if wall_on and cfg.forces_enabled else None          # collective
+            if writing:
+                out_mod.export_merged_mesh(out_step, grids, fields, out_dir, cfg.output_fields, derived=derived)
+                if cfg.forces_enabled:
+                    extra = list(wall_mod.finalize(wall_vals, params).items()) if wall_vals is not None else None
+                    out_mod.save_surface_vtk(os.path.join(out_dir, "surface_%06d" % out_step), mesh, *fr.maps, extra=extra)
+            if stats_on and stats_window[0] > 0:
+                finals = {lvl: st.statistics(lvl) for lvl in levels}                                     # collective
+                sgs, sgs_extra = {}, None
+                if subgrid_on:
+                    for lvl in sorted(finals):
+                        sums = st.subgrid_stats_sums(lvl)                                                # collective
+                        if sums is not None:
+                            sgs[lvl] = subgrid_mod.finalize(*sums, subgrid_mod.level_viscosity(grids[lvl].tau),
+                                                            cfg.statistics_subgrid_ck, finals[lvl]["tke"])
+                    sgs_extra = [(name, (lambda lvl, k=k: sgs[lvl][k])) for name, k in subgrid_mod.MEAN_ARRAYS]
+                if writing:
+                    out_mod.export_mean_mesh(out_step, grids, finals.__getitem__, tuple(stats_window), out_dir, extra=sgs_extra)
+            if surf_on:
+                got = surf_host.download() if surf_host is not None else st.surface_stats_sums()        # collective
+                if writing and got is not None and got[1] > 0:
+                    window = surface_mod.window_of(got[1], surf_start, surf_interval)
+                    fin_stats = surface_mod.finalize(got[0], got[1], params)
+                    surface_mod.save_surface_mean_vtk(os.path.join(out_dir, "surface_mean_%06d" % out_step), mesh, fin_stats, splan.found,
+                                                      window)
+                    fr_mean = surface_mod.mean_forces(mesh, fin_stats, params, cfg.symmetric_analysis)
+                    append_csv("forces_mean.csv", [surface_mod.forces_mean_csv_row(out_step, window, fr_mean)])
+
+        # ---- the time loop ----
+        t = first_step
         while t <= total_steps:
             batch_end = min(t + batch - 1, total_steps)
-            actual = batch_end - t + 1
             u_curr = ramp_velocity(batch_end, cfg.ramp_steps, cfg.u_lattice)
-            if (stats_on or surf_host is not None or slices_on or iso_on or stream_on or render_on or tracers_on
-                    or (flux_on and not dev_fluxes) or modes_live[0] or state_on):
-                # a batch is cut after every sampled step, with the batch's own inlet speed: the same steps, the same bits
-                cuts = set()
-                if stats_on:
-                    cuts.update(stats_mod.sample_steps(t, batch_end, cfg.statistics_start_step, cfg.statistics_interval))
-                if surf_host is not None:
-                    cuts.update(stats_mod.sample_steps(t, batch_end, surf_start, surf_interval))
-                if slices_on:
-                    cuts.update(stats_mod.sample_steps(t, batch_end, sl_start, sl_interval))
-                if iso_on:
-                    cuts.update(stats_mod.sample_steps(t, batch_end, iso_start, iso_interval))
-                if stream_on:
-                    cuts.update(stats_mod.sample_steps(t, batch_end, stream_start, stream_interval))
-                if render_on:
-                    cuts.update(stats_mod.sample_steps(t, batch_end, rd_start, rd_interval))
-                if tracers_on:           # on the device an advance cuts nothing: only the snapshot steps do
-                    tr_cuts = set(stats_mod.sample_steps(t, batch_end, tr_start, tr_interval if tr_host is not None else tr_out))
-                    cuts.update(tr_cuts)
-                if flux_on and not dev_fluxes:      # on the device a sample cuts nothing
-                    cuts.update(stats_mod.sample_steps(t, batch_end, fx_start, fx_interval))
-                mode_cuts = set()
-                if modes_live[0]:        # a sample cuts nothing: only a window's last step does (the first one alone without `repeat`)
-                    ends = modes_mod.window_end_steps(t, batch_end, mplan.start_step, mplan.interval, mplan.samples)
-                    mode_cuts = set(ends if mplan.repeat else ends[:1])
-                    cuts.update(mode_cuts)
-                state_cuts = set()
-                if state_on:             # the multiples of the interval, and the last step
-                    if cfg.state_files_interval > 0:
-                        state_cuts.update(stats_mod.sample_steps(t, batch_end, cfg.state_files_interval, cfg.state_files_interval))
-                    if batch_end == total_steps:
-                        state_cuts.add(total_steps)
-                    cuts.update(state_cuts)
-                seg = t
-                for s_step in sorted(cuts):
-                    st.batch(seg, s_step - seg + 1, u_curr, sp)
-                    if stats_on and stats_mod.is_sample_step(s_step, cfg.statistics_start_step, cfg.statistics_interval):
-                        if s_step == cfg.statistics_start_step:
-                            st.stats_reset()
-                            if subgrid_on:
-                                st.subgrid_stats_reset()
-                            stats_window = [0, s_step, s_step]
-                        st.stats_sample(s_step)
-                        if subgrid_on:
-                            st.subgrid_stats_sample(s_step)
-                        stats_window[0] += 1
-                        stats_window[2] = s_step
-                    if surf_host is not None and stats_mod.is_sample_step(s_step, surf_start, surf_interval):
-                        t_sub = stats_mod.t_sub_after(fin, s_step)
-                        surf_host.accumulate(st.field(fin, "rho"), st.field(fin, "vel_temp" if t_sub % 2 == 0 else "vel"))
-                    if slices_on and stats_mod.is_sample_step(s_step, sl_start, sl_interval):
-                        got = st.slices_sample(s_step) if dev_slices else slices_mod.host_sample(st, splans, grids, s_step)
-                        if writing:
-                            slice_writer.write(s_step, got)
-                    if iso_on and stats_mod.is_sample_step(s_step, iso_start, iso_interval):
-                        take_isosurfaces(s_step)
-                    if stream_on and stats_mod.is_sample_step(s_step, stream_start, stream_interval):
-                        take_streamlines(s_step)
-                    if render_on and stats_mod.is_sample_step(s_step, rd_start, rd_interval):
-                        take_render(s_step)
-                    if tracers_on and s_step in tr_cuts:
-                        take_tracers(s_step)
-                    if flux_on and not dev_fluxes and stats_mod.is_sample_step(s_step, fx_start, fx_interval):
-                        flux_host.append((s_step, *flux_mod.host_sample(st, fplans, s_step)))
-                    if s_step in mode_cuts:
-                        take_modes(s_step)
-                    if s_step in state_cuts:
-                        warm_mod.save_state(os.path.join(out_dir, warm_mod.state_file_name(s_step)),
-                                            warm_mod.state_from_stepper(st, grids, s_step, params.mesh_offset, float(cfg.u_lattice),
-                                                                        os.path.basename(cfg.case_dir)))
-                        if log:
-                            log(f"state file {warm_mod.state_file_name(s_step)} written")
-                    seg = s_step + 1
-                if seg <= batch_end:
-                    st.batch(seg, batch_end - seg + 1, u_curr, sp)
-            else:
-                st.batch(t, actual, u_curr, sp)
+            run_batch(t, batch_end, u_curr)
             if fseries_on:
                 flush_force_series(u_curr)
             if flux_on:
                 flush_fluxes()
-            monitored = wall_done = False
-            if batch_end % cfg.diag_freq < actual or batch_end == total_steps:
-                diag_step = (batch_end // cfg.diag_freq) * cfg.diag_freq
-                if t <= diag_step <= batch_end:
-                    rho1 = None
-                    if hasattr(st, "rho_min"):
-                        rho_min = st.rho_min(0)
-                    else:
-                        rho1 = st.field(0, "rho")
-                        rho_min = flow_stats(rho1, grids[0].obstacle)
-                    cd = cl = cs = cmy = float("nan")
-                    if cfg.forces_enabled:
-                        fr = _aerodynamics(st, grids, mesh, params, cfg.symmetric_analysis, rho1 if len(grids) == 1 else None)
-                        cd, cl, cs, cmy = fr.Cd, fr.Cl, fr.Cs, fr.Cmy
-                    rows.append(DiagRow(diag_step, float(u_curr), rho_min, cd, cl, cs, cmy))
-                    now = _time.time()
-                    mlups = (total_cells * cfg.diag_freq) / (max(now - last_diag, 1e-9) * 1e6)     # src/main.jl:189
-                    last_diag = now
-                    if writing:
-                        time_phys = float(diag_step) * params.time_scale
-                        if cfg.forces_enabled:
-                            out_mod.append_force_csv(os.path.join(out_dir, "forces.csv"), diag_step, time_phys, fr, u_curr)
-                        with open(os.path.join(out_dir, "convergence.csv"), "a") as io:
-                            io.write(out_mod.convergence_csv_row(diag_step, now - t0, time_phys, u_curr, rho_min, mlups,
-                                                                 cd if cfg.forces_enabled else None, cl if cfg.forces_enabled else None) + "\n")
-                    if log:
-                        log(f"{diag_step:8d} | {float(u_curr):.4f} | {rho_min:.4f} | {cd:8.4f} | {cl:8.4f}")
-                    if probes_on:
-                        flush_probes()
-                    if monitor_on:
-                        diverged = take_monitor(diag_step, batch_end)
-                        monitored = True
-                    if wall_on:
-                        take_wall(diag_step, batch_end)
-                        wall_done = True
-            if monitor_on and batch_end == total_steps and not monitored:
-                diverged = take_monitor(batch_end, batch_end)          # the last step is no diagnostics step: a record of the end state
-            if wall_on and batch_end == total_steps and not wall_done:
-                take_wall(batch_end, batch_end)
-            if out_dir is not None and batch_end % cfg.output_freq < actual:                      # src/main.jl:213-231
-                out_step = (batch_end // cfg.output_freq) * cfg.output_freq
-                if t <= out_step <= batch_end:
-                    fetched = {}
-
-                    def fields(lvl, name):
-                        if name == "obstacle":
-                            return grids[lvl].obstacle
-                        if (lvl, name) not in fetched:
-                            fetched[(lvl, name)] = st.field(lvl, name)          # collective in a distributed run
-                        return fetched[(lvl, name)]
-
-                    mesh_arrays_needed = out_mod.select_export_blocks([g.active_block_coords for g in grids])
-                    vel_name = "vel_temp" if out_step % 2 == 0 else "vel"
-                    for lvl in sorted({l for l, _ in mesh_arrays_needed}):
-                        fields(lvl, "rho"); fields(lvl, vel_name)
-                    derived = None
-                    if grad_names:
-                        # the buffer the file's Velocity comes from, derivatives per unit length of the file's coordinates
-                        grad = {lvl: st.gradient_fields(lvl, vel_name, np.float32(1.0 / grids[lvl].dx))      # collective
-                                for lvl in sorted({l for l, _ in mesh_arrays_needed})}
-                        derived = [(name, (lambda lvl, k=k: grad[lvl][k]), ncomp) for name, k, ncomp in grad_names]
-                    if eddy_on:
-                        # nu_t of the buffer the file's Velocity comes from over the level's nu, both Float32
-                        eddy = {}
-                        for lvl in sorted({l for l, _ in mesh_arrays_needed}):
-                            got = st.subgrid_fields(lvl, vel_name)                                               # collective
-                            eddy[lvl] = subgrid_mod.ratio_field(got[0], grids[lvl].tau) if got is not None else None
-                        derived = (derived or []) + [("EddyViscosityRatio", eddy.__getitem__, 1)]
-                    if cfg.forces_enabled and (fr is None or fr.maps is None or out_step != (out_step // cfg.diag_freq) * cfg.diag_freq):
-                        fr = _aerodynamics(st, grids, mesh, params, cfg.symmetric_analysis, want_maps=True)
-                    wall_vals = wall_values(batch_end) if wall_on and cfg.forces_enabled else None          # collective
-                    if writing:
-                        out_mod.export_merged_mesh(out_step, grids, fields, out_dir, cfg.output_fields, derived=derived)
-                        if cfg.forces_enabled:
-                            extra = list(wall_mod.finalize(wall_vals, params).items()) if wall_vals is not None else None
-                            out_mod.save_surface_vtk(os.path.join(out_dir, "surface_%06d" % out_step), mesh, *fr.maps, extra=extra)
-                    if stats_on and stats_window[0] > 0:
-                        finals = {lvl: st.statistics(lvl) for lvl in sorted({l for l, _ in mesh_arrays_needed})}   # collective
-                        sgs, sgs_extra = {}, None
-                        if subgrid_on:
-                            for lvl in sorted(finals):
-                                sums = st.subgrid_stats_sums(lvl)                                                # collective
-                                if sums is not None:
-                                    sgs[lvl] = subgrid_mod.finalize(*sums, subgrid_mod.level_viscosity(grids[lvl].tau),
-                                                                    cfg.statistics_subgrid_ck, finals[lvl]["tke"])
-                            sgs_extra = [(name, (lambda lvl, k=k: sgs[lvl][k])) for name, k in subgrid_mod.MEAN_ARRAYS]
-                        if writing:
-                            out_mod.export_mean_mesh(out_step, grids, finals.__getitem__, tuple(stats_window), out_dir, extra=sgs_extra)
-                    if surf_on:
-                        got = surf_host.download() if surf_host is not None else st.surface_stats_sums()        # collective
-                        if writing and got is not None and got[1] > 0:
-                            window = surface_mod.window_of(got[1], surf_start, surf_interval)
-                            fin_stats = surface_mod.finalize(got[0], got[1], params)
-                            surface_mod.save_surface_mean_vtk(os.path.join(out_dir, "surface_mean_%06d" % out_step), mesh, fin_stats,
-                                                              splan.found, window)
-                            fr_mean = surface_mod.mean_forces(mesh, fin_stats, params, cfg.symmetric_analysis)
-                            with open(os.path.join(out_dir, "forces_mean.csv"), "a") as io:
-                                io.write(surface_mod.forces_mean_csv_row(out_step, window, fr_mean) + "\n")
+            diverged = diagnostics_step(t, batch_end, u_curr)
+            output_step(t, batch_end)
             if diverged is not None and cfg.flow_monitor_stop_on_divergence:
                 if probes_on:
                     flush_probes()
